@@ -6,7 +6,13 @@ A "step" (--steps K) is ONE network.run() of T = 250 timesteps over one resident
 batch [250, 32, 784] u8 followed by network.reset_state_variables() (what eth_mnist.py does per
 sample); `value` = timesteps simulated per second summed over all ranks.
 
-  python bench.py [--gpus N --steps K --warmup W]            (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]      (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step` = milliseconds per timed step).
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller as float32 .npy files: the three monitor
+rasters (X_spikes, Ae_spikes, Ai_spikes, [T, batch, ...]), the learned X -> Ae weights (W_X_Ae) and the adaptive thresholds (theta_Ae).
+The inputs and seeds are fixed, so two builds given the same arguments can be compared file for file.
+`--full` adds the secondary legs below (CPU baseline, parity, synchronous runs, roofline, N > 1: the per-input collective on its own).
 
 N > 1 (weak scaling): every rank simulates its own batch of 32 with replicated weights; after
 each input the weight and threshold deltas are all-reduced over RCCL and re-normalised
@@ -21,13 +27,13 @@ Input: the generator BASELINE.md section 2 states for this config -- per sample 
 Poisson-encoded (bindsnet.encoding.poisson, time=250, dt=1) from torch.manual_seed(1): ~1.17 % spike density; the first
 three batches are the trains tests/golden/full_cfg2_dc_n400_b32_poisson.npz holds from the REFERENCE encoder.
 
-Order of the legs (N = 1): CPU baseline first (8-thread / 1-thread legs pinned to 8 CPUs = one CCD), then GPU warm-up +
-timed region, parity, roofline profile last.
-Extra objects on the JSON line: "roofline" (dominant kernel, HIP-event-timed, vs HBM peak), "cpu_baseline"
+Order of the legs with --full (N = 1): CPU baseline first (8-thread / 1-thread legs pinned to 8 CPUs = one CCD), then GPU warm-up +
+timed region, synchronous runs, parity, roofline profile last.
+Extra objects on the JSON line with --full (null without): "roofline" (dominant kernel, HIP-event-timed, vs HBM peak), "cpu_baseline"
 (oracle/torch_cpu_ref.py -- the reference's own ATen operator sequence on the host CPU -- 8 threads = `value`,
 median of 3 whole inputs; 1 thread; cpu_count()-1 threads [eth_mnist.py:77]; the scalar C port) and "parity" (the
 same three inputs from a fresh network on the GPU vs that CPU run, same host, same process: rasters bit for bit,
-weights / theta after every input).
+weights / theta after every input) and "sync_runs" (the same K steps with every network.run() waiting for the device).
 """
 import argparse
 import json
@@ -424,7 +430,10 @@ def main():
 
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the secondary legs: CPU baseline, parity against it, synchronous runs, "
+                    "roofline, and with N > 1 the per-input collective timed on its own")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (and so without the parity leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--plan", default="auto", choices=["auto", "generic", "per-step"])
     ap.add_argument("--sync-runs", action="store_true", help="every network.run() waits for the device (the reference's call-by-call "
                     "behaviour) instead of the pipelined section the timed region normally is")
@@ -439,6 +448,8 @@ def main():
             raise SystemExit(f"bench.py --gpus {args.gpus}: only {torch.cuda.device_count()} GPU(s) visible")
         respawn_under_launcher(args)
     if args.config == "cfg3":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the headline workload's outputs (--config cfg2)")
         return main_cfg3(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -451,7 +462,7 @@ def main():
     #      threads alive the same operators ran 3-4x slower on the GPU box's EPYC: 21 vs 80 timesteps/s).  The 8-thread and
     #      1-thread legs run PINNED to the first 8 CPUs this process may use (one CCD of the EPYC: 8 cores, one L3): unpinned,
     #      the 8-thread figure flipped between ~27 and ~170 timesteps/s from one input to the next on the same box.
-    cpu_leg = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_leg = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
     aff_all = pin = None
     if cpu_leg and hasattr(os, "sched_setaffinity"):
         try:
@@ -539,12 +550,14 @@ def main():
     # put back after every reset (one 25 KB device copy, INSIDE the timed region) so every pass simulates the stated input.
     last = [x[T - 1].clone() for x in pool]
 
-    def one(k):
+    def one(k, keep=None):
         x = {"X": pool[k % len(pool)]}
         if world > 1:
             parallel.sharded_run(net, x, T)
         else:
             net.run(x, time=T)
+        if keep is not None:        # --dump-outputs, last timed step: the recordings run() handed the monitors (fresh buffers every run)
+            keep.update({l + "_spikes": net.monitors[l + "_spikes"].get("s") for l in ("X", "Ae", "Ai")})
         net.reset_state_variables()
         pool[k % len(pool)][T - 1].copy_(last[k % len(pool)])
 
@@ -569,11 +582,13 @@ def main():
             fence()
             enter("timed region")
             # HIP events (on the launch stream) around the dominant launch of every run of the timed region itself (the first 256 of them): the
-            # `roofline` of the line is the kernel as it ran inside the number it stands beside (two event records per run)
+            # `roofline` of the line is the kernel as it ran inside the number it stands beside (two event records per run; recorded without
+            # --full too, so that the timed region is the same either way)
             _lib.lib().snn_profile_enable(4)
+            outputs = {}
             t0 = time.perf_counter()
             for k in range(args.steps):
-                one(args.warmup + k)
+                one(args.warmup + k, outputs if args.dump_outputs and k == args.steps - 1 else None)
             host_enqueue = time.perf_counter() - t0            # the host has issued every step: its own cost per step
             net.sync()                                         # status of every run checked, host generator written back
             fence()
@@ -585,10 +600,16 @@ def main():
     except Exception as e:                                     # noqa: BLE001
         error_line(f"rank {rank}, stage '{stage['name']}': {type(e).__name__}: {str(e)[:400]}")
         raise
-    # ---- the same K steps as a reference user's loop runs them (examples/mnist/eth_mnist.py:243-250 reads its monitors after every
+    if args.dump_outputs and rank == 0:                        # before anything else runs on this network
+        outputs["W_X_Ae"] = net.connections[("X", "Ae")].pipeline[0].value
+        outputs["theta_Ae"] = net.layers["Ae"].theta
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+    # ---- --full: the same K steps as a reference user's loop runs them (examples/mnist/eth_mnist.py:243-250 reads its monitors after every
     #      network.run()): no section, every run() waits for the device.  A secondary figure of the same line (`sync_runs`), N = 1 only.
     sync_leg = None
-    if world == 1 and not args.sync_runs:
+    if world == 1 and not args.sync_runs and args.full:
         enter("sync runs")
         try:
             for k in range(2):                                 # (untimed: the process's FIRST cooperative launch creates the runtime's cooperative queue, several ms)
@@ -618,7 +639,7 @@ def main():
         devices = ids
         # the per-input collective on its own: the flat delta buffer sharded_run all-reduces (weights + thresholds), 20 times
         st = net.__dict__.get("_shard_state")
-        if st is not None and "delta" in st:
+        if args.full and st is not None and "delta" in st:
             buf = st["delta"].clone()
             fence()
             c0 = time.perf_counter()
@@ -640,11 +661,11 @@ def main():
         # runs of the same input pool, LAST, so the device is busy until the process prints its line
         roof = None
         prof = None
-        if ev_n.value > 0 and plan_timed.startswith("dc2015-resident"):     # the timed region's own launches
+        if args.full and ev_n.value > 0 and plan_timed.startswith("dc2015-resident"):     # the timed region's own launches
             form = _lib.lib().snn_dc2015_last_form()
             prof = {"kernel": _lib.resident_kernel_name(form) + " (one launch per network.run(); HIP events around the launches of the timed region)",
                     "resident_form": form, "avg_ms": ev_sum.value / ev_n.value, "n": ev_n.value, "timesteps_per_launch": T}
-        if prof is None:                                                    # per-step / generic plans: sampled launches of extra runs
+        if args.full and prof is None:                                      # per-step / generic plans: sampled launches of extra runs
             prof = _lib.profile_run(net, {"X": pool[0].clone()}, T, repeats=25, pipelined=not args.sync_runs)
         if prof is not None:
             ab = algorithmic_bytes_per_timestep() * prof["timesteps_per_launch"]

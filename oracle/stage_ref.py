@@ -9,6 +9,11 @@ not exist, like the built .so files do.  What IS committed is oracle/ref_manifes
   stage()   -- copy from /root/reference when it exists (the build container); returns the number of files staged
   verify()  -- True when every file of the manifest is present under oracle/_ref/ with the recorded sha256
   manifest(write=True) -- recompute from /root/reference (run once here:  python -m oracle.stage_ref manifest)
+  staged_file(rel) -- the staged copy of one of CHECKOUT_FILES, or None where none was staged
+
+stage() also copies CHECKOUT_FILES: the reference's MNIST example scripts and three of its own test files, which the tests run
+unmodified (the scripts are sha256-checked against the fixtures under tests/golden/).  Tests read them from oracle/_ref/ only and
+skip where build() could not stage them.
 """
 import hashlib
 import json
@@ -21,6 +26,8 @@ STAGED_ROOT = os.path.join(HERE, "_ref", "bindsnet")
 MANIFEST = os.path.join(HERE, "ref_manifest.json")
 PACKAGES = ("network", "learning", "models", "encoding")
 FILES = ("utils.py",)
+CHECKOUT_FILES = ("examples/mnist/eth_mnist.py", "examples/mnist/conv_mnist.py", "examples/mnist/reservoir.py",
+                  "test/models/test_models.py", "test/encoding/test_encoding.py", "test/network/test_network.py")
 
 
 def _listing(root):
@@ -38,8 +45,8 @@ def _sha(path):
         return hashlib.sha256(f.read()).hexdigest()
 
 
-def manifest(write=False):
-    m = {rel: _sha(os.path.join(REF_ROOT, rel)) for rel in _listing(REF_ROOT)}
+def manifest(write=False, root=REF_ROOT):
+    m = {rel: _sha(os.path.join(root, rel)) for rel in _listing(root)}
     if write:
         with open(MANIFEST, "w") as f:
             json.dump({"source": "BindsNET/bindsnet checkout at /root/reference (bindsnet/)", "sha256": m}, f, indent=1, sort_keys=True)
@@ -55,7 +62,19 @@ def stage():
         os.makedirs(os.path.dirname(dst), exist_ok=True)
         shutil.copyfile(os.path.join(REF_ROOT, rel), dst)
         n += 1
+    checkout, staged = os.path.dirname(REF_ROOT), os.path.dirname(STAGED_ROOT)
+    for rel in CHECKOUT_FILES:
+        if os.path.exists(os.path.join(checkout, rel)):
+            dst = os.path.join(staged, rel)
+            os.makedirs(os.path.dirname(dst), exist_ok=True)
+            shutil.copyfile(os.path.join(checkout, rel), dst)
+            n += 1
     return n
+
+
+def staged_file(rel):
+    path = os.path.join(os.path.dirname(STAGED_ROOT), rel)
+    return path if os.path.exists(path) else None
 
 
 def verify():

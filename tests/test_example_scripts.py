@@ -1,4 +1,4 @@
-"""The reference's second MNIST example, examples/mnist/conv_mnist.py, ITSELF (sha256-checked byte copy or the checkout's file),
+"""The reference's second MNIST example, examples/mnist/conv_mnist.py, ITSELF (the sha256-checked byte copy build() stages under oracle/_ref),
 with `bindsnet` = this package: on the host here (network/host_path.py), on the MI355X in tests/test_gpu_zz_experimental.py.  It
 must reproduce what the same file produced on the reference's CPU path (tests/golden/make_golden_conv_mnist.py): the Y raster of
 every training input, theta, and the convolution weights (Conv2d + PostPre + per-filter normalisation) within the convolution's
@@ -11,14 +11,14 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SCRIPT = "/root/reference/examples/mnist/conv_mnist.py"
-STAGED = os.path.join(ROOT, "tests", "_staged", "conv_mnist.py")
+sys.path.insert(0, ROOT)
+from oracle import stage_ref  # noqa: E402
 
 
 def literal_script(g):
-    path = REF_SCRIPT if os.path.exists(REF_SCRIPT) else STAGED
-    if not os.path.exists(path):
-        pytest.skip("no copy of examples/mnist/conv_mnist.py on this machine (python __graft_entry__.py build stages one where the reference checkout exists)")
+    path = stage_ref.staged_file("examples/mnist/conv_mnist.py")
+    if path is None:
+        pytest.skip("no copy of examples/mnist/conv_mnist.py under oracle/_ref (python __graft_entry__.py build stages one where the reference checkout exists)")
     assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(g["script_sha"]), "not the reference's conv_mnist.py"
     return path
 
@@ -47,8 +47,6 @@ def test_conv_mnist_script_itself_on_the_host():
 
 
 # ---------------------------------------------------------------------------------------------------- examples/mnist/reservoir.py
-REF_RESERVOIR = "/root/reference/examples/mnist/reservoir.py"
-STAGED_RESERVOIR = os.path.join(ROOT, "tests", "_staged", "reservoir.py")
 
 
 def run_reservoir(extra_argv, plan):
@@ -63,9 +61,9 @@ def run_reservoir(extra_argv, plan):
     import conv_mnist_harness as H
     from cases import gold
     g = gold("reservoir_literal")
-    path = REF_RESERVOIR if os.path.exists(REF_RESERVOIR) else STAGED_RESERVOIR
-    if not os.path.exists(path):
-        pytest.skip("no copy of examples/mnist/reservoir.py on this machine")
+    path = stage_ref.staged_file("examples/mnist/reservoir.py")
+    if path is None:
+        pytest.skip("no copy of examples/mnist/reservoir.py under oracle/_ref")
     assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(g["script_sha"])
     np.random.seed(0)
     r = H.run_script(path, netmod, [str(a) for a in g["argv"]] + list(extra_argv), seed=0, monitor="O_spikes",

@@ -289,8 +289,9 @@ def _bench(args, env_extra=None, timeout=400):
 def test_bench_two_ranks_on_one_gpu_gloo_end_to_end():
     """`python bench.py --gpus 2 --backend gloo`: the launcher re-exec, the rendezvous on 127.0.0.1, sharded_run inside a pipelined
     section on both ranks, the merge collective, barrier + MAX of the elapsed times and rank 0's ONE JSON line -- everything the
-    driver's N-GPU command goes through except RCCL itself, with both ranks on the one GPU of the box."""
-    res, line = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    driver's N-GPU command goes through except RCCL itself, with both ranks on the one GPU of the box.  (--full: the per-input
+    collective timed on its own.)"""
+    res, line = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert res.returncode == 0 and line is not None, (res.stdout[-1500:], res.stderr[-3000:])
     assert line.get("error") is None, line
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["steps"] == 3 and line["scaling"] == "weak"

@@ -5,7 +5,7 @@
     python tools/eth_mnist_timing.py --impl ref [...]                          (build container: the reference, CPU path)
 
 The script file is executed unmodified through runpy (the reference checkout's file, or the byte copy
-__graft_entry__.build() stages under tests/_staged/); MNIST is the synthetic stand-in of tests/tv_shim.py (no
+__graft_entry__.build() stages under oracle/_ref/); MNIST is the synthetic stand-in of tests/tv_shim.py (no
 network here), matplotlib runs on the Agg backend (the script ALWAYS plots: parser.set_defaults(plot=True),
 eth_mnist.py:45).  Timers are wrappers around the callables the script uses -- nothing in the script changes:
 
@@ -31,7 +31,7 @@ import warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 REF_SCRIPT = "/root/reference/examples/mnist/eth_mnist.py"
-STAGED = os.path.join(ROOT, "tests", "_staged", "eth_mnist.py")
+STAGED = os.path.join(ROOT, "oracle", "_ref", "examples", "mnist", "eth_mnist.py")
 REF_SHA = "ba4f875d097536bf1d935070112f1ad7fdffe50c190d2e9a9de1e0b278fefe4a"
 
 

@@ -56,7 +56,7 @@ def main(out):
         shutil.copy(path, os.path.join(out, "kernel_stats.csv"))
     fetch, n = counter_mean(os.path.join(out, "fetch"), "FETCH_SIZE")
     write, _ = counter_mean(os.path.join(out, "write"), "WRITE_SIZE")
-    res = {"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline",
+    res = {"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline",
            "kernel": KERNEL, "kernel_source_sha16": source_sha16(), "launches": n, "timesteps_per_launch": T,
            "FETCH_SIZE_KB_per_launch_mean": fetch, "WRITE_SIZE_KB_per_launch_mean": write}
     if fetch is not None and write is not None:

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/trace_step
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT" -o tr -- python "$R/bench.py" --steps 6 --warmup 3 --no-cpu-baseline > "$OUT/run.log" 2>&1
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT" -o tr -- python "$R/bench.py" --steps 6 --warmup 3 --full --no-cpu-baseline > "$OUT/run.log" 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, sys
 out = sys.argv[1]
