@@ -524,15 +524,16 @@ __global__ __launch_bounds__(1024) void k_convpp_run(const ConvPPCtx a) {
         __syncthreads();
         PPMARK(3);
         if (multi[2]) { dead = true; break; }
-        // ---- batch reduction in ATen's sum(dim=0) order + apply (k_conv_pp_apply's statements) on the own copy of the filters
-        if (tid < nel) {
-            const long e = (long)c0 * K + tid;
+        // ---- batch reduction in ATen's sum(dim=0) order + apply (k_conv_pp_apply's statements) on the own copy of the filters; a chunk may
+        //      hold more elements than the workgroup has threads (nel = nco * taps, NT follows the output pixels)
+        for (int k = tid; k < nel; k += NT) {
+            const long e = (long)c0 * K + k;
             const bool tail = e >= (E / 32) * 32;
-            float w = wl[tid];
+            float w = wl[k];
             auto ordered = [&](const float *base) {           // (sixteen samples' values are read together, then added in ATen's order)
                 if (tail) {
                     OuterSum accs; accs.init(true);
-                    for (int bb = 0; bb < B; ++bb) accs.add(bb, base[bb * nel + tid], B);
+                    for (int bb = 0; bb < B; ++bb) accs.add(bb, base[bb * nel + k], B);
                     return accs.finish(B);
                 }
                 // OuterSum's cascade (snn_order.hpp Cascade) over the dense positions 0 .. B-1: the sixteen positions of a group share their
@@ -541,7 +542,7 @@ __global__ __launch_bounds__(1024) void k_convpp_run(const ConvPPCtx a) {
                 for (int b0 = 0; b0 < B; b0 += 16) {
                     float vv[16];
 #pragma unroll
-                    for (int u = 0; u < 16; ++u) vv[u] = base[min(b0 + u, B - 1) * nel + tid];
+                    for (int u = 0; u < 16; ++u) vv[u] = base[min(b0 + u, B - 1) * nel + k];
                     if ((b0 >> 4) != cs.cb) cs.advance(b0 >> 4);
 #pragma unroll
                     for (int u = 0; u < 16; ++u) if (b0 + u < B) cs.a0 += vv[u];
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(1024) void k_convpp_run(const ConvPPCtx a) {
             w = w * a.wdecay;
             if (a.has_min && w < a.wmin) w = a.wmin;
             if (a.has_max && w > a.wmax) w = a.wmax;
-            wl[tid] = w;
+            wl[k] = w;
         }
         __syncthreads();                                   // the filters of step t+1 are in place; red and the row tables are free
         PPMARK(4);
