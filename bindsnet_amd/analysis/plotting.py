@@ -131,6 +131,30 @@ def plot_locally_connected_weights(weights: torch.Tensor, n_filters: int, kernel
     return im
 
 
+def plot_local_connection_2d_weights(lc, input_channel: int = 0, output_channel: int = None, im=None, lines: bool = True,
+                                     figsize: Tuple[int, int] = (5, 5), cmap: str = "hot_r", color: str = "r",
+                                     title: Optional[str] = None):
+    """The kernels of a LocalConnection2D as one image (plotting.py:404-485): one input channel, all filters (or only
+    `output_channel`), receptive-field blocks separated by dashed lines.  Returns the AxesImage."""
+    from ..utils import reshape_local_connection_2d_weights
+    fs = int(np.ceil(np.sqrt(lc.n_filters)))
+    w = lc.w.detach().cpu().view(lc.in_channels, lc.n_filters, *lc.conv_size, *lc.kernel_size)[input_channel]
+    side = int(np.sqrt(lc.source.n))
+    if output_channel is None:
+        image = reshape_local_connection_2d_weights(w, lc.n_filters, lc.kernel_size, lc.conv_size, (side, side))
+    else:
+        image = reshape_local_connection_2d_weights(w[output_channel][None], 1, lc.kernel_size, lc.conv_size, (side, side))
+    if im is not None:
+        im.set_data(_np(image))
+        return im
+    im = _image_with_colorbar(_np(image), figsize, cmap, float(lc.wmin), float(lc.wmax), None if title is None else title + " Weights")
+    if lines and output_channel is None:
+        for axis_line, k, c in ((im.axes.axhline, lc.kernel_size[0], lc.conv_size[0]), (im.axes.axvline, lc.kernel_size[1], lc.conv_size[1])):
+            for edge in range(fs * k, fs * c * k, fs * k):
+                axis_line(edge - 0.5, color=color, linestyle="--")
+    return im
+
+
 def plot_assignments(assignments: torch.Tensor, im=None, figsize: Tuple[int, int] = (5, 5),
                      classes: Optional[Sized] = None, save: Optional[str] = None):
     """Grid of per-neuron class labels (plotting.py:487-578).  Returns the AxesImage."""

@@ -145,11 +145,14 @@ struct OuterSum {
 // path under every ATEN_CPU_CAPABILITY; probed).  Lane l of 8 sums x[l], x[8 + l], ... through row_sum over the n / 8 vectors
 // (= RowSum4); then a fresh accumulator takes the n mod 8 leftover elements in order and after them the 8 lane sums in lane
 // order.  Rows shorter than one vector: scalar row_sum over the n terms.
-__host__ __device__ inline float inner_sum8(const float *x, int n) {
+// `term(k)` yields element k of the row (inner_sum8_terms: rows whose elements are formed on the fly, e.g. the event-driven
+// LocalConnection sums of snn_local.hip, which return +0 for a silent tap without loading its weight).
+template <class TERM>
+__host__ __device__ inline float inner_sum8_terms(TERM term, int n) {
     if (n < 8) {
         RowSum4 r;
         r.init();
-        for (int i = 0; i < n; ++i) r.add(i, x[i], n);
+        for (int i = 0; i < n; ++i) r.add(i, term(i), n);
         return r.finish(n);
     }
     const int vs = n >> 3;
@@ -157,13 +160,17 @@ __host__ __device__ inline float inner_sum8(const float *x, int n) {
     for (int l = 0; l < 8; ++l) {
         RowSum4 r;
         r.init();
-        for (int i = 0; i < vs; ++i) r.add(i, x[i * 8 + l], vs);
+        for (int i = 0; i < vs; ++i) r.add(i, term(i * 8 + l), vs);
         part[l] = r.finish(vs);
     }
     float fin = 0.f;
-    for (int k = vs * 8; k < n; ++k) fin += x[k];
+    for (int k = vs * 8; k < n; ++k) fin += term(k);
     for (int l = 0; l < 8; ++l) fin += part[l];
     return fin;
+}
+
+__host__ __device__ inline float inner_sum8(const float *x, int n) {
+    return inner_sum8_terms([x](int k) { return x[k]; }, n);
 }
 
 // Plain ascending sequential sum (canonical order of the dense Connection path).

@@ -130,6 +130,13 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
         if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_MSTDPET) return SNN_ERR_INVALID;
+        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_LOCAL) return SNN_ERR_INVALID;
+        if (d.kind == SNN_CONN_LOCAL) {        // LocalConnection1D / 2D / 3D: no rule or PostPre (learning.py:208-389)
+            if (!d.local_src || d.cin <= 0 || d.local_F <= 0 || d.local_conv_prod <= 0 || d.local_kernel_prod <= 0 || d.mask) return SNN_ERR_INVALID;
+            if (d.local_n_src != L[d.src].n || (long)d.local_F * d.local_conv_prod != L[d.dst].n) return SNN_ERR_INVALID;
+            if (d.rule != SNN_RULE_NONE && d.rule != SNN_RULE_POSTPRE) return SNN_ERR_UNSUPPORTED;
+            continue;                          // has_norm: snn_normalize_conv2d, no column scratch
+        }
         if (d.has_norm && (!d.norm_ws || d.kind == SNN_CONN_CONV2D)) return SNN_ERR_INVALID;
     }
     return SNN_OK;
@@ -163,6 +170,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 const int acc = fed[d.dst] ? 1 : 0;
                 if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_LOCAL) TRY(snn_prop_local_f32(d.w, d.local_src, sp, D.current, B, d.cin, d.local_F,
+                                                                          d.local_conv_prod, d.local_kernel_prod, d.local_n_src, acc, st));
                 else TRY(snn_prop_conv2d_f32(d.w, d.bias, sp, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw,
                                              d.stride, d.pad, acc, st));
                 fed[d.dst] = true;
@@ -220,6 +229,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                     TRY(snn_conv2d_mstdp_step(d.w, d.e_trace, d.p_plus, d.p_minus, ss, D.s, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride,
                                               d.pad, d.reward, d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay,
                                               d.has_min, d.wmin, d.has_max, d.wmax, st));
+                else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_LOCAL)
+                    TRY(snn_local_postpre(d.w, d.local_src, ss, S.x, D.s, D.x, B, d.cin, d.local_F, d.local_conv_prod, d.local_kernel_prod,
+                                          d.local_n_src, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONV2D)
                     TRY(snn_conv2d_postpre(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
                                            d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
@@ -245,6 +257,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
         for (int c = 0; c < nC; ++c)          // network.py:456-458: monitors record last, i.e. the weights this step leaves behind
             if (C[c].raster_w) {
                 const size_t ne = C[c].kind == SNN_CONN_CONV2D ? (size_t)C[c].cout * C[c].cin * C[c].kh * C[c].kw
+                                : C[c].kind == SNN_CONN_LOCAL  ? (size_t)C[c].cin * C[c].local_F * C[c].local_conv_prod * C[c].local_kernel_prod
                                                                : (size_t)L[C[c].src].n * L[C[c].dst].n;
                 if (hipMemcpyAsync(C[c].raster_w + (size_t)t * ne, C[c].w, ne * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                     return SNN_ERR_LAUNCH;
@@ -308,6 +321,9 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (L[l].thresh_vec) mode = 1;      // per-neuron thresholds: generic plan
+    bool local = false;                                                // LocalConnection1D / 2D / 3D: generic plan only; no fused plan is
+    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL) local = true;     // offered the graph
+    if (local) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));
         if (!handled) mode = 1;
@@ -321,7 +337,9 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     }
     // network.py:464-465: normalise every connection after the loop (learning or not)
     for (int c = 0; c < nC; ++c)
-        if (C[c].has_norm && !((normalized >> c) & 1u))
+        if (C[c].has_norm && C[c].kind == SNN_CONN_LOCAL)     // topology.py:1601 / :1748-1759 / :1898: every [kernel_prod] row to sum `norm`
+            TRY(snn_normalize_conv2d(C[c].w, C[c].cin * C[c].local_F * C[c].local_conv_prod, C[c].local_kernel_prod, C[c].norm, st));
+        else if (C[c].has_norm && !((normalized >> c) & 1u))
             TRY(snn_normalize(C[c].w, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_abs, C[c].norm_ws, st));
     return SNN_OK;
 }

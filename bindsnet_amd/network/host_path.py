@@ -168,12 +168,48 @@ def _propagate(conn, s):
         return _sum(value * spikes, 1).view(B, *conn.target.shape)
     if isinstance(conn, Conv2dConnection):
         return F.conv2d(s.float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding, dilation=conn.dilation)
+    from .topology import _LocalConnectionND
+    if isinstance(conn, _LocalConnectionND):
+        return _propagate_local(conn, s)
     if isinstance(conn, (Connection, LocalConnection)):
         post = s.reshape(B, -1).float() @ conn.w.view(conn.source.n, conn.target.n)
         if getattr(conn, "b", None) is not None:
             post = post + conn.b
         return post.view(B, *conn.target.shape)
     raise NotImplementedError(f"bindsnet_amd host path: connection type {type(conn).__name__}")
+
+
+def _propagate_local(conn, s):
+    """LocalConnection1D / 2D / 3D.compute, the reference's expression (topology.py:1573-1597 / :1731-1746 / :1880-1896)."""
+    B = s.shape[0]
+    s_unfold = conn._unfold(s.reshape(B, *conn.source.shape)).reshape(B, conn.in_channels, conn.conv_prod, conn.kernel_prod)
+    a_post = s_unfold.repeat(1, 1, conn.n_filters, 1) * conn.w
+    return a_post.sum(-1).sum(1).view(B, *conn.target.shape)
+
+
+def _update_local(conn, rule) -> None:
+    """PostPre on LocalConnection1D / 2D / 3D, the reference's expressions (learning.py:208-389 + :87-104)."""
+    B, R, J = conn.source.batch_size, conn.n_filters * conn.conv_prod, conn.in_channels * conn.kernel_prod
+    W = conn.w.data
+    eye = torch.eye(R)
+
+    def unfolded(t):
+        u = conn._unfold(t.reshape(B, *conn.source.shape)).reshape(B, conn.conv_prod, J)
+        return u.repeat(1, conn.n_filters, 1)
+
+    target_x = conn.target.x.reshape(B, R, 1) * eye
+    target_s = conn.target.s.type(torch.float).reshape(B, R, 1) * eye
+    if rule.nu[0].any():
+        pre = _reduce(rule, torch.bmm(target_x, unfolded(conn.source.s.type(torch.float))))
+        W -= rule.nu[0] * pre.view(W.size())
+    if rule.nu[1].any():
+        post = _reduce(rule, torch.bmm(target_s, unfolded(conn.source.x)))
+        W += rule.nu[1] * post.view(W.size())
+    if rule.weight_decay:
+        W *= rule.weight_decay
+    lo, hi = rule._bounds()
+    if lo is not None or hi is not None:
+        W.clamp_(conn.wmin, conn.wmax)
 
 
 def _reduce(rule, t):
@@ -299,10 +335,13 @@ def _update_mcc(conn, dt, kwargs) -> None:
 
 def _update_dense(conn, kwargs, mask) -> None:
     from ..learning import learning as rules
-    from .topology import Conv2dConnection
+    from .topology import Conv2dConnection, _LocalConnectionND
     rule = conn.update_rule
     if rule is None or isinstance(rule, rules.NoOp):
         return
+    if isinstance(conn, _LocalConnectionND):
+        rule._check_reduction()
+        return _update_local(conn, rule)
     B = conn.source.batch_size
     W = conn.w.data
     conv = isinstance(conn, Conv2dConnection)
@@ -355,7 +394,7 @@ def _update_dense(conn, kwargs, mask) -> None:
 
 
 def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs) -> None:
-    from .nodes import DiehlAndCookNodes, Input, LIFNodes
+    from .nodes import Input, LIFNodes, _AdaptiveThresholdNodes
     from .topology import MulticompartmentConnection
     clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
     injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
@@ -365,7 +404,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
         # this one does not, and says so instead of failing inside torch.tensor(dict)
         raise NotImplementedError("bindsnet_amd: per-connection a_plus/a_minus dicts are not supported")
     for name, layer in network.layers.items():
-        if not isinstance(layer, (Input, LIFNodes, DiehlAndCookNodes)):
+        if not isinstance(layer, (Input, LIFNodes, _AdaptiveThresholdNodes)):
             raise NotImplementedError(f"bindsnet_amd host path: layer type {type(layer).__name__}")
         if isinstance(layer, Input) and name not in inputs:
             raise NotImplementedError(f"bindsnet_amd: Input layer '{name}' needs an entry in `inputs`")
@@ -406,7 +445,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
                 if inj is not None:
                     inj = torch.as_tensor(inj)
                     layer.v += inj[t] if inj.dim() >= 2 else inj
-                (_step_dc if isinstance(layer, DiehlAndCookNodes) else _step_lif)(layer, x)
+                (_step_dc if isinstance(layer, _AdaptiveThresholdNodes) else _step_lif)(layer, x)
                 for table, value in ((clamps, 1), (unclamps, 0)):
                     m = table.get(name)
                     if m is not None:
@@ -438,7 +477,13 @@ def normalize_connection(conn) -> None:
     """One connection's normalisation -- Weight features by their SIGNED column sums (topology_features.py:250-266), dense
     connections by the absolute ones (topology.py:383-392), a LocalConnection by the signed ones again (topology.py:1475-1482),
     a Conv2dConnection filter by filter (topology.py:824-837)."""
-    from .topology import Conv2dConnection, LocalConnection, MulticompartmentConnection
+    from .topology import Conv2dConnection, LocalConnection, MulticompartmentConnection, _LocalConnectionND
+    if isinstance(conn, _LocalConnectionND):                     # topology.py:1601 / :1748-1759 / :1898
+        if conn.norm is not None:
+            w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], conn.w.shape[2])
+            for fltr in range(w.shape[0]):
+                w[fltr, :] *= conn.norm / w[fltr, :].sum(0)
+        return
     if isinstance(conn, Conv2dConnection):                       # topology.py:824-837: every [KH*KW] filter to sum `norm`
         if conn.norm is not None:
             w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], conn.w.shape[2] * conn.w.shape[3])

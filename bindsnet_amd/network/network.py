@@ -16,8 +16,9 @@ import torch
 from .. import _lib
 from ..rng import DeviceGenerator
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
-from .nodes import DiehlAndCookNodes, Input, LIFNodes, Nodes, _f
-from .topology import AbstractConnection, Connection, Conv2dConnection, LocalConnection, MulticompartmentConnection
+from .nodes import AdaptiveLIFNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
+from .topology import (AbstractConnection, Connection, Conv2dConnection, LocalConnection, MulticompartmentConnection,
+                       _LocalConnectionND)
 
 
 def load(file_name: str, map_location: str = "cpu", learning: bool = None) -> "Network":
@@ -111,7 +112,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         if plan is None or plan["epoch"] != _lib.epoch() or not _DESC_CACHE:
             segs, others, rebind = [], [], []
             for l in self.layers.values():
-                if type(l) in (Input, LIFNodes, DiehlAndCookNodes) and l.s.is_cuda and l.s.is_contiguous():
+                if type(l) in (Input, LIFNodes, DiehlAndCookNodes, AdaptiveLIFNodes) and l.s.is_cuda and l.s.is_contiguous():
                     if type(l) is Input:
                         rebind.append((len(segs), l))
                     segs.append((l.s, 0))
@@ -480,7 +481,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     inj = (inj[:T] if per_step else inj).contiguous()
                     keep.append(inj)
                     d.inject_v, d.inject_per_step, d.inject_len = _dptr(inj), int(per_step), one.numel()
-                if isinstance(layer, DiehlAndCookNodes):
+                if isinstance(layer, _AdaptiveThresholdNodes):        # DiehlAndCookNodes, AdaptiveLIFNodes (one_spike = 0)
                     d.kind, d.p, d.theta = _lib.LAYER_DC, layer._dc_params(), _dptr(layer.theta)
                     if layer.one_spike:
                         max_draws = max(max_draws, B * layer.n)
@@ -494,7 +495,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                         scalars.append((layer.thresh, layer.thresh._version))      # (an in-place change rebuilds: tv may be a converted copy)
                 else:
                     raise NotImplementedError(f"bindsnet_amd: layer type {type(layer).__name__} is outside the "
-                                              "accelerated path (Input, LIFNodes, DiehlAndCookNodes)")
+                                              "accelerated path (Input, LIFNodes, DiehlAndCookNodes, AdaptiveLIFNodes)")
         except BaseException:
             _nodes._SCALARS = None
             raise
@@ -523,7 +524,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 if mask is None:
                     mask = getattr(conn, "mask", None)         # LocalConnection's structural mask (topology.py:1468-1470)
                 if mask is not None:
-                    if not hasattr(conn, "w") or isinstance(conn, Conv2dConnection):
+                    if not hasattr(conn, "w") or isinstance(conn, (Conv2dConnection, _LocalConnectionND)):
                         raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
                     m = torch.as_tensor(mask).to(dev).ne(0).to(torch.uint8).contiguous()
                     if m.numel() != conn.w.numel():
@@ -549,7 +550,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if isinstance(conn, MulticompartmentConnection):
                 ptrs.append((conn._weight(), "value", conn._weight().value.data_ptr()))
             else:
-                for attr in ("w", "b"):
+                for attr in ("w", "b", "src"):
                     t = getattr(conn, attr, None)
                     if isinstance(t, torch.Tensor):
                         ptrs.append((conn, attr, t.data_ptr()))
@@ -796,7 +797,12 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
         d.w = _dptr(conn.w.data)
         d.bias = _dptr(conn.b.data) if getattr(conn, "b", None) is not None else None
-        if isinstance(conn, Conv2dConnection):
+        if isinstance(conn, _LocalConnectionND):              # LocalConnection1D / 2D / 3D (topology.py:1488-1910): generic plan
+            if conn.src.device != dev:
+                raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
+            d.kind, d.bias, d.cin, d.local_src = _lib.CONN_LOCAL, None, conn.in_channels, _dptr(conn.src)
+            d.local_F, d.local_conv_prod, d.local_kernel_prod, d.local_n_src = conn.n_filters, conn.conv_prod, conn.kernel_prod, conn.source.n
+        elif isinstance(conn, Conv2dConnection):
             d.kind = _lib.CONN_CONV2D
             d.cin, d.h, d.wd = conn.in_channels, conn.source.shape[1], conn.source.shape[2]
             d.cout, d.kh, d.kw = conn.out_channels, conn.kernel_size[0], conn.kernel_size[1]
@@ -862,7 +868,12 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             raise NotImplementedError("bindsnet_amd: weight_decay on a connection without a learning rule is not supported")
         if conn.w.dtype != torch.float32 or not conn.w.is_contiguous():
             raise NotImplementedError("bindsnet_amd: connection weights must be contiguous float32")
-        if conn.norm is not None and isinstance(conn, Conv2dConnection):
+        if conn.norm is not None and isinstance(conn, _LocalConnectionND):
+            # every [kernel_prod] row to sum `norm` (topology.py:1748-1759): snn_net_run's post-loop step, through snn_normalize_conv2d
+            if isinstance(conn.norm, torch.Tensor):
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+            d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(conn.norm), 0, None
+        elif conn.norm is not None and isinstance(conn, Conv2dConnection):
             # Conv2dConnection.normalize (topology.py:824-837) scales every filter to sum `norm`: not a column normalisation, so
             # not snn_net_run's post-loop step -- run() calls the connection's own normalize() (snn_normalize_conv2d) behind it
             if isinstance(conn.norm, torch.Tensor):

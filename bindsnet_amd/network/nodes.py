@@ -1,5 +1,5 @@
 """Neuron groups: API mirror of bindsnet/network/nodes.py for the layer types on the hot path
-(`Nodes`, `Input`, `LIFNodes`, `DiehlAndCookNodes`); the arithmetic lives in libsnnhip
+(`Nodes`, `Input`, `LIFNodes`, `DiehlAndCookNodes`, `AdaptiveLIFNodes`); the arithmetic lives in libsnnhip
 (snn_input_step / snn_lif_step / snn_dc_step).
 
 State is held in the same attributes as the reference (`s`, `x`, `v`, `refrac_count`, `theta`,
@@ -199,8 +199,10 @@ class LIFNodes(Nodes):
                      thresh_vec=self._thresh_vec())
 
 
-class DiehlAndCookNodes(Nodes):
-    """LIF with adaptive threshold and one-spike arbitration (reference: nodes.py:981-1144)."""
+class _AdaptiveThresholdNodes(Nodes):
+    """What DiehlAndCookNodes (nodes.py:981-1144) and AdaptiveLIFNodes (nodes.py:829-978) share: the same buffers, decays and
+    membrane / threshold arithmetic (SNN_LAYER_DC).  They differ only in DiehlAndCookNodes' one-spike arbitration.  Private, so
+    that neither class is an instance of the other, as in the reference."""
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -213,7 +215,7 @@ class DiehlAndCookNodes(Nodes):
         self.register_buffer("thresh", _buf(thresh))
         self.register_buffer("refrac", _buf(refrac))
         self.register_buffer("tc_decay", _buf(tc_decay))
-        self.register_buffer("decay", torch.empty_like(self.tc_decay))
+        self.register_buffer("decay", torch.empty_like(self.tc_decay, dtype=torch.float32))
         self.register_buffer("theta_plus", _buf(theta_plus))
         self.register_buffer("tc_theta_decay", _buf(tc_theta_decay))
         self.register_buffer("theta_decay", torch.empty_like(self.tc_theta_decay))
@@ -265,3 +267,31 @@ class DiehlAndCookNodes(Nodes):
         with NoiseStream(self.v.device, max_draws=B * self.n if self.one_spike else 0) as ns:
             ops.dc_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, self.theta, x,
                         self._dc_params(), ns.q, ns.cursor, ns.status)
+
+
+class DiehlAndCookNodes(_AdaptiveThresholdNodes):
+    """LIF with adaptive threshold and one-spike arbitration (reference: nodes.py:981-1144)."""
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
+                 refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 100.0, theta_plus: Scalar = 0.05,
+                 tc_theta_decay: Scalar = 1e7, lbound: float = None, one_spike: bool = True, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input, thresh=thresh, rest=rest, reset=reset, refrac=refrac,
+                         tc_decay=tc_decay, theta_plus=theta_plus, tc_theta_decay=tc_theta_decay, lbound=lbound,
+                         one_spike=one_spike)
+
+
+class AdaptiveLIFNodes(_AdaptiveThresholdNodes):
+    """LIF with an adaptive threshold (reference: nodes.py:829-978): DiehlAndCookNodes' step without the one-spike
+    arbitration -- every neuron that crosses its threshold spikes.  Same constructor arguments, buffers and decays as the
+    reference; runs as an SNN_LAYER_DC layer with one_spike = 0."""
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, rest: Scalar = -65.0, reset: Scalar = -65.0, thresh: Scalar = -52.0,
+                 refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 100.0, theta_plus: Scalar = 0.05,
+                 tc_theta_decay: Scalar = 1e7, lbound: float = None, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input, thresh=thresh, rest=rest, reset=reset, refrac=refrac,
+                         tc_decay=tc_decay, theta_plus=theta_plus, tc_theta_decay=tc_theta_decay, lbound=lbound,
+                         one_spike=False)

@@ -1,5 +1,5 @@
 """Connections: API mirror of bindsnet/network/topology.py for the connection types on the hot
-path (`Connection`, `MulticompartmentConnection`, `Conv2dConnection`).  `compute()` launches the
+path (`Connection`, `MulticompartmentConnection`, `Conv2dConnection`, `LocalConnection`, `LocalConnection1D/2D/3D`).  `compute()` launches the
 matching propagation kernel of libsnnhip; inside Network.run the same kernels are driven from C++.
 """
 import warnings
@@ -8,7 +8,7 @@ from typing import Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 from torch.nn import Module, Parameter
-from torch.nn.modules.utils import _pair
+from torch.nn.modules.utils import _pair, _triple
 
 from .. import _lib, ops
 from .nodes import Nodes
@@ -235,6 +235,116 @@ class Conv2dConnection(AbstractConnection):
             if isinstance(self.norm, torch.Tensor):
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
             ops.normalize_conv2d(self.w.data, float(self.norm))
+
+
+class _LocalConnectionND(AbstractConnection):
+    """What LocalConnection1D / 2D / 3D (reference: topology.py:1488-1910) share.  Weights [Cin, n_filters*conv_prod,
+    kernel_prod]; target neuron r = f*conv_prod + o sees receptive field o.  The three classes differ only in the `unfold`
+    calls that gather a receptive field's source spikes, so the gather is kept as a table: the int32 buffer `src`
+    [Cin, conv_prod, kernel_prod] holds the flat source index of every tap, built by pushing arange(source.n) through
+    those same unfolds (`_unfold`).  `compute` and PostPre (learning.py:208-389) run in libsnnhip (snn_prop_local_f32,
+    snn_local_postpre); on the host the reference's own torch expressions (network/host_path.py).
+
+    Deviation: the reference's `w=` branch asserts against an attribute it never defines (`self.out_channels`) and so
+    raises AttributeError for any `w`; here a `w` of shape [Cin, n_filters*conv_prod, kernel_prod] is accepted (and clamped
+    to [wmin, wmax] like a drawn one), any other shape raises AssertionError."""
+
+    _ndim = 0
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size, stride, n_filters: int, nu=None, reduction=None,
+                 weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
+        if w_dtype != torch.float32:
+            raise NotImplementedError("bindsnet_amd computes in float32 only")
+        nd = self._ndim
+        self.n_filters = n_filters
+        self.in_channels = source.shape[0]
+        spatial = [int(v) for v in source.shape[1:1 + nd]]
+        ks = kernel_size if nd == 1 else tuple(kernel_size)
+        st = stride if nd == 1 else tuple(stride)
+        kl, sl = ([ks], [st]) if nd == 1 else (list(ks), list(st))
+        conv = [int((spatial[i] - kl[i]) / sl[i]) + 1 for i in range(nd)]
+        self.conv_size = conv[0] if nd == 1 else tuple(conv)
+        self.conv_prod, self.kernel_prod = int(np.prod(conv)), int(np.prod(kl))
+        idx = torch.arange(self.in_channels * int(np.prod(spatial))).view(1, self.in_channels, *spatial)
+        self.register_buffer("src", self._unfold(idx).reshape(self.in_channels, self.conv_prod, self.kernel_prod)
+                             .to(torch.int32).contiguous())
+        shape = (self.in_channels, self.n_filters * self.conv_prod, self.kernel_prod)
+        w = kwargs.get("w", None)
+        if w is None:            # topology.py:1551-1554 / :1704-1707 / :1853-1856: one draw from the global generator
+            w = torch.rand(*shape).to(dtype=w_dtype)
+        else:
+            assert tuple(w.shape) == shape, ("Target dimensionality must be (in_channels,n_filters*conv_prod,kernel_prod)")
+            w = self.cast_dtype_if_needed(w, w_dtype)
+        if self.wmin != -np.inf or self.wmax != np.inf:
+            w = torch.clamp(w, self.wmin, self.wmax)
+        self.w = Parameter(w, requires_grad=False)
+        self.b = Parameter(kwargs.get("b", None), requires_grad=False)
+
+    def _unfold(self, t: torch.Tensor) -> torch.Tensor:
+        """The reference's unfold chain on t [B, Cin, *spatial] -> [B, Cin, conv..., kernel...] (a view)."""
+        if self._ndim == 1:
+            return t.unfold(-1, self.kernel_size, self.stride)
+        for i in range(self._ndim):
+            t = t.unfold(-self._ndim, self.kernel_size[i], self.stride[i])
+        return t
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        """a_post = unfold(s) * w; a_post.sum(-1).sum(1) (topology.py:1573-1597 / :1731-1746 / :1880-1896)."""
+        B = s.shape[0]
+        if not self.w.is_cuda:
+            from . import host_path
+            return host_path._propagate_local(self, s)
+        out = torch.empty(B, self.target.n, device=self.w.device)
+        ops.prop_local(self.w.data, self.src, s.reshape(B, -1).contiguous(), out, self.n_filters)
+        return out.view(B, *self.target.shape)
+
+    def normalize(self) -> None:
+        """Every [kernel_prod] row of the [Cin*n_filters*conv_prod, kernel_prod] view scaled to sum `norm` (topology.py:1601,
+        :1748-1759, :1898)."""
+        if self.norm is not None:
+            if not self.w.is_cuda:
+                from . import host_path
+                return host_path.normalize_connection(self)
+            if isinstance(self.norm, torch.Tensor):
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+            ops.normalize_local(self.w.data, float(self.norm))
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.target.reset_state_variables()          # as the reference does (topology.py:1612-1618)
+
+
+class LocalConnection1D(_LocalConnectionND):
+    """One-dimensional local connection, source shape (C, H) (reference: topology.py:1488-1618)."""
+    _ndim = 1
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: int, stride: int, n_filters: int, nu=None, reduction=None,
+                 weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        self.kernel_size, self.stride = kernel_size, stride
+        super().__init__(source, target, kernel_size, stride, n_filters, nu, reduction, weight_decay, w_dtype, **kwargs)
+
+
+class LocalConnection2D(_LocalConnectionND):
+    """Two-dimensional local connection, source shape (C, H, W) (reference: topology.py:1621-1767)."""
+    _ndim = 2
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]], stride: Union[int, Tuple[int, int]],
+                 n_filters: int, nu=None, reduction=None, weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32,
+                 **kwargs) -> None:
+        self.kernel_size, self.stride = _pair(kernel_size), _pair(stride)
+        super().__init__(source, target, self.kernel_size, self.stride, n_filters, nu, reduction, weight_decay, w_dtype, **kwargs)
+
+
+class LocalConnection3D(_LocalConnectionND):
+    """Three-dimensional local connection, source shape (C, H, W, D) (reference: topology.py:1770-1917)."""
+    _ndim = 3
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int, int]],
+                 stride: Union[int, Tuple[int, int, int]], n_filters: int, nu=None, reduction=None, weight_decay: float = 0.0,
+                 w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        self.kernel_size, self.stride = _triple(kernel_size), _triple(stride)
+        super().__init__(source, target, self.kernel_size, self.stride, n_filters, nu, reduction, weight_decay, w_dtype, **kwargs)
 
 
 class AbstractMulticompartmentConnection(_lib.TouchingModule, Module):

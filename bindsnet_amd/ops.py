@@ -76,6 +76,40 @@ def prop_conv2d(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
     return out
 
 
+def prop_local(W, src, s, out, n_filters, accumulate=False):
+    """f5: LocalConnection1D/2D/3D.compute; W [Cin, F*conv_prod, kernel_prod] f32, src int32 [Cin, conv_prod, kernel_prod],
+    s [B, n_src] spikes, out [B, F*conv_prod]."""
+    B = s.shape[0]
+    Cin, conv_prod, kernel_prod = src.shape
+    n_src = s.numel() // B
+    if tuple(W.shape) != (Cin, n_filters * conv_prod, kernel_prod) or out.numel() != B * n_filters * conv_prod:
+        raise ValueError("prop_local: W / out do not match the gather table")
+    check(lib().snn_prop_local_f32(_ptr(W, F32), _ptr(src, torch.int32), _ptr(s, "spike"), _ptr(out, F32), B, Cin, n_filters,
+                                   conv_prod, kernel_prod, n_src, int(accumulate), _stream()), "prop_local")
+    return out
+
+
+def local_postpre(W, src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, n_filters, decay=1.0, wmin=None, wmax=None):
+    """f5: PostPre on LocalConnection1D/2D/3D weights (learning.py:208-389); s_src / x_src [B, n_src], s_tgt / x_tgt
+    [B, F*conv_prod]."""
+    B = s_src.shape[0]
+    Cin, conv_prod, kernel_prod = src.shape
+    n_src = s_src.numel() // B
+    if tuple(W.shape) != (Cin, n_filters * conv_prod, kernel_prod) or x_src.numel() != B * n_src \
+            or s_tgt.numel() != B * n_filters * conv_prod or x_tgt.numel() != s_tgt.numel():
+        raise ValueError("local_postpre: operand shapes do not match the gather table")
+    check(lib().snn_local_postpre(_ptr(W, F32), _ptr(src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
+                                  _ptr(x_tgt, F32), B, Cin, n_filters, conv_prod, kernel_prod, n_src, float(nu0), float(nu1),
+                                  float(decay), int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None),
+                                  0.0 if wmax is None else wmax, _stream()), "local_postpre")
+
+
+def normalize_local(W, norm):
+    """LocalConnection1D/2D/3D.normalize (topology.py:1601 / :1748-1759 / :1898): every [kernel_prod] row of W
+    [Cin, F*conv_prod, kernel_prod] scaled to sum `norm` (snn_normalize_conv2d's arithmetic)."""
+    check(lib().snn_normalize_conv2d(_ptr(W, F32), W.shape[0] * W.shape[1], W.shape[2], float(norm), _stream()), "normalize_local")
+
+
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None):
     check(lib().snn_input_step(_ptr(s, "spike"), _ptr(x, F32, True), s.numel(), trace_decay, trace_scale,
                                int(additive), _ptr(raster, "spike", True), _stream()), "input_step")

@@ -74,11 +74,22 @@ def _shard_buffers(network, tensors):
     return st
 
 
+def _reject_local(network, mode: str) -> None:
+    """None of the multi-device modes handles LocalConnection1D / 2D / 3D (their weights are not [source.n, target.n]
+    matrices): such a graph raises instead of being routed through a mode built for other layouts."""
+    from .network.topology import LocalConnection1D, LocalConnection2D, LocalConnection3D
+    for key, conn in network.connections.items():
+        if isinstance(conn, (LocalConnection1D, LocalConnection2D, LocalConnection3D)):
+            raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} is not supported by the multi-device modes; "
+                                      "run the network on one device")
+
+
 def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, **kwargs) -> None:
     """network.run on this rank's batch shard, then merge learning across ranks (see module doc): the weights and
     thresholds become  before + sum_over_ranks(after - before), are clamped, and only then normalised.  The post-run
     normalisation inside run() is switched off through the network's `_defer_norm` flag (part of the key of the kept
     descriptor arrays, so consecutive sharded runs re-use them like plain runs do)."""
+    _reject_local(network, "sharded_run")
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
     tensors = [t for t, _, _, _ in learned] + thetas
@@ -151,6 +162,7 @@ def column_shard(network, rank: int, world: int):
     from .network.nodes import Input, LIFNodes
     from .network.topology import Connection
     from .network.topology_features import Weight
+    _reject_local(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
         raise NotImplementedError("column sharding applies to Input -> one connection -> LIFNodes graphs (no coupling "
@@ -261,6 +273,7 @@ def gather_columns(local: torch.Tensor, n_columns: int, group=None) -> torch.Ten
 # On the host (CPU tensors, gloo) the same schedule runs on network/host_path.py's operators: tests/test_parallel_gloo.py.
 # =====================================================================================================
 def _exact_check(network):
+    _reject_local(network, "exact_run")
     from .learning import MCC_learning as mcc_rules
     from .learning import learning as dense_rules
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes

@@ -72,3 +72,21 @@ def reshape_locally_connected_weights(w: Tensor, n_filters: int, kernel_size: Un
     grid = torch.zeros(c1, fs * fs, k1, c2, k2)
     grid[:, :n_filters] = fields.permute(1, 0, 3, 2, 4)
     return grid.view(c1, fs, fs, k1, c2, k2).permute(0, 1, 3, 4, 2, 5).reshape(c1 * fs * k1, c2 * fs * k2)
+
+
+def reshape_local_connection_2d_weights(w: Tensor, n_filters: int, kernel_size: Union[int, Tuple[int, int]],
+                                        conv_size: Union[int, Tuple[int, int]], input_sqrt: Union[int, Tuple[int, int]]) -> Tensor:
+    """One input channel's weights of a LocalConnection2D, [n_filters, c1, c2, k1, k2] (any view of that many elements), as one
+    image (utils.py:219-278): the k1 x k2 kernel of filter f at position (n1, n2) lands in block (n1 * fs + f // fs,
+    n2 * fs + f % fs) of a grid with fs = ceil(sqrt(n_filters)).  With a single position (c1 = c2 = 1) the filters tile an
+    fs x fs grid of input-sized images."""
+    (k1, k2), (c1, c2), (i1, i2) = _pair(kernel_size), _pair(conv_size), _pair(input_sqrt)
+    fs = int(math.ceil(math.sqrt(n_filters)))
+    fields = w.detach().cpu().reshape(n_filters, c1, c2, k1, k2).float()
+    if c1 == 1 and c2 == 1:
+        grid = torch.zeros(fs * fs, i1, i2)
+        grid[:n_filters, :k1, :k2] = fields.view(n_filters, k1, k2)[:, :i1, :i2]
+        return grid.view(fs, fs, i1, i2).permute(0, 2, 1, 3).reshape(fs * i1, fs * i2)
+    grid = torch.zeros(c1, fs * fs, k1, c2, k2)
+    grid[:, :n_filters] = fields.permute(1, 0, 3, 2, 4)
+    return grid.view(c1, fs, fs, k1, c2, k2).permute(0, 1, 3, 4, 2, 5).reshape(c1 * fs * k1, c2 * fs * k2)

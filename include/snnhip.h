@@ -84,6 +84,30 @@ int snn_prop_conv2d_f32(const float *W, const float *bias, const uint8_t *s, flo
                         int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
                         int stride, int pad, int accumulate, snn_stream_t stream);
 
+/* ---- f5: LocalConnection1D / 2D / 3D.compute --------------------------------------------------
+ * bindsnet/network/topology.py:1573-1597 (1D), :1731-1746 (2D), :1880-1896 (3D).  s [B, n_src] u8, W [Cin, F*conv_prod,
+ * kernel_prod], out [B, F*conv_prod]; src int32 [Cin, conv_prod, kernel_prod] = flat source index of tap k of receptive
+ * field o in channel ci (what the class's `unfold` calls gather; one table covers 1D, 2D and 3D).
+ * out[b, r] (+)= sum_ci sum_k s[b, src[ci, r % conv_prod, k]] * W[ci, r, k]: the tap sum in ATen's vectorised inner-sum
+ * order (snn_normalize_conv2d's order: 8 interleaved lanes of row_sum, leftovers, then the lanes), the channel sum
+ * ascending.  accumulate as in snn_prop_cascade_f32.  Event-driven: one sample's spikes are staged in LDS (n_src <= 32768,
+ * else read from global memory) and only the taps whose source spiked load their weight.  (ABI 8, additive)           */
+int snn_prop_local_f32(const float *W, const int *src, const uint8_t *s, float *out, int B, int Cin, int F,
+                       int conv_prod, int kernel_prod, int n_src, int accumulate, snn_stream_t stream);
+
+/* ---- f5: PostPre on a LocalConnection1D / 2D / 3D -------------------------------------------------
+ * bindsnet/learning/learning.py:208-389 (+ :87-104).  The reference views its [F*conv_prod, Cin*kernel_prod] update as
+ * w.size() = [Cin, F*conv_prod, kernel_prod] -- a raw reinterpretation, restated as it is: W is treated as the flat
+ * [F*conv_prod, Cin*kernel_prod] matrix, and element (r, j) pairs target r with the source at flat unfolded position
+ * (r % conv_prod)*Cin*kernel_prod + j, decoded as (ci, o, k) and looked up in src.  For Cin = 1 this is the synapse
+ * snn_prop_local_f32 reads.  pre = sum_b x_tgt[b,r] * s_src[b,.], post = sum_b s_tgt[b,r] * x_src[b,.] (batch sums in
+ * ATen sum(dim=0) order); W -= nu0*pre (nu0 != 0), W += nu1*post (nu1 != 0), W *= decay, clamp.  Every weight is read
+ * and written once per call.  (ABI 8, additive)                                                                        */
+int snn_local_postpre(float *W, const int *src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                      const float *x_tgt, int B, int Cin, int F, int conv_prod, int kernel_prod, int n_src,
+                      float nu0, float nu1, float decay, int has_min, float wmin, int has_max, float wmax,
+                      snn_stream_t stream);
+
 /* ---- a2: Input.forward + Nodes.forward trace ------------------------------------------------
  * bindsnet/network/nodes.py:211-221, :96-107.  s is the caller's input slice (aliased, never
  * copied); x (nullable) is the trace, updated in place; raster_out (nullable) receives s.   */
@@ -280,7 +304,11 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
  * structs holding DEVICE pointers; layers and connections are listed in network insertion
  * order, which fixes the evaluation order exactly as the reference's dict iteration does.   */
 enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2 };
-enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2 };
+/* SNN_CONN_LOCAL (LocalConnection1D / 2D / 3D, rules NONE or POSTPRE, generic plan only) and the local_* fields at the end of
+ * snn_conn_desc were added without changing SNN_ABI_VERSION: the change is purely additive.  A library built before it is
+ * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
+ * snn_prop_local_f32 / snn_local_postpre; tests/test_abi.py compares sizeof(snn_conn_desc) with the ctypes mirror.  */
+enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5 };
 
@@ -333,6 +361,11 @@ typedef struct {
     float *raster_w;            /* nullable [T, numel(w)] weight monitor (Monitor / NetworkMonitor on a connection's `w`,
                                    monitors.py:94-111,222-262): w as it stands at the END of every timestep, i.e. after that
                                    step's learning update and mask and before the post-run normalisation (generic plan) */
+    /* LOCAL: w is [cin, local_F*local_conv_prod, local_kernel_prod]; local_src the int32 [cin, local_conv_prod,
+     * local_kernel_prod] gather table of snn_prop_local_f32; local_n_src == the source layer's n.  has_norm: every
+     * [local_kernel_prod] row scaled to sum `norm` (snn_normalize_conv2d, topology.py:1601 / :1748-1759 / :1898). */
+    const int *local_src;
+    int local_F, local_conv_prod, local_kernel_prod, local_n_src;
 } snn_conn_desc;
 
 typedef struct {
