@@ -93,7 +93,9 @@ class ConnDesc(C.Structure):
                 ("e_trace", C.c_void_p), ("decay_e", C.c_float), ("tc_e", C.c_float), ("rule_ws", C.c_void_p),
                 ("mask", C.c_void_p), ("raster_w", C.c_void_p),
                 ("local_src", C.c_void_p), ("local_F", C.c_int), ("local_conv_prod", C.c_int),
-                ("local_kernel_prod", C.c_int), ("local_n_src", C.c_int)]
+                ("local_kernel_prod", C.c_int), ("local_n_src", C.c_int),
+                ("conv_nd", C.c_int), ("conv_d", C.c_int), ("conv_kd", C.c_int), ("conv_pp_src", C.c_void_p),
+                ("conv_pp_rows", C.c_int)]
 
 
 class RunDesc(C.Structure):
@@ -110,7 +112,7 @@ class FillSegment(C.Structure):
 
 MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
-CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL = 0, 1, 2, 3
+CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND = 0, 1, 2, 3, 4
 RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET = 0, 1, 2, 3, 4, 5
 
 _lib = None
@@ -127,6 +129,8 @@ _SIGS = {
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
     "snn_prop_local_f32": ([_vp] * 4 + [_i] * 7 + [_vp], _i),
     "snn_local_postpre": ([_vp] * 6 + [_i] * 6 + [_f] * 3 + [_i, _f, _i, _f, _vp], _i),
+    "snn_prop_convnd_f32": ([_vp] * 4 + [_i] * 12 + [_vp], _i),
+    "snn_convnd_postpre": ([_vp] * 6 + [_i] * 5 + [_f] * 3 + [_i, _f, _i, _f, _vp, _vp], _i),
     "snn_input_step": ([_vp, _vp, _l, _f, _f, _i, _vp, _vp], _i),
     "snn_lif_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_lif_step_vth": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp, _vp], _i),

@@ -55,18 +55,6 @@ __global__ __launch_bounds__(kLocalThreads) void k_prop_local(const float *__res
     }
 }
 
-// ATen's sum(dim=0) of a contiguous [B, E] tensor, column e (probed on the reference's torch): E == 1 is an inner reduction
-// (inner_sum8_terms); 4 <= E < 8 takes the first 4 columns through the cascade and the rest through row_sum; otherwise the
-// columns below 32*floor(E/32) take the cascade, the rest row_sum (OuterSum).
-template <class TERM>
-__device__ __forceinline__ float batch_sum(TERM term, int B, long e, long E) {
-    if (E == 1) return inner_sum8_terms(term, B);
-    const bool tail = (E >= 4 && E < 8) ? e >= 4 : e >= (E / 32) * 32;
-    OuterSum acc; acc.init(tail);
-    for (int b = 0; b < B; ++b) acc.add(b, term(b), B);
-    return acc.finish(B);
-}
-
 // PostPre (learning.py:208-389 + LearningRule.update :87-104).  W is the flat [R = F*conv_prod, J = Cin*kernel_prod]
 // matrix the reference's `pre.view(w.size())` writes into: element (r, j) takes the source at flat unfolded position
 // p = (r % conv_prod) * J + j of the [Cin, conv_prod, kernel_prod] unfold, decoded as (ci, o, k) and looked up in src.

@@ -173,6 +173,19 @@ __host__ __device__ inline float inner_sum8(const float *x, int n) {
     return inner_sum8_terms([x](int k) { return x[k]; }, n);
 }
 
+// ATen's sum(dim=0) of a contiguous [B, E] tensor, column e, with term(b) = element (b, e) (probed on the reference's torch):
+// E == 1 is an inner reduction (inner_sum8_terms); 4 <= E < 8 takes the first 4 columns through the cascade and the rest
+// through row_sum; otherwise the columns below 32*floor(E/32) take the cascade, the rest row_sum (OuterSum).  Used by the
+// PostPre batch reductions of snn_local.hip and snn_convnd.hip.
+template <class TERM>
+__host__ __device__ inline float batch_sum(TERM term, int B, long e, long E) {
+    if (E == 1) return inner_sum8_terms(term, B);
+    const bool tail = (E >= 4 && E < 8) ? e >= 4 : e >= (E / 32) * 32;
+    OuterSum acc; acc.init(tail);
+    for (int b = 0; b < B; ++b) acc.add(b, term(b), B);
+    return acc.finish(B);
+}
+
 // Plain ascending sequential sum (canonical order of the dense Connection path).
 struct SeqSum {
     float a;

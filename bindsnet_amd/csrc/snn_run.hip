@@ -130,7 +130,15 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
         if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_MSTDPET) return SNN_ERR_INVALID;
-        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_LOCAL) return SNN_ERR_INVALID;
+        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_CONVND) return SNN_ERR_INVALID;
+        if (d.kind == SNN_CONN_CONVND) {       // Conv1dConnection / Conv3dConnection: no rule or PostPre (learning.py:422-455, :499-559)
+            if ((d.conv_nd != 1 && d.conv_nd != 3) || d.cin <= 0 || d.conv_d <= 0 || d.h <= 0 || d.wd <= 0 || d.cout <= 0 || d.conv_kd <= 0 ||
+                d.kh <= 0 || d.kw <= 0 || d.mask || d.has_norm) return SNN_ERR_INVALID;
+            if ((long)d.cin * d.conv_d * d.h * d.wd != L[d.src].n) return SNN_ERR_INVALID;
+            if (d.rule != SNN_RULE_NONE && d.rule != SNN_RULE_POSTPRE) return SNN_ERR_UNSUPPORTED;
+            if (d.rule == SNN_RULE_POSTPRE && (!d.conv_pp_src || (long)d.cout * d.conv_pp_rows != L[d.dst].n)) return SNN_ERR_INVALID;
+            continue;
+        }
         if (d.kind == SNN_CONN_LOCAL) {        // LocalConnection1D / 2D / 3D: no rule or PostPre (learning.py:208-389)
             if (!d.local_src || d.cin <= 0 || d.local_F <= 0 || d.local_conv_prod <= 0 || d.local_kernel_prod <= 0 || d.mask) return SNN_ERR_INVALID;
             if (d.local_n_src != L[d.src].n || (long)d.local_F * d.local_conv_prod != L[d.dst].n) return SNN_ERR_INVALID;
@@ -170,6 +178,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 const int acc = fed[d.dst] ? 1 : 0;
                 if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_CONVND) TRY(snn_prop_convnd_f32(d.w, d.bias, sp, D.current, B, d.cin, d.conv_d, d.h, d.wd, d.cout,
+                                                                             d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
                 else if (d.kind == SNN_CONN_LOCAL) TRY(snn_prop_local_f32(d.w, d.local_src, sp, D.current, B, d.cin, d.local_F,
                                                                           d.local_conv_prod, d.local_kernel_prod, d.local_n_src, acc, st));
                 else TRY(snn_prop_conv2d_f32(d.w, d.bias, sp, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw,
@@ -232,6 +242,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_LOCAL)
                     TRY(snn_local_postpre(d.w, d.local_src, ss, S.x, D.s, D.x, B, d.cin, d.local_F, d.local_conv_prod, d.local_kernel_prod,
                                           d.local_n_src, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, st));
+                else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONVND)
+                    TRY(snn_convnd_postpre(d.w, d.conv_pp_src, ss, S.x, D.s, D.x, B, d.cout, d.conv_pp_rows, d.cin * d.conv_kd * d.kh * d.kw,
+                                           S.n, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, (uint32_t *)d.rule_ws, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONV2D)
                     TRY(snn_conv2d_postpre(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
                                            d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
@@ -258,6 +271,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             if (C[c].raster_w) {
                 const size_t ne = C[c].kind == SNN_CONN_CONV2D ? (size_t)C[c].cout * C[c].cin * C[c].kh * C[c].kw
                                 : C[c].kind == SNN_CONN_LOCAL  ? (size_t)C[c].cin * C[c].local_F * C[c].local_conv_prod * C[c].local_kernel_prod
+                                : C[c].kind == SNN_CONN_CONVND ? (size_t)C[c].cout * C[c].cin * C[c].conv_kd * C[c].kh * C[c].kw
                                                                : (size_t)L[C[c].src].n * L[C[c].dst].n;
                 if (hipMemcpyAsync(C[c].raster_w + (size_t)t * ne, C[c].w, ne * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                     return SNN_ERR_LAUNCH;
@@ -321,8 +335,8 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (L[l].thresh_vec) mode = 1;      // per-neuron thresholds: generic plan
-    bool local = false;                                                // LocalConnection1D / 2D / 3D: generic plan only; no fused plan is
-    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL) local = true;     // offered the graph
+    bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
+    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND) local = true;   // plan only; no fused plan is offered the graph
     if (local) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));

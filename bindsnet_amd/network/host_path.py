@@ -168,7 +168,13 @@ def _propagate(conn, s):
         return _sum(value * spikes, 1).view(B, *conn.target.shape)
     if isinstance(conn, Conv2dConnection):
         return F.conv2d(s.float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding, dilation=conn.dilation)
-    from .topology import _LocalConnectionND
+    from .topology import Conv1dConnection, Conv3dConnection, _LocalConnectionND
+    if isinstance(conn, Conv1dConnection):                     # topology.py:640-656
+        return F.conv1d(s.reshape(B, *conn.source.shape).float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding,
+                        dilation=conn.dilation)
+    if isinstance(conn, Conv3dConnection):                     # topology.py:979-995
+        return F.conv3d(s.reshape(B, *conn.source.shape).float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding,
+                        dilation=conn.dilation)
     if isinstance(conn, _LocalConnectionND):
         return _propagate_local(conn, s)
     if isinstance(conn, (Connection, LocalConnection)):
@@ -204,6 +210,30 @@ def _update_local(conn, rule) -> None:
         W -= rule.nu[0] * pre.view(W.size())
     if rule.nu[1].any():
         post = _reduce(rule, torch.bmm(target_s, unfolded(conn.source.x)))
+        W += rule.nu[1] * post.view(W.size())
+    if rule.weight_decay:
+        W *= rule.weight_decay
+    lo, hi = rule._bounds()
+    if lo is not None or hi is not None:
+        W.clamp_(conn.wmin, conn.wmax)
+
+
+def _update_convnd(conn, rule) -> None:
+    """PostPre on Conv1dConnection / Conv3dConnection, the reference's expressions (learning.py:422-455 / :499-559 + :87-104).
+    The source operands go through the connection's `_pp_unfold`, the reference's own pad + unfold + reshape chain."""
+    err = conn._postpre_error(rule)
+    if err is not None:
+        raise RuntimeError(err)
+    B, Cout = conn.source.batch_size, conn.out_channels
+    W = conn.w.data
+    shape = (B, *conn.source.shape)
+    target_x = conn.target.x.view(B, Cout, -1)
+    target_s = conn.target.s.view(B, Cout, -1).float()
+    if rule.nu[0].any():
+        pre = _reduce(rule, torch.bmm(target_x, conn._pp_unfold(conn.source.s.reshape(shape).float())))
+        W -= rule.nu[0] * pre.view(W.size())
+    if rule.nu[1].any():
+        post = _reduce(rule, torch.bmm(target_s, conn._pp_unfold(conn.source.x.reshape(shape))))
         W += rule.nu[1] * post.view(W.size())
     if rule.weight_decay:
         W *= rule.weight_decay
@@ -335,13 +365,16 @@ def _update_mcc(conn, dt, kwargs) -> None:
 
 def _update_dense(conn, kwargs, mask) -> None:
     from ..learning import learning as rules
-    from .topology import Conv2dConnection, _LocalConnectionND
+    from .topology import Conv2dConnection, _ConvNdConnection, _LocalConnectionND
     rule = conn.update_rule
     if rule is None or isinstance(rule, rules.NoOp):
         return
     if isinstance(conn, _LocalConnectionND):
         rule._check_reduction()
         return _update_local(conn, rule)
+    if isinstance(conn, _ConvNdConnection):
+        rule._check_reduction()
+        return _update_convnd(conn, rule)
     B = conn.source.batch_size
     W = conn.w.data
     conv = isinstance(conn, Conv2dConnection)
@@ -403,6 +436,10 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
         # network.py:356-378, 432-447 also takes {connection key: value} tables; like the MI355X path (network.py::_fill_conn)
         # this one does not, and says so instead of failing inside torch.tensor(dict)
         raise NotImplementedError("bindsnet_amd: per-connection a_plus/a_minus dicts are not supported")
+    from .topology import _ConvNdConnection
+    for key, conn in network.connections.items():
+        if isinstance(conn, _ConvNdConnection) and masks.get(key) is not None:
+            raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
     for name, layer in network.layers.items():
         if not isinstance(layer, (Input, LIFNodes, _AdaptiveThresholdNodes)):
             raise NotImplementedError(f"bindsnet_amd host path: layer type {type(layer).__name__}")
@@ -477,7 +514,13 @@ def normalize_connection(conn) -> None:
     """One connection's normalisation -- Weight features by their SIGNED column sums (topology_features.py:250-266), dense
     connections by the absolute ones (topology.py:383-392), a LocalConnection by the signed ones again (topology.py:1475-1482),
     a Conv2dConnection filter by filter (topology.py:824-837)."""
-    from .topology import Conv2dConnection, LocalConnection, MulticompartmentConnection, _LocalConnectionND
+    from .topology import Conv2dConnection, LocalConnection, MulticompartmentConnection, _ConvNdConnection, _LocalConnectionND
+    if isinstance(conn, _ConvNdConnection):                      # topology.py:665-675 / :1004-1017: every [K] filter to sum `norm`
+        if conn.norm is not None:
+            w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], -1)
+            for fltr in range(w.shape[0]):
+                w[fltr] *= conn.norm / w[fltr].sum(0)
+        return
     if isinstance(conn, _LocalConnectionND):                     # topology.py:1601 / :1748-1759 / :1898
         if conn.norm is not None:
             w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], conn.w.shape[2])

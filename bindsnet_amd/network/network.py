@@ -18,7 +18,7 @@ from ..rng import DeviceGenerator
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
 from .nodes import AdaptiveLIFNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
 from .topology import (AbstractConnection, Connection, Conv2dConnection, LocalConnection, MulticompartmentConnection,
-                       _LocalConnectionND)
+                       _ConvNdConnection, _LocalConnectionND)
 
 
 def load(file_name: str, map_location: str = "cpu", learning: bool = None) -> "Network":
@@ -300,6 +300,15 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             f"Got {type(inputs).__name__} instead.")
         clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
         injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
+        if self.learning and int(time / self.dt) > 0:
+            # PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference at its first learning step (a bool bmm
+            # operand); here before the run changes any state -- a deliberate deviation in timing
+            for conn in self.connections.values():
+                rule = getattr(conn, "update_rule", None)
+                if isinstance(conn, _ConvNdConnection) and type(rule).__name__ == "PostPre":
+                    err = conn._postpre_error(rule)
+                    if err is not None:
+                        raise RuntimeError(err)
         if self.reward_fn is not None:
             kwargs["reward"] = self.reward_fn.compute(**kwargs)
 
@@ -387,7 +396,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 R.plan = 2
         if not self.__dict__.get("_defer_norm", False):     # network.py:463-465 for the connections snn_net_run does not normalise itself
             for conn in self.connections.values():
-                if isinstance(conn, Conv2dConnection) and conn.norm is not None:
+                if isinstance(conn, (Conv2dConnection, _ConvNdConnection)) and conn.norm is not None:
                     conn.normalize()
         # Input.s aliases the last input slice, as in the reference (nodes.py:219)
         before = _lib.epoch()
@@ -524,7 +533,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 if mask is None:
                     mask = getattr(conn, "mask", None)         # LocalConnection's structural mask (topology.py:1468-1470)
                 if mask is not None:
-                    if not hasattr(conn, "w") or isinstance(conn, (Conv2dConnection, _LocalConnectionND)):
+                    if not hasattr(conn, "w") or isinstance(conn, (Conv2dConnection, _LocalConnectionND, _ConvNdConnection)):
                         raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
                     m = torch.as_tensor(mask).to(dev).ne(0).to(torch.uint8).contiguous()
                     if m.numel() != conn.w.numel():
@@ -550,7 +559,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if isinstance(conn, MulticompartmentConnection):
                 ptrs.append((conn._weight(), "value", conn._weight().value.data_ptr()))
             else:
-                for attr in ("w", "b", "src"):
+                for attr in ("w", "b", "src", "pp_src"):
                     t = getattr(conn, attr, None)
                     if isinstance(t, torch.Tensor):
                         ptrs.append((conn, attr, t.data_ptr()))
@@ -802,6 +811,17 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
             d.kind, d.bias, d.cin, d.local_src = _lib.CONN_LOCAL, None, conn.in_channels, _dptr(conn.src)
             d.local_F, d.local_conv_prod, d.local_kernel_prod, d.local_n_src = conn.n_filters, conn.conv_prod, conn.kernel_prod, conn.source.n
+        elif isinstance(conn, _ConvNdConnection):            # Conv1dConnection / Conv3dConnection (topology.py:540-1025): generic plan
+            if conn.pp_src.device != dev:
+                raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
+            k = conn._kernel()
+            d.kind, d.cin, d.cout = _lib.CONN_CONVND, conn.in_channels, conn.out_channels
+            d.conv_nd, d.stride, d.pad = conn._ndim, conn._stride(), conn._padding()
+            if conn._ndim == 1:
+                d.conv_d, d.h, d.wd, d.conv_kd, d.kh, d.kw = 1, 1, conn.source.shape[1], 1, 1, k[0]
+            else:
+                (d.conv_d, d.h, d.wd), (d.conv_kd, d.kh, d.kw) = conn.source.shape[1:4], k
+            d.conv_pp_src, d.conv_pp_rows = _dptr(conn.pp_src), conn.pp_src.shape[0]
         elif isinstance(conn, Conv2dConnection):
             d.kind = _lib.CONN_CONV2D
             d.cin, d.h, d.wd = conn.in_channels, conn.source.shape[1], conn.source.shape[2]
@@ -823,6 +843,10 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 d.rule, d.use_dt = _lib.RULE_POSTPRE, 0
                 if isinstance(conn, Conv2dConnection):       # learning.py:457-497: per-sample partial sums live in scratch
                     ws = self._scratch(f"convpp_{src}_{dst}", (2 * B * conn.w.numel(),), torch.float32, dev)
+                    d.rule_ws = _dptr(ws)
+                elif isinstance(conn, _ConvNdConnection):    # the packed target spikes, when they exceed the kernel's LDS
+                    L = max(int(conn.pp_src.shape[0]), 1)
+                    ws = self._scratch(f"convndpp_{src}_{dst}", (B * conn.out_channels * ((L + 31) // 32),), torch.int32, dev)
                     d.rule_ws = _dptr(ws)
             elif isinstance(conn, Conv2dConnection):         # learning.py:1942-2015, batch 1
                 if B != 1:
@@ -873,7 +897,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if isinstance(conn.norm, torch.Tensor):
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
             d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(conn.norm), 0, None
-        elif conn.norm is not None and isinstance(conn, Conv2dConnection):
+        elif conn.norm is not None and isinstance(conn, (Conv2dConnection, _ConvNdConnection)):
             # Conv2dConnection.normalize (topology.py:824-837) scales every filter to sum `norm`: not a column normalisation, so
             # not snn_net_run's post-loop step -- run() calls the connection's own normalize() (snn_normalize_conv2d) behind it
             if isinstance(conn.norm, torch.Tensor):

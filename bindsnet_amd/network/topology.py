@@ -1,5 +1,6 @@
 """Connections: API mirror of bindsnet/network/topology.py for the connection types on the hot
-path (`Connection`, `MulticompartmentConnection`, `Conv2dConnection`, `LocalConnection`, `LocalConnection1D/2D/3D`).  `compute()` launches the
+path (`Connection`, `MulticompartmentConnection`, `Conv1dConnection`, `Conv2dConnection`, `Conv3dConnection`, `LocalConnection`,
+`LocalConnection1D/2D/3D`).  `compute()` launches the
 matching propagation kernel of libsnnhip; inside Network.run the same kernels are driven from C++.
 """
 import warnings
@@ -235,6 +236,176 @@ class Conv2dConnection(AbstractConnection):
             if isinstance(self.norm, torch.Tensor):
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
             ops.normalize_conv2d(self.w.data, float(self.norm))
+
+
+class _ConvNdConnection(AbstractConnection):
+    """What Conv1dConnection and Conv3dConnection (reference: topology.py:540-683, :847-1025) share.  Weights [Cout, Cin,
+    *kernel], bias `b` zeros(Cout).  `compute` runs snn_prop_convnd_f32 on the device (one kernel for both: a conv1d is the
+    conv3d with D = H = 1), the reference's F.conv1d / F.conv3d on the host.
+
+    PostPre (learning.py:422-455 / :499-559) hands torch.bmm a source operand built by pad + unfold + a raw reshape; that
+    matrix is kept as the int32 buffer `pp_src` [L, Cin*K]: the reference's own expressions (`_pp_unfold`) applied to
+    arange(source.n) + 1, so that 0 marks padding (stored as -1).  It reproduces conv1d's raw view (which mixes channels and
+    positions when Cin > 1) and conv3d's swapped unfold axes without restating them.  When those expressions fail, or give
+    another L than the target's position count (the reference's bmm then fails), the table is empty and PostPre raises."""
+
+    _ndim = 0
+
+    def _init_weights(self, shape, w_dtype, kwargs) -> None:
+        """The reference's draws and clamps (topology.py:611-630 / :950-969), as Conv2dConnection's."""
+        w = kwargs.get("w", None)
+        inf = torch.tensor(np.inf)
+        unbounded = bool((self.wmin == -inf).any() or (self.wmax == inf).any())
+        if w is None:
+            r = torch.rand(*shape)
+            w = torch.clamp(r, self.wmin, self.wmax) if unbounded else (self.wmax - self.wmin) * r + self.wmin
+            w = w.to(dtype=w_dtype)
+        else:
+            if unbounded:
+                w = torch.clamp(w, self.wmin, self.wmax)
+            w = self.cast_dtype_if_needed(w, w_dtype)
+        self.w = Parameter(w, requires_grad=False)
+        self.b = Parameter(kwargs.get("b", torch.zeros(self.out_channels)), requires_grad=False)
+        J = self.in_channels * int(np.prod(self._kernel()))
+        self._pp_error = None
+        try:
+            idx = (torch.arange(self.source.n, dtype=torch.int64) + 1).view(1, *self.source.shape)
+            tab = self._pp_unfold(idx)[0] - 1
+            if tab.shape[0] != int(np.prod(self.target.shape[1:])):
+                raise RuntimeError(f"the unfolded source has {tab.shape[0]} positions, the target "
+                                   f"{int(np.prod(self.target.shape[1:]))}")
+        except RuntimeError as e:
+            self._pp_error = (f"PostPre on this {type(self).__name__} fails in the reference (its torch.bmm operands do not "
+                              f"match: {e})")
+            tab = torch.empty(0, J, dtype=torch.int64)
+        self.register_buffer("pp_src", tab.to(torch.int32).contiguous())
+
+    def _postpre_error(self, rule):
+        """Why the reference's PostPre update fails on this connection, or None."""
+        if isinstance(self, Conv3dConnection) and bool(rule.nu[0] != 0):
+            # learning.py:526-547: source_s is never cast to float, so torch.bmm(target_x, source_s) raises
+            return ("PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference: torch.bmm raises 'expected m1 and m2 "
+                    "to have the same dtype, but got: float != bool' (learning.py:526-551, source_s is never cast to float); "
+                    "use nu[0] == 0 or network.train(False)")
+        return self._pp_error
+        return None
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        B = s.size(0)
+        if not self.w.is_cuda:
+            from . import host_path
+            return host_path._propagate(self, s)
+        out = torch.empty(B, *self.target.shape, device=self.w.device)
+        ops.prop_convnd(self.w.data, s.reshape(B, *self.source.shape).contiguous(), out, bias=self.b.data,
+                        stride=self._stride(), pad=self._padding())
+        return out
+
+    def normalize(self) -> None:
+        """Every [K] filter of the [Cout*Cin, K] view scaled to sum `norm` (topology.py:665-675 / :1004-1017)."""
+        if self.norm is not None:
+            if not self.w.is_cuda:
+                from . import host_path
+                return host_path.normalize_connection(self)
+            if isinstance(self.norm, torch.Tensor):
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+            ops.normalize_conv2d(self.w.data.view(self.w.shape[0], self.w.shape[1], -1, 1), float(self.norm))
+
+
+class Conv1dConnection(_ConvNdConnection):
+    """1-D convolutional synapses, source shape (Cin, N), target (Cout, L) (reference: topology.py:540-683): propagation and
+    PostPre.  Input channels are limited to 16 (the reference's oneDNN accumulation order is characterised up to there)."""
+
+    _ndim = 1
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: int, stride: int = 1, padding: int = 0, dilation: int = 1,
+                 nu=None, reduction=None, weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
+        if dilation != 1:
+            raise NotImplementedError("Dilation is not currently supported for 1-D spiking convolution.")
+        self.kernel_size, self.stride, self.padding, self.dilation = kernel_size, stride, padding, dilation
+        self.in_channels, input_size = source.shape[0], source.shape[1]
+        self.out_channels, output_size = target.shape[0], target.shape[1]
+        conv_size = (input_size - self.kernel_size + 2 * self.padding) / self.stride + 1
+        assert target.shape[0] == self.out_channels and target.shape[1] == int(conv_size), (
+            "Target dimensionality must be (out_channels, ?,(input_size - filter_size + 2 * padding) / stride + 1,")
+        if self.in_channels > 16:
+            raise NotImplementedError("bindsnet_amd: Conv1dConnection with more than 16 input channels is not supported (the "
+                                      "reference's oneDNN accumulation order is only characterised up to 16)")
+        if self.in_channels > 1 and self.kernel_size == 1:
+            raise NotImplementedError("bindsnet_amd: Conv1dConnection with kernel_size 1 and more than one input channel is not "
+                                      "supported (the reference's oneDNN takes a 1x1 kernel whose order depends on the shape)")
+        self._init_weights((self.out_channels, self.in_channels, self.kernel_size), w_dtype, kwargs)
+
+    def _kernel(self):
+        return (self.kernel_size,)
+
+    def _stride(self):
+        return self.stride
+
+    def _padding(self):
+        return self.padding
+
+    def _pp_unfold(self, t: torch.Tensor) -> torch.Tensor:
+        """learning.py:434-438 on t [B, Cin, N]."""
+        t = torch.nn.functional.pad(t, _pair(self.padding))
+        return t.unfold(-1, self.kernel_size, self.stride).reshape(t.shape[0], -1, self.in_channels * self.kernel_size)
+
+
+class Conv3dConnection(_ConvNdConnection):
+    """3-D convolutional synapses, source shape (Cin, D, H, W), target (Cout, OD, OH, OW) (reference: topology.py:847-1025):
+    propagation and PostPre with nu[0] == 0.  One input channel (the reference's oneDNN order at Cin > 1 depends on the
+    shape), isotropic stride and padding.
+
+    Deviation: PostPre with nu[0] != 0 fails in the reference at the first learning step, after that step's neuron update
+    (learning.py:526-551 hands torch.bmm a bool operand).  Here Network.run raises the same RuntimeError before the run
+    changes any state."""
+
+    _ndim = 3
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int, int]],
+                 stride: Union[int, Tuple[int, int, int]] = 1, padding: Union[int, Tuple[int, int, int]] = 0,
+                 dilation: Union[int, Tuple[int, int, int]] = 1, nu=None, reduction=None, weight_decay: float = 0.0,
+                 w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
+        if dilation != 1 and dilation != (1, 1, 1):
+            raise NotImplementedError("Dilation is not currently supported for 3-D spiking convolution.")
+        self.kernel_size, self.stride = _triple(kernel_size), _triple(stride)
+        self.padding, self.dilation = _triple(padding), _triple(dilation)
+        self.in_channels, idepth, iheight, iwidth = source.shape[0], source.shape[1], source.shape[2], source.shape[3]
+        self.out_channels = target.shape[0]
+        out = [int((n - k + 2 * p) / s + 1) for n, k, p, s in zip((idepth, iheight, iwidth), self.kernel_size, self.padding,
+                                                                  self.stride)]
+        assert target.shape[0] == self.out_channels and list(target.shape[1:4]) == out, (
+            "Target dimensionality must be (out_channels, ?,"
+            "(input_depth - filter_depth + 2 * padding_depth) / stride_depth + 1,"
+            "(input_height - filter_height + 2 * padding_height) / stride_height + 1,"
+            "(input_width - filter_width + 2 * padding_width) / stride_width + 1")
+        if self.in_channels != 1:
+            raise NotImplementedError("bindsnet_amd: Conv3dConnection supports one input channel (the reference's oneDNN "
+                                      "accumulation order at Cin > 1 depends on the shape)")
+        if len(set(self.stride)) != 1 or len(set(self.padding)) != 1:
+            raise NotImplementedError("bindsnet_amd: Conv3dConnection supports isotropic stride and padding only")
+        if self.padding[0] and any(n == 1 and k == 1 for n, k in zip((idepth, iheight), self.kernel_size[:2])):
+            raise NotImplementedError("bindsnet_amd: Conv3dConnection with padding and a depth or height of 1 with a kernel of 1 "
+                                      "is not supported (the kernel's C ABI reads such an axis as unpadded)")
+        self._init_weights((self.out_channels, self.in_channels, *self.kernel_size), w_dtype, kwargs)
+
+    def _kernel(self):
+        return self.kernel_size
+
+    def _stride(self):
+        return self.stride[0]
+
+    def _padding(self):
+        return self.padding[0]
+
+    def _pp_unfold(self, t: torch.Tensor) -> torch.Tensor:
+        """learning.py:523-534 on t [B, Cin, D, H, W] (D unfolded with the kernel's width, W with its depth, as there)."""
+        kd, kh, kw = self.kernel_size
+        p, s = self.padding, self.stride
+        t = torch.nn.functional.pad(t, (p[0], p[0], p[1], p[1], p[2], p[2]))
+        return t.unfold(-3, kw, s[0]).unfold(-3, kh, s[1]).unfold(-3, kd, s[2]).reshape(t.shape[0], -1,
+                                                                                           self.in_channels * kw * kh * kd)
 
 
 class _LocalConnectionND(AbstractConnection):

@@ -110,6 +110,47 @@ def normalize_local(W, norm):
     check(lib().snn_normalize_conv2d(_ptr(W, F32), W.shape[0] * W.shape[1], W.shape[2], float(norm), _stream()), "normalize_local")
 
 
+def prop_convnd(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
+    """f6: Conv1dConnection / Conv3dConnection.compute (F.conv1d / F.conv3d on 0/1 spikes); W [Cout, Cin, K] with s [B, Cin, N],
+    or W [Cout, Cin, KD, KH, KW] with s [B, Cin, D, H, W]; out [B, Cout, *positions]."""
+    B, Cin = s.shape[0], s.shape[1]
+    Cout = W.shape[0]
+    if W.dim() == 3 and s.dim() == 3:
+        (D, H, Wd), (KD, KH, KW) = (1, 1, s.shape[2]), (1, 1, W.shape[2])
+    elif W.dim() == 5 and s.dim() == 5:
+        (D, H, Wd), (KD, KH, KW) = s.shape[2:], W.shape[2:]
+    else:
+        raise ValueError("prop_convnd: W [Cout, Cin, K] with s [B, Cin, N], or W [Cout, Cin, KD, KH, KW] with s [B, Cin, D, H, W]")
+    if W.shape[1] != Cin:
+        raise ValueError("prop_convnd: W and s disagree on the input channels")
+    pads = (0 if (D, KD) == (1, 1) else pad, 0 if (H, KH) == (1, 1) else pad, pad)   # (a unit axis is not padded: snnhip.h)
+    P = 1
+    for n, k, q in zip((D, H, Wd), (KD, KH, KW), pads):
+        P *= (n + 2 * q - k) // stride + 1
+    if out.numel() != B * Cout * P:
+        raise ValueError("prop_convnd: out does not hold [B, Cout, *positions]")
+    check(lib().snn_prop_convnd_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(s, "spike"), _ptr(out, F32), B, Cin, D, H, Wd, Cout,
+                                    KD, KH, KW, int(stride), int(pad), int(accumulate), _stream()), "prop_convnd")
+    return out
+
+
+def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, wmin=None, wmax=None, ws=None):
+    """f6: PostPre on Conv1dConnection / Conv3dConnection weights [Cout, Cin, *kernel] (learning.py:422-455 / :499-559);
+    pp_src int32 [L, Cin*K] (the connection's gather table), s_src / x_src [B, n_src], s_tgt / x_tgt [B, Cout*L]."""
+    B = s_src.shape[0]
+    L, J = pp_src.shape
+    Cout = W.shape[0]
+    n_src = s_src.numel() // B
+    if W.numel() != Cout * J or x_src.numel() != B * n_src or s_tgt.numel() != B * Cout * L or x_tgt.numel() != s_tgt.numel():
+        raise ValueError("convnd_postpre: operand shapes do not match the gather table")
+    if ws is None:
+        ws = torch.empty(B * Cout * ((L + 31) // 32), dtype=torch.int32, device=W.device)
+    check(lib().snn_convnd_postpre(_ptr(W, F32), _ptr(pp_src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32),
+                                   _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Cout, L, J, n_src, float(nu0), float(nu1), float(decay),
+                                   int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None),
+                                   0.0 if wmax is None else wmax, _ptr(ws, torch.int32), _stream()), "convnd_postpre")
+
+
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None):
     check(lib().snn_input_step(_ptr(s, "spike"), _ptr(x, F32, True), s.numel(), trace_decay, trace_scale,
                                int(additive), _ptr(raster, "spike", True), _stream()), "input_step")

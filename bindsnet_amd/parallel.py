@@ -75,11 +75,13 @@ def _shard_buffers(network, tensors):
 
 
 def _reject_local(network, mode: str) -> None:
-    """None of the multi-device modes handles LocalConnection1D / 2D / 3D (their weights are not [source.n, target.n]
-    matrices): such a graph raises instead of being routed through a mode built for other layouts."""
-    from .network.topology import LocalConnection1D, LocalConnection2D, LocalConnection3D
+    """None of the multi-device modes handles LocalConnection1D / 2D / 3D or Conv1dConnection / Conv3dConnection (their
+    weights are not [source.n, target.n] matrices): such a graph raises instead of being routed through a mode built for other
+    layouts."""
+    from .network.topology import (Conv1dConnection, Conv3dConnection, LocalConnection1D, LocalConnection2D,
+                                   LocalConnection3D)
     for key, conn in network.connections.items():
-        if isinstance(conn, (LocalConnection1D, LocalConnection2D, LocalConnection3D)):
+        if isinstance(conn, (LocalConnection1D, LocalConnection2D, LocalConnection3D, Conv1dConnection, Conv3dConnection)):
             raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} is not supported by the multi-device modes; "
                                       "run the network on one device")
 

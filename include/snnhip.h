@@ -108,6 +108,31 @@ int snn_local_postpre(float *W, const int *src, const uint8_t *s_src, const floa
                       float nu0, float nu1, float decay, int has_min, float wmin, int has_max, float wmax,
                       snn_stream_t stream);
 
+/* ---- f6: Conv1dConnection / Conv3dConnection.compute -----------------------------------------
+ * bindsnet/network/topology.py:640-656 (F.conv1d), :979-995 (F.conv3d).  s [B, Cin, D, H, Wd] u8 0/1 spikes, W [Cout, Cin,
+ * KD, KH, KW], bias nullable [Cout], out [B, Cout, OD, OH, OW].  Isotropic stride and padding, except that an axis of
+ * extent 1 with a kernel of 1 is not padded: a conv1d is D = H = KD = KH = 1.  Dilation 1, Cin <= 16.  Order contract (probed on the reference's torch: conv1d at Cin 1..16, conv3d at Cin 1):
+ * per output ONE sequential f32 chain over the taps in ascending (kd, kh, kw), input channel innermost, then + bias;
+ * out (+)= that as in snn_prop_conv2d_f32.  Event-driven: a sample's spikes are packed into a channels-last bitstream and
+ * only the set bits of each tap row are visited (a silent tap adds +-0).  Filters are staged in LDS where Cin*K <= 12288,
+ * else read from L2; the bitstream is staged where n_src <= 131072, else packed where it is read.  (ABI 8, additive)   */
+int snn_prop_convnd_f32(const float *W, const float *bias, const uint8_t *s, float *out, int B, int Cin, int D, int H,
+                        int Wd, int Cout, int KD, int KH, int KW, int stride, int pad, int accumulate,
+                        snn_stream_t stream);
+
+/* ---- f6: PostPre on a Conv1dConnection / Conv3dConnection -------------------------------------
+ * bindsnet/learning/learning.py:422-455 (conv1d), :499-559 (conv3d), + :87-104.  pp_src int32 [L, J] (J = Cin*K) is the
+ * matrix the reference hands to bmm as the source operand (pad + unfold + raw reshape, applied to arange(n_src) + 1),
+ * flat source index or -1 for padding; W is its flat [Cout, J] view.  s_src / x_src [B, n_src], s_tgt / x_tgt [B, Cout, L].
+ * Order contract: per sample pre = sum_l x_tgt[co,l] * s_src[pp_src[l,j]], post = sum_l s_tgt[co,l] * x_src[pp_src[l,j]],
+ * l ascending (torch.bmm at these shapes; every product exact); batch sums in ATen's sum(dim=0) order (one term at B = 1);
+ * W -= nu0*pre (nu0 != 0), W += nu1*post (nu1 != 0), W *= decay, clamp.  The post term walks only the spiking target
+ * positions.  ws: uint32 [B*Cout*ceil(L/32)] scratch for the packed target spikes, needed (nu1 != 0) only when they exceed
+ * 32 KiB of LDS; nullable otherwise.  Every weight is read and written once per call.  (ABI 8, additive)               */
+int snn_convnd_postpre(float *W, const int *pp_src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                       const float *x_tgt, int B, int Cout, int L, int J, int n_src, float nu0, float nu1, float decay,
+                       int has_min, float wmin, int has_max, float wmax, uint32_t *ws, snn_stream_t stream);
+
 /* ---- a2: Input.forward + Nodes.forward trace ------------------------------------------------
  * bindsnet/network/nodes.py:211-221, :96-107.  s is the caller's input slice (aliased, never
  * copied); x (nullable) is the trace, updated in place; raster_out (nullable) receives s.   */
@@ -308,7 +333,9 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2 };
  * snn_conn_desc were added without changing SNN_ABI_VERSION: the change is purely additive.  A library built before it is
  * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
  * snn_prop_local_f32 / snn_local_postpre; tests/test_abi.py compares sizeof(snn_conn_desc) with the ctypes mirror.  */
-enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3 };
+/* SNN_CONN_CONVND (Conv1dConnection / Conv3dConnection, rules NONE or POSTPRE, generic plan only) and the conv_* fields
+ * after them were added the same way, again without changing SNN_ABI_VERSION.  */
+enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5 };
 
@@ -366,6 +393,13 @@ typedef struct {
      * [local_kernel_prod] row scaled to sum `norm` (snn_normalize_conv2d, topology.py:1601 / :1748-1759 / :1898). */
     const int *local_src;
     int local_F, local_conv_prod, local_kernel_prod, local_n_src;
+    /* CONVND: w is [cout, cin, conv_kd, kh, kw]; the source is [cin, conv_d, h, wd] (conv1d: conv_nd 1, conv_d = h = conv_kd
+     * = kh = 1), stride / pad isotropic.  conv_pp_src: the int32 [conv_pp_rows, cin*conv_kd*kh*kw] PostPre gather table of
+     * snn_convnd_postpre (conv_pp_rows == the target's positions); rule_ws its mask scratch.  has_norm is 0: the caller
+     * normalises after the run, as for CONV2D. */
+    int conv_nd, conv_d, conv_kd;
+    const int *conv_pp_src;
+    int conv_pp_rows;
 } snn_conn_desc;
 
 typedef struct {
