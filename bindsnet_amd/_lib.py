@@ -196,6 +196,11 @@ def check(rc: int, what: str = ""):
         raise SnnError(f"libsnnhip {what}: {msg} (code {rc})")
 
 
+def dptr(t):
+    """A tensor's address as a descriptor field (None: a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def resident_kernel_name(form: int) -> str:
     return {3: "k_dc2015_async [lean form, third generation: compute workgroups + arbiter + raster writers + producer workgroups (the digest / X-trace "
                "pre-passes and the input monitor's copy run inside the launch)]", 2: "k_dc2015_spec [lean form, second generation]",

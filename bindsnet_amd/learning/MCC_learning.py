@@ -7,10 +7,13 @@ from typing import Optional, Sequence, Union
 import torch
 
 from .. import _lib
+from . import _descriptor
 
 
 class MCC_LearningRule(_lib.Touching):
     """Reference: MCC_learning.py:16-118 (nu parsing, reduction default, decay, clamp range)."""
+
+    _rule_code = None                  # snn_conn_desc.rule (include/snnhip.h)
 
     def __init__(self, connection, feature_value, range: Optional[Union[list, tuple]] = None,
                  nu: Optional[Union[float, Sequence[float]]] = None, reduction: Optional[callable] = None,
@@ -49,6 +52,19 @@ class MCC_LearningRule(_lib.Touching):
             return None if v in (float("inf"), float("-inf")) else v
         return one(self.min), one(self.max)
 
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        """Write the rule's fields of the connection's snn_conn_desc `d` for a Network.run at batch size B.  A rule that
+        does not say how is refused, and so is every rule but NoOp on a manual_update connection."""
+        raise NotImplementedError(f"bindsnet_amd: MCC rule {type(self).__name__} is not supported")
+
+    def _describe_batched(self, d, conn, B) -> None:
+        """What PostPre and MSTDP share: the refusals, then bounds, decay and learning rates."""
+        if conn.manual_update:
+            MCC_LearningRule._describe(self, d, conn, B, None, None, None)
+        if self.reduction is torch.squeeze and B != 1:
+            raise RuntimeError("reduction=torch.squeeze requires batch size 1")
+        _descriptor.fill_update(d, self, self.decay)
+
     def update(self, **kwargs) -> None:
         raise NotImplementedError
 
@@ -57,6 +73,8 @@ class MCC_LearningRule(_lib.Touching):
 
 
 class NoOp(MCC_LearningRule):
+    _rule_code = _lib.RULE_NONE
+
     def __init__(self, **args) -> None:
         pass
 
@@ -86,6 +104,10 @@ class PostPre(MCC_LearningRule):
             raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         if self.reduction not in (torch.sum, torch.squeeze):
             raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        self._describe_batched(d, conn, B)
+        d.rule, d.use_dt = _lib.RULE_POSTPRE, 1
 
     def update(self, **kwargs) -> None:
         """One step of MCC_learning.py:224-302 through the C ABI (used when a connection is
@@ -133,20 +155,21 @@ class MSTDP(MCC_LearningRule):
         dt = self.connection.dt
         return float(torch.exp(-dt / self.tc_plus)), float(torch.exp(-dt / self.tc_minus))   # MCC_learning.py:538,540
 
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        self._describe_batched(d, conn, B)
+        _descriptor.fill_mstdp(d, self, kwargs, dev, keep)
+
     def update(self, **kwargs) -> None:
         from .. import ops
         B = self.source.batch_size
         if self.reduction is torch.squeeze and B != 1:
             raise RuntimeError("reduction=torch.squeeze requires batch size 1 (as in the reference)")
         self._ensure_state()
-        reward = kwargs["reward"]
-        rvec = None
-        if isinstance(reward, torch.Tensor) and reward.numel() > 1:
-            rvec, reward = reward.to(self.feature_value.device, torch.float32).reshape(-1).contiguous(), 0.0
+        reward, rvec = _descriptor.split_reward(kwargs["reward"], self.feature_value.device)
         dp, dm = self._decays()
         lo, hi = self._bounds()
         ops.mstdp_step(self.feature_value.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
-                       self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), float(reward),
+                       self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
                        float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
                        wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec)
 
@@ -197,6 +220,13 @@ class MSTDPET(MCC_LearningRule):
         """Dense view of the point eligibility (MCC_learning.py:724-726), for inspection only."""
         self._ensure_state()
         return torch.outer(self.p_plus, self._s_tgt_prev.float()) + torch.outer(self._s_src_prev.float(), self.p_minus)
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        if conn.manual_update:
+            super()._describe(d, conn, B, dev, keep, kwargs)
+        if B != 1:
+            raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
+        _descriptor.fill_mstdpet(d, self, self.decay, kwargs)
 
     def update(self, **kwargs) -> None:
         from .. import ops

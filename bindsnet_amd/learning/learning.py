@@ -10,17 +10,19 @@ import torch
 from ..network.nodes import _f
 
 from .. import _lib
+from . import _descriptor
 
 
 class LearningRule(_lib.Touching):
-    """Reference: learning.py:25-104."""
+    """Reference: learning.py:25-104.  Which rules a connection family takes is the family's `_rules` (network/topology.py)."""
+
+    _rule_code = None                       # snn_conn_desc.rule (include/snnhip.h)
 
     def __init__(self, connection, nu: Optional[Union[float, Sequence[float], Sequence[torch.Tensor]]] = None,
                  reduction: Optional[callable] = None, weight_decay: float = 0.0, **kwargs) -> None:
-        from ..network.topology import _ConvNdConnection, _LocalConnectionND
-        if isinstance(connection, (_LocalConnectionND, _ConvNdConnection)) and not isinstance(self, (PostPre, NoOp)):
+        if getattr(connection, "_rules_only", None) and not _descriptor.accepts(connection, self):
             raise NotImplementedError(f"bindsnet_amd: {type(self).__name__} on {type(connection).__name__} is not supported "
-                                      "(PostPre is)")
+                                      f"({connection._rules_only})")
         self.connection = connection
         self.source, self.target = connection.source, connection.target
         self.wmin, self.wmax = connection.wmin, connection.wmax
@@ -59,6 +61,19 @@ class LearningRule(_lib.Touching):
         elif self.reduction is not torch.sum:
             raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
 
+    def _require_accepted(self) -> None:
+        if not _descriptor.accepts(self.connection, self):
+            raise NotImplementedError("This learning rule is not supported for this Connection type.")
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        """Write the rule's fields of the connection's snn_conn_desc `d` for a Network.run at batch size B: here what
+        PostPre, Hebbian and WeightDependentPostPre need (use_dt stays 0), and what MSTDP starts with."""
+        if self._rule_code is None:
+            raise NotImplementedError(f"bindsnet_amd: rule {type(self).__name__} is not supported")
+        self._check_reduction()
+        _descriptor.fill_update(d, self, self.weight_decay)
+        d.rule = self._rule_code
+
     def update(self, **kwargs) -> None:
         raise NotImplementedError
 
@@ -67,53 +82,26 @@ class LearningRule(_lib.Touching):
 
 
 class NoOp(LearningRule):
+    _rule_code = _lib.RULE_NONE
+
     def update(self, **kwargs) -> None:
         if self.weight_decay != 1.0:
             raise NotImplementedError("bindsnet_amd: weight_decay without a learning rule is not supported")
 
 
 class PostPre(LearningRule):
-    """Reference: learning.py:149-206, _connection_update :390-420."""
+    """Reference: learning.py:149-206, _connection_update :390-420 (the device op is the connection family's `_postpre`)."""
+
+    _rule_code = _lib.RULE_POSTPRE
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
         assert self.source.traces and self.target.traces, "Both pre- and post-synaptic nodes must record spike traces."
-        from ..network.topology import Connection, Conv2dConnection, LocalConnection, _ConvNdConnection, _LocalConnectionND
-        if not isinstance(connection, (Connection, LocalConnection, Conv2dConnection, _LocalConnectionND, _ConvNdConnection)):
-            raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        self._require_accepted()
 
     def update(self, **kwargs) -> None:
-        from .. import ops
-        from ..network.topology import Conv2dConnection, _ConvNdConnection, _LocalConnectionND
         self._check_reduction()
-        B = self.source.batch_size
-        lo, hi = self._bounds()
-        if isinstance(self.connection, _ConvNdConnection):          # learning.py:422-455 / :499-559
-            c = self.connection
-            err = c._postpre_error(self)
-            if err is not None:
-                raise RuntimeError(err)
-            ops.convnd_postpre(c.w.data, c.pp_src, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
-                               self.target.s.reshape(B, -1).contiguous(), self.target.x.reshape(B, -1), float(self.nu[0]),
-                               float(self.nu[1]), decay=float(self.weight_decay), wmin=lo, wmax=hi)
-            return
-        if isinstance(self.connection, _LocalConnectionND):        # learning.py:208-389
-            c = self.connection
-            ops.local_postpre(c.w.data, c.src, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
-                              self.target.s.reshape(B, -1).contiguous(), self.target.x.reshape(B, -1), float(self.nu[0]),
-                              float(self.nu[1]), c.n_filters, decay=float(self.weight_decay), wmin=lo, wmax=hi)
-            return
-        if isinstance(self.connection, Conv2dConnection):         # learning.py:457-497
-            c = self.connection
-            ops.conv2d_postpre(c.w.data, self.source.s.reshape(B, *self.source.shape).contiguous(),
-                               self.source.x.reshape(B, *self.source.shape), self.target.s.reshape(B, *self.target.shape),
-                               self.target.x.reshape(B, *self.target.shape), float(self.nu[0]), float(self.nu[1]),
-                               stride=c.stride[0], pad=c.padding[0], decay=float(self.weight_decay), wmin=lo, wmax=hi)
-            return
-        ops.stdp_postpre(self.connection.w.data, self.source.s.reshape(B, -1).contiguous(),
-                         self.source.x.reshape(B, -1), self.target.s.reshape(B, -1), self.target.x.reshape(B, -1),
-                         float(self.nu[0]), float(self.nu[1]), use_dt=False, decay=float(self.weight_decay),
-                         wmin=lo, wmax=hi)
+        self.connection._postpre(self, self.source.batch_size, *self._bounds())
 
 
 class MSTDP(LearningRule):
@@ -126,12 +114,12 @@ class MSTDP(LearningRule):
     [Cout, Cin, KH, KW] state, `p_minus` is [Cout, OH*OW] and `p_plus` is kept in INPUT space [Cin, H, W] -- the
     reference's attribute is its im2col (`bindsnet.utils.im2col_indices(rule.p_plus[None], ...)` gives that layout)."""
 
+    _rule_code = _lib.RULE_MSTDP
+
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
-        from ..network.topology import Connection, Conv2dConnection, LocalConnection
-        if not isinstance(connection, (Connection, LocalConnection, Conv2dConnection)):
-            raise NotImplementedError("This learning rule is not supported for this Connection type.")
-        self._conv = isinstance(connection, Conv2dConnection)
+        self._require_accepted()
+        self._conv = connection._kind == _lib.CONN_CONV2D
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))
         self.tc_minus = torch.tensor(kwargs.get("tc_minus", 20.0))
 
@@ -154,21 +142,35 @@ class MSTDP(LearningRule):
         dt = torch.tensor(self.connection.dt)
         return float(torch.exp(-dt / self.tc_plus)), float(torch.exp(-dt / self.tc_minus))   # learning.py:1564,1566
 
-    def _conv_update(self, **kwargs) -> None:
-        from .. import ops
-        if self.source.batch_size != 1:
+    def _conv_reward(self, B, kwargs) -> float:
+        if B != 1:
             raise NotImplementedError("MSTDP on a Conv2dConnection is defined for batch size 1 (learning.py:2013)")
-        reward = kwargs["reward"]
+        reward = _descriptor.reward(kwargs)
         if isinstance(reward, torch.Tensor):
             if reward.numel() != 1:
                 raise NotImplementedError("bindsnet_amd: MSTDP on a Conv2dConnection takes a scalar reward")
             reward = reward.item()
+        return float(reward)
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        super()._describe(d, conn, B, dev, keep, kwargs)
+        if not self._conv:
+            return _descriptor.fill_mstdp(d, self, kwargs, dev, keep)
+        d.reward = self._conv_reward(B, kwargs)                                    # learning.py:1942-2015, batch 1
+        d.a_plus, d.a_minus = _descriptor.a_plus_minus(kwargs)
+        self._ensure_state()
+        d.decay_plus, d.decay_minus = self._decays()
+        d.p_plus, d.p_minus, d.e_trace = _lib.dptr(self.p_plus), _lib.dptr(self.p_minus), _lib.dptr(self._elig)
+
+    def _conv_update(self, **kwargs) -> None:
+        from .. import ops
+        reward = self._conv_reward(self.source.batch_size, kwargs)
         self._ensure_state()
         dp, dm = self._decays()
         lo, hi = self._bounds()
         c = self.connection
         ops.conv2d_mstdp_step(c.w.data, self._elig, self.p_plus, self.p_minus, self.source.s.contiguous(), self.target.s.contiguous(),
-                              float(reward), float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)),
+                              reward, float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)),
                               dp, dm, stride=c.stride[0], pad=c.padding[0], wdecay=float(self.weight_decay), wmin=lo, wmax=hi)
 
     def update(self, **kwargs) -> None:
@@ -178,14 +180,11 @@ class MSTDP(LearningRule):
         self._check_reduction()
         self._ensure_state()
         B = self.source.batch_size
-        reward = kwargs["reward"]
-        rvec = None
-        if isinstance(reward, torch.Tensor) and reward.numel() > 1:
-            rvec, reward = reward.to(self.connection.w.device, torch.float32).reshape(-1).contiguous(), 0.0
+        reward, rvec = _descriptor.split_reward(kwargs["reward"], self.connection.w.device)
         dp, dm = self._decays()
         lo, hi = self._bounds()
         ops.mstdp_step(self.connection.w.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
-                       self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), float(reward),
+                       self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
                        float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
                        wdecay=float(self.weight_decay), wmin=lo, wmax=hi, reward_vec=rvec)
 
@@ -205,9 +204,7 @@ class _OuterProductRule(LearningRule):
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
-        from ..network.topology import Connection, LocalConnection
-        if not isinstance(connection, (Connection, LocalConnection)):
-            raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        self._require_accepted()
 
     def update(self, **kwargs) -> None:
         from .. import ops
@@ -221,6 +218,7 @@ class _OuterProductRule(LearningRule):
 
 class Hebbian(_OuterProductRule):
     """Both the pre- and the post-synaptic term potentiate (reference: learning.py:1052-1135)."""
+    _rule_code = _lib.RULE_HEBBIAN
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
@@ -229,7 +227,7 @@ class Hebbian(_OuterProductRule):
 
 class WeightDependentPostPre(_OuterProductRule):
     """PostPre whose depression scales with (w - wmin) and potentiation with (wmax - w) (reference: learning.py:562-653)."""
-    _weight_dependent = True
+    _rule_code, _weight_dependent = _lib.RULE_WDPOSTPRE, True
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
@@ -245,11 +243,11 @@ class MSTDPET(LearningRule):
     """Reward-modulated STDP with an eligibility trace (reference: learning.py:2124-2248); like the reference's dense
     form it is defined for batch size 1.  `eligibility_trace` is the rule's dense [Nin, N] state on the device."""
 
+    _rule_code = _lib.RULE_MSTDPET
+
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
-        from ..network.topology import Connection, LocalConnection
-        if not isinstance(connection, (Connection, LocalConnection)):
-            raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        self._require_accepted()
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))
         self.tc_minus = torch.tensor(kwargs.get("tc_minus", 20.0))
         self.tc_e_trace = torch.tensor(kwargs.get("tc_e_trace", 25.0))
@@ -272,6 +270,11 @@ class MSTDPET(LearningRule):
     def eligibility(self) -> torch.Tensor:
         self._ensure_state()
         return torch.outer(self.p_plus, self._s_tgt_prev.float()) + torch.outer(self._s_src_prev.float(), self.p_minus)
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        if B != 1:
+            raise NotImplementedError("MSTDPET on a dense Connection is defined for batch size 1 (learning.py:2211-2212)")
+        _descriptor.fill_mstdpet(d, self, self.weight_decay, kwargs)
 
     def update(self, **kwargs) -> None:
         from .. import ops

@@ -19,6 +19,8 @@ from typing import Dict
 import torch
 import torch.nn.functional as F
 
+from .. import _lib
+
 
 def aten_sum_leaves_serial_order(outer: int, n_reduced: int, n_cols: int, threads: int) -> bool:
     """True when torch.sum over the middle dimension of a contiguous float [outer, n_reduced, n_cols] tensor (outer = 1: also
@@ -159,30 +161,27 @@ def _step_dc(layer, x) -> None:
     _trace(layer, layer.s)
 
 
-def _propagate(conn, s):
-    from .topology import Connection, Conv2dConnection, LocalConnection, MulticompartmentConnection
+def _propagate_mcc(conn, s):
+    """MulticompartmentConnection.compute with one Weight (topology.py:437-479, topology_features.py:633-645)."""
     B = s.shape[0]
-    if isinstance(conn, MulticompartmentConnection):
-        value = conn._weight().value
-        spikes = s.reshape(B, conn.source.n, 1).repeat(1, 1, conn.target.n)
-        return _sum(value * spikes, 1).view(B, *conn.target.shape)
-    if isinstance(conn, Conv2dConnection):
-        return F.conv2d(s.float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding, dilation=conn.dilation)
-    from .topology import Conv1dConnection, Conv3dConnection, _LocalConnectionND
-    if isinstance(conn, Conv1dConnection):                     # topology.py:640-656
-        return F.conv1d(s.reshape(B, *conn.source.shape).float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding,
-                        dilation=conn.dilation)
-    if isinstance(conn, Conv3dConnection):                     # topology.py:979-995
-        return F.conv3d(s.reshape(B, *conn.source.shape).float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding,
-                        dilation=conn.dilation)
-    if isinstance(conn, _LocalConnectionND):
-        return _propagate_local(conn, s)
-    if isinstance(conn, (Connection, LocalConnection)):
-        post = s.reshape(B, -1).float() @ conn.w.view(conn.source.n, conn.target.n)
-        if getattr(conn, "b", None) is not None:
-            post = post + conn.b
-        return post.view(B, *conn.target.shape)
-    raise NotImplementedError(f"bindsnet_amd host path: connection type {type(conn).__name__}")
+    spikes = s.reshape(B, conn.source.n, 1).repeat(1, 1, conn.target.n)
+    return _sum(conn._weight().value * spikes, 1).view(B, *conn.target.shape)
+
+
+def _propagate_conv(conn, s):
+    """Conv1d / Conv2d / Conv3dConnection.compute: F.conv1d / conv2d / conv3d (topology.py:640-656, :799-815, :979-995)."""
+    conv = (F.conv1d, F.conv2d, F.conv3d)[conn._ndim - 1]
+    return conv(s.reshape(s.shape[0], *conn.source.shape).float(), conn.w, conn.b, stride=conn.stride, padding=conn.padding,
+                dilation=conn.dilation)
+
+
+def _propagate_dense(conn, s):
+    """Connection / LocalConnection.compute (topology.py:332-346, :1440-1453)."""
+    B = s.shape[0]
+    post = s.reshape(B, -1).float() @ conn.w.view(conn.source.n, conn.target.n)
+    if getattr(conn, "b", None) is not None:
+        post = post + conn.b
+    return post.view(B, *conn.target.shape)
 
 
 def _propagate_local(conn, s):
@@ -196,17 +195,21 @@ def _propagate_local(conn, s):
 def _update_local(conn, rule) -> None:
     """PostPre on LocalConnection1D / 2D / 3D, the reference's expressions (learning.py:208-389 + :87-104)."""
     B, R, J = conn.source.batch_size, conn.n_filters * conn.conv_prod, conn.in_channels * conn.kernel_prod
-    W = conn.w.data
     eye = torch.eye(R)
 
     def unfolded(t):
         u = conn._unfold(t.reshape(B, *conn.source.shape)).reshape(B, conn.conv_prod, J)
         return u.repeat(1, conn.n_filters, 1)
 
-    target_x = conn.target.x.reshape(B, R, 1) * eye
-    target_s = conn.target.s.type(torch.float).reshape(B, R, 1) * eye
+    _postpre_unfolded(conn, rule, conn.target.x.reshape(B, R, 1) * eye, conn.target.s.float().reshape(B, R, 1) * eye, unfolded)
+
+
+def _postpre_unfolded(conn, rule, target_x, target_s, unfolded) -> None:
+    """What the two functions around this one share: one bmm per term against the unfolded source spikes / traces, reduced
+    over the batch; then learning.py:87-104 as these families have it (no decay at factor 0, clamp to the connection's bounds)."""
+    W = conn.w.data
     if rule.nu[0].any():
-        pre = _reduce(rule, torch.bmm(target_x, unfolded(conn.source.s.type(torch.float))))
+        pre = _reduce(rule, torch.bmm(target_x, unfolded(conn.source.s.float())))
         W -= rule.nu[0] * pre.view(W.size())
     if rule.nu[1].any():
         post = _reduce(rule, torch.bmm(target_s, unfolded(conn.source.x)))
@@ -225,21 +228,8 @@ def _update_convnd(conn, rule) -> None:
     if err is not None:
         raise RuntimeError(err)
     B, Cout = conn.source.batch_size, conn.out_channels
-    W = conn.w.data
-    shape = (B, *conn.source.shape)
-    target_x = conn.target.x.view(B, Cout, -1)
-    target_s = conn.target.s.view(B, Cout, -1).float()
-    if rule.nu[0].any():
-        pre = _reduce(rule, torch.bmm(target_x, conn._pp_unfold(conn.source.s.reshape(shape).float())))
-        W -= rule.nu[0] * pre.view(W.size())
-    if rule.nu[1].any():
-        post = _reduce(rule, torch.bmm(target_s, conn._pp_unfold(conn.source.x.reshape(shape))))
-        W += rule.nu[1] * post.view(W.size())
-    if rule.weight_decay:
-        W *= rule.weight_decay
-    lo, hi = rule._bounds()
-    if lo is not None or hi is not None:
-        W.clamp_(conn.wmin, conn.wmax)
+    _postpre_unfolded(conn, rule, conn.target.x.view(B, Cout, -1), conn.target.s.view(B, Cout, -1).float(),
+                      lambda t: conn._pp_unfold(t.reshape(B, *conn.source.shape)))
 
 
 def _reduce(rule, t):
@@ -259,7 +249,11 @@ def _mstdp(rule, W, src_s, tgt_s, kwargs) -> None:
     if isinstance(reward, torch.Tensor) and reward.numel() > 1:
         reward = reward.view(-1, 1, 1).float()
     W += float(rule.nu[0]) * _reduce(rule, reward * elig)
-    dp, dm = rule._decays()
+    _advance_p(rule, *rule._decays(), src_s, tgt_s, kwargs)
+
+
+def _advance_p(rule, dp, dm, src_s, tgt_s, kwargs) -> None:
+    """P+ / P- decay and take this step's spikes, which become the previous step's (learning.py:1560-1570 / :2236-2246)."""
     rule.p_plus *= dp
     rule.p_plus += torch.tensor(kwargs.get("a_plus", 1.0)) * src_s
     rule.p_minus *= dm
@@ -277,11 +271,7 @@ def _mstdpet(rule, W, dt, src_s, tgt_s, kwargs) -> None:
     rule.eligibility_trace *= de
     rule.eligibility_trace += rule.eligibility / rule.tc_e_trace
     W += rule.nu[0] * dt * kwargs["reward"] * rule.eligibility_trace
-    rule.p_plus *= dp
-    rule.p_plus += torch.tensor(kwargs.get("a_plus", 1.0)) * src_s
-    rule.p_minus *= dm
-    rule.p_minus += torch.tensor(kwargs.get("a_minus", -1.0)) * tgt_s
-    rule._s_src_prev, rule._s_tgt_prev = src_s.to(torch.uint8), tgt_s.to(torch.uint8)
+    _advance_p(rule, dp, dm, src_s, tgt_s, kwargs)
 
 
 def _conv_postpre(conn, rule) -> None:
@@ -331,10 +321,7 @@ def _postpre_mcc(rule, W, s_src, x_src, s_tgt, x_tgt, dt) -> None:
     if nu1:
         post = torch.bmm(x_src.unsqueeze(2), s_tgt.unsqueeze(1).float() * nu1)
         W += _reduce(rule, post) * dt
-    W *= float(rule.decay)
-    lo, hi = rule._bounds()
-    if lo is not None or hi is not None:
-        W.clamp_(lo, hi)
+    _decay_clamp(rule, W, rule.decay)
 
 
 def _update_mcc(conn, dt, kwargs) -> None:
@@ -357,39 +344,54 @@ def _update_mcc(conn, dt, kwargs) -> None:
         _mstdpet(rule, W, dt, conn.source.s.view(-1).float(), conn.target.s.view(-1).float(), kwargs)
     else:
         raise NotImplementedError(f"bindsnet_amd host path: MCC rule {type(rule).__name__} (supported: PostPre, MSTDP, MSTDPET)")
-    W *= float(rule.decay)                               # MCC_learning.py:86-110
+    _decay_clamp(rule, W, rule.decay)
+
+
+def _decay_clamp(rule, W, factor) -> None:
+    """learning.py:87-104 / MCC_learning.py:86-110: what a rule's update ends with (dense rules keep the factor in
+    `weight_decay`, MCC rules in `decay`)."""
+    W *= float(factor)
     lo, hi = rule._bounds()
     if lo is not None or hi is not None:
         W.clamp_(lo, hi)
 
 
-def _update_dense(conn, kwargs, mask) -> None:
+def _update_postpre_only(conn, kwargs, mask) -> None:
+    """LocalConnection1D / 2D / 3D and Conv1d / Conv3dConnection.update: PostPre, by the family's `_host_postpre`."""
+    rule = conn.update_rule
+    if rule._rule_code != _lib.RULE_NONE:
+        rule._check_reduction()
+        conn._host_postpre(rule)
+
+
+def _update_conv2d(conn, kwargs, mask=None) -> None:
+    """Conv2dConnection.update: PostPre, MSTDP at batch 1."""
     from ..learning import learning as rules
-    from .topology import Conv2dConnection, _ConvNdConnection, _LocalConnectionND
     rule = conn.update_rule
     if rule is None or isinstance(rule, rules.NoOp):
         return
-    if isinstance(conn, _LocalConnectionND):
+    if isinstance(rule, rules.PostPre):
         rule._check_reduction()
-        return _update_local(conn, rule)
-    if isinstance(conn, _ConvNdConnection):
-        rule._check_reduction()
-        return _update_convnd(conn, rule)
+        _conv_postpre(conn, rule)
+    elif isinstance(rule, rules.MSTDP):
+        _conv_mstdp(conn, rule, kwargs)
+    else:
+        raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on a Conv2dConnection (supported: PostPre, MSTDP)")
+    _decay_clamp(rule, conn.w.data, rule.weight_decay)
+
+
+def _update_dense(conn, kwargs, mask) -> None:
+    """Connection / LocalConnection.update: every dense rule on the [source.n, target.n] matrix, then the weight mask."""
+    from ..learning import learning as rules
+    rule = conn.update_rule
+    if rule is None or isinstance(rule, rules.NoOp):
+        return
     B = conn.source.batch_size
     W = conn.w.data
-    conv = isinstance(conn, Conv2dConnection)
-    if W.dim() != 2 and not conv:
+    if W.dim() != 2:
         raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on {type(conn).__name__}")
     nu0, nu1 = float(rule.nu[0]), float(rule.nu[1])
-    if conv:
-        if isinstance(rule, rules.PostPre):
-            rule._check_reduction()
-            _conv_postpre(conn, rule)
-        elif isinstance(rule, rules.MSTDP):
-            _conv_mstdp(conn, rule, kwargs)
-        else:
-            raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on a Conv2dConnection (supported: PostPre, MSTDP)")
-    elif isinstance(rule, rules.MSTDPET):
+    if isinstance(rule, rules.MSTDPET):
         _mstdpet(rule, W, conn.dt, conn.source.s.view(-1).float(), conn.target.s.view(-1).float(), kwargs)
     else:
         rule._check_reduction()
@@ -418,27 +420,21 @@ def _update_dense(conn, kwargs, mask) -> None:
         else:
             raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} (supported: PostPre, MSTDP, Hebbian, "
                                       "WeightDependentPostPre, MSTDPET)")
-    W *= float(rule.weight_decay)                          # learning.py:87-104
-    lo, hi = rule._bounds()
-    if lo is not None or hi is not None:
-        W.clamp_(lo, hi)
-    if mask is not None and not conv:
+    _decay_clamp(rule, W, rule.weight_decay)
+    if mask is not None:
         W.masked_fill_(torch.as_tensor(mask).bool().view_as(W), 0.0)
 
 
 def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs) -> None:
     from .nodes import Input, LIFNodes, _AdaptiveThresholdNodes
-    from .topology import MulticompartmentConnection
     clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
     injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
-    dt = float(network.dt)
     if isinstance(kwargs.get("a_plus"), dict) or isinstance(kwargs.get("a_minus"), dict):
-        # network.py:356-378, 432-447 also takes {connection key: value} tables; like the MI355X path (network.py::_fill_conn)
+        # network.py:356-378, 432-447 also takes {connection key: value} tables; like the MI355X path (learning/_descriptor.py)
         # this one does not, and says so instead of failing inside torch.tensor(dict)
         raise NotImplementedError("bindsnet_amd: per-connection a_plus/a_minus dicts are not supported")
-    from .topology import _ConvNdConnection
     for key, conn in network.connections.items():
-        if isinstance(conn, _ConvNdConnection) and masks.get(key) is not None:
+        if conn._host_refuses_mask and masks.get(key) is not None:
             raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
     for name, layer in network.layers.items():
         if not isinstance(layer, (Input, LIFNodes, _AdaptiveThresholdNodes)):
@@ -455,7 +451,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
             tgt = network.layers[dst]
             if dst not in cur:
                 cur[dst] = torch.zeros(network.batch_size, *tgt.shape)
-            cur[dst] += _propagate(conn, network.layers[src].s)
+            cur[dst] += conn._host_compute(network.layers[src].s)
         return cur
 
     for t in range(T):
@@ -491,10 +487,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
                         layer.s[:, m.view(*layer.shape)] = bool(value)
         if network.learning:
             for key, conn in network.connections.items():
-                if isinstance(conn, MulticompartmentConnection):
-                    _update_mcc(conn, dt, kwargs)
-                else:
-                    _update_dense(conn, kwargs, _mask_of(conn, masks.get(key)))
+                conn._host_update(kwargs, _mask_of(conn, masks.get(key)))
         for key, conn in network.connections.items():                  # masks apply every step, learning or not
             mask = _mask_of(conn, masks.get(key))
             if mask is not None and hasattr(conn, "w") and conn.w.dim() == 2:
@@ -510,42 +503,23 @@ def _mask_of(conn, mask):
     return mask if mask is not None else getattr(conn, "mask", None)
 
 
-def normalize_connection(conn) -> None:
-    """One connection's normalisation -- Weight features by their SIGNED column sums (topology_features.py:250-266), dense
-    connections by the absolute ones (topology.py:383-392), a LocalConnection by the signed ones again (topology.py:1475-1482),
-    a Conv2dConnection filter by filter (topology.py:824-837)."""
-    from .topology import Conv2dConnection, LocalConnection, MulticompartmentConnection, _ConvNdConnection, _LocalConnectionND
-    if isinstance(conn, _ConvNdConnection):                      # topology.py:665-675 / :1004-1017: every [K] filter to sum `norm`
-        if conn.norm is not None:
-            w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], -1)
-            for fltr in range(w.shape[0]):
-                w[fltr] *= conn.norm / w[fltr].sum(0)
-        return
-    if isinstance(conn, _LocalConnectionND):                     # topology.py:1601 / :1748-1759 / :1898
-        if conn.norm is not None:
-            w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], conn.w.shape[2])
-            for fltr in range(w.shape[0]):
-                w[fltr, :] *= conn.norm / w[fltr, :].sum(0)
-        return
-    if isinstance(conn, Conv2dConnection):                       # topology.py:824-837: every [KH*KW] filter to sum `norm`
-        if conn.norm is not None:
-            w = conn.w.data.view(conn.w.shape[0] * conn.w.shape[1], conn.w.shape[2] * conn.w.shape[3])
-            for fltr in range(w.shape[0]):
-                w[fltr] *= conn.norm / w[fltr].sum(0)
-        return
-    if isinstance(conn, MulticompartmentConnection):
-        feat = conn._weight()
-        if feat.norm is not None:
-            colsum = _sum(feat.value.data, 0).unsqueeze(0)
-            colsum[colsum == 0] = 1.0
-            feat.value.data *= feat.norm / colsum
-    elif getattr(conn, "norm", None) is not None and hasattr(conn, "w") and conn.w.dim() == 2:
-        colsum = _sum(conn.w.data if isinstance(conn, LocalConnection) else conn.w.data.abs(), 0).unsqueeze(0)
-        colsum[colsum == 0] = 1.0
-        conn.w.data *= conn.norm / colsum
+def _normalize_rows(w, norm) -> None:
+    """Every row of the 2-D view `w` scaled to sum `norm`: a Conv2dConnection's [KH*KW] filters (topology.py:824-837), a
+    Conv1d / Conv3dConnection's [K] filters (:665-675 / :1004-1017), a LocalConnection1D / 2D / 3D's [kernel_prod] rows
+    (:1601 / :1748-1759 / :1898)."""
+    for fltr in range(w.shape[0]):
+        w[fltr] *= norm / w[fltr].sum(0)
+
+
+def _normalize_columns(w, norm, use_abs: bool) -> None:
+    """Every column of `w` scaled to `norm` -- Weight features by their SIGNED column sums (topology_features.py:250-266), dense
+    connections by the absolute ones (topology.py:383-392), a LocalConnection by the signed ones again (topology.py:1475-1482)."""
+    colsum = _sum(w.abs() if use_abs else w, 0).unsqueeze(0)
+    colsum[colsum == 0] = 1.0
+    w *= norm / colsum
 
 
 def normalize(network) -> None:
     """network.py:463-465: every connection's normalisation."""
     for conn in network.connections.values():
-        normalize_connection(conn)
+        conn._host_normalize()

@@ -14,11 +14,11 @@ from typing import Dict, Optional, Type
 import torch
 
 from .. import _lib
+from .._lib import dptr as _dptr
 from ..rng import DeviceGenerator
+from . import host_path
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
 from .nodes import AdaptiveLIFNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
-from .topology import (AbstractConnection, Connection, Conv2dConnection, LocalConnection, MulticompartmentConnection,
-                       _ConvNdConnection, _LocalConnectionND)
 
 
 def load(file_name: str, map_location: str = "cpu", learning: bool = None) -> "Network":
@@ -43,10 +43,6 @@ class _Pipeline:
         self.host0 = None              # host generator state at the start of the batch (None: no run of the batch draws)
         self.enabled = False
         self.stream = None             # the stream the batch's runs were enqueued on (settlement waits for THAT stream)
-
-
-def _dptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class Network(_lib.TouchingModule, torch.nn.Module):
@@ -301,14 +297,10 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
         injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
         if self.learning and int(time / self.dt) > 0:
-            # PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference at its first learning step (a bool bmm
-            # operand); here before the run changes any state -- a deliberate deviation in timing
-            for conn in self.connections.values():
-                rule = getattr(conn, "update_rule", None)
-                if isinstance(conn, _ConvNdConnection) and type(rule).__name__ == "PostPre":
-                    err = conn._postpre_error(rule)
-                    if err is not None:
-                        raise RuntimeError(err)
+            for conn in self.connections.values():         # what a family knows it cannot learn: before the run changes any state
+                err = conn._refusal() if hasattr(conn, "_refusal") else None
+                if err is not None:
+                    raise RuntimeError(err)
         if self.reward_fn is not None:
             kwargs["reward"] = self.reward_fn.compute(**kwargs)
 
@@ -336,7 +328,6 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if any(v.is_cuda for v in inputs.values()):
                 raise _lib.SnnError("bindsnet_amd: the network is on the host but an input tensor is on the GPU: move the "
                                     "network with network.to('cuda')")
-            from . import host_path
             if T <= 0:
                 host_path.normalize(self)
                 return
@@ -396,7 +387,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 R.plan = 2
         if not self.__dict__.get("_defer_norm", False):     # network.py:463-465 for the connections snn_net_run does not normalise itself
             for conn in self.connections.values():
-                if isinstance(conn, (Conv2dConnection, _ConvNdConnection)) and conn.norm is not None:
+                if conn._norm_by == "after" and conn.norm is not None:
                     conn.normalize()
         # Input.s aliases the last input slice, as in the reference (nodes.py:219)
         before = _lib.epoch()
@@ -471,8 +462,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 for key, table in (("clamp", clamps), ("unclamp", unclamps)):
                     m = table.get(name)
                     if m is not None:
-                        from .host_path import clamp_mask      # boolean masks, or neuron INDICES like supervised_mnist.py:201-207
-                        m = clamp_mask(m, layer.n).to(dev)
+                        m = host_path.clamp_mask(m, layer.n).to(dev)      # boolean masks, or neuron INDICES like supervised_mnist.py:201-207
                         per_step = m.dim() >= 2
                         if m.numel() != (T if per_step else 1) * layer.n and not (per_step and m.shape[0] >= T and m[0].numel() == layer.n):
                             raise ValueError(f"{key}['{name}'] must have {layer.n} entries (optionally one row per timestep)")
@@ -515,25 +505,22 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     if lname not in self.layers or isinstance(self.layers[lname], Input):
                         raise NotImplementedError(f"bindsnet_amd: {what}['{lname}'] must name a non-Input layer of the network")
             Cn = (_lib.ConnDesc * max(1, len(self.connections)))()
-            lists, dyn_conns = [], []
+            lists, dyn_conns, described = [], [], []
             for k, ((src, dst), conn) in enumerate(self.connections.items()):
-                self._fill_conn(Cn[k], conn, index[src], index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
+                described += self._fill_conn(Cn[k], conn, index[src], index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
                 if self.__dict__.get("_defer_norm", False):    # parallel.sharded_run normalises the MERGED weights itself
                     Cn[k].has_norm = 0
                 wanted = self._conn_monitor_requests(conn, (src, dst))
                 if wanted:
                     dyn_conns.append((k, conn, wanted))
-                rule = conn._weight().learning_rule if isinstance(conn, MulticompartmentConnection) else getattr(conn, "update_rule", None)
-                nu = getattr(rule, "nu", None)
+                nu = getattr(conn._rule(), "nu", None)
                 if isinstance(nu, torch.Tensor):
                     lists.append((nu, nu._version))
                 elif isinstance(nu, (list, tuple)):
                     lists.append((nu, tuple(nu)))
-                mask = masks.get((src, dst))
-                if mask is None:
-                    mask = getattr(conn, "mask", None)         # LocalConnection's structural mask (topology.py:1468-1470)
+                mask = host_path._mask_of(conn, masks.get((src, dst)))
                 if mask is not None:
-                    if not hasattr(conn, "w") or isinstance(conn, (Conv2dConnection, _LocalConnectionND, _ConvNdConnection)):
+                    if not conn._takes_mask:
                         raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
                     m = torch.as_tensor(mask).to(dev).ne(0).to(torch.uint8).contiguous()
                     if m.numel() != conn.w.numel():
@@ -555,14 +542,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     ptrs.append((layer, attr, t.data_ptr()))
             if not isinstance(layer, Input) and isinstance(getattr(layer, "s", None), torch.Tensor):
                 ptrs.append((layer, "s", layer.s.data_ptr()))
-        for conn in self.connections.values():
-            if isinstance(conn, MulticompartmentConnection):
-                ptrs.append((conn._weight(), "value", conn._weight().value.data_ptr()))
-            else:
-                for attr in ("w", "b", "src", "pp_src"):
-                    t = getattr(conn, attr, None)
-                    if isinstance(t, torch.Tensor):
-                        ptrs.append((conn, attr, t.data_ptr()))
+        ptrs += [(obj, attr, getattr(obj, attr).data_ptr()) for obj, attr in described]     # what the connections' _describe wrote
         R = _lib.RunDesc()
         R.B, R.T, R.dt, R.learning = B, T, float(self.dt), int(self.learning)
         R.one_step = int(bool(one_step))                  # network.py:388-393 (generic plan)
@@ -661,7 +641,6 @@ class Network(_lib.TouchingModule, torch.nn.Module):
 
     def _normalize_all(self):
         if self._device().type != "cuda":          # a network on the host: plain PyTorch (network/host_path.py)
-            from . import host_path
             host_path.normalize(self)
             return
         for c in self.connections.values():
@@ -718,191 +697,19 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             raise NotImplementedError("bindsnet_amd: monitored connection weights must be contiguous float32")
         return requests
 
-    @staticmethod
-    def _fill_mstdp(d, rule, kwargs, dev, keep):
-        """Reward / a_plus / a_minus keyword arguments and the rule's device state (learning.py:1504-1574,
-        MCC_learning.py:468-551)."""
-        reward = kwargs["reward"]
-        if isinstance(reward, torch.Tensor) and reward.numel() > 1:
-            rv = reward.to(dev, torch.float32).reshape(-1).contiguous()
-            keep.append(rv)
-            d.reward_vec, reward = _dptr(rv), 0.0
-        a_plus, a_minus = kwargs.get("a_plus", 1.0), kwargs.get("a_minus", -1.0)
-        if isinstance(a_plus, dict) or isinstance(a_minus, dict):
-            raise NotImplementedError("bindsnet_amd: per-connection a_plus/a_minus dicts are not supported")
-        d.rule, d.reward, d.a_plus, d.a_minus = _lib.RULE_MSTDP, float(reward), float(a_plus), float(a_minus)
-        d.decay_plus, d.decay_minus = rule._decays()
-        d.p_plus, d.p_minus = _dptr(rule.p_plus), _dptr(rule.p_minus)
-        d.s_src_prev, d.s_tgt_prev = _dptr(rule._s_src_prev), _dptr(rule._s_tgt_prev)
-
-    @staticmethod
-    def _fill_mstdpet(d, rule, wdecay, kwargs):
-        """MSTDPET's keyword arguments and device state (learning.py:2187-2248, MCC_learning.py:652-729)."""
-        lo, hi = rule._bounds()
-        d.wdecay = wdecay
-        d.has_min, d.wmin = int(lo is not None), lo or 0.0
-        d.has_max, d.wmax = int(hi is not None), hi or 0.0
-        d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
-        dp, dm, de = rule._decays()
-        d.rule, d.reward = _lib.RULE_MSTDPET, float(kwargs["reward"])
-        d.a_plus, d.a_minus = float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0))
-        d.decay_plus, d.decay_minus, d.decay_e, d.tc_e = dp, dm, de, float(rule.tc_e_trace)
-        d.p_plus, d.p_minus, d.e_trace = _dptr(rule.p_plus), _dptr(rule.p_minus), _dptr(rule.eligibility_trace)
-        d.s_src_prev, d.s_tgt_prev = _dptr(rule._s_src_prev), _dptr(rule._s_tgt_prev)
-
     def _fill_conn(self, d, conn, src, dst, B, dev, keep, kwargs):
-        from ..learning import learning as dense_rules
-        from ..learning import MCC_learning as mcc_rules
+        """One snn_conn_desc: the connection describes itself, then its rule does.  Returns the connection's (owner, attribute)
+        pairs of the tensors whose addresses `d` now holds."""
+        if not hasattr(conn, "_describe"):
+            raise NotImplementedError(f"bindsnet_amd: connection type {type(conn).__name__} is not supported")
         d.src, d.dst, d.rule, d.wdecay = src, dst, _lib.RULE_NONE, 1.0
-        if isinstance(conn, MulticompartmentConnection):
-            feat = conn._weight()
-            if feat.value.device != dev:
-                feat.to(dev)
-            val = feat.value
-            if val.dtype != torch.float32 or not val.is_contiguous() or tuple(val.shape) != (conn.source.n, conn.target.n):
-                raise NotImplementedError(f"bindsnet_amd: Weight.value must be a contiguous float32 [{conn.source.n}, "
-                                          f"{conn.target.n}] tensor (got {val.dtype}, shape {tuple(val.shape)}, "
-                                          f"contiguous={val.is_contiguous()})")
-            d.kind, d.w = _lib.CONN_MCC, _dptr(feat.value.data)
-            rule = feat.learning_rule
-            if isinstance(rule, mcc_rules.PostPre) and not conn.manual_update:
-                if rule.reduction is torch.squeeze and B != 1:
-                    raise RuntimeError("reduction=torch.squeeze requires batch size 1")
-                lo, hi = rule._bounds()
-                d.rule, d.use_dt, d.wdecay = _lib.RULE_POSTPRE, 1, float(rule.decay)
-                d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
-                d.has_min, d.wmin = int(lo is not None), lo or 0.0
-                d.has_max, d.wmax = int(hi is not None), hi or 0.0
-            elif isinstance(rule, mcc_rules.MSTDP) and not conn.manual_update:
-                if rule.reduction is torch.squeeze and B != 1:
-                    raise RuntimeError("reduction=torch.squeeze requires batch size 1")
-                if "reward" not in kwargs:
-                    raise KeyError("reward")
-                rule._ensure_state()
-                lo, hi = rule._bounds()
-                d.wdecay = float(rule.decay)
-                d.has_min, d.wmin = int(lo is not None), lo or 0.0
-                d.has_max, d.wmax = int(hi is not None), hi or 0.0
-                d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
-                self._fill_mstdp(d, rule, kwargs, dev, keep)
-            elif isinstance(rule, mcc_rules.MSTDPET) and not conn.manual_update:
-                if B != 1:
-                    raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
-                if "reward" not in kwargs:
-                    raise KeyError("reward")
-                rule._ensure_state()
-                self._fill_mstdpet(d, rule, float(rule.decay), kwargs)
-            elif not isinstance(rule, mcc_rules.NoOp):
-                raise NotImplementedError(f"bindsnet_amd: MCC rule {type(rule).__name__} is not supported")
-            if feat.norm is not None:
-                if isinstance(feat.norm, torch.Tensor):
-                    raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-                ws = self._scratch(f"norm_{src}_{dst}", (conn.target.n,), torch.float32, dev)
-                d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, _dptr(ws)
-            return
-        if not isinstance(conn, AbstractConnection):
-            raise NotImplementedError(f"bindsnet_amd: connection type {type(conn).__name__} is not supported")
-        if conn.w.device != dev:
-            raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
-        d.w = _dptr(conn.w.data)
-        d.bias = _dptr(conn.b.data) if getattr(conn, "b", None) is not None else None
-        if isinstance(conn, _LocalConnectionND):              # LocalConnection1D / 2D / 3D (topology.py:1488-1910): generic plan
-            if conn.src.device != dev:
-                raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
-            d.kind, d.bias, d.cin, d.local_src = _lib.CONN_LOCAL, None, conn.in_channels, _dptr(conn.src)
-            d.local_F, d.local_conv_prod, d.local_kernel_prod, d.local_n_src = conn.n_filters, conn.conv_prod, conn.kernel_prod, conn.source.n
-        elif isinstance(conn, _ConvNdConnection):            # Conv1dConnection / Conv3dConnection (topology.py:540-1025): generic plan
-            if conn.pp_src.device != dev:
-                raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
-            k = conn._kernel()
-            d.kind, d.cin, d.cout = _lib.CONN_CONVND, conn.in_channels, conn.out_channels
-            d.conv_nd, d.stride, d.pad = conn._ndim, conn._stride(), conn._padding()
-            if conn._ndim == 1:
-                d.conv_d, d.h, d.wd, d.conv_kd, d.kh, d.kw = 1, 1, conn.source.shape[1], 1, 1, k[0]
-            else:
-                (d.conv_d, d.h, d.wd), (d.conv_kd, d.kh, d.kw) = conn.source.shape[1:4], k
-            d.conv_pp_src, d.conv_pp_rows = _dptr(conn.pp_src), conn.pp_src.shape[0]
-        elif isinstance(conn, Conv2dConnection):
-            d.kind = _lib.CONN_CONV2D
-            d.cin, d.h, d.wd = conn.in_channels, conn.source.shape[1], conn.source.shape[2]
-            d.cout, d.kh, d.kw = conn.out_channels, conn.kernel_size[0], conn.kernel_size[1]
-            d.stride, d.pad = conn.stride[0], conn.padding[0]
-        elif isinstance(conn, (Connection, LocalConnection)):
-            d.kind = _lib.CONN_DENSE
-        else:
-            raise NotImplementedError(f"bindsnet_amd: connection type {type(conn).__name__} is not supported")
-        rule = conn.update_rule
-        if isinstance(rule, (dense_rules.PostPre, dense_rules.MSTDP)):
-            rule._check_reduction()
-            lo, hi = rule._bounds()
-            d.wdecay = float(rule.weight_decay)
-            d.has_min, d.wmin = int(lo is not None), lo or 0.0
-            d.has_max, d.wmax = int(hi is not None), hi or 0.0
-            d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
-            if isinstance(rule, dense_rules.PostPre):
-                d.rule, d.use_dt = _lib.RULE_POSTPRE, 0
-                if isinstance(conn, Conv2dConnection):       # learning.py:457-497: per-sample partial sums live in scratch
-                    ws = self._scratch(f"convpp_{src}_{dst}", (2 * B * conn.w.numel(),), torch.float32, dev)
-                    d.rule_ws = _dptr(ws)
-                elif isinstance(conn, _ConvNdConnection):    # the packed target spikes, when they exceed the kernel's LDS
-                    L = max(int(conn.pp_src.shape[0]), 1)
-                    ws = self._scratch(f"convndpp_{src}_{dst}", (B * conn.out_channels * ((L + 31) // 32),), torch.int32, dev)
-                    d.rule_ws = _dptr(ws)
-            elif isinstance(conn, Conv2dConnection):         # learning.py:1942-2015, batch 1
-                if B != 1:
-                    raise NotImplementedError("MSTDP on a Conv2dConnection is defined for batch size 1 (learning.py:2013)")
-                if "reward" not in kwargs:
-                    raise KeyError("reward")
-                reward = kwargs["reward"]
-                if isinstance(reward, torch.Tensor):
-                    if reward.numel() != 1:
-                        raise NotImplementedError("bindsnet_amd: MSTDP on a Conv2dConnection takes a scalar reward")
-                    reward = reward.item()
-                a_plus, a_minus = kwargs.get("a_plus", 1.0), kwargs.get("a_minus", -1.0)
-                if isinstance(a_plus, dict) or isinstance(a_minus, dict):
-                    raise NotImplementedError("bindsnet_amd: per-connection a_plus/a_minus dicts are not supported")
-                rule._ensure_state()
-                d.rule, d.reward, d.a_plus, d.a_minus = _lib.RULE_MSTDP, float(reward), float(a_plus), float(a_minus)
-                d.decay_plus, d.decay_minus = rule._decays()
-                d.p_plus, d.p_minus, d.e_trace = _dptr(rule.p_plus), _dptr(rule.p_minus), _dptr(rule._elig)
-            else:
-                if "reward" not in kwargs:
-                    raise KeyError("reward")
-                rule._ensure_state()
-                self._fill_mstdp(d, rule, kwargs, dev, keep)
-        elif isinstance(rule, (dense_rules.Hebbian, dense_rules.WeightDependentPostPre)):
-            rule._check_reduction()
-            lo, hi = rule._bounds()
-            d.rule = _lib.RULE_WDPOSTPRE if isinstance(rule, dense_rules.WeightDependentPostPre) else _lib.RULE_HEBBIAN
-            d.wdecay = float(rule.weight_decay)
-            d.has_min, d.wmin = int(lo is not None), lo or 0.0
-            d.has_max, d.wmax = int(hi is not None), hi or 0.0
-            d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
-        elif isinstance(rule, dense_rules.MSTDPET):
-            if B != 1:
-                raise NotImplementedError("MSTDPET on a dense Connection is defined for batch size 1 (learning.py:2211-2212)")
-            if "reward" not in kwargs:
-                raise KeyError("reward")
-            rule._ensure_state()
-            self._fill_mstdpet(d, rule, float(rule.weight_decay), kwargs)
-        elif not isinstance(rule, dense_rules.NoOp):
+        described = conn._describe(d, B, dev, self._scratch)
+        rule = conn._rule()
+        if not hasattr(rule, "_describe"):
             raise NotImplementedError(f"bindsnet_amd: rule {type(rule).__name__} is not supported")
-        elif rule.weight_decay != 1.0 and self.learning:
+        if rule._rule_code != _lib.RULE_NONE:
+            rule._describe(d, conn, B, dev, keep, kwargs)
+        elif getattr(rule, "weight_decay", 1.0) != 1.0 and self.learning:
             # the reference's NoOp.update still decays w every step (learning.py:87-104); not on the accelerated path
             raise NotImplementedError("bindsnet_amd: weight_decay on a connection without a learning rule is not supported")
-        if conn.w.dtype != torch.float32 or not conn.w.is_contiguous():
-            raise NotImplementedError("bindsnet_amd: connection weights must be contiguous float32")
-        if conn.norm is not None and isinstance(conn, _LocalConnectionND):
-            # every [kernel_prod] row to sum `norm` (topology.py:1748-1759): snn_net_run's post-loop step, through snn_normalize_conv2d
-            if isinstance(conn.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-            d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(conn.norm), 0, None
-        elif conn.norm is not None and isinstance(conn, (Conv2dConnection, _ConvNdConnection)):
-            # Conv2dConnection.normalize (topology.py:824-837) scales every filter to sum `norm`: not a column normalisation, so
-            # not snn_net_run's post-loop step -- run() calls the connection's own normalize() (snn_normalize_conv2d) behind it
-            if isinstance(conn.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-        elif conn.norm is not None:
-            ws = self._scratch(f"norm_{src}_{dst}", (conn.target.n,), torch.float32, dev)
-            # Connection.normalize sums |w| (topology.py:383-392), LocalConnection.normalize the signed weights (:1475-1482)
-            d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(conn.norm), int(not isinstance(conn, LocalConnection)), _dptr(ws)
+        return described

@@ -12,11 +12,47 @@ from torch.nn import Module, Parameter
 from torch.nn.modules.utils import _pair, _triple
 
 from .. import _lib, ops
+from .._lib import dptr
+from . import host_path
 from .nodes import Nodes
 
 
+def _rand_weights(conn, shape, bias_n, w_dtype, kwargs) -> None:
+    """`w` and `b` of the convolutional families as the reference draws and clamps them (topology.py:611-630 / :772-791 /
+    :950-969): one torch.rand from the global generator, clamped when a bound is infinite, spread over [wmin, wmax] otherwise."""
+    w = kwargs.get("w", None)
+    inf = torch.tensor(np.inf)
+    unbounded = bool((conn.wmin == -inf).any() or (conn.wmax == inf).any())
+    if w is None:
+        r = torch.rand(*shape)
+        w = torch.clamp(r, conn.wmin, conn.wmax) if unbounded else (conn.wmax - conn.wmin) * r + conn.wmin
+        w = w.to(dtype=w_dtype)
+    else:
+        if unbounded:
+            w = torch.clamp(w, conn.wmin, conn.wmax)
+        w = conn.cast_dtype_if_needed(w, w_dtype)
+    conn.w = Parameter(w, requires_grad=False)
+    conn.b = Parameter(kwargs.get("b", torch.zeros(bias_n)), requires_grad=False)
+
+
 class AbstractConnection(_lib.TouchingModule, Module):
-    """Reference: topology.py:17-156 (wmin/wmax/norm/update_rule plumbing)."""
+    """Reference: topology.py:17-156 (wmin/wmax/norm/update_rule plumbing).
+
+    What a connection family is, is written in its class and asked for by network.py, host_path.py, learning.py and
+    parallel.py, none of which names a family: the class-level facts below, `_describe` (its part of a snn_conn_desc),
+    `_prop_into` and `_postpre` (its device ops), `_host_compute` / `_host_update` (its host arithmetic in host_path.py).
+    The facts default to "nothing": a family that leaves one out is refused, not taken for a dense one."""
+
+    _kind = None                       # snn_conn_desc.kind
+    # who normalises: "columns" -- snn_net_run, every column to `norm` (by |w| or signed: _norm_abs) with a [target.n] scratch;
+    # "rows" -- snn_net_run, every last-dimension row; "after" -- Network.run calls normalize() behind snn_net_run
+    _norm_by = _norm_abs = None
+    # run(..., masks=) on the device: refused unless _takes_mask.  The host path refuses only where _host_refuses_mask and
+    # ignores the mask on the other families whose `w` is not 2-D: an asymmetry kept as it is
+    _takes_mask = _host_refuses_mask = False
+    _multi_device = False              # parallel.py's modes refuse it outright (weights gathered through a table)
+    # names of the learning.py rules it accepts and, where the refusal comes before anything else in the rule's constructor, its wording
+    _rules, _rules_only = frozenset(), None
 
     def __init__(self, source: Nodes, target: Nodes, nu=None, reduction: Optional[callable] = None,
                  weight_decay: float = 0.0, **kwargs) -> None:
@@ -40,13 +76,84 @@ class AbstractConnection(_lib.TouchingModule, Module):
         """Reference: topology.py:112-139."""
         if kwargs.get("learning", True):
             if not self.w.is_cuda:                        # a connection on the host: plain PyTorch (network/host_path.py)
-                from . import host_path
-                host_path._update_dense(self, kwargs, None)
+                self._host_update(kwargs, None)
             else:
                 self.update_rule.update(**kwargs)
         mask = kwargs.get("mask", None)
         if mask is not None:                       # topology.py:129-133
             self.w.masked_fill_(torch.as_tensor(mask, device=self.w.device).bool(), 0)
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        """The family's propagation kernel (`_prop_into`) on the device, its host_path function on the host."""
+        if not self.w.is_cuda:
+            return self._host_compute(s)
+        out = torch.empty(s.size(0), *self.target.shape, device=self.w.device)
+        self._prop_into(s, out)
+        return out
+
+    def normalize(self) -> None:
+        """Reference: topology.py:383-392 and its siblings; what is scaled to `norm` is the family's (`_norm_by`)."""
+        if self.norm is None:
+            return
+        if not self.w.is_cuda:
+            return self._host_normalize()
+        if self._norm_by == "columns":
+            ops.normalize(self.w.data.view(self.source.n, self.target.n), float(self.norm), use_abs=self._norm_abs)
+        elif isinstance(self.norm, torch.Tensor):
+            raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+        else:                     # every row of the [w.shape[0] * w.shape[1], rest] view (snn_normalize_conv2d)
+            ops.normalize_conv2d(self.w.data.view(self.w.shape[0], self.w.shape[1], -1, 1), float(self.norm))
+
+    def _host_normalize(self) -> None:
+        if self.norm is not None and self._norm_by != "columns":
+            host_path._normalize_rows(self.w.data.view(self.w.shape[0] * self.w.shape[1], -1), self.norm)
+        elif self.norm is not None and self.w.dim() == 2:
+            host_path._normalize_columns(self.w.data, self.norm, self._norm_abs)
+
+    def _rule(self):
+        """The learning rule whose `nu` and descriptor fields belong to this connection."""
+        return self.update_rule
+
+    def _weights(self):
+        """(owner, attribute) of the learned tensor; the owner also holds its `norm`."""
+        return self, "w"
+
+    def _describe(self, d, B: int, dev, scratch) -> list:
+        """Fill this connection's part of the snn_conn_desc `d` (d.src / d.dst are set) for batch size B on `dev`; `scratch` is
+        Network._scratch.  Returns (owner, attribute) of every tensor whose ADDRESS went in: the descriptor cache re-checks them."""
+        if self.w.device != dev:
+            raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
+        if self.w.dtype != torch.float32 or not self.w.is_contiguous():
+            raise NotImplementedError("bindsnet_amd: connection weights must be contiguous float32")
+        d.kind, d.w = self._kind, dptr(self.w.data)
+        described = [self._weights()]
+        if isinstance(getattr(self, "b", None), torch.Tensor):
+            d.bias = dptr(self.b.data)
+            described.append((self, "b"))
+        if self.norm is not None:
+            if self._norm_by == "columns":
+                ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
+                d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(self.norm), int(self._norm_abs), dptr(ws)
+            elif isinstance(self.norm, torch.Tensor):
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+            elif self._norm_by == "rows":
+                d.has_norm, d.norm, d.norm_abs = 1, float(self.norm), 0
+        return described
+
+    def _table(self, described: list, name: str, dev):
+        """A gather table (an int32 buffer) for `_describe`: its address, once it is on the device and listed in `described`."""
+        if getattr(self, name).device != dev:
+            raise ValueError("connection tables are not on the network's device; call network.to('cuda')")
+        described.append((self, name))
+        return dptr(getattr(self, name))
+
+    def _column_slice(self, source: Nodes, target: Nodes, lo: int, hi: int):
+        """parallel.column_shard: a connection source -> target holding target columns [lo, hi), same rule and constants (on the host)."""
+        raise NotImplementedError(f"column sharding of {type(self).__name__} is not supported")
+
+    def _exact_learns(self) -> bool:
+        """parallel.exact_run: whether this connection learns there (a family or rule the mode does not handle raises)."""
+        raise NotImplementedError(f"exact_run: connection type {type(self).__name__}")
 
     def reset_state_variables(self) -> None:
         pass
@@ -59,7 +166,28 @@ class AbstractConnection(_lib.TouchingModule, Module):
         return w
 
 
-class Connection(AbstractConnection):
+class _DenseConnection(AbstractConnection):
+    """What Connection and LocalConnection share: a [source.n, target.n] matrix, propagated by snn_prop_dense_f32, learned by
+    every rule of learning.py, its columns normalised."""
+
+    _kind, _norm_by, _norm_abs = _lib.CONN_DENSE, "columns", True
+    _takes_mask = _multi_device = True
+    _rules = frozenset(("NoOp", "PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET"))
+    _host_compute, _host_update = host_path._propagate_dense, host_path._update_dense
+
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        """s.view(B,-1) @ w (+ b) in canonical ascending-source order (topology.py:332-346)."""
+        ops.prop_dense(self.w.data, s.reshape(s.size(0), -1).contiguous(), out, bias=None if self.b is None else self.b.data,
+                       accumulate=accumulate)
+
+    def _postpre(self, rule, B, lo, hi) -> None:
+        """learning.py:390-420."""
+        ops.stdp_postpre(self.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
+                         self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
+                         use_dt=False, decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+
+
+class Connection(_DenseConnection):
     """Dense all-to-all synapses (reference: topology.py:265-399)."""
 
     def __init__(self, source: Nodes, target: Nodes, nu=None, reduction=None, weight_decay: float = 0.0,
@@ -83,31 +211,39 @@ class Connection(AbstractConnection):
         b = kwargs.get("b", None)
         self.b = Parameter(b, requires_grad=False) if b is not None else None
 
-    def compute(self, s: torch.Tensor) -> torch.Tensor:
-        """s.view(B,-1) @ w (+ b) in canonical ascending-source order (topology.py:332-346)."""
-        if not self.w.is_cuda:
-            from . import host_path
-            return host_path._propagate(self, s)
-        B = s.size(0)
-        out = torch.empty(B, self.target.n, device=self.w.device)
-        ops.prop_dense(self.w.data, s.reshape(B, -1).contiguous(), out, bias=None if self.b is None else self.b.data)
-        return out.view(B, *self.target.shape)
+    def _column_slice(self, source, target, lo, hi):
+        def scalar(t) -> float:
+            if isinstance(t, torch.Tensor) and t.numel() != 1:
+                raise NotImplementedError("column sharding needs scalar wmin / wmax (per-synapse bounds are not supported)")
+            return float(t)
+        rule = self.update_rule
+        from ..learning import MSTDP, PostPre
+        rule_cls = type(rule) if isinstance(rule, (PostPre, MSTDP)) else None
+        kw = {}
+        if isinstance(rule, MSTDP):
+            kw.update(tc_plus=float(rule.tc_plus), tc_minus=float(rule.tc_minus))
+        return Connection(source, target, w=self.w.data[:, lo:hi].clone().cpu(),
+                          b=None if self.b is None else self.b.data[lo:hi].clone().cpu(), wmin=scalar(self.wmin),
+                          wmax=scalar(self.wmax), norm=self.norm, update_rule=rule_cls,
+                          nu=None if rule_cls is None else (float(rule.nu[0]), float(rule.nu[1])), reduction=rule.reduction,
+                          weight_decay=0.0 if rule.weight_decay == 1.0 else 1.0 - float(rule.weight_decay), **kw)
 
-    def normalize(self) -> None:
-        """Reference: topology.py:383-392 (abs column sums)."""
-        if self.norm is not None:
-            if not self.w.is_cuda:
-                from . import host_path
-                return host_path.normalize_connection(self)
-            ops.normalize(self.w.data, float(self.norm), use_abs=True)
+    def _exact_learns(self) -> bool:
+        from ..learning import NoOp
+        if not isinstance(self.update_rule, NoOp):
+            raise NotImplementedError("exact_run: learning on a dense Connection (Input -> Connection -> LIFNodes graphs shard "
+                                      "their columns exactly with column_shard, without any collective)")
+        return False
 
 
-class LocalConnection(AbstractConnection):
+class LocalConnection(_DenseConnection):
     """Locally connected synapses (reference: topology.py:1304-1485): a dense [source.n, target.n] matrix that is zero
     outside each target neuron's receptive field (`mask`), propagated like `Connection` (+ bias), learned with the dense
     rules, masked again after every update, normalised by the SIGNED column sums (norm scaled by the kernel size).  Like
     the reference it draws its initial weights from numpy's global generator, and its `compute` output carries no batch
     dimension, i.e. it is meant for batch size 1."""
+
+    _norm_abs = False                  # signed column sums (topology.py:1475-1482)
 
     def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]],
                  stride: Union[int, Tuple[int, int]], n_filters: int, nu=None, reduction=None, weight_decay: float = 0.0,
@@ -155,31 +291,23 @@ class LocalConnection(AbstractConnection):
             self.norm *= kernel_prod
 
     def compute(self, s: torch.Tensor) -> torch.Tensor:
-        B = s.size(0)
-        if not self.w.is_cuda:
-            from . import host_path
-            out = host_path._propagate(self, s)
-            return out.view(*self.target.shape) if B == 1 else out
-        out = torch.empty(B, self.target.n, device=self.w.device)
-        ops.prop_dense(self.w.data, s.reshape(B, -1).contiguous(), out, bias=self.b.data)
-        return out.view(*self.target.shape) if B == 1 else out.view(B, *self.target.shape)
+        out = super().compute(s)
+        return out.view(*self.target.shape) if s.size(0) == 1 else out
 
     def update(self, **kwargs) -> None:
         if kwargs.get("mask", None) is None:
             kwargs["mask"] = self.mask
         super().update(**kwargs)
 
-    def normalize(self) -> None:
-        """Signed column sums (topology.py:1475-1482)."""
-        if self.norm is not None:
-            if not self.w.is_cuda:
-                from . import host_path
-                return host_path.normalize_connection(self)
-            ops.normalize(self.w.data.view(self.source.n, self.target.n), float(self.norm), use_abs=False)
-
 
 class Conv2dConnection(AbstractConnection):
     """2-D convolutional synapses (reference: topology.py:686-844): propagation, PostPre, and MSTDP at batch 1."""
+
+    _kind, _ndim = _lib.CONN_CONV2D, 2
+    _norm_by = "after"      # every [KH*KW] filter to sum `norm` (topology.py:824-837): not snn_net_run's column step
+    _multi_device = True
+    _rules = frozenset(("NoOp", "PostPre", "MSTDP"))
+    _host_compute, _host_update = host_path._propagate_conv, host_path._update_conv2d
 
     def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]],
                  stride: Union[int, Tuple[int, int]] = 1, padding: Union[int, Tuple[int, int]] = 0,
@@ -191,7 +319,7 @@ class Conv2dConnection(AbstractConnection):
         if self.dilation != (1, 1) or self.stride[0] != self.stride[1] or self.padding[0] != self.padding[1]:
             raise NotImplementedError("bindsnet_amd: conv2d supports dilation 1 and symmetric stride/padding only")
         rule = kwargs.get("update_rule", None)
-        if rule is not None and rule.__name__ not in ("PostPre", "MSTDP", "NoOp"):
+        if rule is not None and rule.__name__ not in self._rules:
             raise NotImplementedError(f"bindsnet_amd: {rule.__name__} on Conv2dConnection is not supported (PostPre and MSTDP are)")
         self.in_channels, ih, iw = source.shape[0], source.shape[1], source.shape[2]
         if self.in_channels > 16:
@@ -204,38 +332,27 @@ class Conv2dConnection(AbstractConnection):
             "Target dimensionality must be (out_channels, ?,"
             "(input_height - filter_height + 2 * padding_height) / stride_height + 1,"
             "(input_width - filter_width + 2 * padding_width) / stride_width + 1")
-        w = kwargs.get("w", None)
-        inf = torch.tensor(np.inf)
-        unbounded = bool((self.wmin == -inf).any() or (self.wmax == inf).any())
-        if w is None:
-            r = torch.rand(self.out_channels, self.in_channels, *self.kernel_size)
-            w = torch.clamp(r, self.wmin, self.wmax) if unbounded else (self.wmax - self.wmin) * r + self.wmin
-            w = w.to(dtype=w_dtype)
-        else:
-            if unbounded:
-                w = torch.clamp(w, self.wmin, self.wmax)
-            w = self.cast_dtype_if_needed(w, w_dtype)
-        self.w = Parameter(w, requires_grad=False)
-        self.b = Parameter(kwargs.get("b", torch.zeros(self.out_channels)), requires_grad=False)
+        _rand_weights(self, (self.out_channels, self.in_channels, *self.kernel_size), self.out_channels, w_dtype, kwargs)
 
-    def compute(self, s: torch.Tensor) -> torch.Tensor:
-        B = s.size(0)
-        if not self.w.is_cuda:
-            from . import host_path
-            return host_path._propagate(self, s)
-        out = torch.empty(B, *self.target.shape, device=self.w.device)
-        ops.prop_conv2d(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0])
-        return out
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        ops.prop_conv2d(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0],
+                        accumulate=accumulate)
 
-    def normalize(self) -> None:
-        """Every [KH*KW] filter scaled to sum `norm` (topology.py:824-837)."""
-        if self.norm is not None:
-            if not self.w.is_cuda:
-                from . import host_path
-                return host_path.normalize_connection(self)
-            if isinstance(self.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-            ops.normalize_conv2d(self.w.data, float(self.norm))
+    def _describe(self, d, B, dev, scratch):
+        described = super()._describe(d, B, dev, scratch)
+        d.cin, d.h, d.wd = self.in_channels, self.source.shape[1], self.source.shape[2]
+        d.cout, d.kh, d.kw = self.out_channels, self.kernel_size[0], self.kernel_size[1]
+        d.stride, d.pad = self.stride[0], self.padding[0]
+        if getattr(self.update_rule, "_rule_code", None) == _lib.RULE_POSTPRE:      # learning.py:457-497: per-sample partial sums live in scratch
+            d.rule_ws = dptr(scratch(f"convpp_{d.src}_{d.dst}", (2 * B * self.w.numel(),), torch.float32, dev))
+        return described
+
+    def _postpre(self, rule, B, lo, hi) -> None:
+        """learning.py:457-497."""
+        src, tgt = self.source, self.target
+        ops.conv2d_postpre(self.w.data, src.s.reshape(B, *src.shape).contiguous(), src.x.reshape(B, *src.shape),
+                           tgt.s.reshape(B, *tgt.shape), tgt.x.reshape(B, *tgt.shape), float(rule.nu[0]), float(rule.nu[1]),
+                           stride=self.stride[0], pad=self.padding[0], decay=float(rule.weight_decay), wmin=lo, wmax=hi)
 
 
 class _ConvNdConnection(AbstractConnection):
@@ -249,23 +366,15 @@ class _ConvNdConnection(AbstractConnection):
     positions when Cin > 1) and conv3d's swapped unfold axes without restating them.  When those expressions fail, or give
     another L than the target's position count (the reference's bmm then fails), the table is empty and PostPre raises."""
 
-    _ndim = 0
+    _kind, _ndim = _lib.CONN_CONVND, 0
+    _norm_by = "after"      # every [K] filter of the [Cout*Cin, K] view to sum `norm` (topology.py:665-675 / :1004-1017)
+    _host_refuses_mask = True
+    _rules, _rules_only = frozenset(("NoOp", "PostPre")), "PostPre is"
+    _host_compute, _host_update, _host_postpre = host_path._propagate_conv, host_path._update_postpre_only, host_path._update_convnd
 
     def _init_weights(self, shape, w_dtype, kwargs) -> None:
-        """The reference's draws and clamps (topology.py:611-630 / :950-969), as Conv2dConnection's."""
-        w = kwargs.get("w", None)
-        inf = torch.tensor(np.inf)
-        unbounded = bool((self.wmin == -inf).any() or (self.wmax == inf).any())
-        if w is None:
-            r = torch.rand(*shape)
-            w = torch.clamp(r, self.wmin, self.wmax) if unbounded else (self.wmax - self.wmin) * r + self.wmin
-            w = w.to(dtype=w_dtype)
-        else:
-            if unbounded:
-                w = torch.clamp(w, self.wmin, self.wmax)
-            w = self.cast_dtype_if_needed(w, w_dtype)
-        self.w = Parameter(w, requires_grad=False)
-        self.b = Parameter(kwargs.get("b", torch.zeros(self.out_channels)), requires_grad=False)
+        """The weights, and the PostPre gather table `pp_src`."""
+        _rand_weights(self, shape, self.out_channels, w_dtype, kwargs)
         J = self.in_channels * int(np.prod(self._kernel()))
         self._pp_error = None
         try:
@@ -280,35 +389,56 @@ class _ConvNdConnection(AbstractConnection):
             tab = torch.empty(0, J, dtype=torch.int64)
         self.register_buffer("pp_src", tab.to(torch.int32).contiguous())
 
+    def _kernel(self):
+        return (self.kernel_size,) if self._ndim == 1 else self.kernel_size
+
+    def _stride(self):
+        return self.stride if self._ndim == 1 else self.stride[0]        # (isotropic: checked by Conv3dConnection's constructor)
+
+    def _padding(self):
+        return self.padding if self._ndim == 1 else self.padding[0]
+
     def _postpre_error(self, rule):
         """Why the reference's PostPre update fails on this connection, or None."""
-        if isinstance(self, Conv3dConnection) and bool(rule.nu[0] != 0):
+        if self._ndim == 3 and bool(rule.nu[0] != 0):
             # learning.py:526-547: source_s is never cast to float, so torch.bmm(target_x, source_s) raises
             return ("PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference: torch.bmm raises 'expected m1 and m2 "
                     "to have the same dtype, but got: float != bool' (learning.py:526-551, source_s is never cast to float); "
                     "use nu[0] == 0 or network.train(False)")
         return self._pp_error
-        return None
 
-    def compute(self, s: torch.Tensor) -> torch.Tensor:
-        B = s.size(0)
-        if not self.w.is_cuda:
-            from . import host_path
-            return host_path._propagate(self, s)
-        out = torch.empty(B, *self.target.shape, device=self.w.device)
-        ops.prop_convnd(self.w.data, s.reshape(B, *self.source.shape).contiguous(), out, bias=self.b.data,
-                        stride=self._stride(), pad=self._padding())
-        return out
+    def _refusal(self):
+        """Why a learning run must not start on this connection, or None: asked by Network.run, of the families that define it."""
+        # PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference at its first learning step (a bool bmm
+        # operand); here before the run changes any state -- a deliberate deviation in timing (DESIGN.md section 8)
+        return self._postpre_error(self.update_rule) if type(self.update_rule).__name__ == "PostPre" else None
 
-    def normalize(self) -> None:
-        """Every [K] filter of the [Cout*Cin, K] view scaled to sum `norm` (topology.py:665-675 / :1004-1017)."""
-        if self.norm is not None:
-            if not self.w.is_cuda:
-                from . import host_path
-                return host_path.normalize_connection(self)
-            if isinstance(self.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-            ops.normalize_conv2d(self.w.data.view(self.w.shape[0], self.w.shape[1], -1, 1), float(self.norm))
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        ops.prop_convnd(self.w.data, s.reshape(s.size(0), *self.source.shape).contiguous(), out, bias=self.b.data,
+                        stride=self._stride(), pad=self._padding(), accumulate=accumulate)
+
+    def _describe(self, d, B, dev, scratch):
+        described = super()._describe(d, B, dev, scratch)
+        k = self._kernel()
+        d.cin, d.cout = self.in_channels, self.out_channels
+        d.conv_nd, d.stride, d.pad = self._ndim, self._stride(), self._padding()
+        unit = (1,) * (3 - self._ndim)                        # a conv1d is the conv3d with D = H = 1
+        (d.conv_d, d.h, d.wd), (d.conv_kd, d.kh, d.kw) = unit + tuple(self.source.shape[1:]), unit + tuple(k)
+        d.conv_pp_src, d.conv_pp_rows = self._table(described, "pp_src", dev), self.pp_src.shape[0]
+        if getattr(self.update_rule, "_rule_code", None) == _lib.RULE_POSTPRE:      # the packed target spikes, when they exceed the kernel's LDS
+            L = max(int(self.pp_src.shape[0]), 1)
+            d.rule_ws = dptr(scratch(f"convndpp_{d.src}_{d.dst}", (B * self.out_channels * ((L + 31) // 32),), torch.int32, dev))
+        return described
+
+    def _postpre(self, rule, B, lo, hi) -> None:
+        """learning.py:422-455 / :499-559."""
+        err = self._postpre_error(rule)
+        if err is not None:
+            raise RuntimeError(err)
+        src, tgt = self.source, self.target
+        ops.convnd_postpre(self.w.data, self.pp_src, src.s.reshape(B, -1).contiguous(), src.x.reshape(B, -1),
+                           tgt.s.reshape(B, -1).contiguous(), tgt.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
+                           decay=float(rule.weight_decay), wmin=lo, wmax=hi)
 
 
 class Conv1dConnection(_ConvNdConnection):
@@ -335,15 +465,6 @@ class Conv1dConnection(_ConvNdConnection):
             raise NotImplementedError("bindsnet_amd: Conv1dConnection with kernel_size 1 and more than one input channel is not "
                                       "supported (the reference's oneDNN takes a 1x1 kernel whose order depends on the shape)")
         self._init_weights((self.out_channels, self.in_channels, self.kernel_size), w_dtype, kwargs)
-
-    def _kernel(self):
-        return (self.kernel_size,)
-
-    def _stride(self):
-        return self.stride
-
-    def _padding(self):
-        return self.padding
 
     def _pp_unfold(self, t: torch.Tensor) -> torch.Tensor:
         """learning.py:434-438 on t [B, Cin, N]."""
@@ -390,15 +511,6 @@ class Conv3dConnection(_ConvNdConnection):
                                       "is not supported (the kernel's C ABI reads such an axis as unpadded)")
         self._init_weights((self.out_channels, self.in_channels, *self.kernel_size), w_dtype, kwargs)
 
-    def _kernel(self):
-        return self.kernel_size
-
-    def _stride(self):
-        return self.stride[0]
-
-    def _padding(self):
-        return self.padding[0]
-
     def _pp_unfold(self, t: torch.Tensor) -> torch.Tensor:
         """learning.py:523-534 on t [B, Cin, D, H, W] (D unfolded with the kernel's width, W with its depth, as there)."""
         kd, kh, kw = self.kernel_size
@@ -420,7 +532,10 @@ class _LocalConnectionND(AbstractConnection):
     raises AttributeError for any `w`; here a `w` of shape [Cin, n_filters*conv_prod, kernel_prod] is accepted (and clamped
     to [wmin, wmax] like a drawn one), any other shape raises AssertionError."""
 
-    _ndim = 0
+    _kind, _ndim = _lib.CONN_LOCAL, 0
+    _norm_by = "rows"       # every [kernel_prod] row to sum `norm` (topology.py:1748-1759): snn_net_run, through snn_normalize_conv2d
+    _rules, _rules_only = frozenset(("NoOp", "PostPre")), "PostPre is"
+    _host_compute, _host_update, _host_postpre = host_path._propagate_local, host_path._update_postpre_only, host_path._update_local
 
     def __init__(self, source: Nodes, target: Nodes, kernel_size, stride, n_filters: int, nu=None, reduction=None,
                  weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
@@ -460,26 +575,22 @@ class _LocalConnectionND(AbstractConnection):
             t = t.unfold(-self._ndim, self.kernel_size[i], self.stride[i])
         return t
 
-    def compute(self, s: torch.Tensor) -> torch.Tensor:
+    def _prop_into(self, s, out, accumulate=False) -> None:
         """a_post = unfold(s) * w; a_post.sum(-1).sum(1) (topology.py:1573-1597 / :1731-1746 / :1880-1896)."""
-        B = s.shape[0]
-        if not self.w.is_cuda:
-            from . import host_path
-            return host_path._propagate_local(self, s)
-        out = torch.empty(B, self.target.n, device=self.w.device)
-        ops.prop_local(self.w.data, self.src, s.reshape(B, -1).contiguous(), out, self.n_filters)
-        return out.view(B, *self.target.shape)
+        ops.prop_local(self.w.data, self.src, s.reshape(s.shape[0], -1).contiguous(), out, self.n_filters, accumulate=accumulate)
 
-    def normalize(self) -> None:
-        """Every [kernel_prod] row of the [Cin*n_filters*conv_prod, kernel_prod] view scaled to sum `norm` (topology.py:1601,
-        :1748-1759, :1898)."""
-        if self.norm is not None:
-            if not self.w.is_cuda:
-                from . import host_path
-                return host_path.normalize_connection(self)
-            if isinstance(self.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
-            ops.normalize_local(self.w.data, float(self.norm))
+    def _describe(self, d, B, dev, scratch):
+        described = super()._describe(d, B, dev, scratch)
+        d.bias, d.cin, d.local_src = None, self.in_channels, self._table(described, "src", dev)
+        d.local_F, d.local_conv_prod, d.local_kernel_prod, d.local_n_src = self.n_filters, self.conv_prod, self.kernel_prod, self.source.n
+        return described
+
+    def _postpre(self, rule, B, lo, hi) -> None:
+        """learning.py:208-389."""
+        src, tgt = self.source, self.target
+        ops.local_postpre(self.w.data, self.src, src.s.reshape(B, -1).contiguous(), src.x.reshape(B, -1),
+                          tgt.s.reshape(B, -1).contiguous(), tgt.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
+                          self.n_filters, decay=float(rule.weight_decay), wmin=lo, wmax=hi)
 
     def reset_state_variables(self) -> None:
         super().reset_state_variables()
@@ -556,6 +667,12 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
     """Feature-pipeline connection (reference: topology.py:402-537).  The accelerated path is a
     pipeline of exactly one `Weight`."""
 
+    _kind = _lib.CONN_MCC
+    _norm_by = "columns"               # the Weight's SIGNED column sums (topology_features.py:250-266), by snn_net_run
+    _takes_mask = _host_refuses_mask = False           # (no `w`: the device path refuses a mask, the host path ignores it)
+    _multi_device = True
+    _host_compute = host_path._propagate_mcc
+
     def __init__(self, source: Nodes, target: Nodes, device, pipeline: list = [], manual_update: bool = False,
                  traces: bool = False, **kwargs) -> None:
         super().__init__(source, target, device, pipeline, **kwargs)
@@ -570,30 +687,90 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
                                       f"feature; got {[type(f).__name__ for f in self.pipeline]}")
         return self.pipeline[0]
 
+    def _on_host(self) -> bool:
+        return len(self.pipeline) == 1 and isinstance(self.pipeline[0].value, torch.Tensor) and not self.pipeline[0].value.is_cuda
+
     def compute(self, s: torch.Tensor) -> torch.Tensor:
         """out[b,j] = sum_i value[i,j]*s[b,i] in the reference's ATen sum order (topology.py:437-479)."""
         w = self._weight().value
         B = s.size(0)
         if not w.is_cuda:
-            from . import host_path
-            return host_path._propagate(self, s)
+            return self._host_compute(s)
         out = torch.empty(B, self.target.n, device=w.device)
-        ops.prop_cascade(w.data, s.reshape(B, -1).contiguous(), out)
+        self._prop_into(s.reshape(B, -1).contiguous(), out)
         return out.view(B, *self.target.shape)
+
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        ops.prop_cascade(self._weight().value.data, s, out, accumulate=accumulate)
+
+    def _host_update(self, kwargs, mask) -> None:
+        host_path._update_mcc(self, float(self.dt), kwargs)
+
+    def _host_normalize(self) -> None:
+        feat = self._weight()
+        if feat.norm is not None:
+            host_path._normalize_columns(feat.value.data, feat.norm, False)
+
+    def _rule(self):
+        return self._weight().learning_rule
+
+    def _column_slice(self, source, target, lo, hi):
+        from .topology_features import Weight
+        feat = self._weight()
+        rule = feat.learning_rule
+        from ..learning import MCC_learning
+        rule_cls = type(rule) if type(rule) in (MCC_learning.PostPre, MCC_learning.MSTDP) else None
+        lo_b, hi_b = (rule.min, rule.max) if rule_cls is not None else (-float("inf"), float("inf"))
+        f2 = Weight(feat.name, feat.value.data[:, lo:hi].clone().cpu(), range=[lo_b, hi_b], norm=feat.norm,
+                    nu=None if rule_cls is None else (float(rule.nu[0]), float(rule.nu[1])), learning_rule=rule_cls,
+                    decay=0.0 if rule_cls is None or rule.decay == 1.0 else 1.0 - float(rule.decay))
+        c2 = MulticompartmentConnection(source, target, device="cpu", pipeline=[f2], manual_update=self.manual_update)
+        if rule_cls is not None:
+            f2.learning_rule.reduction = rule.reduction
+        return c2
+
+    def _exact_learns(self) -> bool:
+        from ..learning import MCC_learning
+        rule = self._weight().learning_rule
+        if self.manual_update or isinstance(rule, MCC_learning.NoOp):
+            return False
+        if not isinstance(rule, MCC_learning.PostPre):
+            raise NotImplementedError(f"exact_run: MCC rule {type(rule).__name__} (supported: PostPre)")
+        if not (self.source.traces and self.target.traces):
+            raise AssertionError("PostPre needs traces on both layers")
+        return True
+
+    def _weights(self):
+        return self._weight(), "value"
+
+    def _describe(self, d, B, dev, scratch):
+        feat = self._weight()
+        if feat.value.device != dev:
+            feat.to(dev)
+        val = feat.value
+        if val.dtype != torch.float32 or not val.is_contiguous() or tuple(val.shape) != (self.source.n, self.target.n):
+            raise NotImplementedError(f"bindsnet_amd: Weight.value must be a contiguous float32 [{self.source.n}, "
+                                      f"{self.target.n}] tensor (got {val.dtype}, shape {tuple(val.shape)}, "
+                                      f"contiguous={val.is_contiguous()})")
+        d.kind, d.w = self._kind, dptr(val.data)
+        if feat.norm is not None:
+            if isinstance(feat.norm, torch.Tensor):
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+            ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
+            d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, dptr(ws)
+        return [self._weights()]
 
     def update(self, **kwargs) -> None:
         """Reference: topology.py:509-518 (note the default learning=False)."""
         if kwargs.get("learning", False) and not self.manual_update:
-            if len(self.pipeline) == 1 and isinstance(self.pipeline[0].value, torch.Tensor) and not self.pipeline[0].value.is_cuda:
-                from . import host_path                 # a connection on the host: plain PyTorch (network/host_path.py)
-                return host_path._update_mcc(self, float(self.dt), kwargs)
+            if self._on_host():                         # a connection on the host: plain PyTorch (network/host_path.py)
+                return self._host_update(kwargs, None)
             for f in self.pipeline:
                 f.update(**kwargs)
 
     def normalize(self) -> None:
-        if len(self.pipeline) == 1 and isinstance(self.pipeline[0].value, torch.Tensor) and not self.pipeline[0].value.is_cuda:
-            from . import host_path
-            return host_path.normalize_connection(self)
+        if self._on_host():
+            return self._host_normalize()
         for f in self.pipeline:
             f.normalize()
 

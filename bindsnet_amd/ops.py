@@ -36,6 +36,11 @@ def _ptr(t, dtype=None, allow_none=False):
 F32 = torch.float32
 
 
+def _bounds(wmin, wmax):
+    """The clamp arguments of the C ABI (has_min, wmin, has_max, wmax) from optional bounds."""
+    return int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax
+
+
 def prop_cascade(W, s, out, accumulate=False):
     """a5: out[b,j] (+)= sum_i W[i,j]*s[b,i] in ATen sum(dim=1) order."""
     B = s.shape[0]
@@ -100,14 +105,7 @@ def local_postpre(W, src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, n_filters, decay
         raise ValueError("local_postpre: operand shapes do not match the gather table")
     check(lib().snn_local_postpre(_ptr(W, F32), _ptr(src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                   _ptr(x_tgt, F32), B, Cin, n_filters, conv_prod, kernel_prod, n_src, float(nu0), float(nu1),
-                                  float(decay), int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None),
-                                  0.0 if wmax is None else wmax, _stream()), "local_postpre")
-
-
-def normalize_local(W, norm):
-    """LocalConnection1D/2D/3D.normalize (topology.py:1601 / :1748-1759 / :1898): every [kernel_prod] row of W
-    [Cin, F*conv_prod, kernel_prod] scaled to sum `norm` (snn_normalize_conv2d's arithmetic)."""
-    check(lib().snn_normalize_conv2d(_ptr(W, F32), W.shape[0] * W.shape[1], W.shape[2], float(norm), _stream()), "normalize_local")
+                                  float(decay), *_bounds(wmin, wmax), _stream()), "local_postpre")
 
 
 def prop_convnd(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
@@ -147,8 +145,7 @@ def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, w
         ws = torch.empty(B * Cout * ((L + 31) // 32), dtype=torch.int32, device=W.device)
     check(lib().snn_convnd_postpre(_ptr(W, F32), _ptr(pp_src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32),
                                    _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Cout, L, J, n_src, float(nu0), float(nu1), float(decay),
-                                   int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None),
-                                   0.0 if wmax is None else wmax, _ptr(ws, torch.int32), _stream()), "convnd_postpre")
+                                   *_bounds(wmin, wmax), _ptr(ws, torch.int32), _stream()), "convnd_postpre")
 
 
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None):
@@ -196,9 +193,7 @@ def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=
     Nin, N = W.shape
     check(lib().snn_stdp_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                  _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay,
-                                 int(wmin is not None), 0.0 if wmin is None else wmin,
-                                 int(wmax is not None), 0.0 if wmax is None else wmax,
-                                 int(assume_clamped), _stream()), "stdp_postpre")
+                                 *_bounds(wmin, wmax), int(assume_clamped), _stream()), "stdp_postpre")
 
 
 def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus,
@@ -208,8 +203,7 @@ def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward,
     check(lib().snn_mstdp_step(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
                                _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
                                reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
-                               wdecay, int(wmin is not None), 0.0 if wmin is None else wmin,
-                               int(wmax is not None), 0.0 if wmax is None else wmax, _stream()), "mstdp_step")
+                               wdecay, *_bounds(wmin, wmax), _stream()), "mstdp_step")
 
 
 def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, decay=1.0, wmin=None, wmax=None, ws=None):
@@ -219,8 +213,7 @@ def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, dec
     if ws is None:
         ws = torch.empty(2 * B * W.numel(), dtype=F32, device=W.device)
     check(lib().snn_conv2d_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                   B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, decay, int(wmin is not None),
-                                   0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax,
+                                   B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, decay, *_bounds(wmin, wmax),
                                    _ptr(ws, F32), _stream()), "conv2d_postpre")
 
 
@@ -232,8 +225,7 @@ def conv2d_mstdp_step(W, elig, p_plus, p_minus, s_src, s_tgt, reward, nu0, a_plu
     Cout, _, KH, KW = W.shape
     check(lib().snn_conv2d_mstdp_step(_ptr(W, F32), _ptr(elig, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src, "spike"),
                                       _ptr(s_tgt, "spike"), Cin, H, Wd, Cout, KH, KW, stride, pad, reward, nu0, a_plus, a_minus,
-                                      decay_plus, decay_minus, wdecay, int(wmin is not None), 0.0 if wmin is None else wmin,
-                                      int(wmax is not None), 0.0 if wmax is None else wmax, _stream()), "conv2d_mstdp_step")
+                                      decay_plus, decay_minus, wdecay, *_bounds(wmin, wmax), _stream()), "conv2d_mstdp_step")
 
 
 def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False, decay=1.0, wmin=None, wmax=None):
@@ -241,8 +233,7 @@ def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False
     B = s_src.shape[0]
     Nin, N = W.shape
     check(lib().snn_stdp_hebbian(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                 B, Nin, N, nu0, nu1, int(weight_dependent), decay, int(wmin is not None),
-                                 0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax, _stream()),
+                                 B, Nin, N, nu0, nu1, int(weight_dependent), decay, *_bounds(wmin, wmax), _stream()),
           "stdp_hebbian")
 
 
@@ -251,8 +242,7 @@ def mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_t
     Nin, N = W.shape
     check(lib().snn_mstdpet_step(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
                                  _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
-                                 a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, int(wmin is not None),
-                                 0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax, _stream()),
+                                 a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *_bounds(wmin, wmax), _stream()),
           "mstdpet_step")
 
 

@@ -24,22 +24,15 @@ from typing import Dict
 import torch
 import torch.distributed as dist
 
-from .network.topology import MulticompartmentConnection
-
 
 def _learned(network):
     """(tensor, lo, hi, norm_holder) for every connection that learns."""
     out = []
     for conn in network.connections.values():
-        if isinstance(conn, MulticompartmentConnection):
-            feat = conn.pipeline[0]
-            rule = feat.learning_rule
-            if type(rule).__name__ in ("PostPre", "MSTDP", "MSTDPET"):     # every MCC rule this package implements
-                lo, hi = rule._bounds()
-                out.append((feat.value.data, lo, hi, feat))
-        elif type(conn.update_rule).__name__ in ("PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET"):
-            lo, hi = conn.update_rule._bounds()
-            out.append((conn.w.data, lo, hi, conn))
+        rule = conn._rule()
+        if type(rule).__name__ in ("PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET"):     # every rule that learns
+            holder, attr = conn._weights()
+            out.append((getattr(holder, attr).data, *rule._bounds(), holder))
     return out
 
 
@@ -78,10 +71,8 @@ def _reject_local(network, mode: str) -> None:
     """None of the multi-device modes handles LocalConnection1D / 2D / 3D or Conv1dConnection / Conv3dConnection (their
     weights are not [source.n, target.n] matrices): such a graph raises instead of being routed through a mode built for other
     layouts."""
-    from .network.topology import (Conv1dConnection, Conv3dConnection, LocalConnection1D, LocalConnection2D,
-                                   LocalConnection3D)
     for key, conn in network.connections.items():
-        if isinstance(conn, (LocalConnection1D, LocalConnection2D, LocalConnection3D, Conv1dConnection, Conv3dConnection)):
+        if not conn._multi_device:
             raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} is not supported by the multi-device modes; "
                                       "run the network on one device")
 
@@ -130,12 +121,6 @@ def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None,
 # This is the mode whose 2 / 4 / 8-GPU results meet the north star's parity bar; the batch-sharded `sharded_run` above
 # is the north star's RCCL schedule, which does not (SURVEY.md 8(e)).
 # =====================================================================================================
-def _scalar_bound(t) -> float:
-    if isinstance(t, torch.Tensor) and t.numel() != 1:
-        raise NotImplementedError("column sharding needs scalar wmin / wmax (per-synapse bounds are not supported)")
-    return float(t)
-
-
 def column_shard_bounds(n_columns: int, world: int, rank: int, align: int = 32):
     """[lo, hi) of rank's column slice: whole blocks of `align` columns dealt out as evenly as possible (the first
     ranks get the extra blocks); a trailing partial block belongs to the last non-empty slice."""
@@ -158,12 +143,8 @@ def column_shard(network, rank: int, world: int):
     """A new Network holding target columns [lo, hi) of a coupling-free two-layer `network` (same input layer, same
     rule and constants, weights / bias / layer state sliced).  Running it on the full batch gives exactly the
     full network's numbers for those columns.  Returns (shard_network, lo, hi)."""
-    from .learning import learning as dense_rules
-    from .learning import MCC_learning as mcc_rules
     from .network import Network
     from .network.nodes import Input, LIFNodes
-    from .network.topology import Connection
-    from .network.topology_features import Weight
     _reject_local(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
@@ -185,29 +166,7 @@ def column_shard(network, rank: int, world: int):
                   trace_scale=float(Y.trace_scale) if Y.traces else 1.0, thresh=float(Y.thresh), rest=float(Y.rest),
                   reset=float(Y.reset), refrac=Y.refrac.item(), tc_decay=float(Y.tc_decay),
                   lbound=None if Y.lbound is None else float(Y.lbound))
-    if isinstance(conn, MulticompartmentConnection):
-        feat = conn._weight()
-        rule = feat.learning_rule
-        rule_cls = {mcc_rules.PostPre: mcc_rules.PostPre, mcc_rules.MSTDP: mcc_rules.MSTDP}.get(type(rule))
-        lo_b, hi_b = (rule.min, rule.max) if rule_cls is not None else (-float("inf"), float("inf"))
-        f2 = Weight(feat.name, feat.value.data[:, lo:hi].clone().cpu(), range=[lo_b, hi_b], norm=feat.norm,
-                    nu=None if rule_cls is None else (float(rule.nu[0]), float(rule.nu[1])), learning_rule=rule_cls,
-                    decay=0.0 if rule_cls is None or rule.decay == 1.0 else 1.0 - float(rule.decay))
-        c2 = MulticompartmentConnection(X2, Y2, device="cpu", pipeline=[f2], manual_update=conn.manual_update)
-        if rule_cls is not None:
-            f2.learning_rule.reduction = rule.reduction
-    elif isinstance(conn, Connection):
-        rule = conn.update_rule
-        rule_cls = type(rule) if isinstance(rule, (dense_rules.PostPre, dense_rules.MSTDP)) else None
-        kw = {}
-        if isinstance(rule, dense_rules.MSTDP):
-            kw.update(tc_plus=float(rule.tc_plus), tc_minus=float(rule.tc_minus))
-        c2 = Connection(X2, Y2, w=conn.w.data[:, lo:hi].clone().cpu(), b=None if conn.b is None else conn.b.data[lo:hi].clone().cpu(),
-                        wmin=_scalar_bound(conn.wmin), wmax=_scalar_bound(conn.wmax), norm=conn.norm, update_rule=rule_cls,
-                        nu=None if rule_cls is None else (float(rule.nu[0]), float(rule.nu[1])), reduction=rule.reduction,
-                        weight_decay=0.0 if rule.weight_decay == 1.0 else 1.0 - float(rule.weight_decay), **kw)
-    else:
-        raise NotImplementedError(f"column sharding of {type(conn).__name__} is not supported")
+    c2 = conn._column_slice(X2, Y2, lo, hi)
     shard.add_layer(X2, xn)
     shard.add_layer(Y2, yn)
     shard.add_connection(c2, *key)
@@ -217,8 +176,7 @@ def column_shard(network, rank: int, world: int):
     # an MSTDP rule keeps p_plus / p_minus / the previous spikes across run() and reset_state_variables() (learning.py:
     # 1501-1574): a rule that has already run carries them into its shard -- p_plus and the source spikes whole, p_minus
     # and the target spikes by column -- so that the exact mode stays exact for a network sharded in mid-training
-    old_rule = conn._weight().learning_rule if isinstance(conn, MulticompartmentConnection) else conn.update_rule
-    new_rule = c2._weight().learning_rule if isinstance(c2, MulticompartmentConnection) else c2.update_rule
+    old_rule, new_rule = conn._rule(), c2._rule()
     if hasattr(old_rule, "p_plus") and hasattr(new_rule, "_ensure_state"):
         if old_rule.p_plus.dim() != 2 or old_rule.p_minus.shape[-1] != N:
             raise NotImplementedError("column sharding of a rule whose state is not [batch, n] (Conv2d MSTDP, MSTDPET) is not supported")
@@ -276,29 +234,14 @@ def gather_columns(local: torch.Tensor, n_columns: int, group=None) -> torch.Ten
 # =====================================================================================================
 def _exact_check(network):
     _reject_local(network, "exact_run")
-    from .learning import MCC_learning as mcc_rules
-    from .learning import learning as dense_rules
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes
-    from .network.topology import Connection
     for name, layer in network.layers.items():
         if type(layer) not in (Input, LIFNodes, DiehlAndCookNodes):
             raise NotImplementedError(f"exact_run: layer type {type(layer).__name__} ('{name}')")
     learned = []
     for key, conn in network.connections.items():
-        if isinstance(conn, MulticompartmentConnection):
-            rule = conn._weight().learning_rule
-            if isinstance(rule, mcc_rules.PostPre) and not conn.manual_update:
-                if not (conn.source.traces and conn.target.traces):
-                    raise AssertionError("PostPre needs traces on both layers")
-                learned.append(key)
-            elif not isinstance(rule, mcc_rules.NoOp) and not conn.manual_update:
-                raise NotImplementedError(f"exact_run: MCC rule {type(rule).__name__} (supported: PostPre)")
-        elif type(conn) is Connection:
-            if not isinstance(conn.update_rule, dense_rules.NoOp):
-                raise NotImplementedError("exact_run: learning on a dense Connection (Input -> Connection -> LIFNodes graphs shard "
-                                          "their columns exactly with column_shard, without any collective)")
-        else:
-            raise NotImplementedError(f"exact_run: connection type {type(conn).__name__}")
+        if conn._exact_learns():
+            learned.append(key)
         if isinstance(network.layers[key[1]], Input):
             raise NotImplementedError("exact_run: a connection into an Input layer")
     return learned
@@ -315,7 +258,7 @@ class _ExactHost:
         return self
 
     def prop(self, conn, s_rows, cur, acc):
-        out = self.hp._propagate(conn, s_rows.view(s_rows.shape[0], *conn.source.shape))
+        out = conn._host_compute(s_rows.view(s_rows.shape[0], *conn.source.shape))
         if acc:
             cur += out.view_as(cur)
         else:
@@ -369,11 +312,7 @@ class _ExactDevice:
         return self
 
     def prop(self, conn, s_rows, cur, acc):
-        if isinstance(conn, MulticompartmentConnection):
-            self.ops.prop_cascade(conn._weight().value.data, s_rows, cur, accumulate=acc)
-        else:
-            b = getattr(conn, "b", None)
-            self.ops.prop_dense(conn.w.data, s_rows, cur, bias=None if b is None else b.data, accumulate=acc)
+        conn._prop_into(s_rows, cur, accumulate=acc)
 
     def trace(self, layer, s, x):
         from .network.nodes import _f
