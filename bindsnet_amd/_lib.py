@@ -75,7 +75,10 @@ class LayerDesc(C.Structure):
                 ("raster_v", C.c_void_p), ("current", C.c_void_p),
                 ("clamp", C.c_void_p), ("unclamp", C.c_void_p), ("clamp_per_step", C.c_int), ("unclamp_per_step", C.c_int),
                 ("inject_v", C.c_void_p), ("inject_per_step", C.c_int), ("inject_len", C.c_int),
-                ("ext_current", C.c_void_p), ("thresh_vec", C.c_void_p)]
+                ("ext_current", C.c_void_p), ("thresh_vec", C.c_void_p),
+                ("aux", C.c_void_p), ("aux_decay", C.c_float),
+                ("izh_a", C.c_void_p), ("izh_b", C.c_void_p), ("izh_c", C.c_void_p), ("izh_d", C.c_void_p),
+                ("izh_St", C.c_void_p)]
 
 
 class ConnDesc(C.Structure):
@@ -112,6 +115,8 @@ class FillSegment(C.Structure):
 
 MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
+LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH = 3, 4, 5, 6, 7
+IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND = 0, 1, 2, 3, 4
 RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET = 0, 1, 2, 3, 4, 5
 
@@ -134,6 +139,11 @@ _SIGS = {
     "snn_input_step": ([_vp, _vp, _l, _f, _f, _i, _vp, _vp], _i),
     "snn_lif_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_lif_step_vth": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp, _vp], _i),
+    "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
+    "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
+    "snn_boosted_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
+    "snn_clif_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _f, _vp, _vp, _vp], _i),
+    "snn_izh_step": ([_vp] * 10 + [_i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_dc_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(DcParams), _vp, _ll, _vp, _vp, _vp, _vp, _vp], _i),
     "snn_dc_arbitrate": ([_vp, _vp, _i, _i, C.POINTER(DcParams), _vp, _ll, _vp, _vp, _vp, _vp], _i),
     "snn_stdp_postpre": ([_vp] * 5 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _i, _vp], _i),

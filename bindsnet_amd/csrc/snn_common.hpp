@@ -51,4 +51,82 @@ __host__ __device__ __forceinline__ uint8_t dc_update(float &v, float &rc, float
     return sp;
 }
 
+// McCullochPitts.forward, bindsnet/network/nodes.py:285-286.
+__host__ __device__ __forceinline__ uint8_t mcp_update(float &v, float cur, const snn_lif_params &p) {
+    v = cur;                            // :285 (the reference aliases; the layer keeps a copy)
+    return v >= p.thresh;               // :286
+}
+
+// IFNodes.forward, bindsnet/network/nodes.py:379-393.  No decay, no rest; the gate reads rc BEFORE the decrement.
+__host__ __device__ __forceinline__ uint8_t if_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+    const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :379 (refrac_count <= 0).float() * x
+    const float gx = gate * cur;
+    float vv = v + gx;
+    rc = rc - p.dt;                     // :382
+    const uint8_t sp = vv >= p.thresh;  // :385
+    if (sp) { rc = p.refrac; vv = p.reset; }                 // :388-389
+    if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :392-393
+    v = vv;
+    return sp;
+}
+
+// BoostedLIFNodes.forward, bindsnet/network/nodes.py:629-646.  `cur` must already be zeroed by the caller where rc > 0
+// (:633 masks with the counter BEFORE it is decremented).  No rest, no lbound; the reset value is the constant 0.
+__host__ __device__ __forceinline__ uint8_t boosted_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+    float vv = v * p.decay;             // :629
+    rc = rc - p.dt;                     // :636
+    vv = vv + cur;                      // :639
+    const uint8_t sp = vv >= p.thresh;  // :642
+    if (sp) { rc = p.refrac; vv = 0.f; }                     // :645-646
+    v = vv;
+    return sp;
+}
+
+// CurrentLIFNodes.forward, bindsnet/network/nodes.py:770-789.  The gate reads rc AFTER the decrement.
+__host__ __device__ __forceinline__ uint8_t clif_update(float &v, float &rc, float &i, float cur, float i_decay,
+                                                        const snn_lif_params &p) {
+    float vv = v - p.rest;              // :770
+    vv = p.decay * vv;
+    vv = vv + p.rest;
+    float ii = i * i_decay;             // :771
+    rc = rc - p.dt;                     // :774
+    ii = ii + cur;                      // :777
+    const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :778
+    const float gi = gate * ii;
+    vv = vv + gi;
+    const uint8_t sp = vv >= p.thresh;  // :781
+    if (sp) { rc = p.refrac; vv = p.reset; }                 // :784-785
+    if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :788-789
+    v = vv; i = ii;
+    return sp;
+}
+
+// IzhikevichNodes.forward without its lateral sum, bindsnet/network/nodes.py:1274-1294.  s_in: last step's spike of this
+// neuron; cur: the input current with the lateral sum already added (:1279).
+__host__ __device__ __forceinline__ uint8_t izh_update(float &v, float &u, uint8_t s_in, float cur, float a, float b, float c,
+                                                       float d, const snn_lif_params &p) {
+    float vv = v, uu = u;
+    if (s_in) { vv = c; uu = uu + d; }  // :1274-1275
+    const float h = p.dt * 0.5f;
+    for (int half = 0; half < 2; ++half) {                   // :1285-1286, left to right
+        float t = vv * vv;              // v**2
+        t = 0.04f * t;
+        const float t5 = 5.0f * vv;
+        t = t + t5;
+        t = t + 140.0f;
+        t = t - uu;
+        t = t + cur;
+        t = h * t;
+        vv = vv + t;
+    }
+    const float da = p.dt * a;          // :1287
+    float w = b * vv;
+    w = w - uu;
+    w = da * w;
+    uu = uu + w;
+    if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :1290-1291
+    v = vv; u = uu;
+    return vv >= p.thresh;              // :1294
+}
+
 }  // namespace snn

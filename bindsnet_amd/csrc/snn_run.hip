@@ -114,6 +114,23 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (!d.v || !d.refrac || !d.s || !d.current) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
                 break;
+            case SNN_LAYER_IZH:               // nodes.py:1147: u in aux, a .. d and the transposed lateral matrix
+                if (!d.aux || !d.izh_a || !d.izh_b || !d.izh_c || !d.izh_d || !d.izh_St) return SNN_ERR_INVALID;
+                if (d.n > SNN_IZH_MAX_N) return SNN_ERR_UNSUPPORTED;
+                if (!d.v || !d.s || !d.current || d.thresh_vec) return SNN_ERR_INVALID;
+                if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
+                break;
+            case SNN_LAYER_CURRENT:           // nodes.py:681: the synaptic current i in aux
+                if (!d.aux) return SNN_ERR_INVALID;
+                /* fallthrough */
+            case SNN_LAYER_IF:                // nodes.py:308
+            case SNN_LAYER_BOOSTED:           // nodes.py:562
+                if (!d.refrac) return SNN_ERR_INVALID;
+                /* fallthrough */
+            case SNN_LAYER_MCP:               // nodes.py:231
+                if (!d.v || !d.s || !d.current || d.thresh_vec) return SNN_ERR_INVALID;
+                if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
+                break;
             default: return SNN_ERR_INVALID;
         }
     }
@@ -214,6 +231,12 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                    d.inject_v + (d.inject_per_step ? (size_t)t * len : 0), (long)B * d.n, len);
             }
             if (d.kind == SNN_LAYER_LIF) TRY(snn_lif_step_vth(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, d.thresh_vec, rs, rv, st));
+            else if (d.kind == SNN_LAYER_MCP) TRY(snn_mcp_step(d.v, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
+            else if (d.kind == SNN_LAYER_IF) TRY(snn_if_step(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
+            else if (d.kind == SNN_LAYER_BOOSTED) TRY(snn_boosted_step(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
+            else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, rs, rv, st));
+            else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
+                                                              &d.p.lif, rs, rv, st));
             else if (R->rng && d.p.one_spike) {   // device generator: membrane -> draws for this step -> arbitration
                 TRY(snn_launch_dc_membrane(d.v, d.refrac, d.s, d.theta, d.current, B, d.n, d.p, R->cursor, rv, st));
                 TRY(snn_launch_rng_fill(R->rng, d.s, B, d.n, R->qbuf, R->cursor, st));
@@ -335,9 +358,11 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (L[l].thresh_vec) mode = 1;      // per-neuron thresholds: generic plan
+    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes: generic plan only
+    for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND) local = true;   // plan only; no fused plan is offered the graph
-    if (local) { mode = 1; conv_rule = false; }
+    if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));
         if (!handled) mode = 1;

@@ -5,7 +5,7 @@ package still constructs and runs where there is no GPU (SURVEY.md 8(b) fallback
 second, independent statement of the same semantics: tests/test_host_path.py pins it to the reference-generated fixtures
 the GPU tests use.  It is selected by Network.run only when the network's tensors are CPU tensors; it never touches
 libsnnhip and has nothing to do with oracle/ (test infrastructure).  Supported on this path: Input / LIFNodes /
-DiehlAndCookNodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
+DiehlAndCookNodes / AdaptiveLIFNodes / McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
 rule / PostPre / MSTDP / Hebbian / WeightDependentPostPre / MSTDPET), Conv2dConnection (no rule / PostPre / MSTDP at batch 1);
 clamp / unclamp / injects_v / masks / one_step / reward; Monitor / NetworkMonitor.
 
@@ -118,6 +118,69 @@ def _lif_membrane(layer, x) -> None:
 
 def _step_lif(layer, x) -> None:
     _lif_membrane(layer, x)
+    _trace(layer, layer.s)
+
+
+def _step_mcp(layer, x) -> None:
+    """nodes.py:278-288."""
+    layer.v = x
+    layer.s = layer.v >= layer.thresh
+    _trace(layer, layer.s)
+
+
+def _reset_and_bound(layer, reset) -> None:
+    """What the threshold test is followed by in nodes.py:388-393 / :784-789: refractory period, reset, lower bound."""
+    layer.refrac_count.masked_fill_(layer.s, layer.refrac)
+    layer.v.masked_fill_(layer.s, reset)
+    if layer.lbound is not None:
+        layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
+
+
+def _step_if(layer, x) -> None:
+    """nodes.py:371-395."""
+    layer.v += (layer.refrac_count <= 0).float() * x
+    layer.refrac_count -= layer.dt
+    layer.s = layer.v >= layer.thresh
+    _reset_and_bound(layer, layer.reset)
+    _trace(layer, layer.s)
+
+
+def _step_boosted(layer, x) -> None:
+    """nodes.py:621-648."""
+    layer.v *= layer.decay
+    x.masked_fill_(layer.refrac_count > 0, 0.0)        # (in place on the summed input, as the reference does)
+    layer.refrac_count -= layer.dt
+    layer.v += x
+    layer.s = layer.v >= layer.thresh
+    layer.refrac_count.masked_fill_(layer.s, layer.refrac)
+    layer.v.masked_fill_(layer.s, 0)
+    _trace(layer, layer.s)
+
+
+def _step_clif(layer, x) -> None:
+    """nodes.py:762-791."""
+    layer.v = layer.decay * (layer.v - layer.rest) + layer.rest
+    layer.i *= layer.i_decay
+    layer.refrac_count -= layer.dt
+    layer.i += x
+    layer.v += (layer.refrac_count <= 0).float() * layer.i
+    layer.s = layer.v >= layer.thresh
+    _reset_and_bound(layer, layer.reset)
+    _trace(layer, layer.s)
+
+
+def _step_izh(layer, x) -> None:
+    """nodes.py:1265-1296; the lateral sum goes into `x` in place, as in the reference."""
+    layer.v = torch.where(layer.s, layer.c, layer.v)
+    layer.u = torch.where(layer.s, layer.u + layer.d, layer.u)
+    if layer.s.any():
+        x += torch.cat([layer.S[:, layer.s[b]].sum(dim=1)[None] for b in range(layer.s.shape[0])], dim=0)
+    for _ in range(2):
+        layer.v += layer.dt * 0.5 * (0.04 * layer.v ** 2 + 5 * layer.v + 140 - layer.u + x)
+    layer.u += layer.dt * layer.a * (layer.b * layer.v - layer.u)
+    if layer.lbound is not None:
+        layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
+    layer.s = layer.v >= layer.thresh
     _trace(layer, layer.s)
 
 
@@ -426,7 +489,7 @@ def _update_dense(conn, kwargs, mask) -> None:
 
 
 def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs) -> None:
-    from .nodes import Input, LIFNodes, _AdaptiveThresholdNodes
+    from .nodes import Input, Nodes
     clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
     injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
     if isinstance(kwargs.get("a_plus"), dict) or isinstance(kwargs.get("a_minus"), dict):
@@ -437,7 +500,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
         if conn._host_refuses_mask and masks.get(key) is not None:
             raise NotImplementedError("bindsnet_amd: weight masks are supported on dense connections")
     for name, layer in network.layers.items():
-        if not isinstance(layer, (Input, LIFNodes, _AdaptiveThresholdNodes)):
+        if type(layer)._host_step is Nodes._host_step:
             raise NotImplementedError(f"bindsnet_amd host path: layer type {type(layer).__name__}")
         if isinstance(layer, Input) and name not in inputs:
             raise NotImplementedError(f"bindsnet_amd: Input layer '{name}' needs an entry in `inputs`")
@@ -478,7 +541,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
                 if inj is not None:
                     inj = torch.as_tensor(inj)
                     layer.v += inj[t] if inj.dim() >= 2 else inj
-                (_step_dc if isinstance(layer, _AdaptiveThresholdNodes) else _step_lif)(layer, x)
+                layer._host_step(x)
                 for table, value in ((clamps, 1), (unclamps, 0)):
                     m = table.get(name)
                     if m is not None:

@@ -452,10 +452,13 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                             wanted.append((m, (name, "s")))
                     dyn_inputs.append((i, name, layer, wanted))
                     continue
+                if type(layer)._describe is Nodes._describe:
+                    layer._describe(d, keep, scalars)             # (raises: a layer type outside the accelerated path)
                 self._check_state(layer, B, dev)
                 requests = self._monitor_requests(layer, name)
                 cur = self._scratch("cur_" + name, (B, layer.n), torch.float32, dev)
-                d.v, d.refrac, d.s, d.current = _dptr(layer.v), _dptr(layer.refrac_count), _dptr(layer.s), _dptr(cur)
+                d.v, d.s, d.current = _dptr(layer.v), _dptr(layer.s), _dptr(cur)
+                d.refrac = _dptr(layer.refrac_count) if "refrac_count" in layer._STATE else None
                 d.x = _dptr(layer.x) if layer.traces else None
                 dyn_layers.append((i, layer, requests))
                 # clamp / unclamp / injects_v (network.py:395-429): [n] masks or values, or one slice per timestep
@@ -480,21 +483,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     inj = (inj[:T] if per_step else inj).contiguous()
                     keep.append(inj)
                     d.inject_v, d.inject_per_step, d.inject_len = _dptr(inj), int(per_step), one.numel()
-                if isinstance(layer, _AdaptiveThresholdNodes):        # DiehlAndCookNodes, AdaptiveLIFNodes (one_spike = 0)
-                    d.kind, d.p, d.theta = _lib.LAYER_DC, layer._dc_params(), _dptr(layer.theta)
-                    if layer.one_spike:
-                        max_draws = max(max_draws, B * layer.n)
-                elif isinstance(layer, LIFNodes):
-                    d.kind = _lib.LAYER_LIF
-                    d.p.lif = layer._lif_params()
-                    tv = layer._thresh_vec()               # per-neuron thresholds (nodes.py:425-498; generic plan)
-                    if tv is not None:
-                        keep.append(tv)
-                        d.thresh_vec = _dptr(tv)
-                        scalars.append((layer.thresh, layer.thresh._version))      # (an in-place change rebuilds: tv may be a converted copy)
-                else:
-                    raise NotImplementedError(f"bindsnet_amd: layer type {type(layer).__name__} is outside the "
-                                              "accelerated path (Input, LIFNodes, DiehlAndCookNodes, AdaptiveLIFNodes)")
+                max_draws = max(max_draws, layer._describe(d, keep, scalars))      # the class's own part: kind, parameters, extra state
         except BaseException:
             _nodes._SCALARS = None
             raise
@@ -536,7 +525,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta") + (("thresh",) if isinstance(getattr(layer, "thresh", None), torch.Tensor) and layer.thresh.numel() > 1 else ()):
+            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d") + (("thresh",) if isinstance(getattr(layer, "thresh", None), torch.Tensor) and layer.thresh.numel() > 1 else ()):
                 t = getattr(layer, attr, None)
                 if isinstance(t, torch.Tensor):
                     ptrs.append((layer, attr, t.data_ptr()))
@@ -656,7 +645,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
 
     @staticmethod
     def _check_state(layer, B, dev):
-        for nm in ("v", "refrac_count") + (("x",) if layer.traces else ()):
+        for nm in layer._STATE + (("x",) if layer.traces else ()):
             t = getattr(layer, nm)
             if t.device != dev or t.dtype != torch.float32 or t.numel() != B * layer.n or not t.is_contiguous():
                 raise ValueError(f"layer state '{nm}' must be a contiguous float32 [{B}, {layer.n}] tensor on {dev}")

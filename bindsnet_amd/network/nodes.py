@@ -1,6 +1,8 @@
 """Neuron groups: API mirror of bindsnet/network/nodes.py for the layer types on the hot path
-(`Nodes`, `Input`, `LIFNodes`, `DiehlAndCookNodes`, `AdaptiveLIFNodes`); the arithmetic lives in libsnnhip
-(snn_input_step / snn_lif_step / snn_dc_step).
+(`Nodes`, `Input`, `McCullochPitts`, `IFNodes`, `LIFNodes`, `BoostedLIFNodes`, `CurrentLIFNodes`, `AdaptiveLIFNodes`,
+`DiehlAndCookNodes`, `IzhikevichNodes`); the arithmetic lives in libsnnhip (snn_input_step / snn_lif_step / snn_dc_step /
+snn_mcp_step / snn_if_step / snn_boosted_step / snn_clif_step / snn_izh_step).  Each class fills its own snn_layer_desc
+(`_describe`), so Network._build_descriptors needs no table of layer types.
 
 State is held in the same attributes as the reference (`s`, `x`, `v`, `refrac_count`, `theta`,
 `decay`, `trace_decay`, ...), so monitors, pickling and user code that pokes at them keep working.
@@ -102,6 +104,39 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
             p.trace_decay, p.trace_scale = _f(self.trace_decay), _f(self.trace_scale)
             p.traces_additive = int(self.traces_additive)
 
+    # float32 [B, n] state tensors (beside `s` and `x`) whose addresses the layer's snn_layer_desc holds
+    _STATE = ("v", "refrac_count")
+
+    def _node_params(self, **fields) -> _lib.LifParams:
+        """snn_lif_params of a layer that has `thresh`: thresh, dt, lbound and the trace fields, plus the named ones."""
+        p = _lib.LifParams()
+        p.thresh, p.dt = _f(self.thresh), _f(self.dt)
+        for key, value in fields.items():
+            setattr(p, key, _f(value))
+        lbound = getattr(self, "lbound", None)
+        p.has_lbound = int(lbound is not None)
+        p.lbound = _f(lbound) if lbound is not None else 0.0
+        self._trace_fields(p)
+        return p
+
+    def _describe(self, d: _lib.LayerDesc, keep: list, scalars: list) -> int:
+        """Fill the class-specific part of this layer's snn_layer_desc `d` (kind, parameters, extra state); the caller has set n,
+        v, s, x, refrac, current and the run() options.  `keep` takes tensors that must outlive the launch, `scalars` (tensor,
+        version) pairs whose in-place change must rebuild the descriptors.  Returns the number of one_spike draws one step of
+        the layer may consume."""
+        raise NotImplementedError(f"bindsnet_amd: layer type {type(self).__name__} is outside the accelerated path (Input, "
+                                  "McCullochPitts, IFNodes, LIFNodes, BoostedLIFNodes, CurrentLIFNodes, AdaptiveLIFNodes, "
+                                  "DiehlAndCookNodes, IzhikevichNodes)")
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        """One step on the host path (network/host_path.py)."""
+        raise NotImplementedError(f"bindsnet_amd host path: layer type {type(self).__name__}")
+
+    def _own_spikes(self) -> None:
+        """`s` as the step kernels write it: a bool [B, *shape] tensor beside `v`."""
+        if self.s.dtype != torch.bool or self.s.shape != self.v.shape:
+            self.s = torch.zeros_like(self.v, dtype=torch.bool)
+
     def forward(self, x: torch.Tensor) -> None:
         raise NotImplementedError
 
@@ -118,10 +153,13 @@ class Input(Nodes, AbstractInput):
         super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
                          trace_scale=trace_scale, sum_input=sum_input)
 
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_input(self, x)
+
     def forward(self, x: torch.Tensor) -> None:
         if not x.is_cuda:                                 # a layer on the host: plain PyTorch (network/host_path.py)
-            from . import host_path
-            return host_path._step_input(self, x)
+            return self._host_step(x)
         self.s = x
         if self.traces:
             ops.input_step(x.contiguous(), self.x, _f(self.trace_decay), _f(self.trace_scale), self.traces_additive)
@@ -188,11 +226,24 @@ class LIFNodes(Nodes):
         self._trace_fields(p)
         return p
 
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind = _lib.LAYER_LIF
+        d.p.lif = self._lif_params()
+        tv = self._thresh_vec()                           # per-neuron thresholds (nodes.py:425-498; generic plan)
+        if tv is not None:
+            keep.append(tv)
+            d.thresh_vec = _lib.dptr(tv)
+            scalars.append((self.thresh, self.thresh._version))      # (an in-place change rebuilds: tv may be a converted copy)
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_lif(self, x)
+
     def forward(self, x: torch.Tensor) -> None:
         """One step (nodes.py:500-529); `x` is masked in place where refractory, as in the reference."""
         if not self.v.is_cuda:                            # a layer on the host: plain PyTorch (network/host_path.py)
-            from . import host_path
-            return host_path._step_lif(self, x)
+            return self._host_step(x)
         if self.s.dtype != torch.bool or self.s.shape != self.v.shape:
             self.s = torch.zeros_like(self.v, dtype=torch.bool)
         ops.lif_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._lif_params(),
@@ -254,12 +305,19 @@ class _AdaptiveThresholdNodes(Nodes):
         p.learning, p.one_spike = int(self.learning), int(self.one_spike)
         return p
 
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind, d.p, d.theta = _lib.LAYER_DC, self._dc_params(), _lib.dptr(self.theta)
+        return self.v.shape[0] * self.n if self.one_spike else 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_dc(self, x)
+
     def forward(self, x: torch.Tensor) -> None:
         """One step (nodes.py:1069-1111).  The winner draw consumes the global CPU generator
         exactly like torch.multinomial does in the reference (see bindsnet_amd/rng.py)."""
         if not self.v.is_cuda:                            # a layer on the host: plain PyTorch (network/host_path.py)
-            from . import host_path
-            return host_path._step_dc(self, x)
+            return self._host_step(x)
         from ..rng import NoiseStream
         if self.s.dtype != torch.bool or self.s.shape != self.v.shape:
             self.s = torch.zeros_like(self.v, dtype=torch.bool)
@@ -295,3 +353,297 @@ class AdaptiveLIFNodes(_AdaptiveThresholdNodes):
                          trace_scale=trace_scale, sum_input=sum_input, thresh=thresh, rest=rest, reset=reset, refrac=refrac,
                          tc_decay=tc_decay, theta_plus=theta_plus, tc_theta_decay=tc_theta_decay, lbound=lbound,
                          one_spike=False)
+
+
+class McCullochPitts(Nodes):
+    """McCulloch-Pitts layer (reference: nodes.py:231-305): v = x, s = v >= thresh.  The reference makes `v` an alias of the
+    input tensor; on the device this layer holds its own [B, n] copy of it (the step kernel writes it), on the host it
+    aliases like the reference."""
+    _STATE = ("v",)
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = 1.0, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("thresh", _buf(thresh, torch.float))
+        self.register_buffer("v", torch.FloatTensor())
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        self.v = torch.zeros(batch_size, *self.shape, device=self.v.device)
+
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind, d.p.lif = _lib.LAYER_MCP, self._node_params()
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_mcp(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:278-288)."""
+        if not x.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        ops.mcp_step(self.v, self.s, self.x if self.traces else None, x, self._node_params())
+
+
+class IFNodes(Nodes):
+    """Integrate-and-fire layer (reference: nodes.py:308-415): no decay, no rest; state starts at `reset`."""
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = -52.0, reset: Scalar = -65.0, refrac: Union[int, torch.Tensor] = 5,
+                 lbound: float = None, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("reset", _buf(reset, torch.float))
+        self.register_buffer("thresh", _buf(thresh, torch.float))
+        self.register_buffer("refrac", _buf(refrac))
+        self.register_buffer("v", torch.FloatTensor())
+        self.register_buffer("refrac_count", torch.FloatTensor())
+        self.lbound = lbound
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        dev = self.v.device
+        self.v = self.reset.to(dev) * torch.ones(batch_size, *self.shape, device=dev)
+        self.refrac_count = torch.zeros_like(self.v)
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.v.fill_(_f(self.reset))
+        self.refrac_count.zero_()
+
+    def _params(self) -> _lib.LifParams:
+        return self._node_params(reset=self.reset, refrac=self.refrac)
+
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind, d.p.lif = _lib.LAYER_IF, self._params()
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_if(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:371-395)."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        ops.if_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._params())
+
+
+class BoostedLIFNodes(Nodes):
+    """LIF without rest, reset value or lower bound (reference: nodes.py:562-678): the membrane decays towards 0 and is reset
+    to 0.  `refrac_count` is an integer scalar until set_batch_size() makes it a float [B, n] tensor, as in the reference."""
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = 13.0, refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 100.0,
+                 **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("thresh", _buf(thresh, torch.float))
+        self.register_buffer("refrac", _buf(refrac))
+        self.register_buffer("tc_decay", _buf(tc_decay, torch.float))
+        self.register_buffer("decay", torch.zeros(*self.shape))
+        self.register_buffer("v", torch.FloatTensor())
+        self.register_buffer("refrac_count", torch.tensor(0))
+
+    def compute_decays(self, dt) -> None:
+        super().compute_decays(dt=dt)
+        self.decay = torch.exp(-self.dt / self.tc_decay.cpu()).to(self.tc_decay.device)
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        self.v = torch.zeros(batch_size, *self.shape, device=self.v.device)
+        self.refrac_count = torch.zeros_like(self.v, device=self.refrac_count.device)
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.v.fill_(0)
+        self.refrac_count.zero_()
+
+    def _params(self) -> _lib.LifParams:
+        return self._node_params(decay=self.decay, refrac=self.refrac)
+
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind, d.p.lif = _lib.LAYER_BOOSTED, self._params()
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_boosted(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:621-648); `x` is masked in place where refractory, as in the reference."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        ops.boosted_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._params())
+
+
+class CurrentLIFNodes(Nodes):
+    """Current-based LIF layer (reference: nodes.py:681-826): the input feeds a decaying synaptic current `i`, which feeds
+    the membrane."""
+    _STATE = ("v", "refrac_count", "i")
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
+                 refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 100.0, tc_i_decay: Scalar = 2.0,
+                 lbound: float = None, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("rest", _buf(rest))
+        self.register_buffer("reset", _buf(reset))
+        self.register_buffer("thresh", _buf(thresh))
+        self.register_buffer("refrac", _buf(refrac))
+        self.register_buffer("tc_decay", _buf(tc_decay))
+        self.register_buffer("decay", torch.empty_like(self.tc_decay))
+        self.register_buffer("tc_i_decay", _buf(tc_i_decay))
+        self.register_buffer("i_decay", torch.empty_like(self.tc_i_decay))
+        self.register_buffer("v", torch.FloatTensor())
+        self.register_buffer("i", torch.FloatTensor())
+        self.register_buffer("refrac_count", torch.FloatTensor())
+        self.lbound = lbound
+
+    def compute_decays(self, dt) -> None:
+        super().compute_decays(dt=dt)
+        dev = self.tc_decay.device
+        self.decay = torch.exp(-self.dt / self.tc_decay.cpu()).to(dev)
+        self.i_decay = torch.exp(-self.dt / self.tc_i_decay.cpu()).to(dev)
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        dev = self.v.device
+        self.v = self.rest.to(dev) * torch.ones(batch_size, *self.shape, device=dev)
+        self.i = torch.zeros_like(self.v, device=self.i.device)
+        self.refrac_count = torch.zeros_like(self.v, device=self.refrac_count.device)
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.v.fill_(_f(self.rest))
+        self.i.zero_()
+        self.refrac_count.zero_()
+
+    def _params(self) -> _lib.LifParams:
+        return self._node_params(decay=self.decay, rest=self.rest, reset=self.reset, refrac=self.refrac)
+
+    def _describe(self, d, keep, scalars) -> int:
+        d.kind, d.p.lif = _lib.LAYER_CURRENT, self._params()
+        d.aux, d.aux_decay = _lib.dptr(self.i), _f(self.i_decay)
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_clif(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:762-791)."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        ops.clif_step(self.v, self.refrac_count, self.i, self.s, self.x if self.traces else None, x, self._params(),
+                      _f(self.i_decay))
+
+
+class IzhikevichNodes(Nodes):
+    """Izhikevich layer (reference: nodes.py:1147-1316) with its lateral matrix `S`.  The constructor draws `r` and `S` from
+    the global generator in the reference's order and leaves it where the reference does.  `n` is required.
+
+    On the device the step is one kernel (snn_izh_step); it reads the lateral matrix transposed, from a copy kept beside the
+    user-visible `S` and refreshed when `S` is replaced, changed in place or moved.  Layers of more than `_lib.IZH_MAX_N`
+    neurons raise NotImplementedError there: the lateral sum's order is pinned against torch up to that size only."""
+    _STATE = ("v", "u")
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, excitatory: float = 1, thresh: Scalar = 45.0, rest: Scalar = -65.0, lbound: float = None,
+                 **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        if n is None:
+            raise TypeError("IzhikevichNodes needs `n` (the reference draws torch.rand(n))")
+        self.register_buffer("rest", _buf(rest))
+        self.register_buffer("thresh", _buf(thresh))
+        self.lbound = lbound
+        excitatory = min(1, max(0, excitatory))
+
+        def population(count: int, excit: bool):
+            """(r, a, b, c, d, columns of S) of `count` regular-spiking excitatory / fast-spiking inhibitory neurons: r first,
+            then S, from the global generator."""
+            r = torch.rand(count)
+            if excit:
+                return (r, 0.02 * torch.ones(count), 0.2 * torch.ones(count), -65.0 + 15 * (r ** 2), 8 - 6 * (r ** 2),
+                        0.5 * torch.rand(n, count))
+            return r, 0.02 + 0.08 * r, 0.25 - 0.05 * r, -65.0 * torch.ones(count), 2 * torch.ones(count), -torch.rand(n, count)
+
+        if excitatory == 1 or excitatory == 0:
+            parts = population(n, excitatory == 1)
+            flags = (torch.ones(n) if excitatory == 1 else torch.zeros(n)).byte()
+        else:
+            ex = int(n * excitatory)
+            parts = [torch.zeros(n) for _ in range(5)] + [torch.zeros(n, n)]
+            for cols, excit in ((slice(0, ex), True), (slice(ex, n), False)):      # excitatory draws first
+                for whole, part in zip(parts, population(len(range(n)[cols]), excit)):
+                    whole[..., cols] = part
+            flags = torch.zeros(n).byte()
+            flags[:ex] = 1
+        for name, value in zip(("r", "a", "b", "c", "d", "S"), parts):
+            self.register_buffer(name, value)
+        self.register_buffer("excitatory", flags)
+        self.register_buffer("v", self.rest * torch.ones(n))
+        self.register_buffer("u", self.b * self.v)
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        dev = self.v.device
+        self.v = self.rest.to(dev) * torch.ones(batch_size, *self.shape, device=dev)
+        self.u = self.b * self.v
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.v.fill_(_f(self.rest))
+        self.u = self.b * self.v
+
+    def _St(self) -> torch.Tensor:
+        """The lateral matrix as the step kernel reads it: transposed, contiguous f32 beside `v` (cached like _thresh_vec)."""
+        S = self.S
+        cached = self.__dict__.get("_St_dev")
+        if cached is None or cached[0] is not S or cached[1] != S._version or cached[2].device != self.v.device:
+            cached = self.__dict__["_St_dev"] = (S, S._version, S.detach().to(self.v.device, torch.float32).t().contiguous())
+        return cached[2]
+
+    def _abcd(self):
+        if self.n > _lib.IZH_MAX_N:
+            raise NotImplementedError(f"bindsnet_amd: IzhikevichNodes of more than {_lib.IZH_MAX_N} neurons (the order of the "
+                                      "lateral sum is pinned against torch up to that size only)")
+        out = []
+        for name in ("a", "b", "c", "d"):
+            t = getattr(self, name)
+            if t.device != self.v.device or t.dtype != torch.float32 or t.numel() != self.n or not t.is_contiguous():
+                raise ValueError(f"IzhikevichNodes.{name} must be a contiguous float32 [{self.n}] tensor on {self.v.device}")
+            out.append(t)
+        if tuple(self.S.shape) != (self.n, self.n):
+            raise ValueError(f"IzhikevichNodes.S must be [{self.n}, {self.n}]")
+        return out
+
+    def _describe(self, d, keep, scalars) -> int:
+        a, b, c, dd = self._abcd()
+        St = self._St()
+        keep.append(St)
+        scalars.append((self.S, self.S._version))         # (an in-place change of S rebuilds: St is a copy)
+        d.kind, d.p.lif = _lib.LAYER_IZH, self._node_params()
+        d.aux = _lib.dptr(self.u)
+        d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St = (_lib.dptr(t) for t in (a, b, c, dd, St))
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_izh(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:1265-1296); the lateral sum is added to `x` in place, as in the reference."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        a, b, c, d = self._abcd()
+        ops.izh_step(self.v, self.u, self.s, self.x if self.traces else None, x, a, b, c, d, self._St(), self._node_params())

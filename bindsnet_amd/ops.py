@@ -164,6 +164,52 @@ def lif_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None, thr
           "lif_step")
 
 
+def _node_args(v):
+    B = v.shape[0]
+    return B, v.numel() // B
+
+
+def mcp_step(v, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+    """McCullochPitts.forward (nodes.py:278-288): v = I, s = v >= thresh, trace."""
+    B, N = _node_args(v)
+    check(lib().snn_mcp_step(_ptr(v, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p),
+                             _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "mcp_step")
+
+
+def if_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+    """IFNodes.forward (nodes.py:371-395)."""
+    B, N = _node_args(v)
+    check(lib().snn_if_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p),
+                            _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "if_step")
+
+
+def boosted_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+    """BoostedLIFNodes.forward (nodes.py:621-648); I is masked in place where refractory."""
+    B, N = _node_args(v)
+    check(lib().snn_boosted_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
+                                 C.byref(p), _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "boosted_step")
+
+
+def clif_step(v, refrac, i, s, x, I, p: LifParams, i_decay, raster_s=None, raster_v=None):
+    """CurrentLIFNodes.forward (nodes.py:762-791); i [B,N] is the synaptic current."""
+    B, N = _node_args(v)
+    check(lib().snn_clif_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(i, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
+                              C.byref(p), i_decay, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "clif_step")
+
+
+def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None):
+    """IzhikevichNodes.forward (nodes.py:1265-1296) in one launch; s holds the previous step's spikes at entry; St is the
+    lateral matrix transposed ([N, N], St[i, j] = S[j, i]); the lateral sum is added to I in place."""
+    B, N = _node_args(v)
+    if St.numel() != N * N or any(t.numel() != N for t in (a, b, c, d)):
+        raise ValueError(f"a, b, c, d must have {N} entries and St {N} x {N}")
+    if N > _lib.IZH_MAX_N:
+        raise NotImplementedError(f"bindsnet_amd: IzhikevichNodes of more than {_lib.IZH_MAX_N} neurons")
+    check(lib().snn_izh_step(_ptr(v, F32), _ptr(u, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), _ptr(a, F32), _ptr(b, F32),
+                             _ptr(c, F32), _ptr(d, F32), _ptr(St, F32), B, N, C.byref(p), _ptr(raster_s, "spike", True),
+                             _ptr(raster_v, F32, True), _stream()), "izh_step")
+
+
 def dc_step(v, refrac, s, x, theta, I, p: DcParams, noise_q, cursor, status, raster_s=None, raster_v=None):
     """cursor: int64[2] device tensor ([0] running count, [1] scratch); status: int32[1]."""
     B = v.shape[0]

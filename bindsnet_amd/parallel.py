@@ -149,7 +149,8 @@ def column_shard(network, rank: int, world: int):
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
         raise NotImplementedError("column sharding applies to Input -> one connection -> LIFNodes graphs (no coupling "
-                                  "between target neurons); DiehlAndCook2015's lateral inhibition couples them")
+                                  "between target neurons); DiehlAndCook2015's lateral inhibition couples them -- this network's "
+                                  "layers are " + ", ".join(type(l).__name__ for _, l in layers))
     (xn, X), (yn, Y) = layers
     (key, conn) = conns[0]
     N, Nin = Y.n, X.n

@@ -166,6 +166,40 @@ typedef struct {
     int one_spike;     /* nodes.py:1097 */
 } snn_dc_params;
 
+/* ---- f7: McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes.forward --------------------
+ * One launch per layer per timestep; every kernel also writes its raster_s / raster_v slice (nullable) and the trace x
+ * (nullable unless h_p->traces).  h_p carries the fields the class has (thresh, dt, trace_* always; the rest as listed).
+ * Each * and + of the reference is rounded separately (csrc/snn_common.hpp restates the op order).  (ABI 8, additive)
+ *
+ * snn_mcp_step      bindsnet/network/nodes.py:278-288.  v = I (the mirror keeps its own [B,N] copy), s = v >= thresh.
+ * snn_if_step       bindsnet/network/nodes.py:371-395.  v += (refrac <= 0) * I with the gate taken BEFORE the decrement;
+ *                   uses reset, refrac, lbound.
+ * snn_boosted_step  bindsnet/network/nodes.py:621-648.  v *= decay; I masked in place where refrac > 0 (before the
+ *                   decrement); v += I; spiking neurons are reset to the constant 0.  Uses decay, refrac.
+ * snn_clif_step     bindsnet/network/nodes.py:762-791.  i [B,N] in/out is the synaptic current: v = decay*(v-rest)+rest,
+ *                   i *= i_decay, refrac -= dt, i += I, v += (refrac <= 0) * i with the gate taken AFTER the decrement.
+ *                   Uses decay, rest, reset, refrac, lbound.                                                          */
+int snn_mcp_step(float *v, uint8_t *s, float *x, const float *I, int B, int N, const snn_lif_params *h_p,
+                 uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_if_step(float *v, float *refrac, uint8_t *s, float *x, const float *I, int B, int N, const snn_lif_params *h_p,
+                uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_boosted_step(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N, const snn_lif_params *h_p,
+                     uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_clif_step(float *v, float *refrac, float *i, uint8_t *s, float *x, const float *I, int B, int N,
+                  const snn_lif_params *h_p, float i_decay, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+/* snn_izh_step      bindsnet/network/nodes.py:1265-1296, the whole step in one launch (one workgroup per sample, one thread
+ * per neuron).  s [B,N] holds the PREVIOUS step's spikes at entry and this step's at exit.  Where s: v = c, u = u + d.
+ * I [B,N] += sum over the spiking neurons i of S[j,i], in the order of ATen's S[:, s[b]].sum(dim=1) (vectorised inner sum
+ * over the selected columns in ascending i: csrc/snn_order.hpp inner_sum8_terms); a sample without a spike adds +0.  Then
+ * two half-steps v += (dt*0.5) * (0.04*v*v + 5*v + 140 - u + I), u += (dt*a) * (b*v - u), lbound, s = v >= thresh, trace.
+ * a, b, c, d: [N].  St: the lateral matrix TRANSPOSED, St[i*N + j] = S[j,i], so that a step reads rows.  Uses thresh, dt,
+ * lbound.  Limits: N <= SNN_IZH_MAX_N (the size up to which the summation order is pinned against torch:
+ * tests/test_nodes_hostcheck.py), else SNN_ERR_UNSUPPORTED.                                                          */
+#define SNN_IZH_MAX_N 1024
+int snn_izh_step(float *v, float *u, uint8_t *s, float *x, float *I, const float *a, const float *b, const float *c,
+                 const float *d, const float *St, int B, int N, const snn_lif_params *h_p, uint8_t *raster_s,
+                 float *raster_v, snn_stream_t stream);
+
 /* ---- a4: DiehlAndCookNodes.forward ----------------------------------------------------------
  * bindsnet/network/nodes.py:1069-1111.  theta [N] shared by the batch.  one_spike winner
  * selection reproduces torch.multinomial on the CPU generator: noise_q is the pre-drawn
@@ -324,11 +358,16 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
 
 /* ---- a1: Network.run ------------------------------------------------------------------------
  * bindsnet/network/network.py:380-465 (the per-timestep loop and the post-loop normalisation),
- * for graphs built from {Input, LIFNodes, DiehlAndCookNodes} x {MulticompartmentConnection+
- * Weight, Connection, Conv2dConnection} x {no rule, PostPre, MSTDP}.  The descriptors are HOST
+ * for graphs built from {Input, LIFNodes, DiehlAndCookNodes / AdaptiveLIFNodes, McCullochPitts, IFNodes, BoostedLIFNodes,
+ * CurrentLIFNodes, IzhikevichNodes} x {MulticompartmentConnection+Weight, Connection, Conv1d / Conv2d / Conv3dConnection,
+ * LocalConnection1D / 2D / 3D} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
+ * with any other layer kind runs the generic plan.  The descriptors are HOST
  * structs holding DEVICE pointers; layers and connections are listed in network insertion
  * order, which fixes the evaluation order exactly as the reference's dict iteration does.   */
-enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2 };
+/* SNN_LAYER_MCP .. SNN_LAYER_IZH (nodes.py:231, :308, :562, :681, :1147; generic plan only) and the aux / izh_* fields at the
+ * end of snn_layer_desc were added without changing SNN_ABI_VERSION, like the additive connection kinds below.  */
+enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP = 3, SNN_LAYER_IF = 4, SNN_LAYER_BOOSTED = 5,
+       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7 };
 /* SNN_CONN_LOCAL (LocalConnection1D / 2D / 3D, rules NONE or POSTPRE, generic plan only) and the local_* fields at the end of
  * snn_conn_desc were added without changing SNN_ABI_VERSION: the change is purely additive.  A library built before it is
  * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
@@ -361,6 +400,11 @@ typedef struct {
     /* LIF / DC layers with per-neuron thresholds (nodes.py:425-498: `thresh` given as a tensor): nullable f32 [n] that replaces
      * p.lif.thresh, broadcast over the batch.  Generic plan (a graph that has one is not offered to the fused plans).  (ABI 8) */
     const float *thresh_vec;
+    /* CURRENT: aux = the synaptic current i [B,n], aux_decay = i_decay.  IZH: aux = the recovery variable u [B,n]; izh_a .. izh_d
+     * f32 [n]; izh_St f32 [n,n], the lateral matrix transposed (snn_izh_step).  MCP has no refrac; BOOSTED / IF / CURRENT / IZH
+     * use the p.lif fields their snn_*_step lists.  clamp / unclamp / inject_v / ext_current apply as for LIF. */
+    float *aux; float aux_decay;
+    const float *izh_a, *izh_b, *izh_c, *izh_d, *izh_St;
 } snn_layer_desc;
 
 typedef struct {
