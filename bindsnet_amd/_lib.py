@@ -98,7 +98,13 @@ class ConnDesc(C.Structure):
                 ("local_src", C.c_void_p), ("local_F", C.c_int), ("local_conv_prod", C.c_int),
                 ("local_kernel_prod", C.c_int), ("local_n_src", C.c_int),
                 ("conv_nd", C.c_int), ("conv_d", C.c_int), ("conv_kd", C.c_int), ("conv_pp_src", C.c_void_p),
-                ("conv_pp_rows", C.c_int)]
+                ("conv_pp_rows", C.c_int),
+                ("pipe_n", C.c_int), ("pipe_kind", C.c_int * 8), ("pipe_val", C.c_void_p * 8),
+                ("pipe_scalar", C.c_int * 8), ("pipe_bits", C.c_void_p * 8)]
+
+
+class MccOp(C.Structure):
+    _fields_ = [("kind", C.c_int), ("scalar", C.c_int), ("val", C.c_void_p), ("bits", C.c_void_p)]
 
 
 class RunDesc(C.Structure):
@@ -118,6 +124,8 @@ LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH = 3, 4, 5, 6, 7
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND = 0, 1, 2, 3, 4
+MCC_MAX_PIPE = 8          # SNN_MCC_MAX_PIPE
+MCC_OP_MUL_DRAW, MCC_OP_MUL_MASK, MCC_OP_MUL_F32, MCC_OP_ADD_F32 = 1, 2, 3, 4
 RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET = 0, 1, 2, 3, 4, 5
 
 _lib = None
@@ -129,6 +137,8 @@ _SIGS = {
     "snn_last_hip_error": ([], C.c_char_p),
     "snn_device_count": ([], _i),
     "snn_prop_cascade_f32": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_prop_mcc_pipe_f32": ([C.POINTER(MccOp), _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_mcc_bernoulli": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "snn_prop_dense_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_dense_mfma_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),

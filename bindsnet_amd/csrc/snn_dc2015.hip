@@ -642,7 +642,7 @@ static bool matches(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
     if (nL != 3 || nC != 3) return false;
     if (L[0].kind != SNN_LAYER_INPUT || L[1].kind != SNN_LAYER_DC || L[2].kind != SNN_LAYER_LIF) return false;
     if (L[1].n != L[2].n) return false;
-    for (int k = 0; k < 3; ++k) if (C[k].kind != SNN_CONN_MCC || C[k].bias) return false;
+    for (int k = 0; k < 3; ++k) if (C[k].kind != SNN_CONN_MCC || C[k].bias || C[k].pipe_n > 0) return false;   // (a feature pipeline: generic plan)
     if (C[0].src != 0 || C[0].dst != 1 || C[1].src != 1 || C[1].dst != 2 || C[2].src != 2 || C[2].dst != 1) return false;
     if (C[1].rule != SNN_RULE_NONE || C[2].rule != SNN_RULE_NONE) return false;
     if (C[0].rule != SNN_RULE_NONE && C[0].rule != SNN_RULE_POSTPRE) return false;

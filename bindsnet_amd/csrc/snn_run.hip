@@ -136,7 +136,15 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
     }
     for (int c = 0; c < nC; ++c) {
         const snn_conn_desc &d = C[c];
-        if (d.src < 0 || d.src >= nL || d.dst < 0 || d.dst >= nL || !d.w) return SNN_ERR_INVALID;
+        if (d.src < 0 || d.src >= nL || d.dst < 0 || d.dst >= nL) return SNN_ERR_INVALID;
+        if (d.pipe_n != 0) {                   // MCC with a feature pipeline: `w` only where a Weight carries the rule / the norm
+            if (d.kind != SNN_CONN_MCC || d.pipe_n < 0 || d.pipe_n > SNN_MCC_MAX_PIPE || d.mask || d.bias) return SNN_ERR_INVALID;
+            for (int k = 0; k < d.pipe_n; ++k) {
+                if (d.pipe_kind[k] < SNN_MCC_OP_MUL_DRAW || d.pipe_kind[k] > SNN_MCC_OP_ADD_F32 || !d.pipe_val[k]) return SNN_ERR_INVALID;
+                if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW && (!d.pipe_bits[k] || !R->rng)) return SNN_ERR_INVALID;
+            }
+            if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
+        } else if (!d.w) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
         const bool conv_mstdp = d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_MSTDP;      // learning.py:1942-2015, batch 1
         if (d.kind == SNN_CONN_CONV2D && d.rule != SNN_RULE_NONE && !conv_mstdp && (d.rule != SNN_RULE_POSTPRE || !d.rule_ws)) return SNN_ERR_UNSUPPORTED;
@@ -193,7 +201,17 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 const snn_layer_desc &S = L[d.src], &D = L[d.dst];
                 const uint8_t *sp = layer_spikes(S, B, t, only_dst >= 0 && d.src < only_dst);
                 const int acc = fed[d.dst] ? 1 : 0;
-                if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
+                if (d.kind == SNN_CONN_MCC && d.pipe_n > 0) {
+                    // one compute() of the reference: every Probability draws its [S, N] mask, in pipeline order, then the terms are summed
+                    snn_mcc_op ops[SNN_MCC_MAX_PIPE];
+                    for (int k = 0; k < d.pipe_n; ++k) {
+                        ops[k].kind = d.pipe_kind[k]; ops[k].scalar = d.pipe_scalar[k]; ops[k].val = d.pipe_val[k]; ops[k].bits = d.pipe_bits[k];
+                        if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW)
+                            TRY(snn_mcc_bernoulli(R->rng, (const float *)d.pipe_val[k], d.pipe_scalar[k], S.n, D.n, d.pipe_bits[k], st));
+                    }
+                    TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, D.current, B, S.n, D.n, acc, st));
+                }
+                else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_CONVND) TRY(snn_prop_convnd_f32(d.w, d.bias, sp, D.current, B, d.cin, d.conv_d, d.h, d.wd, d.cout,
                                                                              d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
@@ -362,6 +380,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND) local = true;   // plan only; no fused plan is offered the graph
+    for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));

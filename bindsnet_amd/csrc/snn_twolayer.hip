@@ -264,6 +264,7 @@ bool plan(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const
     if (L[0].kind != SNN_LAYER_INPUT || L[1].kind != SNN_LAYER_LIF) return false;
     if (C[0].src != 0 || C[0].dst != 1) return false;
     if (C[0].kind != SNN_CONN_MCC && C[0].kind != SNN_CONN_DENSE) return false;
+    if (C[0].pipe_n > 0) return false;                  // a feature pipeline: snn_prop_mcc_pipe_f32, generic plan
     const bool outer2 = C[0].rule == SNN_RULE_HEBBIAN || C[0].rule == SNN_RULE_WDPOSTPRE;     // dense Connection only
     if (C[0].rule != SNN_RULE_NONE && C[0].rule != SNN_RULE_POSTPRE && C[0].rule != SNN_RULE_MSTDP && !(outer2 && C[0].kind == SNN_CONN_DENSE)) return false;
     if (C[0].rule == SNN_RULE_WDPOSTPRE && !(C[0].has_min && C[0].has_max)) return false;

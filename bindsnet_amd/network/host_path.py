@@ -231,6 +231,29 @@ def _propagate_mcc(conn, s):
     return _sum(conn._weight().value * spikes, 1).view(B, *conn.target.shape)
 
 
+def _propagate_mcc_pipe(conn, s):
+    """MulticompartmentConnection.compute with any pipeline of Probability / Mask / Weight / Bias / Intensity: the reference's
+    operations in the reference's order (topology.py:437-479; topology_features.py:425-429, :507-508, :633-645, :711-712,
+    :755-756), its torch.bernoulli call on the global generator included -- one per Probability and call, whatever the batch."""
+    from .topology_features import Bias, Probability, Weight
+    conn._check_pipeline()
+    B = s.shape[0]
+    x = s.reshape(B, conn.source.n, 1).repeat(1, 1, conn.target.n)
+    for f in conn.pipeline:
+        if isinstance(f, Probability):
+            x = x * torch.bernoulli(f.value)
+        elif isinstance(f, Weight):
+            x = f.value * x
+        elif isinstance(f, Bias):
+            x = x + f.value
+        else:                                       # Mask, Intensity
+            x = x * f.value
+    if tuple(x.shape) != (B, conn.source.n, conn.target.n):
+        x = x.view(B, conn.source.n, conn.target.n)
+    out = _sum(x, 1) if x.dtype == torch.float32 else x.sum(1)      # (a Mask alone: the reference's integer sum)
+    return out.view(B, *conn.target.shape)
+
+
 def _propagate_conv(conn, s):
     """Conv1d / Conv2d / Conv3dConnection.compute: F.conv1d / conv2d / conv3d (topology.py:640-656, :799-815, :979-995)."""
     conv = (F.conv1d, F.conv2d, F.conv3d)[conn._ndim - 1]
@@ -389,7 +412,9 @@ def _postpre_mcc(rule, W, s_src, x_src, s_tgt, x_tgt, dt) -> None:
 
 def _update_mcc(conn, dt, kwargs) -> None:
     from ..learning import MCC_learning as rules
-    feat = conn._weight()
+    feat = conn._learned()
+    if feat is None:                                 # a pipeline without a Weight: nothing learns
+        return
     rule = feat.learning_rule
     if isinstance(rule, rules.NoOp) or conn.manual_update:
         return

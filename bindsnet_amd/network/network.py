@@ -521,6 +521,8 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             raise
 
         _nodes._SCALARS = None
+        if any(Cn[k].pipe_n and _lib.MCC_OP_MUL_DRAW in list(Cn[k].pipe_kind)[:Cn[k].pipe_n] for k in range(len(self.connections))):
+            max_draws = max(max_draws, 1)         # a Probability draws from the host generator: it goes to the device for the run (rng.py)
         # every tensor whose ADDRESS went into the descriptors: `t.data = other`, set_() or resize_() re-home a tensor
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []

@@ -664,14 +664,15 @@ class AbstractMulticompartmentConnection(_lib.TouchingModule, Module):
 
 
 class MulticompartmentConnection(AbstractMulticompartmentConnection):
-    """Feature-pipeline connection (reference: topology.py:402-537).  The accelerated path is a
-    pipeline of exactly one `Weight`."""
+    """Feature-pipeline connection (reference: topology.py:402-537).  A pipeline of exactly one `Weight` is
+    snn_prop_cascade_f32; every other ordered pipeline of up to 8 features out of Probability / Mask / Weight / Bias /
+    Intensity is a feature program evaluated per synapse (snn_mcc_bernoulli + snn_prop_mcc_pipe_f32 on the device,
+    host_path._propagate_mcc_pipe on the host)."""
 
     _kind = _lib.CONN_MCC
     _norm_by = "columns"               # the Weight's SIGNED column sums (topology_features.py:250-266), by snn_net_run
     _takes_mask = _host_refuses_mask = False           # (no `w`: the device path refuses a mask, the host path ignores it)
-    _multi_device = True
-    _host_compute = host_path._propagate_mcc
+    _MAX_PIPE = 8                      # SNN_MCC_MAX_PIPE
 
     def __init__(self, source: Nodes, target: Nodes, device, pipeline: list = [], manual_update: bool = False,
                  traces: bool = False, **kwargs) -> None:
@@ -680,43 +681,129 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             raise NotImplementedError("bindsnet_amd: connection activity traces are outside the accelerated path")
         self.traces, self.manual_update = traces, manual_update
 
-    def _weight(self):
+    def _names(self) -> list:
+        return [type(f).__name__ for f in self.pipeline]
+
+    def _single(self) -> bool:
+        """The pipeline of exactly one Weight: today's code path and descriptor."""
         from .topology_features import Weight
-        if len(self.pipeline) != 1 or not isinstance(self.pipeline[0], Weight):
-            raise NotImplementedError("bindsnet_amd accelerates MulticompartmentConnection with a single Weight "
-                                      f"feature; got {[type(f).__name__ for f in self.pipeline]}")
+        return len(self.pipeline) == 1 and isinstance(self.pipeline[0], Weight)
+
+    @property
+    def _multi_device(self) -> bool:
+        return self._single()
+
+    def _check_pipeline(self) -> None:
+        from .topology_features import Bias, Intensity, Mask, Probability, Weight
+        if not self.pipeline or len(self.pipeline) > self._MAX_PIPE or \
+                any(type(f) not in (Probability, Mask, Weight, Bias, Intensity) for f in self.pipeline):
+            raise NotImplementedError(f"bindsnet_amd runs MulticompartmentConnection pipelines of 1 to {self._MAX_PIPE} features out of "
+                                      f"Probability, Mask, Weight, Bias, Intensity; got {self._names()}")
+
+    def _learned(self):
+        """The Weight the rule, the norm and the weight monitors refer to: the one with a learning rule if there is one, else
+        the only one; None for a pipeline without a Weight (or with several and no rule)."""
+        from ..learning.MCC_learning import NoOp
+        from .topology_features import Weight
+        self._check_pipeline()
+        ws = [f for f in self.pipeline if isinstance(f, Weight)]
+        ruled = [f for f in ws if not isinstance(f.learning_rule, NoOp) and f.learning_rule is not None]
+        if len(ruled) > 1:
+            raise NotImplementedError(f"bindsnet_amd: at most one Weight of a pipeline may have a learning rule; got {self._names()}")
+        if ruled:
+            return ruled[0]
+        return ws[0] if len(ws) == 1 else None
+
+    def _weight(self):
+        feat = self._learned()
+        if feat is None:
+            raise NotImplementedError(f"bindsnet_amd: the pipeline {self._names()} has no single Weight to refer to")
+        return feat
+
+    def _single_weight(self, what: str):
+        if not self._single():
+            raise NotImplementedError(f"{what}: MulticompartmentConnection with the feature pipeline {self._names()} is not supported "
+                                      "(a single Weight is)")
         return self.pipeline[0]
 
     def _on_host(self) -> bool:
-        return len(self.pipeline) == 1 and isinstance(self.pipeline[0].value, torch.Tensor) and not self.pipeline[0].value.is_cuda
+        return bool(self.pipeline) and all(isinstance(f.value, torch.Tensor) and not f.value.is_cuda for f in self.pipeline)
+
+    def _float_result(self) -> bool:
+        """Whether the reference's pipeline result is float32 (what the device computes): some feature's value is."""
+        return any(isinstance(f.value, torch.Tensor) and f.value.dtype == torch.float32 for f in self.pipeline)
 
     def compute(self, s: torch.Tensor) -> torch.Tensor:
-        """out[b,j] = sum_i value[i,j]*s[b,i] in the reference's ATen sum order (topology.py:437-479)."""
-        w = self._weight().value
+        """out[b,j] = sum_i term(b,i,j) in the reference's ATen sum order (topology.py:437-479)."""
         B = s.size(0)
-        if not w.is_cuda:
+        self._check_pipeline()
+        if self._on_host():
             return self._host_compute(s)
-        out = torch.empty(B, self.target.n, device=w.device)
+        dev = self.pipeline[0].value.device
+        out = torch.empty(B, self.target.n, device=dev)
         self._prop_into(s.reshape(B, -1).contiguous(), out)
         return out.view(B, *self.target.shape)
 
+    def _host_compute(self, s):
+        return host_path._propagate_mcc(self, s) if self._single() else host_path._propagate_mcc_pipe(self, s)
+
+    def _program(self, dev, scratch, key):
+        """The feature program of a multi-feature pipeline on `dev`: [(kind, value tensor, scalar flag, bit workspace)] in
+        pipeline order, and the features whose values' addresses it holds."""
+        from .topology_features import Bias, Mask, Probability, Weight
+        self._check_pipeline()
+        S, N = self.source.n, self.target.n
+        if not self._float_result():
+            raise NotImplementedError(f"bindsnet_amd: the pipeline {self._names()} does not yield float32 in the reference; it runs on "
+                                      "the host path only")
+        prog = []
+        for k, f in enumerate(self.pipeline):
+            if f.value.device != dev:
+                f.to(dev)
+            val = f.value
+            want = torch.bool if isinstance(f, Mask) else torch.float32
+            if val.dtype != want or not val.is_contiguous() or (tuple(val.shape) != (S, N) and val.numel() != 1):
+                raise NotImplementedError(f"bindsnet_amd: {type(f).__name__}.value must be a contiguous {want} [{S}, {N}] tensor or a "
+                                          f"single element (got {val.dtype}, shape {tuple(val.shape)})")
+            kind = _lib.MCC_OP_MUL_DRAW if isinstance(f, Probability) else _lib.MCC_OP_MUL_MASK if isinstance(f, Mask) else \
+                _lib.MCC_OP_ADD_F32 if isinstance(f, Bias) else _lib.MCC_OP_MUL_F32
+            bits = scratch(f"mccbits_{key}_{k}", (S * ((N + 31) // 32),), torch.int32, dev) if kind == _lib.MCC_OP_MUL_DRAW else None
+            prog.append((kind, f, int(val.numel() == 1), bits))
+        return prog
+
     def _prop_into(self, s, out, accumulate=False) -> None:
-        ops.prop_cascade(self._weight().value.data, s, out, accumulate=accumulate)
+        if self._single():
+            return ops.prop_cascade(self.pipeline[0].value.data, s, out, accumulate=accumulate)
+        pool = self.__dict__.setdefault("_bits_pool", {})
+
+        def scratch(key, shape, dtype, dev):
+            t = pool.get(key)
+            if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
+                t = pool[key] = torch.empty(shape, dtype=dtype, device=dev)
+            return t
+        prog = self._program(out.device, scratch, "hand")
+        draws = [(f.value.data, bits) for kind, f, _, bits in prog if kind == _lib.MCC_OP_MUL_DRAW]
+        if draws:                                   # the host generator goes to the device and comes back advanced (rng.py)
+            ops.mcc_bernoulli_from_host([p for p, _ in draws], [b for _, b in draws], self.source.n, self.target.n)
+        ops.prop_mcc_pipe([(kind, f.value.data, flag, bits) for kind, f, flag, bits in prog], s, out, self.source.n, self.target.n,
+                          accumulate=accumulate)
 
     def _host_update(self, kwargs, mask) -> None:
         host_path._update_mcc(self, float(self.dt), kwargs)
 
     def _host_normalize(self) -> None:
-        feat = self._weight()
-        if feat.norm is not None:
-            host_path._normalize_columns(feat.value.data, feat.norm, False)
+        for feat in self.pipeline:                    # topology.py:520-527: every feature that has a norm
+            if feat.norm is not None:
+                host_path._normalize_columns(feat.value.data, feat.norm, False)
 
     def _rule(self):
-        return self._weight().learning_rule
+        from ..learning.MCC_learning import NoOp
+        feat = self._learned()
+        return NoOp() if feat is None else feat.learning_rule
 
     def _column_slice(self, source, target, lo, hi):
         from .topology_features import Weight
-        feat = self._weight()
+        feat = self._single_weight("column_shard")
         rule = feat.learning_rule
         from ..learning import MCC_learning
         rule_cls = type(rule) if type(rule) in (MCC_learning.PostPre, MCC_learning.MSTDP) else None
@@ -731,7 +818,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
 
     def _exact_learns(self) -> bool:
         from ..learning import MCC_learning
-        rule = self._weight().learning_rule
+        rule = self._single_weight("exact_run").learning_rule
         if self.manual_update or isinstance(rule, MCC_learning.NoOp):
             return False
         if not isinstance(rule, MCC_learning.PostPre):
@@ -744,7 +831,9 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         return self._weight(), "value"
 
     def _describe(self, d, B, dev, scratch):
-        feat = self._weight()
+        if not self._single():
+            return self._describe_pipe(d, B, dev, scratch)
+        feat = self.pipeline[0]
         if feat.value.device != dev:
             feat.to(dev)
         val = feat.value
@@ -759,6 +848,29 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
             d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, dptr(ws)
         return [self._weights()]
+
+    def _describe_pipe(self, d, B, dev, scratch):
+        """The feature program at the end of snn_conn_desc; d.w is the Weight the rule and the norm refer to (NULL without one)."""
+        from .topology_features import Weight
+        prog = self._program(dev, scratch, f"{d.src}_{d.dst}")
+        feat = self._learned()
+        d.kind, d.pipe_n = self._kind, len(prog)
+        described = []
+        for k, (kind, f, flag, bits) in enumerate(prog):
+            d.pipe_kind[k], d.pipe_val[k], d.pipe_scalar[k], d.pipe_bits[k] = kind, f.value.data_ptr(), flag, 0 if bits is None else bits.data_ptr()
+            described.append((f, "value"))
+            if f is not feat and f.norm is not None:
+                raise NotImplementedError("bindsnet_amd: in a feature pipeline only the Weight the rule refers to may have a norm on the device")
+        if feat is not None:
+            if tuple(feat.value.shape) != (self.source.n, self.target.n):
+                raise NotImplementedError("bindsnet_amd: the Weight of a pipeline must be a [source.n, target.n] tensor")
+            d.w = dptr(feat.value.data)
+            if feat.norm is not None:
+                if isinstance(feat.norm, torch.Tensor):
+                    raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+                ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
+                d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, dptr(ws)
+        return described
 
     def update(self, **kwargs) -> None:
         """Reference: topology.py:509-518 (note the default learning=False)."""

@@ -1,6 +1,8 @@
 """Connection features: API mirror of bindsnet/network/topology_features.py for the features on
-the hot path (`AbstractFeature`, `Weight`).  A `Weight` only holds the [Nin, N] tensor and its
-learning rule; the multiply-and-reduce it stands for runs in snn_prop_cascade_f32."""
+the hot path (`AbstractFeature`, `Weight`, `Probability`, `Mask`, `Bias`, `Intensity`).  A feature only holds its
+[Nin, N] tensor (and, a `Weight`, its learning rule); what a pipeline of them computes runs in snn_prop_cascade_f32
+(one `Weight`) or in snn_mcc_bernoulli + snn_prop_mcc_pipe_f32 (every other pipeline; csrc/snn_mccpipe.hip), and on the
+host in network/host_path.py."""
 import warnings
 from typing import Optional, Sequence, Union
 
@@ -124,3 +126,136 @@ class Weight(AbstractFeature):
 
     def compute(self, conn_spikes):
         raise NotImplementedError("Weight.compute is fused into MulticompartmentConnection.compute on the device")
+
+
+def _tensor_only(feature, value) -> None:
+    """The reference casts every given value with `value.dtype` (topology_features.py:133, :146-153): a python scalar fails
+    there with AttributeError, after the range assertions."""
+    if value is not None and not isinstance(value, torch.Tensor):
+        raise AttributeError(f"'{type(value).__name__}' object has no attribute 'dtype'")
+
+
+class Probability(AbstractFeature):
+    """Bernoulli gate per synapse and timestep (reference: topology_features.py:365-464): one torch.bernoulli(value) per
+    compute() call from the global CPU generator, shared by the samples of the batch."""
+
+    def __init__(self, name: str, value=None, value_dtype: torch.dtype = torch.float32,
+                 range: Optional[Sequence[float]] = None, norm=None, learning_rule=None,
+                 nu: Optional[Union[list, tuple]] = None, reduction=None, decay: float = 0.0, parent_feature=None,
+                 sparse: Optional[bool] = False, batch_size: int = 1) -> None:
+        from ..learning.MCC_learning import NoOp
+        if learning_rule is not None and learning_rule is not NoOp:
+            raise NotImplementedError("bindsnet_amd: a learning rule on a Probability is outside the accelerated path "
+                                      "(rules are accepted on a Weight)")
+        r = [0, 1] if range is None else range
+        if isinstance(r, (list, tuple)) and len(r) == 2:                  # topology_features.py:445-464
+            if isinstance(r[0], torch.Tensor):
+                assert (r[0] >= 0).all(), f"Invalid range for feature {name}: a min value is less than 0"
+            elif isinstance(r[0], (float, int)):
+                assert r[0] >= 0, f"Invalid range for feature {name}: the min value is less than 0"
+            else:
+                assert False, f"Invalid range for feature {name}: the min value must be of type torch.Tensor, float, or int"
+        super().__init__(name=name, value=value, value_dtype=value_dtype, range=r, norm=norm, learning_rule=learning_rule,
+                         nu=nu, reduction=reduction, decay=decay, parent_feature=parent_feature, sparse=sparse,
+                         batch_size=batch_size)
+        _tensor_only(self, value)
+
+    def prime_feature(self, connection, device, **kwargs) -> None:
+        if self.value is None:
+            self.initialize_value = lambda: torch.clamp(torch.rand(connection.source.n, connection.target.n, device=device),
+                                                        self.range[0], self.range[1])
+        super().prime_feature(connection, device, **kwargs)
+
+    def reset_state_variables(self) -> None:
+        pass
+
+    def compute(self, conn_spikes):
+        return conn_spikes * torch.bernoulli(self.value)
+
+
+class Mask(AbstractFeature):
+    """Boolean gate per synapse (reference: topology_features.py:467-549)."""
+
+    def __init__(self, name: str, value=None, sparse: Optional[bool] = False, batch_size: int = 1) -> None:
+        if isinstance(value, torch.Tensor):
+            assert value.dtype == torch.bool, "Mask must be of type bool, not {}".format(value.dtype)
+        elif value is not None:
+            # (the reference formats its assertion message with value.dtype: any other scalar fails with AttributeError)
+            assert isinstance(value, bool), "Mask must be of type bool, not {}".format(value.dtype)
+            value = torch.tensor(value)
+        super().__init__(name=name, value=value, value_dtype=torch.bool, sparse=sparse, batch_size=batch_size)
+        self.name, self.value = name, value
+
+    def prime_feature(self, connection, device, **kwargs) -> None:
+        from ..learning.MCC_learning import NoOp
+        if self.is_primed:
+            return
+        self.is_primed = True
+        if self.value is None:
+            self.value = (torch.rand(connection.source.n, connection.target.n) > 0.99).to(device=device)
+        self.value = Parameter(self.value, requires_grad=False).to(device)
+        if self.value.dim() > 1:                                          # (a scalar is a valid shape: :347-362)
+            assert tuple(self.value.shape) == (connection.source.n, connection.target.n), (
+                f"Feature {self.name} has an incorrect shape of {self.value.shape}. Should be of shape "
+                f"{(connection.source.n, connection.target.n)}")
+        self.learning_rule = NoOp(connection=connection)
+
+    def reset_state_variables(self) -> None:
+        pass
+
+    def compute(self, conn_spikes):
+        return conn_spikes * self.value
+
+
+class Bias(AbstractFeature):
+    """Per-synapse additive term (reference: topology_features.py:674-721): added to EVERY synapse's signal, spike or not."""
+
+    def __init__(self, name: str, value=None, value_dtype: torch.dtype = torch.float32,
+                 range: Optional[Sequence[float]] = None, norm=None, sparse: Optional[bool] = False,
+                 batch_size: int = 1) -> None:
+        super().__init__(name=name, value=value, value_dtype=value_dtype,
+                         range=[-torch.inf, +torch.inf] if range is None else range, norm=norm, sparse=sparse,
+                         batch_size=batch_size)
+        _tensor_only(self, value)
+
+    def prime_feature(self, connection, device, **kwargs) -> None:
+        if self.value is None:
+            self.initialize_value = lambda: torch.rand(connection.source.n, connection.target.n)
+        super().prime_feature(connection, device, **kwargs)
+
+    def reset_state_variables(self) -> None:
+        pass
+
+    def compute(self, conn_spikes):
+        return conn_spikes + self.value
+
+
+class Intensity(AbstractFeature):
+    """Per-synapse scale without a rule (reference: topology_features.py:724-769)."""
+
+    def __init__(self, name: str, value=None, value_dtype: torch.dtype = torch.float32,
+                 range: Optional[Sequence[float]] = None, sparse: Optional[bool] = False, batch_size: int = 1) -> None:
+        super().__init__(name=name, value=value, value_dtype=value_dtype, range=range, sparse=sparse, batch_size=batch_size)
+        _tensor_only(self, value)
+
+    def prime_feature(self, connection, device, **kwargs) -> None:
+        if self.value is None:
+            self.initialize_value = lambda: torch.clamp(
+                torch.sign(torch.randint(-1, +2, (connection.source.n, connection.target.n))), self.range[0], self.range[1])
+        super().prime_feature(connection, device, **kwargs)
+
+    def reset_state_variables(self) -> None:
+        pass
+
+    def compute(self, conn_spikes):
+        return conn_spikes * self.value
+
+
+def _outside(name):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError(f"bindsnet_amd: the {name} feature is outside the accelerated path")
+    return type(name, (AbstractFeature,), {"__init__": __init__, "__doc__": f"Reference feature `{name}`: not provided."})
+
+
+Degradation, MeanField = _outside("Degradation"), _outside("MeanField")
+AdaptationBaseSynapsHistory, AdaptationBaseOtherSynaps = _outside("AdaptationBaseSynapsHistory"), _outside("AdaptationBaseOtherSynaps")

@@ -51,6 +51,54 @@ def prop_cascade(W, s, out, accumulate=False):
     return out
 
 
+def prop_mcc_pipe(program, s, out, Nin, N, accumulate=False):
+    """f8: out[b,j] (+)= sum_i term(b,i,j) of a MulticompartmentConnection feature pipeline, in ATen sum(dim=1) order.
+    program: [(kind, value tensor, scalar flag, bit workspace or None)] in pipeline order (_lib.MCC_OP_*); the bit workspaces
+    of the MUL_DRAW ops must have been filled by mcc_bernoulli for this call."""
+    B = s.shape[0]
+    assert s.numel() == B * Nin and out.numel() == B * N and 0 < len(program) <= _lib.MCC_MAX_PIPE
+    arr = (_lib.MccOp * len(program))()
+    for k, (kind, val, scalar, bits) in enumerate(program):
+        want = torch.bool if kind == _lib.MCC_OP_MUL_MASK else F32
+        if not scalar and val.numel() != Nin * N:
+            raise ValueError(f"op {k}: value must have {Nin} x {N} elements")
+        arr[k].kind, arr[k].scalar, arr[k].val = kind, int(bool(scalar)), _ptr(val, want)
+        arr[k].bits = _ptr(bits, torch.int32) if kind == _lib.MCC_OP_MUL_DRAW else None
+        if kind == _lib.MCC_OP_MUL_DRAW and bits.numel() < Nin * ((N + 31) // 32):
+            raise ValueError(f"op {k}: bit workspace too small")
+    check(lib().snn_prop_mcc_pipe_f32(arr, len(program), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate), _stream()),
+          "prop_mcc_pipe")
+    return out
+
+
+def mcc_bernoulli(p, S, N, bits=None, rng_state=None):
+    """f8: the bit-packed [S, ceil(N/32)] int32 mask torch.bernoulli(p) of an [S, N] (or one-element) f32 `p` draws.
+    rng_state: the int32 image of a device generator state (rng.DeviceGenerator.state), advanced in place; None: the HOST
+    generator is handed to the device for the call and left advanced by S * N outputs, as torch.bernoulli on the CPU leaves it."""
+    if bits is None:
+        bits = torch.empty(S * ((N + 31) // 32), dtype=torch.int32, device=p.device)
+    return mcc_bernoulli_from_host([p], [bits], S, N)[0] if rng_state is None else _mcc_bernoulli(rng_state, p, S, N, bits)
+
+
+def _mcc_bernoulli(rng_state, p, S, N, bits):
+    if p.numel() not in (1, S * N) or bits.numel() < S * ((N + 31) // 32):
+        raise ValueError(f"mcc_bernoulli: p must have 1 or {S} x {N} elements and bits {S * ((N + 31) // 32)} words")
+    check(lib().snn_mcc_bernoulli(_ptr(rng_state, torch.int32), _ptr(p, F32), int(p.numel() == 1), S, N, _ptr(bits, torch.int32),
+                                  _stream()), "mcc_bernoulli")
+    return bits
+
+
+def mcc_bernoulli_from_host(ps, bits, S, N):
+    """Several consecutive draws (the Probability features of one pipeline, in order) from the HOST generator's stream: one
+    hand-over to the device and back (rng.DeviceGenerator), like encode_bernoulli."""
+    from .rng import DeviceGenerator
+    with DeviceGenerator(ps[0].device, 1) as g:
+        for p, b in zip(ps, bits):
+            _mcc_bernoulli(g.state, p, S, N, b)
+        g.finish()
+    return bits
+
+
 def prop_dense(W, s, out, bias=None, accumulate=False):
     """a6: out (+)= s @ W (+ b), ascending-i sequential f32."""
     B = s.shape[0]

@@ -73,6 +73,9 @@ def _reject_local(network, mode: str) -> None:
     layouts."""
     for key, conn in network.connections.items():
         if not conn._multi_device:
+            if hasattr(conn, "pipeline"):
+                raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "
+                                          "by the multi-device modes (a single Weight is); run the network on one device")
             raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} is not supported by the multi-device modes; "
                                       "run the network on one device")
 

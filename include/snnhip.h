@@ -61,6 +61,25 @@ int snn_device_count(void);
 int snn_prop_cascade_f32(const float *W, const uint8_t *s, float *out,
                          int B, int Nin, int N, int accumulate, snn_stream_t stream);
 
+/* ---- f8: MulticompartmentConnection.compute with a feature pipeline ------------------------------
+ * bindsnet/network/topology.py:437-479 + bindsnet/network/topology_features.py (Probability :425-429, Mask :507-508, Weight
+ * :633-645, Bias :711-712, Intensity :755-756).  The pipeline is a program of up to SNN_MCC_MAX_PIPE ops applied, in order, to
+ * float(s[b,i]) per synapse (i, j):
+ *   SNN_MCC_OP_MUL_DRAW  t = t * bit(i,j)    a Probability: bit from the [S, ceil(N/32)] mask snn_mcc_bernoulli wrote into `bits`
+ *   SNN_MCC_OP_MUL_MASK  t = t * (val != 0)  a Mask: val is the bool / u8 [S, N] tensor
+ *   SNN_MCC_OP_MUL_F32   t = t * val         a Weight or an Intensity, f32 [S, N]
+ *   SNN_MCC_OP_ADD_F32   t = t + val         a Bias, f32 [S, N]
+ * `scalar` != 0: val has one element, used for every synapse.  Every op is one rounded f32 multiply or add (no select).
+ * (ABI 8, additive)                                                                                                       */
+#define SNN_MCC_MAX_PIPE 8
+enum { SNN_MCC_OP_MUL_DRAW = 1, SNN_MCC_OP_MUL_MASK = 2, SNN_MCC_OP_MUL_F32 = 3, SNN_MCC_OP_ADD_F32 = 4 };
+typedef struct { int kind; int scalar; const void *val; const uint32_t *bits; } snn_mcc_op;
+/* out[b,j] (+)= sum_i term(b,i,j) in ATen sum(dim=1) order, accumulate as in snn_prop_cascade_f32.  h_ops is a HOST array.
+ * Without an ADD op the rows of silent sources are skipped (their terms are +-0: the values must be finite); with one the
+ * walk is dense.  Limits: Nin <= 2^19.                                                                                   */
+int snn_prop_mcc_pipe_f32(const snn_mcc_op *h_ops, int n_ops, const uint8_t *s, float *out, int B, int Nin, int N,
+                          int accumulate, snn_stream_t stream);
+
 /* ---- a6: Connection.compute ---------------------------------------------------------------
  * bindsnet/network/topology.py:332-346.  out[b,j] (+)= sum_i s[b,i]*W[i,j] (+ bias[j]),
  * canonical ascending-i sequential f32 (the reference's MKL order is not reproducible,
@@ -347,6 +366,14 @@ int snn_encode_bernoulli(snn_rng_state *rng, const float *datum, int n, int step
 int snn_encode_poisson(const float *datum, int n, int steps, float dt, unsigned long long seed, uint8_t *out,
                        snn_stream_t stream);
 
+/* ---- f8: the Bernoulli mask of a Probability feature ---------------------------------------------
+ * bindsnet/network/topology_features.py:425-429: what ONE torch.bernoulli(value) of an [S, N] value draws from the HOST
+ * generator whose state is in *rng -- S*N consecutive 32-bit outputs in row-major order, u = (r & 0xFFFFFF) * 2^-24 < p, the
+ * stream of snn_encode_bernoulli -- written as bits: bits is uint32 [S, ceil(N/32)], bit (j & 31) of word [i, j >> 5] is
+ * element (i, j), the padding bits of a row are 0.  p_scalar != 0: p has one element.  *rng is advanced by S*N outputs; the
+ * partially consumed 624-word block carries over to the next call, whoever makes it.  One workgroup (the stream is serial). */
+int snn_mcc_bernoulli(snn_rng_state *rng, const float *p, int p_scalar, int S, int N, uint32_t *bits, snn_stream_t stream);
+
 /* ---- Network.reset_state_variables ----------------------------------------------------------
  * bindsnet/network/network.py:467-481 (-> nodes.py:109-120, :531-538, :1113-1120): spikes, traces and
  * refractory counters <- 0, voltages <- rest.  One launch fills up to SNN_MAX_FILL_SEGMENTS device buffers:
@@ -444,6 +471,16 @@ typedef struct {
     int conv_nd, conv_d, conv_kd;
     const int *conv_pp_src;
     int conv_pp_rows;
+    /* MCC with a feature pipeline (snn_prop_mcc_pipe_f32; generic plan only, no fused plan is offered such a graph).  pipe_n == 0:
+     * the single Weight in `w`, as before.  pipe_n > 0: op k is (pipe_kind[k], pipe_val[k], pipe_scalar[k]); a MUL_DRAW op's
+     * pipe_val is its f32 probabilities and pipe_bits[k] its uint32 [S, ceil(N/32)] workspace, filled by snn_mcc_bernoulli from
+     * snn_run_desc.rng once per compute() of the reference, in pipeline order.  `w` is then the Weight the rule and the norm
+     * refer to, NULL for a pipeline without one (rule NONE, has_norm 0).  Added like the fields above: SNN_ABI_VERSION stays. */
+    int pipe_n;
+    int pipe_kind[SNN_MCC_MAX_PIPE];
+    const void *pipe_val[SNN_MCC_MAX_PIPE];
+    int pipe_scalar[SNN_MCC_MAX_PIPE];
+    uint32_t *pipe_bits[SNN_MCC_MAX_PIPE];
 } snn_conn_desc;
 
 typedef struct {
