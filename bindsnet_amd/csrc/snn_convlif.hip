@@ -197,7 +197,8 @@ __global__ __launch_bounds__(NTC) void k_convlif_run(const ConvCtx c) {
 
 
 // ======================================================================================================================================
-// Plan "convpp-fused" (round 6): Input -> Conv2dConnection with PostPre (bindsnet/learning/learning.py:457-497) -> LIFNodes, the graph
+// Plan "convpp-fused" (round 6): Input -> Conv2dConnection with PostPre (bindsnet/learning/learning.py:457-497), Hebbian (:1348-1380) or
+// WeightDependentPostPre (:920-976) -> LIFNodes -- the three rules differ in the apply statements of (4) only --, the graph
 // examples/mnist/conv_mnist.py trains, as ONE cooperative launch for the whole run.  The generic plan runs five launches per timestep
 // (input step, convolution, LIF step, per-sample partial sums, batch reduction + apply).
 //
@@ -225,6 +226,7 @@ struct ConvPPCtx {
     ConvCtx c;
     float nu0, nu1, wdecay, wmin, wmax;
     int has_min, has_max, learning;
+    int rule;                     // SNN_RULE_POSTPRE / SNN_RULE_HEBBIAN / SNN_RULE_WDPOSTPRE: which statements the apply step runs
     float *Wout;                  // the connection's weights (written back by the b == 0 workgroups)
     unsigned long long *gr;       // [2][2][B][E] granules
     unsigned *fin;                // [2] behind the granules: workgroups through with the run, "somebody gave up"; zeroed before the launch
@@ -549,8 +551,25 @@ __global__ __launch_bounds__(1024) void k_convpp_run(const ConvPPCtx a) {
                 }
                 return cs.finish(B >> 4);
             };
-            if (a.nu0 != 0.f) w = w - a.nu0 * ordered(red);
-            if (a.nu1 != 0.f) w = w + a.nu1 * ordered(red + B * nel);
+            if (__builtin_expect(a.rule == SNN_RULE_POSTPRE, 1)) {      // (workgroup-uniform: one rule per launch; the other arm is laid out cold)
+                if (a.nu0 != 0.f) w = w - a.nu0 * ordered(red);
+                if (a.nu1 != 0.f) w = w + a.nu1 * ordered(red + B * nel);
+            } else {
+                // k_conv_hebb_apply's statements: Hebbian's two always run (learning.py:1372-1378); WeightDependentPostPre skips a side whose
+                // rate is zero and always adds the update (:950-974)
+                const bool hebb = a.rule == SNN_RULE_HEBBIAN;
+                const float pre = (hebb || a.nu0 != 0.f) ? ordered(red) : 0.f;
+                const float post = (hebb || a.nu1 != 0.f) ? ordered(red + B * nel) : 0.f;
+                if (hebb) {
+                    w = w + a.nu0 * pre;
+                    w = w + a.nu1 * post;
+                } else {
+                    float upd = 0.f;
+                    if (a.nu0 != 0.f) upd = upd - (a.nu0 * pre) * (w - a.wmin);
+                    if (a.nu1 != 0.f) upd = upd + (a.nu1 * post) * (a.wmax - w);
+                    w = w + upd;
+                }
+            }
             w = w * a.wdecay;
             if (a.has_min && w < a.wmin) w = a.wmin;
             if (a.has_max && w > a.wmax) w = a.wmax;
@@ -605,7 +624,9 @@ bool convpp_match(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int n
     if (nL != 2 || nC != 1) return false;
     if (L[0].kind != SNN_LAYER_INPUT || L[1].kind != SNN_LAYER_LIF) return false;
     const snn_conn_desc &d = C[0];
-    if (d.kind != SNN_CONN_CONV2D || d.src != 0 || d.dst != 1 || d.rule != SNN_RULE_POSTPRE || d.has_norm || d.mask || d.raster_w) return false;
+    if (d.kind != SNN_CONN_CONV2D || d.src != 0 || d.dst != 1 || d.has_norm || d.mask || d.raster_w) return false;
+    if (d.rule != SNN_RULE_POSTPRE && d.rule != SNN_RULE_HEBBIAN && d.rule != SNN_RULE_WDPOSTPRE) return false;      // the outer-product rules: same two sums
+    if (d.rule == SNN_RULE_WDPOSTPRE && !(d.has_min && d.has_max)) return false;                                     // (the generic plan reports it)
     if (R->T < 1 || R->one_step || R->B < 1 || R->B > 256) return false;
     if (L[0].clamp || L[0].unclamp || L[0].inject_v || L[0].ext_current || L[1].clamp || L[1].unclamp || L[1].inject_v || L[1].ext_current || L[1].thresh_vec) return false;
     memset(&c, 0, sizeof(c));
@@ -619,7 +640,7 @@ bool convpp_match(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int n
     if ((img + 3) / 4 > 4 * convpp_threads(c, 2)) return false;
     if (convpp_lds(c, 2) > 150 * 1024) return false;
     if ((double)R->T * R->B * L[1].n >= 9.0e15) return false;
-    if (!L[0].x || !L[1].x || !L[0].p.lif.traces || !L[1].p.lif.traces) return false;   // PostPre reads both traces
+    if (!L[0].x || !L[1].x || !L[0].p.lif.traces || !L[1].p.lif.traces) return false;   // the three rules read both traces
     return true;
 }
 size_t convpp_workspace(const ConvCtx &c) {
@@ -708,6 +729,7 @@ int snn_try_fused_convpp(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     c.ras = L[1].raster_s; c.rasV = L[1].raster_v;
     a.nu0 = d.nu0; a.nu1 = d.nu1; a.wdecay = d.wdecay; a.has_min = d.has_min; a.wmin = d.wmin; a.has_max = d.has_max; a.wmax = d.wmax;
     a.learning = R->learning ? 1 : 0;
+    a.rule = d.rule;
     a.Wout = d.w;
     const size_t E = (size_t)c.Cout * taps;
     a.gr = (unsigned long long *)R->workspace;

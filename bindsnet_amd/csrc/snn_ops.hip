@@ -746,39 +746,37 @@ __global__ __launch_bounds__(256) void k_conv_pp_partial_ev(const uint8_t *__res
     part[(size_t)B * E + id] = p;
 }
 
+// element e's partial sums of the B samples in ATen's sum(dim=0) order (the loads of sixteen samples are issued together, then added in that
+// order: one round trip per sixteen terms)
+__device__ __forceinline__ float conv_pp_batch_sum(const float *__restrict__ base, int B, long E, long e, bool tail) {
+    OuterSum acc; acc.init(tail);
+    for (int b0 = 0; b0 < B; b0 += 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = base[(size_t)min(b0 + u, B - 1) * E + e];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) if (b0 + u < B) acc.add(b0 + u, v[u], B);
+    }
+    return acc.finish(B);
+}
+
 __global__ __launch_bounds__(256) void k_conv_pp_apply(float *__restrict__ W, const float *__restrict__ part, int B, long E, float nu0,
                                                        float nu1, float decay, int has_min, float wmin, int has_max, float wmax) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const bool tail = e >= (E / 32) * 32;
     float w = W[e];
-    // (the loads of sixteen samples' partial sums are issued together, then added in ATen's order: one round trip per sixteen terms)
-    auto ordered = [&](const float *base) {
-        OuterSum acc; acc.init(tail);
-        for (int b0 = 0; b0 < B; b0 += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = base[(size_t)min(b0 + u, B - 1) * E + e];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) if (b0 + u < B) acc.add(b0 + u, v[u], B);
-        }
-        return acc.finish(B);
-    };
-    if (nu0 != 0.f) w = w - nu0 * ordered(part);
-    if (nu1 != 0.f) w = w + nu1 * ordered(part + (size_t)B * E);
+    if (nu0 != 0.f) w = w - nu0 * conv_pp_batch_sum(part, B, E, e, tail);
+    if (nu1 != 0.f) w = w + nu1 * conv_pp_batch_sum(part + (size_t)B * E, B, E, e, tail);
     w = w * decay;
     if (has_min && w < wmin) w = wmin;
     if (has_max && w > wmax) w = wmax;
     W[e] = w;
 }
 
-extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
-                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
-                                  float decay, int has_min, float wmin, int has_max, float wmax, float *ws, snn_stream_t stream) {
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || !ws || B <= 0 || Cin <= 0 || H <= 0 || Wd <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 ||
-        stride <= 0 || pad < 0) return SNN_ERR_INVALID;
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1;
-    if (OH <= 0 || OW <= 0) return SNN_ERR_INVALID;
+// phase 1 of the conv2d outer-product rules (PostPre, Hebbian, WeightDependentPostPre): ws <- [pre | post][B][E] per-sample partial sums
+static int conv_pp_partials(const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Cin, int H, int Wd,
+                            int Cout, int KH, int KW, int stride, int pad, int OH, int OW, float *ws, hipStream_t stream) {
     const long E = (long)Cout * Cin * KH * KW, n = (long)B * E;
     static const bool events = [] { const char *v = getenv("SNN_CONV_PP_EVENTS"); return !(v && v[0] == '0'); }();
     const size_t ev_lds_bytes = ((size_t)H + (size_t)8 * OH + 1) * sizeof(uint32_t) + ((size_t)8 * OH * OW + (size_t)H * Wd) * sizeof(float);
@@ -790,8 +788,66 @@ extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x
         hipLaunchKernelGGL(k_conv_pp_partial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s_src, x_src, s_tgt, x_tgt, ws,
                            B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW);
     }
+    return SNN_OK;
+}
+
+extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                  float decay, int has_min, float wmin, int has_max, float wmax, float *ws, snn_stream_t stream) {
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || !ws || B <= 0 || Cin <= 0 || H <= 0 || Wd <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 ||
+        stride <= 0 || pad < 0) return SNN_ERR_INVALID;
+    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1;
+    if (OH <= 0 || OW <= 0) return SNN_ERR_INVALID;
+    const long E = (long)Cout * Cin * KH * KW;
+    const int rc = conv_pp_partials(s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, ws, (hipStream_t)stream);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_conv_pp_apply, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ws, B, E, nu0, nu1, decay,
                        has_min, wmin, has_max, wmax);
+    return snn_check_launch();
+}
+
+// Hebbian (learning.py:1348-1380) / WeightDependentPostPre (:920-976) on a Conv2dConnection: the two sums PostPre reduces (the same partial
+// kernels, k_conv_pp_apply's ordered batch reduction), then the statements k_plasticity runs for the dense family (modes 2 / 3) -- except
+// that the reference's `w += update` also runs when both rates are zero (update is then the integer 0: a -0.0 weight becomes +0.0).
+__global__ __launch_bounds__(256) void k_conv_hebb_apply(float *__restrict__ W, const float *__restrict__ part, int B, long E, float nu0,
+                                                         float nu1, int weight_dependent, float decay, int has_min, float wmin, int has_max,
+                                                         float wmax) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const bool tail = e >= (E / 32) * 32;
+    float w = W[e];
+    // (Hebbian's two statements always run; WeightDependentPostPre skips a side whose rate is zero, and its loads with it)
+    const float pre = (!weight_dependent || nu0 != 0.f) ? conv_pp_batch_sum(part, B, E, e, tail) : 0.f;
+    const float post = (!weight_dependent || nu1 != 0.f) ? conv_pp_batch_sum(part + (size_t)B * E, B, E, e, tail) : 0.f;
+    if (!weight_dependent) {                            // w += nu0 * pre; w += nu1 * post
+        w = w + nu0 * pre;
+        w = w + nu1 * post;
+    } else {                                            // update = 0 - (nu0 pre)(w - wmin) + (nu1 post)(wmax - w); w += update
+        float upd = 0.f;
+        if (nu0 != 0.f) upd = upd - (nu0 * pre) * (w - wmin);
+        if (nu1 != 0.f) upd = upd + (nu1 * post) * (wmax - w);
+        w = w + upd;
+    }
+    w = w * decay;
+    if (has_min && w < wmin) w = wmin;
+    if (has_max && w > wmax) w = wmax;
+    W[e] = w;
+}
+
+extern "C" int snn_conv2d_hebbian(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                  int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax, float *ws,
+                                  snn_stream_t stream) {
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || !ws || B <= 0 || Cin <= 0 || H <= 0 || Wd <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 ||
+        stride <= 0 || pad < 0) return SNN_ERR_INVALID;
+    if (weight_dependent && !(has_min && has_max)) return SNN_ERR_INVALID;      // learning.py:600-602: finite wmin and wmax
+    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1;
+    if (OH <= 0 || OW <= 0) return SNN_ERR_INVALID;
+    const long E = (long)Cout * Cin * KH * KW;
+    const int rc = conv_pp_partials(s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, ws, (hipStream_t)stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_conv_hebb_apply, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ws, B, E, nu0, nu1,
+                       weight_dependent, decay, has_min, wmin, has_max, wmax);
     return snn_check_launch();
 }
 

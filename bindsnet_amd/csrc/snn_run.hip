@@ -147,7 +147,11 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         } else if (!d.w) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
         const bool conv_mstdp = d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_MSTDP;      // learning.py:1942-2015, batch 1
-        if (d.kind == SNN_CONN_CONV2D && d.rule != SNN_RULE_NONE && !conv_mstdp && (d.rule != SNN_RULE_POSTPRE || !d.rule_ws)) return SNN_ERR_UNSUPPORTED;
+        // (the three outer-product rules share the per-sample partial sums in rule_ws: learning.py:457-497, :920-976, :1348-1380; MSTDPET's conv2d
+        //  form never feeds its eligibility trace, :2654-2745 -- it cannot learn and is not offered)
+        const bool conv_outer = d.rule == SNN_RULE_POSTPRE || d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE;
+        if (d.kind == SNN_CONN_CONV2D && d.rule != SNN_RULE_NONE && !conv_mstdp && (!conv_outer || !d.rule_ws)) return SNN_ERR_UNSUPPORTED;
+        if (d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_WDPOSTPRE && !(d.has_min && d.has_max)) return SNN_ERR_INVALID;
         if (conv_mstdp && (!d.p_plus || !d.p_minus || !d.e_trace || d.reward_vec)) return SNN_ERR_INVALID;
         if (conv_mstdp && R->B != 1) return SNN_ERR_UNSUPPORTED;
         if (d.rule == SNN_RULE_POSTPRE && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
@@ -289,6 +293,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONV2D)
                     TRY(snn_conv2d_postpre(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
                                            d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
+                else if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && d.kind == SNN_CONN_CONV2D)
+                    TRY(snn_conv2d_hebbian(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
+                                           d.rule == SNN_RULE_WDPOSTPRE, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
                 else if (d.rule == SNN_RULE_POSTPRE)
                     TRY(snn_stdp_postpre(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                          d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, st));
@@ -370,7 +377,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     unsigned normalized = 0;       // bit c: connection c was already normalised by the plan's own kernel
     int mode = g_plan_mode ? g_plan_mode : R->plan;            // the process-wide test switch wins over the per-run request
     for (int l = 0; l < nL; ++l) if (L[l].clamp || L[l].unclamp || L[l].inject_v || L[l].ext_current) mode = 1;   // only the generic plan implements these
-    // (a Conv2dConnection with a rule: the generic plan, except PostPre on the Input -> Conv2d -> LIF graph -- snn_try_fused_convpp, whole-run form only)
+    // (a Conv2dConnection with a rule: the generic plan, except PostPre / Hebbian / WeightDependentPostPre on the Input -> Conv2d -> LIF graph -- snn_try_fused_convpp, whole-run form only)
     bool conv_rule = false;
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_CONV2D && C[c].rule != SNN_RULE_NONE) conv_rule = true;
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;

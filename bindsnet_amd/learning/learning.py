@@ -1,6 +1,7 @@
 """Learning rules for dense `Connection`s: API mirror of bindsnet/learning/learning.py for `LearningRule`, `NoOp`,
 `PostPre`, `WeightDependentPostPre`, `Hebbian`, `MSTDP`, `MSTDPET`.  Updates run in snn_stdp_postpre /
-snn_stdp_hebbian / snn_mstdp_step / snn_mstdpet_step."""
+snn_stdp_hebbian / snn_mstdp_step / snn_mstdpet_step (on a Conv2dConnection: snn_conv2d_postpre / snn_conv2d_hebbian /
+snn_conv2d_mstdp_step)."""
 import warnings
 from typing import Optional, Sequence, Union
 
@@ -211,13 +212,15 @@ class _OuterProductRule(LearningRule):
         self._check_reduction()
         B = self.source.batch_size
         lo, hi = self._bounds()
+        if self.connection._kind == _lib.CONN_CONV2D:
+            return self.connection._outer_product(self, B, lo, hi)
         ops.stdp_hebbian(self.connection.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
                          self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(self.nu[0]), float(self.nu[1]),
                          weight_dependent=self._weight_dependent, decay=float(self.weight_decay), wmin=lo, wmax=hi)
 
 
 class Hebbian(_OuterProductRule):
-    """Both the pre- and the post-synaptic term potentiate (reference: learning.py:1052-1135)."""
+    """Both the pre- and the post-synaptic term potentiate (reference: learning.py:1052-1135; on a Conv2dConnection :1348-1380)."""
     _rule_code = _lib.RULE_HEBBIAN
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
@@ -226,7 +229,8 @@ class Hebbian(_OuterProductRule):
 
 
 class WeightDependentPostPre(_OuterProductRule):
-    """PostPre whose depression scales with (w - wmin) and potentiation with (wmax - w) (reference: learning.py:562-653)."""
+    """PostPre whose depression scales with (w - wmin) and potentiation with (wmax - w) (reference: learning.py:562-653; on a Conv2dConnection
+    :920-976)."""
     _rule_code, _weight_dependent = _lib.RULE_WDPOSTPRE, True
 
     def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:

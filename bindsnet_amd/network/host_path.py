@@ -452,8 +452,32 @@ def _update_postpre_only(conn, kwargs, mask) -> None:
         conn._host_postpre(rule)
 
 
+def _conv_outer_product(conn, rule) -> None:
+    """learning.py:1348-1380 (Hebbian) / :920-976 (WeightDependentPostPre): PostPre's two batch-reduced bmm sums, the rule's own statements."""
+    from ..learning import learning as rules
+    from ..utils import im2col_indices
+    W = conn.w.data
+    Cout, _, kh, kw = W.shape
+    B = conn.source.batch_size
+    src_x = im2col_indices(conn.source.x.view(B, *conn.source.shape), kh, kw, padding=conn.padding, stride=conn.stride)
+    src_s = im2col_indices(conn.source.s.view(B, *conn.source.shape).float(), kh, kw, padding=conn.padding, stride=conn.stride)
+    tgt_x, tgt_s = conn.target.x.view(B, Cout, -1), conn.target.s.view(B, Cout, -1).float()
+    pre = lambda: _reduce(rule, torch.bmm(tgt_x, src_s.permute(0, 2, 1))).view(W.shape)       # noqa: E731
+    post = lambda: _reduce(rule, torch.bmm(tgt_s, src_x.permute(0, 2, 1))).view(W.shape)      # noqa: E731
+    if isinstance(rule, rules.Hebbian):
+        W += rule.nu[0] * pre()
+        W += rule.nu[1] * post()
+        return
+    update = 0
+    if rule.nu[0].any():
+        update -= rule.nu[0] * pre() * (W - conn.wmin)
+    if rule.nu[1].any():
+        update += rule.nu[1] * post() * (conn.wmax - W)
+    W += update
+
+
 def _update_conv2d(conn, kwargs, mask=None) -> None:
-    """Conv2dConnection.update: PostPre, MSTDP at batch 1."""
+    """Conv2dConnection.update: PostPre, Hebbian, WeightDependentPostPre, MSTDP at batch 1."""
     from ..learning import learning as rules
     rule = conn.update_rule
     if rule is None or isinstance(rule, rules.NoOp):
@@ -461,10 +485,14 @@ def _update_conv2d(conn, kwargs, mask=None) -> None:
     if isinstance(rule, rules.PostPre):
         rule._check_reduction()
         _conv_postpre(conn, rule)
+    elif isinstance(rule, (rules.Hebbian, rules.WeightDependentPostPre)):
+        rule._check_reduction()
+        _conv_outer_product(conn, rule)
     elif isinstance(rule, rules.MSTDP):
         _conv_mstdp(conn, rule, kwargs)
     else:
-        raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on a Conv2dConnection (supported: PostPre, MSTDP)")
+        raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on a Conv2dConnection (supported: PostPre, Hebbian, "
+                                  "WeightDependentPostPre, MSTDP)")
     _decay_clamp(rule, conn.w.data, rule.weight_decay)
 
 

@@ -301,12 +301,16 @@ class LocalConnection(_DenseConnection):
 
 
 class Conv2dConnection(AbstractConnection):
-    """2-D convolutional synapses (reference: topology.py:686-844): propagation, PostPre, and MSTDP at batch 1."""
+    """2-D convolutional synapses (reference: topology.py:686-844): propagation, PostPre, Hebbian, WeightDependentPostPre, and MSTDP
+    at batch 1.  MSTDPET is not offered: the reference's conv2d form (learning.py:2654-2745) never adds the point eligibility to its
+    eligibility trace, so it leaves the weights as they are at batch 1 and fails at larger batches."""
 
     _kind, _ndim = _lib.CONN_CONV2D, 2
     _norm_by = "after"      # every [KH*KW] filter to sum `norm` (topology.py:824-837): not snn_net_run's column step
     _multi_device = True
-    _rules = frozenset(("NoOp", "PostPre", "MSTDP"))
+    _rules = frozenset(("NoOp", "PostPre", "Hebbian", "WeightDependentPostPre", "MSTDP"))
+    _rules_only = "PostPre, Hebbian, WeightDependentPostPre and MSTDP are"      # (any other rule: named in LearningRule's error)
+    _outer_product_rules = (_lib.RULE_POSTPRE, _lib.RULE_HEBBIAN, _lib.RULE_WDPOSTPRE)
     _host_compute, _host_update = host_path._propagate_conv, host_path._update_conv2d
 
     def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]],
@@ -318,9 +322,6 @@ class Conv2dConnection(AbstractConnection):
         self.padding, self.dilation = _pair(padding), _pair(dilation)
         if self.dilation != (1, 1) or self.stride[0] != self.stride[1] or self.padding[0] != self.padding[1]:
             raise NotImplementedError("bindsnet_amd: conv2d supports dilation 1 and symmetric stride/padding only")
-        rule = kwargs.get("update_rule", None)
-        if rule is not None and rule.__name__ not in self._rules:
-            raise NotImplementedError(f"bindsnet_amd: {rule.__name__} on Conv2dConnection is not supported (PostPre and MSTDP are)")
         self.in_channels, ih, iw = source.shape[0], source.shape[1], source.shape[2]
         if self.in_channels > 16:
             raise NotImplementedError("bindsnet_amd: Conv2dConnection with more than 16 input channels is not supported (the "
@@ -343,7 +344,7 @@ class Conv2dConnection(AbstractConnection):
         d.cin, d.h, d.wd = self.in_channels, self.source.shape[1], self.source.shape[2]
         d.cout, d.kh, d.kw = self.out_channels, self.kernel_size[0], self.kernel_size[1]
         d.stride, d.pad = self.stride[0], self.padding[0]
-        if getattr(self.update_rule, "_rule_code", None) == _lib.RULE_POSTPRE:      # learning.py:457-497: per-sample partial sums live in scratch
+        if getattr(self.update_rule, "_rule_code", None) in self._outer_product_rules:      # learning.py:457-497, :920-976, :1348-1380: per-sample partial sums live in scratch
             d.rule_ws = dptr(scratch(f"convpp_{d.src}_{d.dst}", (2 * B * self.w.numel(),), torch.float32, dev))
         return described
 
@@ -353,6 +354,14 @@ class Conv2dConnection(AbstractConnection):
         ops.conv2d_postpre(self.w.data, src.s.reshape(B, *src.shape).contiguous(), src.x.reshape(B, *src.shape),
                            tgt.s.reshape(B, *tgt.shape), tgt.x.reshape(B, *tgt.shape), float(rule.nu[0]), float(rule.nu[1]),
                            stride=self.stride[0], pad=self.padding[0], decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+
+    def _outer_product(self, rule, B, lo, hi) -> None:
+        """learning.py:1348-1380 (Hebbian) / :920-976 (WeightDependentPostPre)."""
+        src, tgt = self.source, self.target
+        ops.conv2d_hebbian(self.w.data, src.s.reshape(B, *src.shape).contiguous(), src.x.reshape(B, *src.shape),
+                           tgt.s.reshape(B, *tgt.shape), tgt.x.reshape(B, *tgt.shape), float(rule.nu[0]), float(rule.nu[1]),
+                           weight_dependent=rule._weight_dependent, stride=self.stride[0], pad=self.padding[0],
+                           decay=float(rule.weight_decay), wmin=lo, wmax=hi)
 
 
 class _ConvNdConnection(AbstractConnection):

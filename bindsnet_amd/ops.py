@@ -311,6 +311,18 @@ def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, dec
                                    _ptr(ws, F32), _stream()), "conv2d_postpre")
 
 
+def conv2d_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False, stride=1, pad=0, decay=1.0, wmin=None, wmax=None,
+                   ws=None):
+    """f4: Hebbian (weight_dependent=False) / WeightDependentPostPre (True) on Conv2dConnection weights; shapes as conv2d_postpre."""
+    B, Cin, H, Wd = s_src.shape
+    Cout, _, KH, KW = W.shape
+    if ws is None:
+        ws = torch.empty(2 * B * W.numel(), dtype=F32, device=W.device)
+    check(lib().snn_conv2d_hebbian(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                   B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, int(weight_dependent), decay,
+                                   *_bounds(wmin, wmax), _ptr(ws, F32), _stream()), "conv2d_hebbian")
+
+
 def conv2d_mstdp_step(W, elig, p_plus, p_minus, s_src, s_tgt, reward, nu0, a_plus, a_minus, decay_plus, decay_minus, stride=1, pad=0,
                       wdecay=1.0, wmin=None, wmax=None):
     """f4: MSTDP on Conv2dConnection weights [Cout,Cin,KH,KW] at batch 1; elig like W, p_plus [Cin,H,W], p_minus [Cout,OH*OW],

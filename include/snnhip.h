@@ -314,6 +314,18 @@ int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x_src, const
                        int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
                        float decay, int has_min, float wmin, int has_max, float wmax, float *ws, snn_stream_t stream);
 
+/* ---- f4: Hebbian / WeightDependentPostPre on a Conv2dConnection --------------------------------------------
+ * bindsnet/learning/learning.py:1348-1380 and :920-976 (+ :87-104).  pre[co,k] = sum_b sum_l x_tgt[b,co,l] * unfold(s_src)[b,k,l] and
+ * post[co,k] = sum_b sum_l s_tgt[b,co,l] * unfold(x_src)[b,k,l] are snn_conv2d_postpre's two sums (same kernels, same order), then
+ *   weight_dependent = 0:  W += nu0 * pre;  W += nu1 * post              (both statements always run)
+ *   weight_dependent = 1:  u = 0;  nu0 != 0: u = u - (nu0 pre)(W - wmin);  nu1 != 0: u = u + (nu1 post)(wmax - W);  W += u
+ *                          (needs both bounds: SNN_ERR_INVALID without)
+ * followed by W *= decay and the clamp; every operation rounds once.  ws: device scratch of 2 * B * Cout*Cin*KH*KW floats. */
+int snn_conv2d_hebbian(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                       int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                       int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax, float *ws,
+                       snn_stream_t stream);
+
 /* ---- f4: MSTDP on a Conv2dConnection (batch 1) -----------------------------------------------------------
  * bindsnet/learning/learning.py:1942-2015 (+ :87-104), defined at batch size 1 only (the reference views its [B, Cout, K]
  * eligibility as the weight's shape, :2013).  elig [Cout, K = Cin*KH*KW] is the rule's eligibility (in/out), p_plus the
@@ -453,7 +465,7 @@ typedef struct {
     float *e_trace;             /* MSTDPET: dense eligibility trace [Nin,N]; CONV2D + MSTDP: the eligibility [Cout,Cin*KH*KW]
                                    (p_plus is then [Cin,H,W], p_minus [Cout,OH*OW]; batch 1, s_*_prev unused) */
     float decay_e, tc_e;        /* MSTDPET: exp(-dt / tc_e_trace), tc_e_trace */
-    float *rule_ws;             /* CONV2D + PostPre: scratch of 2 * B * Cout*Cin*KH*KW floats */
+    float *rule_ws;             /* CONV2D + PostPre / Hebbian / WeightDependentPostPre: scratch of 2 * B * Cout*Cin*KH*KW floats */
     const uint8_t *mask;        /* nullable [Nin,N] (same layout as w): weights forced to zero after every step's update --
                                    run(..., masks=) / LocalConnection.mask, topology.py:129-133 (generic plan) */
     float *raster_w;            /* nullable [T, numel(w)] weight monitor (Monitor / NetworkMonitor on a connection's `w`,

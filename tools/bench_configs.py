@@ -174,9 +174,11 @@ def f_postpre_ref():
     return _rule_two_layer("PostPre")            # the same graph with PostPre, for comparison
 
 
-def f_conv_postpre():
-    """conv_mnist.py's training graph: Input -> Conv2dConnection(PostPre) -> LIFNodes (plan convpp-fused; SNN_CONVPP_FUSED=0: the generic plan)."""
-    from bindsnet_amd.learning import PostPre
+def f_conv_postpre(rule="PostPre"):
+    """conv_mnist.py's training graph: Input -> Conv2dConnection(`rule`) -> LIFNodes (plan convpp-fused; SNN_CONVPP_FUSED=0: the generic plan).
+    `rule` is PostPre (graph (f)), Hebbian or WeightDependentPostPre; the three share nu = (1e-4, 1e-2) and the bounds [0, 1], so that
+    only the apply statements differ between their timings."""
+    from bindsnet_amd import learning
     from bindsnet_amd.network import Network
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import Conv2dConnection
@@ -184,11 +186,19 @@ def f_conv_postpre():
     net = Network(dt=1.0)
     net.add_layer(Input(shape=(1, 28, 28), traces=True), "X")
     net.add_layer(LIFNodes(shape=(32, 24, 24), traces=True), "Y")
-    net.add_connection(Conv2dConnection(net.layers["X"], net.layers["Y"], kernel_size=5, stride=1, update_rule=PostPre, nu=(1e-4, 1e-2),
+    net.add_connection(Conv2dConnection(net.layers["X"], net.layers["Y"], kernel_size=5, stride=1, update_rule=getattr(learning, rule), nu=(1e-4, 1e-2),
                                         wmin=0.0, wmax=1.0, reduction=torch.sum, w=0.3 * torch.rand(32, 1, 5, 5)), "X", "Y")
     net.to(DEV)
     x = torch.from_numpy(synth.dense_spikes(3, (100, 16, 1, 28, 28), 0.05)).to(DEV)
-    return "(f) Conv2d 5x5x32 PostPre -> LIF B=16 T=100", net, {"X": x}, 100, {}
+    return f"(f) Conv2d 5x5x32 {rule} -> LIF B=16 T=100", net, {"X": x}, 100, {}
+
+
+def f_conv_hebbian():
+    return f_conv_postpre("Hebbian")             # the same graph and plan, Hebbian's apply statements
+
+
+def f_conv_wdpp():
+    return f_conv_postpre("WeightDependentPostPre")
 
 
 if __name__ == "__main__":
@@ -197,7 +207,7 @@ if __name__ == "__main__":
     ap.add_argument("--only", default="")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     a = ap.parse_args()
-    for make in (cfg1, cfg3_shard, cfg3_b32, cfg3, cfg4, cfg5, f_postpre_ref, f_hebbian, f_wdpp, f_conv_postpre):
+    for make in (cfg1, cfg3_shard, cfg3_b32, cfg3, cfg4, cfg5, f_postpre_ref, f_hebbian, f_wdpp, f_conv_postpre, f_conv_hebbian, f_conv_wdpp):
         if a.only and make.__name__ not in a.only.split(','):
             continue
         if make.__name__.startswith("cfg"):
