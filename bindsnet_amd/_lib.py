@@ -100,7 +100,8 @@ class ConnDesc(C.Structure):
                 ("conv_nd", C.c_int), ("conv_d", C.c_int), ("conv_kd", C.c_int), ("conv_pp_src", C.c_void_p),
                 ("conv_pp_rows", C.c_int),
                 ("pipe_n", C.c_int), ("pipe_kind", C.c_int * 8), ("pipe_val", C.c_void_p * 8),
-                ("pipe_scalar", C.c_int * 8), ("pipe_bits", C.c_void_p * 8)]
+                ("pipe_scalar", C.c_int * 8), ("pipe_bits", C.c_void_p * 8),
+                ("sparse_ptr", C.c_void_p), ("sparse_col", C.c_void_p), ("sparse_val", C.c_void_p), ("sparse_nnz", C.c_int)]
 
 
 class MccOp(C.Structure):
@@ -123,7 +124,8 @@ MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH = 3, 4, 5, 6, 7
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
-CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND = 0, 1, 2, 3, 4
+CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
+SPARSE_TJ = 256           # SNN_SPARSE_TJ: the column-tile width of SparseConnection's compiled form
 MCC_MAX_PIPE = 8          # SNN_MCC_MAX_PIPE
 MCC_OP_MUL_DRAW, MCC_OP_MUL_MASK, MCC_OP_MUL_F32, MCC_OP_ADD_F32 = 1, 2, 3, 4
 RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET = 0, 1, 2, 3, 4, 5
@@ -140,6 +142,7 @@ _SIGS = {
     "snn_prop_mcc_pipe_f32": ([C.POINTER(MccOp), _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_mcc_bernoulli": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "snn_prop_dense_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_prop_sparse_f32": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_dense_mfma_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
     "snn_prop_local_f32": ([_vp] * 4 + [_i] * 7 + [_vp], _i),

@@ -144,7 +144,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW && (!d.pipe_bits[k] || !R->rng)) return SNN_ERR_INVALID;
             }
             if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
-        } else if (!d.w) return SNN_ERR_INVALID;
+        } else if (!d.w && d.kind != SNN_CONN_SPARSE) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
         const bool conv_mstdp = d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_MSTDP;      // learning.py:1942-2015, batch 1
         // (the three outer-product rules share the per-sample partial sums in rule_ws: learning.py:457-497, :920-976, :1348-1380; MSTDPET's conv2d
@@ -159,7 +159,12 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
         if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_MSTDPET) return SNN_ERR_INVALID;
-        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_CONVND) return SNN_ERR_INVALID;
+        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_SPARSE) return SNN_ERR_INVALID;
+        if (d.kind == SNN_CONN_SPARSE) {       // SparseConnection: propagation only (a rule densifies `w` in the reference; norm and mask raise there)
+            if (d.rule != SNN_RULE_NONE || d.has_norm || d.mask || d.raster_w || d.w) return SNN_ERR_INVALID;
+            if (!d.sparse_ptr || d.sparse_nnz < 0 || (d.sparse_nnz > 0 && (!d.sparse_col || !d.sparse_val))) return SNN_ERR_INVALID;
+            continue;
+        }
         if (d.kind == SNN_CONN_CONVND) {       // Conv1dConnection / Conv3dConnection: no rule or PostPre (learning.py:422-455, :499-559)
             if ((d.conv_nd != 1 && d.conv_nd != 3) || d.cin <= 0 || d.conv_d <= 0 || d.h <= 0 || d.wd <= 0 || d.cout <= 0 || d.conv_kd <= 0 ||
                 d.kh <= 0 || d.kw <= 0 || d.mask || d.has_norm) return SNN_ERR_INVALID;
@@ -217,6 +222,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 }
                 else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_SPARSE) TRY(snn_prop_sparse_f32(d.sparse_ptr, d.sparse_col, d.sparse_val, d.sparse_nnz, d.bias, sp,
+                                                                            D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_CONVND) TRY(snn_prop_convnd_f32(d.w, d.bias, sp, D.current, B, d.cin, d.conv_d, d.h, d.wd, d.cout,
                                                                              d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
                 else if (d.kind == SNN_CONN_LOCAL) TRY(snn_prop_local_f32(d.w, d.local_src, sp, D.current, B, d.cin, d.local_F,
@@ -386,7 +393,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
-    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND) local = true;   // plan only; no fused plan is offered the graph
+    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind == SNN_CONN_SPARSE) local = true;   // (and SparseConnection) plan only; no fused plan is offered the graph
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {

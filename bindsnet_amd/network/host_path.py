@@ -270,6 +270,19 @@ def _propagate_dense(conn, s):
     return post.view(B, *conn.target.shape)
 
 
+def _propagate_sparse(conn, s):
+    """SparseConnection.compute (topology.py:2009-2017 + :332-346): torch's own sparse product, the reference's arithmetic."""
+    B = s.shape[0]
+    post = s.reshape(B, -1).float() @ conn.w
+    if conn.b is not None:
+        post = post + conn.b
+    return post.view(B, *conn.target.shape)
+
+
+def _update_nothing(conn, kwargs, mask) -> None:
+    """SparseConnection.update: NoOp only (learning.py:87-104 multiplies `w` by 1.0)."""
+
+
 def _propagate_local(conn, s):
     """LocalConnection1D / 2D / 3D.compute, the reference's expression (topology.py:1573-1597 / :1731-1746 / :1880-1896)."""
     B = s.shape[0]

@@ -296,6 +296,11 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             f"Got {type(inputs).__name__} instead.")
         clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
         injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
+        for key, conn in self.connections.items():         # what a family knows it cannot run at all: before the run changes any state
+            if hasattr(conn, "_run_refusal"):
+                err = conn._run_refusal(masks.get(key), self._conn_is_monitored(conn, key))
+                if err is not None:
+                    raise err
         if self.learning and int(time / self.dt) > 0:
             for conn in self.connections.values():         # what a family knows it cannot learn: before the run changes any state
                 err = conn._refusal() if hasattr(conn, "_refusal") else None
@@ -672,6 +677,11 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 raise NotImplementedError(f"bindsnet_amd: monitoring '{var}' of {type(layer).__name__} is "
                                           "outside the accelerated path (supported: 's', 'v')")
         return requests
+
+    def _conn_is_monitored(self, conn, cname) -> bool:
+        """Whether any monitor records a variable of this connection."""
+        return any((isinstance(m, Monitor) and m.obj is conn) or
+                   (isinstance(m, NetworkMonitor) and any(c == cname for c, _ in m._wanted_conns())) for m in self.monitors.values())
 
     def _conn_monitor_requests(self, conn, cname):
         """(monitor, key handed back to its _append) for every monitor recording this connection's weights."""

@@ -1,7 +1,11 @@
 """Connections: API mirror of bindsnet/network/topology.py for the connection types on the hot
-path (`Connection`, `MulticompartmentConnection`, `Conv1dConnection`, `Conv2dConnection`, `Conv3dConnection`, `LocalConnection`,
-`LocalConnection1D/2D/3D`).  `compute()` launches the
+path (`Connection`, `SparseConnection`, `MulticompartmentConnection`, `Conv1dConnection`, `Conv2dConnection`, `Conv3dConnection`,
+`LocalConnection`, `LocalConnection1D/2D/3D`).  `compute()` launches the
 matching propagation kernel of libsnnhip; inside Network.run the same kernels are driven from C++.
+
+`SparseConnection` keeps `w` as a sparse COO Parameter, like the reference, and propagates only: its kernel
+(snn_prop_sparse_f32) walks the stored entries of the spiking sources, so its work is spikes x fan-out, and its sums are
+bit-identical to the reference's for float weights too.
 """
 import warnings
 from typing import Optional, Sequence, Tuple, Union
@@ -33,6 +37,27 @@ def _rand_weights(conn, shape, bias_n, w_dtype, kwargs) -> None:
         w = conn.cast_dtype_if_needed(w, w_dtype)
     conn.w = Parameter(w, requires_grad=False)
     conn.b = Parameter(kwargs.get("b", torch.zeros(bias_n)), requires_grad=False)
+
+
+def _matrix_weights(conn, w_dtype, kwargs):
+    """`w` [source.n, target.n] and the optional `b` of Connection and SparseConnection as the reference draws and clamps them
+    (topology.py:309-327)."""
+    if w_dtype != torch.float32:
+        raise NotImplementedError("bindsnet_amd computes in float32 only")
+    w = kwargs.get("w", None)
+    unbounded = bool((conn.wmin == -np.inf).any() or (conn.wmax == np.inf).any())
+    if w is None:  # consumes the global generator exactly like the reference (topology.py:309-315)
+        if unbounded:
+            w = torch.clamp(torch.rand(conn.source.n, conn.target.n), conn.wmin, conn.wmax)
+        else:
+            w = conn.wmin + torch.rand(conn.source.n, conn.target.n) * (conn.wmax - conn.wmin)
+        w = w.to(dtype=w_dtype)
+    else:
+        if bool((conn.wmin != -np.inf).any() or (conn.wmax != np.inf).any()):
+            w = torch.clamp(torch.as_tensor(w), conn.wmin, conn.wmax)
+        w = conn.cast_dtype_if_needed(w, w_dtype)
+    b = kwargs.get("b", None)
+    return Parameter(w, requires_grad=False), (Parameter(b, requires_grad=False) if b is not None else None)
 
 
 class AbstractConnection(_lib.TouchingModule, Module):
@@ -193,23 +218,7 @@ class Connection(_DenseConnection):
     def __init__(self, source: Nodes, target: Nodes, nu=None, reduction=None, weight_decay: float = 0.0,
                  w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
         super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
-        if w_dtype != torch.float32:
-            raise NotImplementedError("bindsnet_amd computes in float32 only")
-        w = kwargs.get("w", None)
-        unbounded = bool((self.wmin == -np.inf).any() or (self.wmax == np.inf).any())
-        if w is None:  # consumes the global generator exactly like the reference (topology.py:309-315)
-            if unbounded:
-                w = torch.clamp(torch.rand(source.n, target.n), self.wmin, self.wmax)
-            else:
-                w = self.wmin + torch.rand(source.n, target.n) * (self.wmax - self.wmin)
-            w = w.to(dtype=w_dtype)
-        else:
-            if bool((self.wmin != -np.inf).any() or (self.wmax != np.inf).any()):
-                w = torch.clamp(torch.as_tensor(w), self.wmin, self.wmax)
-            w = self.cast_dtype_if_needed(w, w_dtype)
-        self.w = Parameter(w, requires_grad=False)
-        b = kwargs.get("b", None)
-        self.b = Parameter(b, requires_grad=False) if b is not None else None
+        self.w, self.b = _matrix_weights(self, w_dtype, kwargs)
 
     def _column_slice(self, source, target, lo, hi):
         def scalar(t) -> float:
@@ -234,6 +243,107 @@ class Connection(_DenseConnection):
             raise NotImplementedError("exact_run: learning on a dense Connection (Input -> Connection -> LIFNodes graphs shard "
                                       "their columns exactly with column_shard, without any collective)")
         return False
+
+
+class SparseConnection(AbstractConnection):
+    """Fixed sparse synapses (reference: topology.py:2009-2017): `Connection`'s constructor, then `w = Parameter(w.to_sparse())`.
+    Propagation only.  On the device `compute` is snn_prop_sparse_f32 over a compiled form of `w` (a column-tiled CSR, ops.sparse_compile;
+    kept as the non-persistent buffers `sp_ptr` / `sp_col` / `sp_val` and rebuilt when `w` is another tensor, was edited in place or
+    has moved); on the host torch's own sparse product.  Both are the reference's arithmetic bit for bit: per column the stored entries
+    of the spiking sources in ascending order, then the bias (DESIGN.md "Summation order").
+
+    What the reference does not define on a sparse `w` is refused, where it fails only later in the reference before a run changes
+    any state: a learning rule (its update densifies `w`), `norm` (normalize() raises), a `mask` (update()
+    raises), Dales_rule, a monitor on `w`, and a `w` that is not float32."""
+
+    _kind = _lib.CONN_SPARSE
+    _takes_mask = _multi_device = False
+    _rules = frozenset(("NoOp",))
+    _rules_only = ("a learning rule adds `update.to_sparse()` to a sparse `w` in the reference, which stores every entry from the "
+                   "first step on: that is dense learning, use Connection for it")
+    _host_compute, _host_update = host_path._propagate_sparse, host_path._update_nothing
+
+    def __init__(self, source: Nodes, target: Nodes, nu=None, reduction=None, weight_decay: float = 0.0,
+                 w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
+        super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
+        w, self.b = _matrix_weights(self, w_dtype, kwargs)
+        self.w = Parameter(w.to_sparse(), requires_grad=False)
+        for name in ("sp_ptr", "sp_col", "sp_val"):
+            self.register_buffer(name, None, persistent=False)
+        self.__dict__["_sp_key"] = None
+
+    def _weights_refusal(self):
+        w = self.w
+        if not isinstance(w, torch.Tensor) or not w.is_sparse or w.dim() != 2 or tuple(w.shape) != (self.source.n, self.target.n):
+            return NotImplementedError(f"bindsnet_amd: SparseConnection.w must be a sparse COO tensor of shape [{self.source.n}, "
+                                       f"{self.target.n}]")
+        if w.dtype != torch.float32:
+            return NotImplementedError(f"bindsnet_amd: SparseConnection.w must be float32 (got {w.dtype}); bindsnet_amd computes in "
+                                       "float32 only")
+        return None
+
+    def _run_refusal(self, mask, monitored: bool):
+        """Why a run must not start on this connection, or None: asked by Network.run before it changes any state."""
+        if self.norm is not None:
+            return NotImplementedError("SparseConnection with `norm`: the reference's normalize() raises NotImplementedError at the end "
+                                       "of the run (aten::eq.Scalar is not defined for a sparse tensor); leave `norm` unset")
+        if mask is not None:
+            return Exception("Mask isn't supported for SparseConnection")              # topology.py:129-130
+        if monitored:
+            return NotImplementedError("bindsnet_amd: a monitor on a SparseConnection's `w` is not supported (monitor buffers take "
+                                       "the shape of a dense tensor); record connection.w.to_dense() where it is needed")
+        return self._weights_refusal()
+
+    def update(self, **kwargs) -> None:
+        """Reference: topology.py:112-139 (NoOp leaves `w` as it is; a mask raises)."""
+        if kwargs.get("mask", None) is not None:
+            raise Exception("Mask isn't supported for SparseConnection")
+        if kwargs.get("learning", True):
+            self.update_rule.update(**kwargs)
+
+    def normalize(self) -> None:
+        if self.norm is not None:
+            raise self._run_refusal(None, False)
+
+    _host_normalize = normalize
+
+    def _compiled(self):
+        """(sp_ptr, sp_col, sp_val) for `w` as it stands.  The key: which tensor `w` is, its in-place version (shared with its
+        values and indices), where its values and indices live, and its device."""
+        err = self._weights_refusal()
+        if err is not None:
+            raise err
+        w = self.w
+        key = (w._version, w._values().data_ptr(), w._indices().data_ptr(), w._nnz(), str(w.device))
+        kept = self.__dict__.get("_sp_key")
+        if kept is None or kept[0] is not w or kept[1] != key or self.sp_ptr is None or self.sp_ptr.device != w.device:
+            self.sp_ptr, self.sp_col, self.sp_val = ops.sparse_compile(w)
+            self.__dict__["_sp_key"] = (w, key)
+        return self.sp_ptr, self.sp_col, self.sp_val
+
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        ops.prop_sparse(self._compiled(), s.reshape(s.size(0), -1).contiguous(), out, bias=None if self.b is None else self.b.data,
+                        accumulate=accumulate)
+
+    def _describe(self, d, B, dev, scratch):
+        from . import nodes as _nodes
+        if self.w.device != dev:
+            raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
+        err = self._run_refusal(None, False)
+        if err is not None:
+            raise err
+        ptr, col, val = self._compiled()
+        d.kind, d.w, d.sparse_nnz = self._kind, None, val.numel()
+        d.sparse_ptr, d.sparse_col, d.sparse_val = dptr(ptr), dptr(col), dptr(val)
+        if _nodes._SCALARS is not None:                   # an in-place edit of the values moves nothing: the kept descriptors
+            _nodes._SCALARS.append((self.w, self.w._version))        # are only good while w's version stands
+        described = [(self, "sp_ptr"), (self, "sp_col"), (self, "sp_val")]
+        if isinstance(self.b, torch.Tensor):
+            if self.b.device != dev or self.b.dtype != torch.float32 or self.b.numel() != self.target.n:
+                raise ValueError(f"SparseConnection.b must be a float32 tensor of {self.target.n} entries on the network's device")
+            d.bias = dptr(self.b.data)
+            described.append((self, "b"))
+        return described
 
 
 class LocalConnection(_DenseConnection):

@@ -196,6 +196,45 @@ def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, w
                                    *_bounds(wmin, wmax), _ptr(ws, torch.int32), _stream()), "convnd_postpre")
 
 
+def sparse_compile(w):
+    """f9: the compiled form of a sparse COO matrix `w` [Nin, N] for snn_prop_sparse_f32 (include/snnhip.h), on w's device:
+    (ptr int32 [ceil(N/256) * Nin + 1], col uint8 [nnz], val float32 [nnz]).  `w` is coalesced first; every stored entry is kept."""
+    if not w.is_sparse or w.dim() != 2 or w.dtype != F32:
+        raise ValueError("sparse_compile: a 2-D float32 sparse COO tensor is required")
+    wc = w.detach().coalesce()                      # entries in (i, j) ascending order, duplicates summed
+    Nin, N = wc.shape
+    TJ = _lib.SPARSE_TJ
+    tiles = (N + TJ - 1) // TJ
+    nnz = wc._nnz()
+    if nnz >= 2 ** 31 or Nin > 2 ** 24 or tiles * Nin + 1 > 2 ** 31 - 1:
+        raise NotImplementedError(f"bindsnet_amd: a sparse [{Nin}, {N}] matrix with {nnz} entries exceeds the int32 indices of "
+                                  "snn_prop_sparse_f32 (nnz < 2^31, Nin <= 2^24, ceil(N/256) * Nin < 2^31 - 1)")
+    i, j = wc.indices()
+    key = torch.div(j, TJ, rounding_mode="floor") * Nin + i
+    order = torch.sort(key, stable=True).indices    # tile-major; inside a tile the coalesced (i, j) order stays
+    ptr = torch.zeros(tiles * Nin + 1, dtype=torch.int64, device=wc.device)
+    ptr[1:] = torch.cumsum(torch.bincount(key, minlength=tiles * Nin), 0)
+    return ptr.to(torch.int32), (j[order] % TJ).to(torch.uint8).contiguous(), wc.values()[order].contiguous()
+
+
+def prop_sparse(compiled, s, out, bias=None, accumulate=False):
+    """f9: out (+)= s @ w (+ b) for the sparse `w` that `compiled` = sparse_compile(w) holds: per column the stored entries of
+    the spiking sources in ascending order, one rounded f32 add each, the bias last."""
+    ptr, col, val = compiled
+    B = s.shape[0]
+    Nin, N = s.numel() // B, out.numel() // B
+    tiles = (N + _lib.SPARSE_TJ - 1) // _lib.SPARSE_TJ
+    if s.numel() != B * Nin or out.numel() != B * N or ptr.numel() != tiles * Nin + 1 or col.numel() != val.numel():
+        raise ValueError("prop_sparse: the compiled form does not belong to a matrix of these shapes")
+    if bias is not None and bias.numel() != N:
+        raise ValueError("prop_sparse: bias must have one entry per target")
+    nnz = val.numel()
+    check(lib().snn_prop_sparse_f32(_ptr(ptr, torch.int32), _ptr(col, torch.uint8) if nnz else None, _ptr(val, F32) if nnz else None,
+                                    nnz, _ptr(bias, F32, True), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate),
+                                    _stream()), "prop_sparse")
+    return out
+
+
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None):
     check(lib().snn_input_step(_ptr(s, "spike"), _ptr(x, F32, True), s.numel(), trace_decay, trace_scale,
                                int(additive), _ptr(raster, "spike", True), _stream()), "input_step")

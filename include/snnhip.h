@@ -87,6 +87,24 @@ int snn_prop_mcc_pipe_f32(const snn_mcc_op *h_ops, int n_ops, const uint8_t *s, 
 int snn_prop_dense_f32(const float *W, const float *bias, const uint8_t *s, float *out,
                        int B, int Nin, int N, int accumulate, snn_stream_t stream);
 
+/* ---- f9: SparseConnection.compute -----------------------------------------------------------
+ * bindsnet/network/topology.py:2009-2017 + :332-346: `s.view(B, -1).float() @ w (+ b)` with `w` a sparse COO tensor.
+ * Order contract: out[b,j] (+)= (...((0 + w[i1,j]) + w[i2,j]) + ...) + bias[j] over the STORED entries of column j whose
+ * source i spiked, i ascending, one rounded f32 add per term, bias (nullable) last; accumulate as in snn_prop_cascade_f32.
+ * This IS the reference's own order (probed at 1 and 8 threads, DESIGN.md "Summation order"), so unlike snn_prop_dense_f32
+ * the result is bit-identical to the reference for float weights too.  A spike byte enters as float(s) * w, one rounded
+ * multiply before the add; silent sources are skipped.  The contract is pinned against the reference for spike bytes 0/1
+ * and finite weights.  Stored entries are those `to_sparse()` keeps (exact zeros and -0 are absent) after coalescing.
+ * Compiled form (a column-tiled CSR, built by the caller): the N columns are cut into tiles of SNN_SPARSE_TJ; entries are
+ * laid out tile by tile, inside a tile by (source, target) ascending.  ptr int32 [ceil(N/SNN_SPARSE_TJ) * Nin + 1]: the
+ * entries of (tile t, source i) are [ptr[t*Nin + i], ptr[t*Nin + i + 1]); col uint8 [nnz]: the column inside the tile;
+ * val f32 [nnz].  col / val may be NULL when nnz == 0.  Every segment bound is clamped into [0, nnz] on the device.
+ * No float atomics.  Limits (int32 indices): nnz < 2^31, Nin <= 2^24, ceil(N/SNN_SPARSE_TJ) * Nin < 2^31 - 1, B <= 65535;
+ * beyond them SNN_ERR_UNSUPPORTED.  (ABI 8, additive)                                                                      */
+#define SNN_SPARSE_TJ 256
+int snn_prop_sparse_f32(const int *ptr, const uint8_t *col, const float *val, int nnz, const float *bias, const uint8_t *s,
+                        float *out, int B, int Nin, int N, int accumulate, snn_stream_t stream);
+
 /* The same product on the f32 matrix cores (v_mfma_f32_16x16x4_f32): ONE k-ordered accumulator chain per output
  * tile, bit-identical to snn_prop_dense_f32 when every spike byte is 0 or 1 (products are then exact and gfx950's
  * f32 MFMA is a k-ordered fmaf chain).  Cost is Nin / 4 dependent MFMAs per tile regardless of sparsity; kept as an
@@ -398,8 +416,8 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
 /* ---- a1: Network.run ------------------------------------------------------------------------
  * bindsnet/network/network.py:380-465 (the per-timestep loop and the post-loop normalisation),
  * for graphs built from {Input, LIFNodes, DiehlAndCookNodes / AdaptiveLIFNodes, McCullochPitts, IFNodes, BoostedLIFNodes,
- * CurrentLIFNodes, IzhikevichNodes} x {MulticompartmentConnection+Weight, Connection, Conv1d / Conv2d / Conv3dConnection,
- * LocalConnection1D / 2D / 3D} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
+ * CurrentLIFNodes, IzhikevichNodes} x {MulticompartmentConnection+Weight, Connection, SparseConnection, Conv1d / Conv2d /
+ * Conv3dConnection, LocalConnection1D / 2D / 3D} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
  * with any other layer kind runs the generic plan.  The descriptors are HOST
  * structs holding DEVICE pointers; layers and connections are listed in network insertion
  * order, which fixes the evaluation order exactly as the reference's dict iteration does.   */
@@ -412,8 +430,9 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP =
  * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
  * snn_prop_local_f32 / snn_local_postpre; tests/test_abi.py compares sizeof(snn_conn_desc) with the ctypes mirror.  */
 /* SNN_CONN_CONVND (Conv1dConnection / Conv3dConnection, rules NONE or POSTPRE, generic plan only) and the conv_* fields
- * after them were added the same way, again without changing SNN_ABI_VERSION.  */
-enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4 };
+ * after them were added the same way, again without changing SNN_ABI_VERSION.  So were SNN_CONN_SPARSE (SparseConnection:
+ * propagation only -- any rule, norm, mask or weight monitor is SNN_ERR_INVALID --, generic plan only) and the sparse_* fields.  */
+enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5 };
 
@@ -493,6 +512,12 @@ typedef struct {
     const void *pipe_val[SNN_MCC_MAX_PIPE];
     int pipe_scalar[SNN_MCC_MAX_PIPE];
     uint32_t *pipe_bits[SNN_MCC_MAX_PIPE];
+    /* SPARSE: the compiled form of snn_prop_sparse_f32 (ptr / col / val / nnz); `w` is NULL -- nothing learns, normalises, masks
+     * or monitors a sparse matrix --, bias nullable.  Added like the fields above: SNN_ABI_VERSION stays. */
+    const int *sparse_ptr;
+    const uint8_t *sparse_col;
+    const float *sparse_val;
+    int sparse_nnz;
 } snn_conn_desc;
 
 typedef struct {
