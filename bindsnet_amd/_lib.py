@@ -68,6 +68,24 @@ class DcParams(C.Structure):
                 ("learning", C.c_int), ("one_spike", C.c_int)]
 
 
+# snn_pervec: the per-neuron quantities the step kernels read, in SNN_PV_* order (named after the layers' derived buffers)
+PERVEC = ("thresh", "decay", "trace_decay", "trace_scale", "theta_decay", "theta_plus", "i_decay")
+
+
+class PerVec(C.Structure):
+    _fields_ = [("v", C.c_void_p * len(PERVEC))]
+
+
+def pervec(vectors):
+    """snn_pervec of {quantity name: f32 [n] device tensor}; None (a null pointer for the *_pv entry points) when empty."""
+    if not vectors:
+        return None
+    pv = PerVec()
+    for name, t in vectors.items():
+        pv.v[PERVEC.index(name)] = t.data_ptr()
+    return pv
+
+
 class LayerDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("n", C.c_int), ("p", DcParams),
                 ("v", C.c_void_p), ("refrac", C.c_void_p), ("x", C.c_void_p), ("theta", C.c_void_p),
@@ -78,7 +96,7 @@ class LayerDesc(C.Structure):
                 ("ext_current", C.c_void_p), ("thresh_vec", C.c_void_p),
                 ("aux", C.c_void_p), ("aux_decay", C.c_float),
                 ("izh_a", C.c_void_p), ("izh_b", C.c_void_p), ("izh_c", C.c_void_p), ("izh_d", C.c_void_p),
-                ("izh_St", C.c_void_p)]
+                ("izh_St", C.c_void_p), ("pv", PerVec)]
 
 
 class ConnDesc(C.Structure):
@@ -152,6 +170,14 @@ _SIGS = {
     "snn_input_step": ([_vp, _vp, _l, _f, _f, _i, _vp, _vp], _i),
     "snn_lif_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_lif_step_vth": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp, _vp], _i),
+    "snn_input_step_pv": ([_vp, _vp, _i, _i, _f, _f, _i, C.POINTER(PerVec), _vp, _vp], _i),
+    "snn_lif_step_pv": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_mcp_step_pv": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_if_step_pv": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_boosted_step_pv": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_clif_step_pv": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _f, C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_izh_step_pv": ([_vp] * 10 + [_i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_dc_step_pv": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(DcParams), C.POINTER(PerVec), _vp, _ll, _vp, _vp, _vp, _vp, _vp], _i),
     "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_boosted_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),

@@ -21,24 +21,32 @@ __host__ __device__ __forceinline__ float trace_next(float x, uint8_t s, float d
 
 // LIFNodes.forward, bindsnet/network/nodes.py:508-527.  `cur` must already be zeroed by the
 // caller where rc > 0 (nodes.py:511 masks with the refractory counter BEFORE it is decremented).
-__host__ __device__ __forceinline__ uint8_t lif_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+// `thresh`, `decay`: this neuron's values (the scalars of `p`, or row j of per-neuron vectors: nodes.py takes either).
+__host__ __device__ __forceinline__ uint8_t lif_update(float &v, float &rc, float cur, const snn_lif_params &p, float thresh,
+                                                       float decay) {
     float vv = v - p.rest;              // :508  decay * (v - rest) + rest, three roundings
-    vv = p.decay * vv;
+    vv = decay * vv;
     vv = vv + p.rest;
     rc = rc - p.dt;                     // :514
     vv = vv + cur;                      // :516
-    const uint8_t sp = vv >= p.thresh;  // :519
+    const uint8_t sp = vv >= thresh;    // :519
     if (sp) { rc = p.refrac; vv = p.reset; }                 // :522-523
     if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :526-527
     v = vv;
     return sp;
 }
 
+__host__ __device__ __forceinline__ uint8_t lif_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+    return lif_update(v, rc, cur, p, p.thresh, p.decay);
+}
+
 // DiehlAndCookNodes.forward membrane part, bindsnet/network/nodes.py:1077-1092 (+ :1108-1109).
 // thr = thresh + theta[j] (already decayed), computed once per neuron by the caller.
-__host__ __device__ __forceinline__ uint8_t dc_update(float &v, float &rc, float cur, float thr, const snn_lif_params &p) {
+// `decay`: this neuron's value, as in lif_update.
+__host__ __device__ __forceinline__ uint8_t dc_update(float &v, float &rc, float cur, float thr, const snn_lif_params &p,
+                                                      float decay) {
     float vv = v - p.rest;              // :1077
-    vv = p.decay * vv;
+    vv = decay * vv;
     vv = vv + p.rest;
     const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :1082 (refrac_count <= 0).float() * x
     const float gx = gate * cur;
@@ -51,42 +59,67 @@ __host__ __device__ __forceinline__ uint8_t dc_update(float &v, float &rc, float
     return sp;
 }
 
+__host__ __device__ __forceinline__ uint8_t dc_update(float &v, float &rc, float cur, float thr, const snn_lif_params &p) {
+    return dc_update(v, rc, cur, thr, p, p.decay);
+}
+
+// The adaptive threshold around dc_update, nodes.py:1078-1079 and :1093-1094: theta decays before the membrane step and grows by
+// theta_plus per crossing of the batch after it, both only while learning.  `count` is exact in f32; one rounded multiply, one add.
+__host__ __device__ __forceinline__ float dc_theta_decayed(float theta, int learning, float theta_decay) {
+    return learning ? theta * theta_decay : theta;
+}
+__host__ __device__ __forceinline__ float dc_theta_bumped(float theta, int learning, float theta_plus, int count) {
+    if (!learning) return theta;
+    const float bump = theta_plus * (float)count;
+    return theta + bump;
+}
+
 // McCullochPitts.forward, bindsnet/network/nodes.py:285-286.
-__host__ __device__ __forceinline__ uint8_t mcp_update(float &v, float cur, const snn_lif_params &p) {
+__host__ __device__ __forceinline__ uint8_t mcp_update(float &v, float cur, float thresh) {
     v = cur;                            // :285 (the reference aliases; the layer keeps a copy)
-    return v >= p.thresh;               // :286
+    return v >= thresh;                 // :286
+}
+__host__ __device__ __forceinline__ uint8_t mcp_update(float &v, float cur, const snn_lif_params &p) {
+    return mcp_update(v, cur, p.thresh);
 }
 
 // IFNodes.forward, bindsnet/network/nodes.py:379-393.  No decay, no rest; the gate reads rc BEFORE the decrement.
-__host__ __device__ __forceinline__ uint8_t if_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+__host__ __device__ __forceinline__ uint8_t if_update(float &v, float &rc, float cur, const snn_lif_params &p, float thresh) {
     const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :379 (refrac_count <= 0).float() * x
     const float gx = gate * cur;
     float vv = v + gx;
     rc = rc - p.dt;                     // :382
-    const uint8_t sp = vv >= p.thresh;  // :385
+    const uint8_t sp = vv >= thresh;    // :385
     if (sp) { rc = p.refrac; vv = p.reset; }                 // :388-389
     if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :392-393
     v = vv;
     return sp;
 }
+__host__ __device__ __forceinline__ uint8_t if_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+    return if_update(v, rc, cur, p, p.thresh);
+}
 
 // BoostedLIFNodes.forward, bindsnet/network/nodes.py:629-646.  `cur` must already be zeroed by the caller where rc > 0
 // (:633 masks with the counter BEFORE it is decremented).  No rest, no lbound; the reset value is the constant 0.
-__host__ __device__ __forceinline__ uint8_t boosted_update(float &v, float &rc, float cur, const snn_lif_params &p) {
-    float vv = v * p.decay;             // :629
+__host__ __device__ __forceinline__ uint8_t boosted_update(float &v, float &rc, float cur, const snn_lif_params &p, float thresh,
+                                                           float decay) {
+    float vv = v * decay;               // :629
     rc = rc - p.dt;                     // :636
     vv = vv + cur;                      // :639
-    const uint8_t sp = vv >= p.thresh;  // :642
+    const uint8_t sp = vv >= thresh;    // :642
     if (sp) { rc = p.refrac; vv = 0.f; }                     // :645-646
     v = vv;
     return sp;
 }
+__host__ __device__ __forceinline__ uint8_t boosted_update(float &v, float &rc, float cur, const snn_lif_params &p) {
+    return boosted_update(v, rc, cur, p, p.thresh, p.decay);
+}
 
 // CurrentLIFNodes.forward, bindsnet/network/nodes.py:770-789.  The gate reads rc AFTER the decrement.
 __host__ __device__ __forceinline__ uint8_t clif_update(float &v, float &rc, float &i, float cur, float i_decay,
-                                                        const snn_lif_params &p) {
+                                                        const snn_lif_params &p, float thresh, float decay) {
     float vv = v - p.rest;              // :770
-    vv = p.decay * vv;
+    vv = decay * vv;
     vv = vv + p.rest;
     float ii = i * i_decay;             // :771
     rc = rc - p.dt;                     // :774
@@ -94,17 +127,21 @@ __host__ __device__ __forceinline__ uint8_t clif_update(float &v, float &rc, flo
     const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :778
     const float gi = gate * ii;
     vv = vv + gi;
-    const uint8_t sp = vv >= p.thresh;  // :781
+    const uint8_t sp = vv >= thresh;    // :781
     if (sp) { rc = p.refrac; vv = p.reset; }                 // :784-785
     if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :788-789
     v = vv; i = ii;
     return sp;
 }
+__host__ __device__ __forceinline__ uint8_t clif_update(float &v, float &rc, float &i, float cur, float i_decay,
+                                                        const snn_lif_params &p) {
+    return clif_update(v, rc, i, cur, i_decay, p, p.thresh, p.decay);
+}
 
 // IzhikevichNodes.forward without its lateral sum, bindsnet/network/nodes.py:1274-1294.  s_in: last step's spike of this
 // neuron; cur: the input current with the lateral sum already added (:1279).
 __host__ __device__ __forceinline__ uint8_t izh_update(float &v, float &u, uint8_t s_in, float cur, float a, float b, float c,
-                                                       float d, const snn_lif_params &p) {
+                                                       float d, const snn_lif_params &p, float thresh) {
     float vv = v, uu = u;
     if (s_in) { vv = c; uu = uu + d; }  // :1274-1275
     const float h = p.dt * 0.5f;
@@ -126,7 +163,49 @@ __host__ __device__ __forceinline__ uint8_t izh_update(float &v, float &u, uint8
     uu = uu + w;
     if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :1290-1291
     v = vv; u = uu;
-    return vv >= p.thresh;              // :1294
+    return vv >= thresh;                // :1294
 }
+__host__ __device__ __forceinline__ uint8_t izh_update(float &v, float &u, uint8_t s_in, float cur, float a, float b, float c,
+                                                       float d, const snn_lif_params &p) {
+    return izh_update(v, u, s_in, cur, a, b, c, d, p, p.thresh);
+}
+
+// One neuron's seven parameters: the scalars of the layer's parameter block, or -- PV, the instance a launch with vectors selects --
+// row j of whichever snn_pervec vectors are given.  The scalar instance reads no pointer and indexes nothing.
+struct node_row { float thresh, decay, trace_decay, trace_scale, theta_decay, theta_plus, i_decay; };
+
+template <bool PV>
+__host__ __device__ __forceinline__ node_row row_of(const snn_dc_params &p, float i_decay, const snn_pervec &pv, long j) {
+    node_row r = {p.lif.thresh, p.lif.decay, p.lif.trace_decay, p.lif.trace_scale, p.theta_decay, p.theta_plus, i_decay};
+    if (PV) {
+        if (pv.v[SNN_PV_THRESH]) r.thresh = pv.v[SNN_PV_THRESH][j];
+        if (pv.v[SNN_PV_DECAY]) r.decay = pv.v[SNN_PV_DECAY][j];
+        if (pv.v[SNN_PV_TRACE_DECAY]) r.trace_decay = pv.v[SNN_PV_TRACE_DECAY][j];
+        if (pv.v[SNN_PV_TRACE_SCALE]) r.trace_scale = pv.v[SNN_PV_TRACE_SCALE][j];
+        if (pv.v[SNN_PV_THETA_DECAY]) r.theta_decay = pv.v[SNN_PV_THETA_DECAY][j];
+        if (pv.v[SNN_PV_THETA_PLUS]) r.theta_plus = pv.v[SNN_PV_THETA_PLUS][j];
+        if (pv.v[SNN_PV_I_DECAY]) r.i_decay = pv.v[SNN_PV_I_DECAY][j];
+    }
+    return r;
+}
+template <bool PV>
+__host__ __device__ __forceinline__ node_row row_of(const snn_lif_params &p, float i_decay, const snn_pervec &pv, long j) {
+    snn_dc_params q = {};
+    q.lif = p;
+    return row_of<PV>(q, i_decay, pv, j);
+}
+
+// True when `pv` names a vector; `allowed`: bit q set where the layer kind reads SNN_PV_q (a vector outside it is an error).
+inline bool pervec_any(const snn_pervec *pv) {
+    if (pv) for (int q = 0; q < SNN_PV_COUNT; ++q) if (pv->v[q]) return true;
+    return false;
+}
+inline bool pervec_within(const snn_pervec *pv, unsigned allowed) {
+    if (pv) for (int q = 0; q < SNN_PV_COUNT; ++q) if (pv->v[q] && !((allowed >> q) & 1u)) return false;
+    return true;
+}
+enum : unsigned { kPvTrace = 1u << SNN_PV_TRACE_DECAY | 1u << SNN_PV_TRACE_SCALE, kPvThresh = 1u << SNN_PV_THRESH,
+                  kPvDecay = 1u << SNN_PV_DECAY, kPvTheta = 1u << SNN_PV_THETA_DECAY | 1u << SNN_PV_THETA_PLUS,
+                  kPvIDecay = 1u << SNN_PV_I_DECAY };
 
 }  // namespace snn

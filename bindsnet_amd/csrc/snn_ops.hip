@@ -179,6 +179,36 @@ __global__ __launch_bounds__(256) void k_input(const uint8_t *__restrict__ s, fl
     }
 }
 
+// The same with per-neuron trace constants (snn_pervec: trace_decay[j], and trace_scale[j] with additive traces): the grid is
+// (blocks over the N neurons, B samples), as in every per-neuron instance -- row j is loaded without a division.
+__global__ __launch_bounds__(256) void k_input_pv(const uint8_t *__restrict__ s, float *__restrict__ x, int N, snn_lif_params p,
+                                                  snn_pervec pv, uint8_t *__restrict__ raster) {
+    const long base = (long)blockIdx.y * N;
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (long)gridDim.x * blockDim.x) {
+        const long k = base + j;
+        const node_row r = row_of<true>(p, 0.f, pv, j);
+        const uint8_t sv = s[k];
+        if (x) x[k] = trace_next(x[k], sv, r.trace_decay, r.trace_scale, p.traces_additive);
+        if (raster) raster[k] = sv;
+    }
+}
+
+extern "C" int snn_input_step(const uint8_t *s, float *x, long n_total, float trace_decay, float trace_scale,
+                              int additive, uint8_t *raster_out, snn_stream_t stream);
+extern "C" int snn_input_step_pv(const uint8_t *s, float *x, int B, int N, float trace_decay, float trace_scale, int additive,
+                                 const snn_pervec *pv, uint8_t *raster_out, snn_stream_t stream) {
+    if (B <= 0 || N <= 0) return SNN_ERR_INVALID;
+    if (!pervec_any(pv)) return snn_input_step(s, x, (long)B * N, trace_decay, trace_scale, additive, raster_out, stream);
+    if (!s || !x) return SNN_ERR_INVALID;
+    if (!pervec_within(pv, kPvTrace) || (pv->v[SNN_PV_TRACE_SCALE] && !additive)) return SNN_ERR_INVALID;
+    if (B > 65535) return SNN_ERR_UNSUPPORTED;
+    snn_lif_params p = {};
+    p.traces = 1; p.trace_decay = trace_decay; p.trace_scale = trace_scale; p.traces_additive = additive;
+    const unsigned gx = (unsigned)((N + 255) / 256 < 2048 ? (N + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_input_pv, dim3(gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, s, x, N, p, *pv, raster_out);
+    return snn_check_launch();
+}
+
 extern "C" int snn_input_step(const uint8_t *s, float *x, long n_total, float trace_decay, float trace_scale,
                               int additive, uint8_t *raster_out, snn_stream_t stream) {
     if (!s || n_total <= 0) return SNN_ERR_INVALID;
@@ -210,6 +240,40 @@ __global__ __launch_bounds__(256) void k_lif(float *__restrict__ v, float *__res
     }
 }
 
+// k_lif with per-neuron parameters (snn_pervec: thresh[j], decay[j], trace_decay[j], trace_scale[j]).  Grid (blocks over the N
+// neurons, B samples): the loop carries the neuron j of sample blockIdx.y, so the [N] rows are loaded coalesced and without the
+// division of the VTH instance above; the B blocks of a column range find them in L2.
+__global__ __launch_bounds__(256) void k_lif_pv(float *__restrict__ v, float *__restrict__ refrac, uint8_t *__restrict__ s,
+                                                float *__restrict__ x, float *__restrict__ I, int N, snn_lif_params p,
+                                                uint8_t *__restrict__ raster_s, float *__restrict__ raster_v, snn_pervec pv) {
+    const long base = (long)blockIdx.y * N;
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (long)gridDim.x * blockDim.x) {
+        const long k = base + j;
+        const node_row r = row_of<true>(p, 0.f, pv, j);
+        float vv = v[k], rc = refrac[k], cur = I[k];
+        if (rc > 0.f) { cur = 0.f; I[k] = 0.f; }   // nodes.py:511 masks the caller's tensor in place
+        const uint8_t sp = lif_update(vv, rc, cur, p, r.thresh, r.decay);
+        v[k] = vv; refrac[k] = rc; s[k] = sp;
+        if (p.traces) x[k] = trace_next(x[k], sp, r.trace_decay, r.trace_scale, p.traces_additive);
+        if (raster_s) raster_s[k] = sp;
+        if (raster_v) raster_v[k] = vv;
+    }
+}
+
+extern "C" int snn_lif_step(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N,
+                            const snn_lif_params *h_p, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+extern "C" int snn_lif_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N, const snn_lif_params *h_p,
+                               const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream) {
+    if (!pervec_any(pv)) return snn_lif_step(v, refrac, s, x, I, B, N, h_p, raster_s, raster_v, stream);
+    if (!v || !refrac || !s || !I || !h_p || B <= 0 || N <= 0) return SNN_ERR_INVALID;
+    if (h_p->traces && !x) return SNN_ERR_INVALID;
+    if (!pervec_within(pv, kPvThresh | kPvDecay | kPvTrace) || (pv->v[SNN_PV_TRACE_SCALE] && !h_p->traces_additive)) return SNN_ERR_INVALID;
+    if (B > 65535) return SNN_ERR_UNSUPPORTED;
+    const unsigned gx = (unsigned)((N + 255) / 256 < 4096 ? (N + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_lif_pv, dim3(gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, v, refrac, s, x, I, N, *h_p, raster_s, raster_v, *pv);
+    return snn_check_launch();
+}
+
 extern "C" int snn_lif_step_vth(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N,
                                 const snn_lif_params *h_p, const float *thresh_vec, uint8_t *raster_s, float *raster_v,
                                 snn_stream_t stream) {
@@ -239,34 +303,37 @@ extern "C" int snn_lif_step(float *v, float *refrac, uint8_t *s, float *x, float
 //                 argmax of 1/q over the candidates (first maximal index), winner written back,
 //                 trace + raster for the row.  The block of the last row publishes the new cursor.
 // =============================================================================================
+// PV (both kernels): the instance for per-neuron parameters (snn_pervec).  Thread <-> neuron j here, so row j -- thresh[j],
+// decay[j], theta_decay[j], theta_plus[j] -- is loaded once, beside theta[j], for the whole batch.
+template <bool PV>
 __global__ __launch_bounds__(256) void k_dc_membrane(float *__restrict__ v, float *__restrict__ refrac,
                                                      uint8_t *__restrict__ s, float *__restrict__ theta,
                                                      const float *__restrict__ I, int B, int N,
                                                      snn_dc_params p, long long *__restrict__ cursor,
-                                                     float *__restrict__ raster_v) {
+                                                     float *__restrict__ raster_v, snn_pervec pv) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j == 0 && cursor) cursor[1] = cursor[0];   // snapshot read by k_dc_arbitrate
     if (j >= N) return;
-    float th = theta[j];
-    if (p.learning) th = th * p.theta_decay;            // nodes.py:1079
-    const float thr = p.lif.thresh + th;                // nodes.py:1088
+    const node_row r = row_of<PV>(p, 0.f, pv, j);
+    const float th0 = dc_theta_decayed(theta[j], p.learning, r.theta_decay);   // nodes.py:1079
+    const float thr = r.thresh + th0;                   // nodes.py:1088
     int cnt = 0;
     for (int b = 0; b < B; ++b) {
         const size_t k = (size_t)b * N + j;
         float vv = v[k], rc = refrac[k];
-        const uint8_t sp = dc_update(vv, rc, I[k], thr, p.lif);
+        const uint8_t sp = dc_update(vv, rc, I[k], thr, p.lif, r.decay);
         v[k] = vv; refrac[k] = rc; s[k] = sp;
         cnt += sp;
         if (raster_v) raster_v[k] = vv;
     }
-    if (p.learning) th = th + p.theta_plus * (float)cnt;   // nodes.py:1094 (count is exact in f32)
-    theta[j] = th;
+    theta[j] = dc_theta_bumped(th0, p.learning, r.theta_plus, cnt);            // nodes.py:1094 (count is exact in f32)
 }
 
+template <bool PV>
 __global__ __launch_bounds__(256) void k_dc_arbitrate(uint8_t *__restrict__ s, float *__restrict__ x, int B,
                                                       int N, snn_dc_params p, const float *__restrict__ Q,
                                                       long long q_len, long long *__restrict__ cursor,
-                                                      int *__restrict__ status, uint8_t *__restrict__ raster_s) {
+                                                      int *__restrict__ status, uint8_t *__restrict__ raster_s, snn_pervec pv) {
     __shared__ int any_row[1024];
     __shared__ float red_v[4];
     __shared__ int red_j[4];
@@ -320,35 +387,58 @@ __global__ __launch_bounds__(256) void k_dc_arbitrate(uint8_t *__restrict__ s, f
         const size_t k = (size_t)b * N + j;
         uint8_t sp = s[k];
         if (win >= 0) { sp = (j == win); s[k] = sp; }
-        if (p.lif.traces) x[k] = trace_next(x[k], sp, p.lif.trace_decay, p.lif.trace_scale, p.lif.traces_additive);
+        if (p.lif.traces) {
+            const node_row r = row_of<PV>(p, 0.f, pv, j);
+            x[k] = trace_next(x[k], sp, r.trace_decay, r.trace_scale, p.lif.traces_additive);
+        }
         if (raster_s) raster_s[k] = sp;
     }
 }
 
+// `pv`: nullable; the vectors a Diehl&Cook / AdaptiveLIF layer reads (anything else was refused by the caller)
 int snn_launch_dc_membrane(float *v, float *refrac, uint8_t *s, float *theta, const float *I, int B, int N,
-                           const snn_dc_params &p, long long *cursor, float *raster_v, hipStream_t st) {
-    hipLaunchKernelGGL(k_dc_membrane, dim3((N + 255) / 256), dim3(256), 0, st, v, refrac, s, theta, I, B, N, p, cursor,
-                       raster_v);
+                           const snn_dc_params &p, long long *cursor, float *raster_v, hipStream_t st, const snn_pervec *pv) {
+    if (pervec_any(pv))
+        hipLaunchKernelGGL(k_dc_membrane<true>, dim3((N + 255) / 256), dim3(256), 0, st, v, refrac, s, theta, I, B, N, p, cursor,
+                           raster_v, *pv);
+    else
+        hipLaunchKernelGGL(k_dc_membrane<false>, dim3((N + 255) / 256), dim3(256), 0, st, v, refrac, s, theta, I, B, N, p, cursor,
+                           raster_v, snn_pervec{});
     return snn_check_launch();
 }
 
 int snn_launch_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc_params &p, const float *Q, long long q_len,
-                            long long *cursor, int *status, uint8_t *raster_s, hipStream_t st) {
-    hipLaunchKernelGGL(k_dc_arbitrate, dim3(B), dim3(256), 0, st, s, x, B, N, p, Q, q_len, cursor, status, raster_s);
+                            long long *cursor, int *status, uint8_t *raster_s, hipStream_t st, const snn_pervec *pv) {
+    if (pv && (pv->v[SNN_PV_TRACE_DECAY] || pv->v[SNN_PV_TRACE_SCALE]))
+        hipLaunchKernelGGL(k_dc_arbitrate<true>, dim3(B), dim3(256), 0, st, s, x, B, N, p, Q, q_len, cursor, status, raster_s, *pv);
+    else
+        hipLaunchKernelGGL(k_dc_arbitrate<false>, dim3(B), dim3(256), 0, st, s, x, B, N, p, Q, q_len, cursor, status, raster_s,
+                           snn_pervec{});
     return snn_check_launch();
+}
+
+static bool pervec_dc_ok(const snn_pervec *pv, const snn_dc_params &p) {
+    return pervec_within(pv, kPvThresh | kPvDecay | kPvTrace | kPvTheta) && !(pv && pv->v[SNN_PV_TRACE_SCALE] && !p.lif.traces_additive);
+}
+
+extern "C" int snn_dc_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *theta, const float *I, int B, int N,
+                              const snn_dc_params *h_p, const snn_pervec *pv, const float *noise_q, long long q_len,
+                              long long *cursor, int *status, uint8_t *raster_s, float *raster_v, snn_stream_t stream) {
+    if (!v || !refrac || !s || !theta || !I || !h_p || B <= 0 || N <= 0) return SNN_ERR_INVALID;
+    if (h_p->lif.traces && !x) return SNN_ERR_INVALID;
+    if (h_p->one_spike && (!noise_q || !cursor || !status)) return SNN_ERR_INVALID;
+    if (!pervec_dc_ok(pv, *h_p)) return SNN_ERR_INVALID;
+    if (B > 1024) return SNN_ERR_UNSUPPORTED;
+    int rc = snn_launch_dc_membrane(v, refrac, s, theta, I, B, N, *h_p, cursor, raster_v, (hipStream_t)stream, pv);
+    if (rc) return rc;
+    return snn_launch_dc_arbitrate(s, x, B, N, *h_p, noise_q, q_len, cursor, status, raster_s, (hipStream_t)stream, pv);
 }
 
 extern "C" int snn_dc_step(float *v, float *refrac, uint8_t *s, float *x, float *theta, const float *I, int B,
                            int N, const snn_dc_params *h_p, const float *noise_q, long long q_len,
                            long long *cursor, int *status, uint8_t *raster_s, float *raster_v,
                            snn_stream_t stream) {
-    if (!v || !refrac || !s || !theta || !I || !h_p || B <= 0 || N <= 0) return SNN_ERR_INVALID;
-    if (h_p->lif.traces && !x) return SNN_ERR_INVALID;
-    if (h_p->one_spike && (!noise_q || !cursor || !status)) return SNN_ERR_INVALID;
-    if (B > 1024) return SNN_ERR_UNSUPPORTED;
-    int rc = snn_launch_dc_membrane(v, refrac, s, theta, I, B, N, *h_p, cursor, raster_v, (hipStream_t)stream);
-    if (rc) return rc;
-    return snn_launch_dc_arbitrate(s, x, B, N, *h_p, noise_q, q_len, cursor, status, raster_s, (hipStream_t)stream);
+    return snn_dc_step_pv(v, refrac, s, x, theta, I, B, N, h_p, nullptr, noise_q, q_len, cursor, status, raster_s, raster_v, stream);
 }
 
 extern "C" int snn_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc_params *h_p, const float *noise_q,
@@ -358,7 +448,7 @@ extern "C" int snn_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc
     if (h_p->lif.traces && !x) return SNN_ERR_INVALID;
     if (h_p->one_spike && (!noise_q || !cursor || !status)) return SNN_ERR_INVALID;
     if (B > 1024) return SNN_ERR_UNSUPPORTED;
-    return snn_launch_dc_arbitrate(s, x, B, N, *h_p, noise_q, q_len, cursor, status, raster_s, (hipStream_t)stream);
+    return snn_launch_dc_arbitrate(s, x, B, N, *h_p, noise_q, q_len, cursor, status, raster_s, (hipStream_t)stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

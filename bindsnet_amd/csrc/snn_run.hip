@@ -62,9 +62,9 @@ int snn_try_fused_convlif(const snn_layer_desc *L, int nL, const snn_conn_desc *
 int snn_try_fused_convpp(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R, hipStream_t st, int *handled);
 
 int snn_launch_dc_membrane(float *v, float *refrac, uint8_t *s, float *theta, const float *I, int B, int N,
-                           const snn_dc_params &p, long long *cursor, float *raster_v, hipStream_t st);
+                           const snn_dc_params &p, long long *cursor, float *raster_v, hipStream_t st, const snn_pervec *pv);
 int snn_launch_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc_params &p, const float *Q, long long q_len,
-                            long long *cursor, int *status, uint8_t *raster_s, hipStream_t st);
+                            long long *cursor, int *status, uint8_t *raster_s, hipStream_t st, const snn_pervec *pv);
 int snn_launch_rng_fill(snn_rng_state *rng, const uint8_t *s, int B, int N, float *qbuf, long long *cursor,
                         hipStream_t st);
 
@@ -93,11 +93,41 @@ __global__ __launch_bounds__(256) void k_mask_fill(float *__restrict__ W, const 
 }
 static unsigned grid_for(long n) { const long g = (n + 255) / 256; return (unsigned)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
 
+// The per-neuron vectors of a layer as its step reads them: d.pv, with thresh_vec (the older field) standing in for the threshold
+// where d.pv names none.
+static snn_pervec layer_pervec(const snn_layer_desc &d) {
+    snn_pervec pv = d.pv;
+    if (!pv.v[SNN_PV_THRESH]) pv.v[SNN_PV_THRESH] = d.thresh_vec;
+    return pv;
+}
+static bool has_pervec(const snn_layer_desc &d) {
+    if (d.thresh_vec) return true;
+    for (int q = 0; q < SNN_PV_COUNT; ++q) if (d.pv.v[q]) return true;
+    return false;
+}
+
 static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R) {
     if (!L || nL <= 0 || (nC > 0 && !C) || !R || R->B <= 0 || R->T < 0) return SNN_ERR_INVALID;
     for (int l = 0; l < nL; ++l) {
         const snn_layer_desc &d = L[l];
         if (d.n <= 0) return SNN_ERR_INVALID;
+        if (has_pervec(d)) {       // a vector the layer's kind does not read (theta_plus on an LIF layer, say): refused up front
+            unsigned allowed = 0;
+            switch (d.kind) {
+                case SNN_LAYER_INPUT: allowed = snn::kPvTrace; break;
+                case SNN_LAYER_LIF: case SNN_LAYER_BOOSTED: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay; break;
+                case SNN_LAYER_DC: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvTheta; break;
+                case SNN_LAYER_MCP: case SNN_LAYER_IF: case SNN_LAYER_IZH: allowed = snn::kPvTrace | snn::kPvThresh; break;
+                case SNN_LAYER_CURRENT: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvIDecay; break;
+                default: return SNN_ERR_INVALID;
+            }
+            const snn_pervec pv = layer_pervec(d);
+            if (!snn::pervec_within(&pv, allowed)) return SNN_ERR_INVALID;
+            if ((pv.v[SNN_PV_TRACE_DECAY] || pv.v[SNN_PV_TRACE_SCALE]) && !d.p.lif.traces) return SNN_ERR_INVALID;
+            if (pv.v[SNN_PV_TRACE_SCALE] && !d.p.lif.traces_additive) return SNN_ERR_INVALID;   // (masked_fill_ takes a 0-dim value)
+            // (the per-neuron instances put the sample into the grid's second dimension; an LIF layer with thresh_vec alone keeps snn_lif_step_vth)
+            if (R->B > 65535 && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
+        }
         switch (d.kind) {
             case SNN_LAYER_INPUT:
                 if (!d.ext_spikes || !d.s) return SNN_ERR_INVALID;
@@ -108,7 +138,6 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (d.p.one_spike && (!R->cursor || !R->status)) return SNN_ERR_INVALID;
                 if (d.p.one_spike && !R->noise_q && !(R->rng && R->qbuf)) return SNN_ERR_INVALID;
                 if (R->B > 1024) return SNN_ERR_UNSUPPORTED;
-                if (d.thresh_vec) return SNN_ERR_UNSUPPORTED;          // per-neuron thresholds: LIF layers
                 /* fallthrough */
             case SNN_LAYER_LIF:
                 if (!d.v || !d.refrac || !d.s || !d.current) return SNN_ERR_INVALID;
@@ -117,7 +146,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             case SNN_LAYER_IZH:               // nodes.py:1147: u in aux, a .. d and the transposed lateral matrix
                 if (!d.aux || !d.izh_a || !d.izh_b || !d.izh_c || !d.izh_d || !d.izh_St) return SNN_ERR_INVALID;
                 if (d.n > SNN_IZH_MAX_N) return SNN_ERR_UNSUPPORTED;
-                if (!d.v || !d.s || !d.current || d.thresh_vec) return SNN_ERR_INVALID;
+                if (!d.v || !d.s || !d.current) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
                 break;
             case SNN_LAYER_CURRENT:           // nodes.py:681: the synaptic current i in aux
@@ -128,7 +157,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (!d.refrac) return SNN_ERR_INVALID;
                 /* fallthrough */
             case SNN_LAYER_MCP:               // nodes.py:231
-                if (!d.v || !d.s || !d.current || d.thresh_vec) return SNN_ERR_INVALID;
+                if (!d.v || !d.s || !d.current) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
                 break;
             default: return SNN_ERR_INVALID;
@@ -242,9 +271,11 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             const size_t off = (size_t)t * B * d.n;
             uint8_t *rs = d.raster_s ? d.raster_s + off : nullptr;
             float *rv = d.raster_v ? d.raster_v + off : nullptr;
+            const snn_pervec pvl = layer_pervec(d);
+            const snn_pervec *pv = has_pervec(d) ? &pvl : nullptr;     // (NULL: every *_pv entry point is its scalar namesake)
             if (d.kind == SNN_LAYER_INPUT) {
-                TRY(snn_input_step(d.ext_spikes + off, d.p.lif.traces ? d.x : nullptr, (long)B * d.n,
-                                   d.p.lif.trace_decay, d.p.lif.trace_scale, d.p.lif.traces_additive, rs, st));
+                TRY(snn_input_step_pv(d.ext_spikes + off, d.p.lif.traces ? d.x : nullptr, B, d.n,
+                                      d.p.lif.trace_decay, d.p.lif.trace_scale, d.p.lif.traces_additive, pv, rs, st));
                 continue;
             }
             if (!fed[l]) TRY(snn_check(hipMemsetAsync(d.current, 0, sizeof(float) * (size_t)B * d.n, st)));  // :409-413
@@ -259,20 +290,22 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 hipLaunchKernelGGL(k_inject, dim3(grid_for((long)B * d.n)), dim3(256), 0, st, d.v,
                                    d.inject_v + (d.inject_per_step ? (size_t)t * len : 0), (long)B * d.n, len);
             }
-            if (d.kind == SNN_LAYER_LIF) TRY(snn_lif_step_vth(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, d.thresh_vec, rs, rv, st));
-            else if (d.kind == SNN_LAYER_MCP) TRY(snn_mcp_step(d.v, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
-            else if (d.kind == SNN_LAYER_IF) TRY(snn_if_step(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
-            else if (d.kind == SNN_LAYER_BOOSTED) TRY(snn_boosted_step(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, rs, rv, st));
-            else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, rs, rv, st));
-            else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
-                                                              &d.p.lif, rs, rv, st));
+            // (an LIF layer whose only vector is thresh_vec keeps its own instance: snn_lif_step_vth)
+            if (d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv)) TRY(snn_lif_step_vth(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, d.thresh_vec, rs, rv, st));
+            else if (d.kind == SNN_LAYER_LIF) TRY(snn_lif_step_pv(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_MCP) TRY(snn_mcp_step_pv(d.v, d.s, d.x, d.current, B, d.n, &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_IF) TRY(snn_if_step_pv(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_BOOSTED) TRY(snn_boosted_step_pv(d.v, d.refrac, d.s, d.x, d.current, B, d.n, &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step_pv(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step_pv(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
+                                                                 &d.p.lif, pv, rs, rv, st));
             else if (R->rng && d.p.one_spike) {   // device generator: membrane -> draws for this step -> arbitration
-                TRY(snn_launch_dc_membrane(d.v, d.refrac, d.s, d.theta, d.current, B, d.n, d.p, R->cursor, rv, st));
+                TRY(snn_launch_dc_membrane(d.v, d.refrac, d.s, d.theta, d.current, B, d.n, d.p, R->cursor, rv, st, pv));
                 TRY(snn_launch_rng_fill(R->rng, d.s, B, d.n, R->qbuf, R->cursor, st));
                 TRY(snn_launch_dc_arbitrate(d.s, d.x, B, d.n, d.p, R->qbuf, (long long)B * d.n, R->cursor, R->status,
-                                            rs, st));
-            } else TRY(snn_dc_step(d.v, d.refrac, d.s, d.x, d.theta, d.current, B, d.n, &d.p, R->noise_q, R->q_len,
-                                   R->cursor, R->status, rs, rv, st));
+                                            rs, st, pv));
+            } else TRY(snn_dc_step_pv(d.v, d.refrac, d.s, d.x, d.theta, d.current, B, d.n, &d.p, pv, R->noise_q, R->q_len,
+                                      R->cursor, R->status, rs, rv, st));
             // clamp / unclamp right behind the layer's own step (network.py:394-429): with one_step a later layer's
             // currents are taken from these spikes
             if (d.clamp || d.unclamp)
@@ -389,7 +422,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_CONV2D && C[c].rule != SNN_RULE_NONE) conv_rule = true;
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
-    for (int l = 0; l < nL; ++l) if (L[l].thresh_vec) mode = 1;      // per-neuron thresholds: generic plan
+    for (int l = 0; l < nL; ++l) if (has_pervec(L[l])) mode = 1;     // per-neuron parameters: generic plan
     bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic

@@ -445,7 +445,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 d.n = layer.n
                 if isinstance(layer, Input):
                     d.kind = _lib.LAYER_INPUT
-                    layer._trace_fields(d.p.lif)
+                    pv = {}                            # per-neuron tc_trace / additive trace_scale (nodes.py:96-107 broadcast them)
+                    layer._trace_fields(d.p.lif, pv)
+                    layer._fill_pv(d, pv, keep)
                     d.x = _dptr(layer.x) if layer.traces else None
                     wanted = []                        # (monitor, key) pairs recording this layer's spikes
                     for m in self.monitors.values():
@@ -532,7 +534,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d") + (("thresh",) if isinstance(getattr(layer, "thresh", None), torch.Tensor) and layer.thresh.numel() > 1 else ()):
+            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
                 t = getattr(layer, attr, None)
                 if isinstance(t, torch.Tensor):
                     ptrs.append((layer, attr, t.data_ptr()))

@@ -20,8 +20,9 @@ _SCALARS = None          # collector of the parameter tensors read while run des
 
 
 def _f(t) -> float:
-    """Python float of a 0-dim parameter.  Per-neuron (tensor-valued) parameters are outside
-    the accelerated path (SURVEY.md 8(b) fallback rule) and are rejected loudly."""
+    """Python float of a 0-dim parameter.  A tensor with more than one element raises: the per-neuron quantities the step kernels
+    index by neuron go through Nodes._sv / Nodes._vec instead; everything else (`rest`, `reset`, `refrac`, `lbound`, and
+    `trace_scale` without additive traces) fails in the reference too, whose fill_ / masked_fill_ take a 0-dim value only."""
     if isinstance(t, torch.Tensor):
         # .item() on a device tensor is a blocking copy (~15 us each, ~20 per run()): remember the value on the
         # tensor object itself, keyed by its in-place version counter
@@ -97,26 +98,81 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         self.learning = mode
         return super().train(mode)
 
+    # -- per-neuron parameters --------------------------------------------------------------------
+    # The quantities (named after the derived buffers the kernels read: _lib.PERVEC) this class may hold as a tensor with one
+    # value per neuron -- the pairs the reference itself runs (INTEGRATION.md section 3 has the table).  `trace_scale` only with
+    # additive traces.  The tc_* constants reach the kernels through compute_decays(), as in the reference.
+    _PERVEC = ("trace_decay", "trace_scale")
+
+    def _state_device(self) -> torch.device:
+        v = getattr(self, "v", None)
+        return v.device if isinstance(v, torch.Tensor) else self.x.device
+
+    def _vec(self, name: str) -> Optional[torch.Tensor]:
+        """Parameter `name` as the step kernels index it by neuron: a contiguous f32 [n] tensor beside the state, or None for a
+        scalar (a one-element tensor is a scalar).  A tensor that is not already such a vector is brought over once and kept,
+        keyed by its in-place version, like the transposed lateral matrix of IzhikevichNodes."""
+        t = getattr(self, name)
+        if not isinstance(t, torch.Tensor) or t.numel() == 1:
+            return None
+        if name not in self._PERVEC or (name == "trace_scale" and not self.traces_additive):
+            raise NotImplementedError(f"bindsnet_amd: a tensor-valued per-neuron `{name}` on {type(self).__name__} is not supported"
+                                      + (" without additive traces" if name == "trace_scale" and name in self._PERVEC else ""))
+        if tuple(t.shape) != tuple(self.shape):
+            raise ValueError(f"{type(self).__name__}.{name} has shape {list(t.shape)}, the layer {list(self.shape)}")
+        if _SCALARS is not None:
+            _SCALARS.append((t, t._version))              # (an in-place change rebuilds the descriptors: the vector may be a copy)
+        dev = self._state_device()
+        if t.device == dev and t.dtype == torch.float32 and t.is_contiguous():
+            return t
+        cache = self.__dict__.setdefault("_pervec_dev", {})
+        hit = cache.get(name)
+        if hit is None or hit[0] is not t or hit[1] != t._version or hit[2].device != dev:
+            hit = cache[name] = (t, t._version, t.detach().to(dev, torch.float32).contiguous())
+        return hit[2]
+
+    def _sv(self, name: str, pv: dict) -> float:
+        """The scalar field for parameter `name`; where it is a per-neuron tensor the vector goes into `pv` and the field is 0."""
+        vec = self._vec(name)
+        if vec is None:
+            return _f(getattr(self, name))
+        pv[name] = vec
+        return 0.0
+
+    def _pervec_names(self) -> list:
+        """Names of this layer's parameters that hold more than one element."""
+        names = ("thresh", "rest", "reset", "refrac", "lbound", "tc_decay", "decay", "tc_trace", "trace_decay", "trace_scale",
+                 "tc_theta_decay", "theta_decay", "theta_plus", "tc_i_decay", "i_decay")
+        return [k for k in names if isinstance(getattr(self, k, None), torch.Tensor) and getattr(self, k).numel() > 1]
+
+    @staticmethod
+    def _fill_pv(d: _lib.LayerDesc, pv: dict, keep: list) -> None:
+        if pv:
+            d.pv = _lib.pervec(pv)
+            keep.extend(pv.values())
+
     # -- descriptor pieces for the run driver ---------------------------------------------------
-    def _trace_fields(self, p: _lib.LifParams) -> None:
+    def _trace_fields(self, p: _lib.LifParams, pv: Optional[dict] = None) -> None:
         p.traces = int(self.traces)
         if self.traces:
-            p.trace_decay, p.trace_scale = _f(self.trace_decay), _f(self.trace_scale)
+            pv = {} if pv is None else pv
+            p.trace_decay, p.trace_scale = self._sv("trace_decay", pv), self._sv("trace_scale", pv)
             p.traces_additive = int(self.traces_additive)
 
     # float32 [B, n] state tensors (beside `s` and `x`) whose addresses the layer's snn_layer_desc holds
     _STATE = ("v", "refrac_count")
 
-    def _node_params(self, **fields) -> _lib.LifParams:
-        """snn_lif_params of a layer that has `thresh`: thresh, dt, lbound and the trace fields, plus the named ones."""
-        p = _lib.LifParams()
-        p.thresh, p.dt = _f(self.thresh), _f(self.dt)
+    def _node_params(self, pv: Optional[dict] = None, **fields) -> _lib.LifParams:
+        """snn_lif_params of a layer that has `thresh`: thresh, dt, lbound and the trace fields, plus the named ones.  Per-neuron
+        vectors go into `pv` (their scalar fields are then 0)."""
+        p, pv = _lib.LifParams(), ({} if pv is None else pv)
+        p.thresh, p.dt = self._sv("thresh", pv), _f(self.dt)
         for key, value in fields.items():
-            setattr(p, key, _f(value))
+            setattr(p, key, self._sv(key, pv) if key in _lib.PERVEC else _f(value))
         lbound = getattr(self, "lbound", None)
         p.has_lbound = int(lbound is not None)
         p.lbound = _f(lbound) if lbound is not None else 0.0
-        self._trace_fields(p)
+        self._trace_fields(p, pv)
         return p
 
     def _describe(self, d: _lib.LayerDesc, keep: list, scalars: list) -> int:
@@ -162,11 +218,14 @@ class Input(Nodes, AbstractInput):
             return self._host_step(x)
         self.s = x
         if self.traces:
-            ops.input_step(x.contiguous(), self.x, _f(self.trace_decay), _f(self.trace_scale), self.traces_additive)
+            pv = {}
+            ops.input_step(x.contiguous(), self.x, self._sv("trace_decay", pv), self._sv("trace_scale", pv), self.traces_additive,
+                           pv=pv)
 
 
 class LIFNodes(Nodes):
     """Leaky integrate-and-fire layer (reference: nodes.py:418-559)."""
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -199,41 +258,27 @@ class LIFNodes(Nodes):
         self.v.fill_(_f(self.rest))
         self.refrac_count.zero_()
 
-    def _thresh_vec(self) -> Optional[torch.Tensor]:
-        """Per-neuron thresholds (nodes.py:425-498 take `thresh` as a tensor; examples/mnist/reservoir.py passes one): the [n] f32
-        device tensor the LIF kernel indexes by neuron, or None for the usual scalar."""
-        t = self.thresh
-        if not isinstance(t, torch.Tensor) or t.numel() == 1:
-            return None
-        if t.numel() != self.n:
-            raise ValueError(f"LIFNodes.thresh has {t.numel()} entries, the layer {self.n} neurons")
-        if t.device != self.v.device or t.dtype != torch.float32 or not t.is_contiguous():
-            # (a buffer: .to() moves it with the layer; anything else is brought over once and kept -- an in-place change of the
-            #  original is then not seen, which the version check below guards)
-            cached = self.__dict__.get("_thresh_dev")
-            if cached is None or cached[0] is not t or cached[1] != t._version or cached[2].device != self.v.device:
-                cached = self.__dict__["_thresh_dev"] = (t, t._version, t.detach().to(self.v.device, torch.float32).contiguous())
-            return cached[2]
-        return t
-
-    def _lif_params(self) -> _lib.LifParams:
+    def _lif_params(self, pv: Optional[dict] = None) -> _lib.LifParams:
+        """snn_lif_params; per-neuron vectors go into `pv` (the callers hand pv["thresh"] on through the older thresh_vec field)."""
+        pv = {} if pv is None else pv
         p = _lib.LifParams()
-        p.decay, p.rest, p.reset = _f(self.decay), _f(self.rest), _f(self.reset)
-        p.thresh = 0.0 if self._thresh_vec() is not None else _f(self.thresh)
+        p.decay, p.rest, p.reset = self._sv("decay", pv), _f(self.rest), _f(self.reset)
+        p.thresh = self._sv("thresh", pv)
         p.refrac, p.dt = _f(self.refrac), _f(self.dt)
         p.has_lbound = int(self.lbound is not None)
         p.lbound = _f(self.lbound) if self.lbound is not None else 0.0
-        self._trace_fields(p)
+        self._trace_fields(p, pv)
         return p
 
     def _describe(self, d, keep, scalars) -> int:
         d.kind = _lib.LAYER_LIF
-        d.p.lif = self._lif_params()
-        tv = self._thresh_vec()                           # per-neuron thresholds (nodes.py:425-498; generic plan)
+        pv = {}
+        d.p.lif = self._lif_params(pv)
+        tv = pv.pop("thresh", None)                       # per-neuron thresholds (nodes.py:425-498; generic plan)
+        self._fill_pv(d, pv, keep)
         if tv is not None:
             keep.append(tv)
             d.thresh_vec = _lib.dptr(tv)
-            scalars.append((self.thresh, self.thresh._version))      # (an in-place change rebuilds: tv may be a converted copy)
         return 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -246,14 +291,16 @@ class LIFNodes(Nodes):
             return self._host_step(x)
         if self.s.dtype != torch.bool or self.s.shape != self.v.shape:
             self.s = torch.zeros_like(self.v, dtype=torch.bool)
-        ops.lif_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._lif_params(),
-                     thresh_vec=self._thresh_vec())
+        pv = {}
+        p = self._lif_params(pv)
+        ops.lif_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, p, thresh_vec=pv.pop("thresh", None), pv=pv)
 
 
 class _AdaptiveThresholdNodes(Nodes):
     """What DiehlAndCookNodes (nodes.py:981-1144) and AdaptiveLIFNodes (nodes.py:829-978) share: the same buffers, decays and
     membrane / threshold arithmetic (SNN_LAYER_DC).  They differ only in DiehlAndCookNodes' one-spike arbitration.  Private, so
     that neither class is an instance of the other, as in the reference."""
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -293,20 +340,24 @@ class _AdaptiveThresholdNodes(Nodes):
         self.v.fill_(_f(self.rest))
         self.refrac_count.zero_()
 
-    def _dc_params(self) -> _lib.DcParams:
+    def _dc_params(self, pv: Optional[dict] = None) -> _lib.DcParams:
+        """snn_dc_params; per-neuron vectors go into `pv`."""
+        pv = {} if pv is None else pv
         p = _lib.DcParams()
         l = p.lif
-        l.decay, l.rest, l.reset, l.thresh = _f(self.decay), _f(self.rest), _f(self.reset), _f(self.thresh)
+        l.decay, l.rest, l.reset, l.thresh = self._sv("decay", pv), _f(self.rest), _f(self.reset), self._sv("thresh", pv)
         l.refrac, l.dt = _f(self.refrac), _f(self.dt)
         l.has_lbound = int(self.lbound is not None)
         l.lbound = (_f(self.lbound) if isinstance(self.lbound, torch.Tensor) else float(self.lbound)) if self.lbound is not None else 0.0
-        self._trace_fields(l)
-        p.theta_decay, p.theta_plus = _f(self.theta_decay), _f(self.theta_plus)
+        self._trace_fields(l, pv)
+        p.theta_decay, p.theta_plus = self._sv("theta_decay", pv), self._sv("theta_plus", pv)
         p.learning, p.one_spike = int(self.learning), int(self.one_spike)
         return p
 
     def _describe(self, d, keep, scalars) -> int:
-        d.kind, d.p, d.theta = _lib.LAYER_DC, self._dc_params(), _lib.dptr(self.theta)
+        pv = {}
+        d.kind, d.p, d.theta = _lib.LAYER_DC, self._dc_params(pv), _lib.dptr(self.theta)
+        self._fill_pv(d, pv, keep)
         return self.v.shape[0] * self.n if self.one_spike else 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -322,9 +373,11 @@ class _AdaptiveThresholdNodes(Nodes):
         if self.s.dtype != torch.bool or self.s.shape != self.v.shape:
             self.s = torch.zeros_like(self.v, dtype=torch.bool)
         B = self.v.shape[0]
+        pv = {}
+        p = self._dc_params(pv)                            # (before the draws: a refused parameter leaves the generator alone)
         with NoiseStream(self.v.device, max_draws=B * self.n if self.one_spike else 0) as ns:
             ops.dc_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, self.theta, x,
-                        self._dc_params(), ns.q, ns.cursor, ns.status)
+                        p, ns.q, ns.cursor, ns.status, pv=pv)
 
 
 class DiehlAndCookNodes(_AdaptiveThresholdNodes):
@@ -360,6 +413,7 @@ class McCullochPitts(Nodes):
     input tensor; on the device this layer holds its own [B, n] copy of it (the step kernel writes it), on the host it
     aliases like the reference."""
     _STATE = ("v",)
+    _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = 1.0, **kwargs) -> None:
@@ -373,7 +427,9 @@ class McCullochPitts(Nodes):
         self.v = torch.zeros(batch_size, *self.shape, device=self.v.device)
 
     def _describe(self, d, keep, scalars) -> int:
-        d.kind, d.p.lif = _lib.LAYER_MCP, self._node_params()
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_MCP, self._node_params(pv)
+        self._fill_pv(d, pv, keep)
         return 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -385,11 +441,14 @@ class McCullochPitts(Nodes):
         if not x.is_cuda:
             return self._host_step(x)
         self._own_spikes()
-        ops.mcp_step(self.v, self.s, self.x if self.traces else None, x, self._node_params())
+        pv = {}
+        p = self._node_params(pv)
+        ops.mcp_step(self.v, self.s, self.x if self.traces else None, x, p, pv=pv)
 
 
 class IFNodes(Nodes):
     """Integrate-and-fire layer (reference: nodes.py:308-415): no decay, no rest; state starts at `reset`."""
+    _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, reset: Scalar = -65.0, refrac: Union[int, torch.Tensor] = 5,
@@ -414,11 +473,13 @@ class IFNodes(Nodes):
         self.v.fill_(_f(self.reset))
         self.refrac_count.zero_()
 
-    def _params(self) -> _lib.LifParams:
-        return self._node_params(reset=self.reset, refrac=self.refrac)
+    def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
+        return self._node_params(pv, reset=self.reset, refrac=self.refrac)
 
     def _describe(self, d, keep, scalars) -> int:
-        d.kind, d.p.lif = _lib.LAYER_IF, self._params()
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_IF, self._params(pv)
+        self._fill_pv(d, pv, keep)
         return 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -430,12 +491,15 @@ class IFNodes(Nodes):
         if not self.v.is_cuda:
             return self._host_step(x)
         self._own_spikes()
-        ops.if_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._params())
+        pv = {}
+        p = self._params(pv)
+        ops.if_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, p, pv=pv)
 
 
 class BoostedLIFNodes(Nodes):
     """LIF without rest, reset value or lower bound (reference: nodes.py:562-678): the membrane decays towards 0 and is reset
     to 0.  `refrac_count` is an integer scalar until set_batch_size() makes it a float [B, n] tensor, as in the reference."""
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = 13.0, refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 100.0,
@@ -463,11 +527,13 @@ class BoostedLIFNodes(Nodes):
         self.v.fill_(0)
         self.refrac_count.zero_()
 
-    def _params(self) -> _lib.LifParams:
-        return self._node_params(decay=self.decay, refrac=self.refrac)
+    def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
+        return self._node_params(pv, decay=self.decay, refrac=self.refrac)
 
     def _describe(self, d, keep, scalars) -> int:
-        d.kind, d.p.lif = _lib.LAYER_BOOSTED, self._params()
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_BOOSTED, self._params(pv)
+        self._fill_pv(d, pv, keep)
         return 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -479,13 +545,16 @@ class BoostedLIFNodes(Nodes):
         if not self.v.is_cuda:
             return self._host_step(x)
         self._own_spikes()
-        ops.boosted_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, self._params())
+        pv = {}
+        p = self._params(pv)
+        ops.boosted_step(self.v, self.refrac_count, self.s, self.x if self.traces else None, x, p, pv=pv)
 
 
 class CurrentLIFNodes(Nodes):
     """Current-based LIF layer (reference: nodes.py:681-826): the input feeds a decaying synaptic current `i`, which feeds
     the membrane."""
     _STATE = ("v", "refrac_count", "i")
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay", "i_decay")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -525,12 +594,14 @@ class CurrentLIFNodes(Nodes):
         self.i.zero_()
         self.refrac_count.zero_()
 
-    def _params(self) -> _lib.LifParams:
-        return self._node_params(decay=self.decay, rest=self.rest, reset=self.reset, refrac=self.refrac)
+    def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
+        return self._node_params(pv, decay=self.decay, rest=self.rest, reset=self.reset, refrac=self.refrac)
 
     def _describe(self, d, keep, scalars) -> int:
-        d.kind, d.p.lif = _lib.LAYER_CURRENT, self._params()
-        d.aux, d.aux_decay = _lib.dptr(self.i), _f(self.i_decay)
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_CURRENT, self._params(pv)
+        d.aux, d.aux_decay = _lib.dptr(self.i), self._sv("i_decay", pv)
+        self._fill_pv(d, pv, keep)
         return 0
 
     def _host_step(self, x: torch.Tensor) -> None:
@@ -542,8 +613,9 @@ class CurrentLIFNodes(Nodes):
         if not self.v.is_cuda:
             return self._host_step(x)
         self._own_spikes()
-        ops.clif_step(self.v, self.refrac_count, self.i, self.s, self.x if self.traces else None, x, self._params(),
-                      _f(self.i_decay))
+        pv = {}
+        p, i_decay = self._params(pv), self._sv("i_decay", pv)
+        ops.clif_step(self.v, self.refrac_count, self.i, self.s, self.x if self.traces else None, x, p, i_decay, pv=pv)
 
 
 class IzhikevichNodes(Nodes):
@@ -554,6 +626,7 @@ class IzhikevichNodes(Nodes):
     user-visible `S` and refreshed when `S` is replaced, changed in place or moved.  Layers of more than `_lib.IZH_MAX_N`
     neurons raise NotImplementedError there: the lateral sum's order is pinned against torch up to that size only."""
     _STATE = ("v", "u")
+    _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, excitatory: float = 1, thresh: Scalar = 45.0, rest: Scalar = -65.0, lbound: float = None,
@@ -605,7 +678,7 @@ class IzhikevichNodes(Nodes):
         self.u = self.b * self.v
 
     def _St(self) -> torch.Tensor:
-        """The lateral matrix as the step kernel reads it: transposed, contiguous f32 beside `v` (cached like _thresh_vec)."""
+        """The lateral matrix as the step kernel reads it: transposed, contiguous f32 beside `v` (cached like Nodes._vec)."""
         S = self.S
         cached = self.__dict__.get("_St_dev")
         if cached is None or cached[0] is not S or cached[1] != S._version or cached[2].device != self.v.device:
@@ -613,6 +686,7 @@ class IzhikevichNodes(Nodes):
         return cached[2]
 
     def _abcd(self):
+        _f(self.rest)       # the step never reads `rest`, reset_state_variables() does: a tensor is refused before the run, not after
         if self.n > _lib.IZH_MAX_N:
             raise NotImplementedError(f"bindsnet_amd: IzhikevichNodes of more than {_lib.IZH_MAX_N} neurons (the order of the "
                                       "lateral sum is pinned against torch up to that size only)")
@@ -631,7 +705,9 @@ class IzhikevichNodes(Nodes):
         St = self._St()
         keep.append(St)
         scalars.append((self.S, self.S._version))         # (an in-place change of S rebuilds: St is a copy)
-        d.kind, d.p.lif = _lib.LAYER_IZH, self._node_params()
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_IZH, self._node_params(pv)
+        self._fill_pv(d, pv, keep)
         d.aux = _lib.dptr(self.u)
         d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St = (_lib.dptr(t) for t in (a, b, c, dd, St))
         return 0
@@ -646,4 +722,6 @@ class IzhikevichNodes(Nodes):
             return self._host_step(x)
         self._own_spikes()
         a, b, c, d = self._abcd()
-        ops.izh_step(self.v, self.u, self.s, self.x if self.traces else None, x, a, b, c, d, self._St(), self._node_params())
+        pv = {}
+        p = self._node_params(pv)
+        ops.izh_step(self.v, self.u, self.s, self.x if self.traces else None, x, a, b, c, d, self._St(), p, pv=pv)

@@ -235,15 +235,43 @@ def prop_sparse(compiled, s, out, bias=None, accumulate=False):
     return out
 
 
-def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None):
+def _pv(vectors, N):
+    """The snn_pervec argument of a *_pv entry point from {quantity: f32 [N] device tensor} (None / empty: a null pointer,
+    the scalar step).  Returns (argument, the struct to keep alive over the call)."""
+    if not vectors:
+        return None, None
+    for name, t in vectors.items():
+        if t.numel() != N:
+            raise ValueError(f"per-neuron `{name}` has {t.numel()} entries, the layer {N} neurons")
+        _ptr(t, F32)
+    pv = _lib.pervec(vectors)
+    return C.byref(pv), pv
+
+
+def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None, pv=None):
+    """pv (here and in every step below): optional {quantity name (_lib.PERVEC): f32 [N] device tensor} of per-neuron
+    parameters that take the place of the scalars (include/snnhip.h f10)."""
+    if pv:
+        B = s.shape[0]
+        arg, _keep = _pv(pv, s.numel() // B)
+        check(lib().snn_input_step_pv(_ptr(s, "spike"), _ptr(x, F32, True), B, s.numel() // B, trace_decay, trace_scale,
+                                      int(additive), arg, _ptr(raster, "spike", True), _stream()), "input_step")
+        return
     check(lib().snn_input_step(_ptr(s, "spike"), _ptr(x, F32, True), s.numel(), trace_decay, trace_scale,
                                int(additive), _ptr(raster, "spike", True), _stream()), "input_step")
 
 
-def lif_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None, thresh_vec=None):
+def lif_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None, thresh_vec=None, pv=None):
     """thresh_vec: optional f32 [N] per-neuron thresholds (replace p.thresh; nodes.py:425-498 with a tensor-valued `thresh`)."""
     B = v.shape[0]
     N = v.numel() // B
+    if pv:
+        if thresh_vec is not None:
+            pv = dict(pv, thresh=thresh_vec)
+        arg, _keep = _pv(pv, N)
+        check(lib().snn_lif_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
+                                    C.byref(p), arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "lif_step")
+        return
     if thresh_vec is not None and thresh_vec.numel() != N:
         raise ValueError(f"thresh_vec has {thresh_vec.numel()} entries, the layer {N} neurons")
     check(lib().snn_lif_step_vth(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
@@ -256,35 +284,39 @@ def _node_args(v):
     return B, v.numel() // B
 
 
-def mcp_step(v, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+def mcp_step(v, s, x, I, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """McCullochPitts.forward (nodes.py:278-288): v = I, s = v >= thresh, trace."""
     B, N = _node_args(v)
-    check(lib().snn_mcp_step(_ptr(v, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p),
-                             _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "mcp_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_mcp_step_pv(_ptr(v, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p), arg,
+                                _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "mcp_step")
 
 
-def if_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+def if_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """IFNodes.forward (nodes.py:371-395)."""
     B, N = _node_args(v)
-    check(lib().snn_if_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p),
-                            _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "if_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_if_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N, C.byref(p), arg,
+                               _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "if_step")
 
 
-def boosted_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None):
+def boosted_step(v, refrac, s, x, I, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """BoostedLIFNodes.forward (nodes.py:621-648); I is masked in place where refractory."""
     B, N = _node_args(v)
-    check(lib().snn_boosted_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
-                                 C.byref(p), _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "boosted_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_boosted_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
+                                    C.byref(p), arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "boosted_step")
 
 
-def clif_step(v, refrac, i, s, x, I, p: LifParams, i_decay, raster_s=None, raster_v=None):
+def clif_step(v, refrac, i, s, x, I, p: LifParams, i_decay, raster_s=None, raster_v=None, pv=None):
     """CurrentLIFNodes.forward (nodes.py:762-791); i [B,N] is the synaptic current."""
     B, N = _node_args(v)
-    check(lib().snn_clif_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(i, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
-                              C.byref(p), i_decay, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "clif_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_clif_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(i, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), B, N,
+                                 C.byref(p), i_decay, arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "clif_step")
 
 
-def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None):
+def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """IzhikevichNodes.forward (nodes.py:1265-1296) in one launch; s holds the previous step's spikes at entry; St is the
     lateral matrix transposed ([N, N], St[i, j] = S[j, i]); the lateral sum is added to I in place."""
     B, N = _node_args(v)
@@ -292,20 +324,22 @@ def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_
         raise ValueError(f"a, b, c, d must have {N} entries and St {N} x {N}")
     if N > _lib.IZH_MAX_N:
         raise NotImplementedError(f"bindsnet_amd: IzhikevichNodes of more than {_lib.IZH_MAX_N} neurons")
-    check(lib().snn_izh_step(_ptr(v, F32), _ptr(u, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), _ptr(a, F32), _ptr(b, F32),
-                             _ptr(c, F32), _ptr(d, F32), _ptr(St, F32), B, N, C.byref(p), _ptr(raster_s, "spike", True),
-                             _ptr(raster_v, F32, True), _stream()), "izh_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_izh_step_pv(_ptr(v, F32), _ptr(u, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(I, F32), _ptr(a, F32), _ptr(b, F32),
+                                _ptr(c, F32), _ptr(d, F32), _ptr(St, F32), B, N, C.byref(p), arg, _ptr(raster_s, "spike", True),
+                                _ptr(raster_v, F32, True), _stream()), "izh_step")
 
 
-def dc_step(v, refrac, s, x, theta, I, p: DcParams, noise_q, cursor, status, raster_s=None, raster_v=None):
+def dc_step(v, refrac, s, x, theta, I, p: DcParams, noise_q, cursor, status, raster_s=None, raster_v=None, pv=None):
     """cursor: int64[2] device tensor ([0] running count, [1] scratch); status: int32[1]."""
     B = v.shape[0]
     N = v.numel() // B
     qlen = 0 if noise_q is None else noise_q.numel()
-    check(lib().snn_dc_step(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(theta, F32),
-                            _ptr(I, F32), B, N, C.byref(p), _ptr(noise_q, F32, True), qlen,
-                            _ptr(cursor, torch.int64, True), _ptr(status, torch.int32, True),
-                            _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "dc_step")
+    arg, _keep = _pv(pv, N)
+    check(lib().snn_dc_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(theta, F32),
+                               _ptr(I, F32), B, N, C.byref(p), arg, _ptr(noise_q, F32, True), qlen,
+                               _ptr(cursor, torch.int64, True), _ptr(status, torch.int32, True),
+                               _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "dc_step")
 
 
 def dc_arbitrate(s, x, p: DcParams, noise_q, cursor, status, raster_s=None):

@@ -80,12 +80,26 @@ def _reject_local(network, mode: str) -> None:
                                       "run the network on one device")
 
 
+def _reject_pervec(network, mode: str, lif_thresh_ok: bool = False) -> None:
+    """None of the multi-device modes reads per-neuron (tensor-valued) node parameters: such a layer raises, naming the layer
+    and the parameter, before any collective.  `lif_thresh_ok`: the mode runs Network.run() itself, which has always taken
+    LIFNodes with a tensor `thresh`."""
+    from .network.nodes import LIFNodes
+    for name, layer in network.layers.items():
+        for param in layer._pervec_names():
+            if lif_thresh_ok and param == "thresh" and type(layer) is LIFNodes:
+                continue
+            raise NotImplementedError(f"{mode}: layer '{name}' ({type(layer).__name__}) has a tensor-valued per-neuron `{param}`, which "
+                                      "the multi-device modes do not support; run the network on one device")
+
+
 def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, **kwargs) -> None:
     """network.run on this rank's batch shard, then merge learning across ranks (see module doc): the weights and
     thresholds become  before + sum_over_ranks(after - before), are clamped, and only then normalised.  The post-run
     normalisation inside run() is switched off through the network's `_defer_norm` flag (part of the key of the kept
     descriptor arrays, so consecutive sharded runs re-use them like plain runs do)."""
     _reject_local(network, "sharded_run")
+    _reject_pervec(network, "sharded_run", lif_thresh_ok=True)
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
     tensors = [t for t, _, _, _ in learned] + thetas
@@ -149,6 +163,7 @@ def column_shard(network, rank: int, world: int):
     from .network import Network
     from .network.nodes import Input, LIFNodes
     _reject_local(network, "column_shard")
+    _reject_pervec(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
         raise NotImplementedError("column sharding applies to Input -> one connection -> LIFNodes graphs (no coupling "
@@ -238,6 +253,7 @@ def gather_columns(local: torch.Tensor, n_columns: int, group=None) -> torch.Ten
 # =====================================================================================================
 def _exact_check(network):
     _reject_local(network, "exact_run")
+    _reject_pervec(network, "exact_run")
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes
     for name, layer in network.layers.items():
         if type(layer) not in (Input, LIFNodes, DiehlAndCookNodes):

@@ -262,6 +262,42 @@ int snn_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc_params *h_
                      const float *noise_q, long long q_len, long long *cursor, int *status,
                      uint8_t *raster_s, snn_stream_t stream);
 
+/* ---- f10: per-neuron parameters on every node layer ------------------------------------------
+ * bindsnet/network/nodes.py declares most node parameters Union[float, torch.Tensor]; a tensor gives every neuron its own
+ * value.  The step kernels read seven per-neuron quantities; each is either the scalar of snn_lif_params / snn_dc_params
+ * (or the i_decay argument), or an f32 [N] DEVICE vector indexed by neuron and broadcast over the batch.  snn_pervec holds the
+ * vectors: v[q] == NULL means "use the scalar".  The arithmetic is unchanged (csrc/snn_common.hpp): where a vector is given,
+ * neuron j's value takes the scalar's place in the same separately rounded operations; the Diehl&Cook threshold bump is
+ * theta[j] += theta_plus[j] * count[j], one rounded multiply and one add.  theta_decay[j] applies only while learning.
+ * Which quantity a layer kind reads:  thresh: all but INPUT;  decay: LIF, DC, BOOSTED, CURRENT;  trace_decay, trace_scale:
+ * every kind (trace_scale only with additive traces: the reference's masked_fill_ takes a 0-dim value);  theta_decay,
+ * theta_plus: DC;  i_decay: CURRENT.  A vector the kind does not read is SNN_ERR_INVALID.
+ * The *_pv entry points are their scalar namesakes with `pv` (nullable: the scalar step) added; B <= 65535 when pv names a
+ * vector (the sample is the launch grid's second dimension, so no kernel divides by N).  (ABI 8, additive)               */
+enum { SNN_PV_THRESH = 0, SNN_PV_DECAY = 1, SNN_PV_TRACE_DECAY = 2, SNN_PV_TRACE_SCALE = 3, SNN_PV_THETA_DECAY = 4,
+       SNN_PV_THETA_PLUS = 5, SNN_PV_I_DECAY = 6, SNN_PV_COUNT = 7 };
+typedef struct { const float *v[SNN_PV_COUNT]; } snn_pervec;
+
+int snn_input_step_pv(const uint8_t *s, float *x, int B, int N, float trace_decay, float trace_scale, int additive,
+                      const snn_pervec *pv, uint8_t *raster_out, snn_stream_t stream);
+int snn_lif_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N, const snn_lif_params *h_p,
+                    const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_mcp_step_pv(float *v, uint8_t *s, float *x, const float *I, int B, int N, const snn_lif_params *h_p,
+                    const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_if_step_pv(float *v, float *refrac, uint8_t *s, float *x, const float *I, int B, int N, const snn_lif_params *h_p,
+                   const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_boosted_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N, const snn_lif_params *h_p,
+                        const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_clif_step_pv(float *v, float *refrac, float *i, uint8_t *s, float *x, const float *I, int B, int N,
+                     const snn_lif_params *h_p, float i_decay, const snn_pervec *pv, uint8_t *raster_s, float *raster_v,
+                     snn_stream_t stream);
+int snn_izh_step_pv(float *v, float *u, uint8_t *s, float *x, float *I, const float *a, const float *b, const float *c,
+                    const float *d, const float *St, int B, int N, const snn_lif_params *h_p, const snn_pervec *pv,
+                    uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_dc_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *theta, const float *I, int B, int N,
+                   const snn_dc_params *h_p, const snn_pervec *pv, const float *noise_q, long long q_len, long long *cursor,
+                   int *status, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+
 /* ---- device-resident emulation of torch's CPU generator --------------------------------------
  * Replaces the pre-drawn noise_q stream: the library reproduces the draws torch.multinomial
  * (bindsnet/network/nodes.py:1100-1102) would consume -- mt19937 -> random64 -> u in [0,1) ->
@@ -455,14 +491,18 @@ typedef struct {
     /* run(inputs={<non-Input layer>: current}), network.py:386-392 (nullable; generic plan): f32 [T,B,n], slice t is added
      * to the layer's summed input current after the connections' contributions, before the layer steps */
     const float *ext_current;
-    /* LIF / DC layers with per-neuron thresholds (nodes.py:425-498: `thresh` given as a tensor): nullable f32 [n] that replaces
-     * p.lif.thresh, broadcast over the batch.  Generic plan (a graph that has one is not offered to the fused plans).  (ABI 8) */
+    /* LIF layers with per-neuron thresholds (nodes.py:425-498: `thresh` given as a tensor): nullable f32 [n] that replaces
+     * p.lif.thresh, broadcast over the batch; on any other kind it is read as pv.v[SNN_PV_THRESH] (see `pv` below).  Generic plan (a graph that has one is not offered to the fused plans).  (ABI 8) */
     const float *thresh_vec;
     /* CURRENT: aux = the synaptic current i [B,n], aux_decay = i_decay.  IZH: aux = the recovery variable u [B,n]; izh_a .. izh_d
      * f32 [n]; izh_St f32 [n,n], the lateral matrix transposed (snn_izh_step).  MCP has no refrac; BOOSTED / IF / CURRENT / IZH
      * use the p.lif fields their snn_*_step lists.  clamp / unclamp / inject_v / ext_current apply as for LIF. */
     float *aux; float aux_decay;
     const float *izh_a, *izh_b, *izh_c, *izh_d, *izh_St;
+    /* Per-neuron parameters (f10): pv.v[SNN_PV_*] nullable f32 [n] vectors that take the place of the scalars in p / aux_decay.
+     * A layer with any of them sends the graph to the generic plan, as thresh_vec does; a vector its kind does not read is
+     * SNN_ERR_INVALID.  Added at the end without changing SNN_ABI_VERSION, like the fields above. */
+    snn_pervec pv;
 } snn_layer_desc;
 
 typedef struct {
