@@ -119,7 +119,10 @@ class ConnDesc(C.Structure):
                 ("conv_pp_rows", C.c_int),
                 ("pipe_n", C.c_int), ("pipe_kind", C.c_int * 8), ("pipe_val", C.c_void_p * 8),
                 ("pipe_scalar", C.c_int * 8), ("pipe_bits", C.c_void_p * 8),
-                ("sparse_ptr", C.c_void_p), ("sparse_col", C.c_void_p), ("sparse_val", C.c_void_p), ("sparse_nnz", C.c_int)]
+                ("sparse_ptr", C.c_void_p), ("sparse_col", C.c_void_p), ("sparse_val", C.c_void_p), ("sparse_nnz", C.c_int),
+                ("firing_rates", C.c_void_p), ("pool_c", C.c_int), ("pool_in", C.c_int * 3), ("pool_k", C.c_int * 3),
+                ("pool_stride", C.c_int * 3), ("pool_pad", C.c_int * 3), ("pool_dil", C.c_int * 3), ("pool_decay", C.c_float),
+                ("w_numel", C.c_int)]
 
 
 class MccOp(C.Structure):
@@ -143,6 +146,10 @@ LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH = 3, 4, 5, 6, 7
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
+CONN_POOL, CONN_MEANFIELD = 6, 7
+POOL_STAGE = 8192         # SNN_POOL_STAGE: the largest (b, c) plane snn_prop_pool_f32 updates and pools in LDS, in one launch
+MEANFIELD_STORE = 2       # SNN_MEANFIELD_STORE: snn_prop_meanfield_f32 writes mean * w itself
+MEANFIELD_MAX = 1 << 24   # B * source.n up to which f32(count) / f32(numel) is the reference's mean
 SPARSE_TJ = 256           # SNN_SPARSE_TJ: the column-tile width of SparseConnection's compiled form
 MCC_MAX_PIPE = 8          # SNN_MCC_MAX_PIPE
 MCC_OP_MUL_DRAW, MCC_OP_MUL_MASK, MCC_OP_MUL_F32, MCC_OP_ADD_F32 = 1, 2, 3, 4
@@ -161,6 +168,8 @@ _SIGS = {
     "snn_mcc_bernoulli": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "snn_prop_dense_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_sparse_f32": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_prop_pool_f32": ([_vp, _vp, _vp, _i, _i] + [C.POINTER(_i)] * 5 + [_f, _i, _vp], _i),
+    "snn_prop_meanfield_f32": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_dense_mfma_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
     "snn_prop_local_f32": ([_vp] * 4 + [_i] * 7 + [_vp], _i),

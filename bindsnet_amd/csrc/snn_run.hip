@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/snnhip.h"
 #include "snn_common.hpp"
+#include "snn_pool.hpp"
 
 static thread_local const char *g_plan = "none";
 static int g_plan_mode = 0;
@@ -173,7 +174,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW && (!d.pipe_bits[k] || !R->rng)) return SNN_ERR_INVALID;
             }
             if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
-        } else if (!d.w && d.kind != SNN_CONN_SPARSE) return SNN_ERR_INVALID;
+        } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
         const bool conv_mstdp = d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_MSTDP;      // learning.py:1942-2015, batch 1
         // (the three outer-product rules share the per-sample partial sums in rule_ws: learning.py:457-497, :920-976, :1348-1380; MSTDPET's conv2d
@@ -188,7 +189,28 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
         if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_MSTDPET) return SNN_ERR_INVALID;
-        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_SPARSE) return SNN_ERR_INVALID;
+        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_MEANFIELD) return SNN_ERR_INVALID;
+        if (d.kind == SNN_CONN_POOL || d.kind == SNN_CONN_MEANFIELD) {     // MaxPoolNdConnection / MeanFieldConnection: propagation only (NoOp)
+            if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
+            if (d.has_norm || d.mask || d.raster_w || d.bias) return SNN_ERR_INVALID;
+            if (d.kind == SNN_CONN_POOL) {
+                if (d.w || !d.firing_rates || d.pool_c <= 0) return SNN_ERR_INVALID;
+                long n_in = d.pool_c, n_out = d.pool_c;
+                for (int a = 0; a < 3; ++a) {
+                    if (d.pool_in[a] <= 0 || d.pool_k[a] <= 0 || d.pool_stride[a] <= 0 || d.pool_pad[a] < 0 || d.pool_dil[a] <= 0) return SNN_ERR_INVALID;
+                    const int o = snn::pool_out_size(d.pool_in[a], d.pool_k[a], d.pool_stride[a], d.pool_pad[a], d.pool_dil[a]);
+                    if (o <= 0 || n_in > (1L << 31) || n_out > (1L << 31)) return SNN_ERR_INVALID;
+                    n_in *= d.pool_in[a];
+                    n_out *= o;
+                }
+                if (n_in != L[d.src].n || n_out != L[d.dst].n) return SNN_ERR_INVALID;
+            } else {
+                const long n_out = (long)R->B * L[d.dst].n;
+                if (d.w_numel <= 0 || n_out % d.w_numel != 0) return SNN_ERR_INVALID;
+                if ((long)R->B * L[d.src].n > (1L << 24)) return SNN_ERR_UNSUPPORTED;
+            }
+            continue;
+        }
         if (d.kind == SNN_CONN_SPARSE) {       // SparseConnection: propagation only (a rule densifies `w` in the reference; norm and mask raise there)
             if (d.rule != SNN_RULE_NONE || d.has_norm || d.mask || d.raster_w || d.w) return SNN_ERR_INVALID;
             if (!d.sparse_ptr || d.sparse_nnz < 0 || (d.sparse_nnz > 0 && (!d.sparse_col || !d.sparse_val))) return SNN_ERR_INVALID;
@@ -253,6 +275,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_SPARSE) TRY(snn_prop_sparse_f32(d.sparse_ptr, d.sparse_col, d.sparse_val, d.sparse_nnz, d.bias, sp,
                                                                             D.current, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_POOL) TRY(snn_prop_pool_f32(d.firing_rates, sp, D.current, B, d.pool_c, d.pool_in, d.pool_k, d.pool_stride,
+                                                                        d.pool_pad, d.pool_dil, d.pool_decay, acc, st));
+                else if (d.kind == SNN_CONN_MEANFIELD) TRY(snn_prop_meanfield_f32(d.w, d.w_numel, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_CONVND) TRY(snn_prop_convnd_f32(d.w, d.bias, sp, D.current, B, d.cin, d.conv_d, d.h, d.wd, d.cout,
                                                                              d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
                 else if (d.kind == SNN_CONN_LOCAL) TRY(snn_prop_local_f32(d.w, d.local_src, sp, D.current, B, d.cin, d.local_F,
@@ -426,7 +451,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
-    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind == SNN_CONN_SPARSE) local = true;   // (and SparseConnection) plan only; no fused plan is offered the graph
+    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection) plan only; no fused plan is offered the graph
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {

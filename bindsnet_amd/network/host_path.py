@@ -279,8 +279,26 @@ def _propagate_sparse(conn, s):
     return post.view(B, *conn.target.shape)
 
 
+def _propagate_pool(conn, s):
+    """MaxPool1d / 2d / 3dConnection.compute (topology.py:1075-1097 / :1171-1187 / :1261-1277): the rates decay and take the spikes,
+    torch's own max_pool picks the indices, the spikes are gathered there."""
+    B = s.shape[0]
+    fr = conn._rates(B, s.device)
+    fr -= conn.decay * fr
+    fr += s.float().view(fr.shape)          # (the reference's .squeeze() broadcasts to the same; what it cannot is refused before)
+    k, stride, pad, dil = conn._fields()
+    pool = getattr(torch.nn.functional, f"max_pool{conn._ndim}d")
+    _, idx = pool(fr, kernel_size=k, stride=stride, padding=pad, dilation=dil, return_indices=True)
+    return s.reshape(B, fr.shape[1], -1).gather(2, idx.flatten(2)).view_as(idx).float()
+
+
+def _propagate_meanfield(conn, s):
+    """MeanFieldConnection.compute (topology.py:1972-1981): the mean over the whole spike tensor, the batch included, times `w`."""
+    return s.float().mean() * conn.w
+
+
 def _update_nothing(conn, kwargs, mask) -> None:
-    """SparseConnection.update: NoOp only (learning.py:87-104 multiplies `w` by 1.0)."""
+    """SparseConnection, MaxPoolNdConnection, MeanFieldConnection.update: NoOp only (learning.py:87-104 multiplies `w` by 1.0)."""
 
 
 def _propagate_local(conn, s):

@@ -325,6 +325,10 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             break
 
         T, B = int(time / self.dt), self.batch_size
+        for conn in self.connections.values():             # ... and what it cannot run at this batch size
+            err = conn._batch_refusal(B) if hasattr(conn, "_batch_refusal") else None
+            if err is not None:
+                raise err
         dev = self._device()
         if dev.type != "cuda":
             # A network whose tensors live on the host: the plain-PyTorch step loop with the reference's semantics

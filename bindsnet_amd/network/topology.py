@@ -1,6 +1,6 @@
 """Connections: API mirror of bindsnet/network/topology.py for the connection types on the hot
 path (`Connection`, `SparseConnection`, `MulticompartmentConnection`, `Conv1dConnection`, `Conv2dConnection`, `Conv3dConnection`,
-`LocalConnection`, `LocalConnection1D/2D/3D`).  `compute()` launches the
+`LocalConnection`, `LocalConnection1D/2D/3D`, `MaxPool1dConnection`, `MaxPool2dConnection`, `MaxPoo3dConnection`, `MeanFieldConnection`).  `compute()` launches the
 matching propagation kernel of libsnnhip; inside Network.run the same kernels are driven from C++.
 
 `SparseConnection` keeps `w` as a sparse COO Parameter, like the reference, and propagates only: its kernel
@@ -344,6 +344,292 @@ class SparseConnection(AbstractConnection):
             d.bias = dptr(self.b.data)
             described.append((self, "b"))
         return described
+
+
+class _MaxPoolConnection(AbstractConnection):
+    """What MaxPool1dConnection, MaxPool2dConnection and MaxPoo3dConnection (reference: topology.py:1028-1301) share: no weights;
+    the state is `firing_rates` [B, *source.shape], an online estimate of every source neuron's rate.  Per `compute(s)` the rates
+    decay by `decay` and take the spikes, F.max_poolNd picks every window's highest rate, and the output is the source's spike at
+    that position.  On the device one kernel serves the three ranks (snn_prop_pool_f32: the missing dimensions have size 1); on
+    the host torch's own max_pool.  Both are the reference's arithmetic bit for bit.
+
+    As the reference, but before a run's first timestep (once its batch size is known): `decay=None` (the default) raises TypeError; a size-1 dimension of
+    [B, *source.shape] behind a larger one raises RuntimeError (the reference's `+= s.float().squeeze()` cannot broadcast), and
+    so does a target whose shape is not (C, *pooled) or rates kept from another batch size.  Two deliberate deviations: the
+    connection runs in training mode (the reference's NoOp multiplies a `w` that does not exist and raises AttributeError), and
+    one built before its layers joined a network -- `firing_rates` of shape [0], which raises in the reference until
+    reset_state_variables() -- gets zero rates of the right shape at first use.  Masks, monitors and Dales_rule raise."""
+
+    _kind, _ndim = _lib.CONN_POOL, 0
+    _rules = frozenset(("NoOp",))
+    _host_compute, _host_update = host_path._propagate_pool, host_path._update_nothing
+
+    def _init_pool(self, source, target, kwargs) -> None:
+        AbstractConnection.__init__(self, source, target, None, None, 0.0, **kwargs)
+        self.register_buffer("firing_rates", torch.zeros(source.s.shape))
+
+    def _fields(self):
+        """kernel_size, stride, padding, dilation as tuples of `_ndim` ints."""
+        nd = self._ndim
+        return tuple(tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v),) * nd
+                     for v in (self.kernel_size, self.stride, self.padding, self.dilation))
+
+    def _pooled(self):
+        """(C, *pooled sizes) of the source's shape; what F.max_poolNd itself refuses raises its RuntimeError here."""
+        shape = tuple(self.source.shape)
+        if len(shape) != self._ndim + 1:
+            raise RuntimeError(f"{type(self).__name__}: the source's shape must be (C, {self._ndim} spatial dimensions), got {shape}")
+        k, s, p, d = self._fields()
+        fn = getattr(torch.nn.functional, f"max_pool{self._ndim}d")
+        key = (shape, k, s, p, d)
+        kept = self.__dict__.get("_pooled_kept")         # (kept beside the attributes: it is no state a run descriptor depends on)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+        probe = fn(torch.empty(1, *shape, device="meta"), kernel_size=k, stride=s, padding=p, dilation=d)
+        pooled = tuple(probe.shape[1:])
+        # A dilated window that misses the plane altogether: torch returns an index outside it.  With torch's own padding <= kernel / 2
+        # a window that starts inside the plane has its first tap there, and one that starts in the padding misses only where the
+        # plane is narrower than the dilation, which leaves a single window on that axis: the last window decides.
+        for a in range(self._ndim):
+            start = (pooled[1 + a] - 1) * s[a] - p[a]
+            j = -(start // d[a]) if start < 0 else 0            # the first tap at or behind position 0
+            if j >= k[a] or start + j * d[a] >= shape[1 + a]:
+                raise RuntimeError(f"{type(self).__name__}: the last window of axis {a} has no tap inside the source (F.max_pool"
+                                   f"{self._ndim}d returns an index outside the plane there, and the reference's gather raises)")
+        self.__dict__["_pooled_kept"] = (key, pooled)
+        return pooled
+
+    def _batch_refusal(self, B: int):
+        """Why a run at batch size B must not start on this connection, or None: asked by Network.run once the batch size is known."""
+        if self.decay is None:
+            return TypeError(f"{type(self).__name__} needs `decay=` (the reference multiplies firing_rates by its default, None: "
+                             "unsupported operand type(s) for *: 'NoneType' and 'Tensor')")
+        full = [int(B), *self.source.shape]
+        while full and full[0] == 1:
+            full.pop(0)
+        if 1 in full:
+            return RuntimeError(f"{type(self).__name__}: [batch, *source.shape] = {[int(B), *self.source.shape]} has a size-1 dimension "
+                                "behind a larger one; the reference's `firing_rates += s.float().squeeze()` cannot broadcast it")
+        try:
+            pooled = self._pooled()
+        except RuntimeError as e:
+            return e
+        if tuple(self.target.shape) != pooled:
+            return RuntimeError(f"{type(self).__name__}: the target's shape must be {pooled} (channels, then the pooled sizes), got "
+                                f"{tuple(self.target.shape)}")
+        fr = self.firing_rates
+        if fr.numel() != 0 and tuple(fr.shape) != (int(B), *self.source.shape):
+            return RuntimeError(f"{type(self).__name__}: firing_rates has shape {tuple(fr.shape)}, the run needs "
+                                f"{(int(B), *self.source.shape)}; call reset_state_variables() after changing the batch size "
+                                "(the reference fails the same way)")
+        return None
+
+    def _run_refusal(self, mask, monitored: bool):
+        if mask is not None:
+            return NotImplementedError(f"bindsnet_amd: a mask on a {type(self).__name__} is not supported (it has no weights)")
+        if monitored:
+            return NotImplementedError(f"bindsnet_amd: a monitor on a {type(self).__name__} (firing_rates) is not supported; read "
+                                       "connection.firing_rates after the run")
+        return None
+
+    def _rates(self, B: int, dev):
+        """`firing_rates` for batch size B on `dev`: zero rates of the right shape where the connection was built before its
+        layers joined a network."""
+        err = self._batch_refusal(B)
+        if err is not None:
+            raise err
+        if self.firing_rates.numel() == 0:
+            self.firing_rates = torch.zeros(int(B), *self.source.shape, device=dev)
+        if self.firing_rates.device != torch.device(dev) or self.firing_rates.dtype != torch.float32:
+            raise ValueError("firing_rates must be a float32 tensor on the network's device; call network.to('cuda')")
+        if not self.firing_rates.is_contiguous():
+            self.firing_rates = self.firing_rates.contiguous()
+        return self.firing_rates
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        if not s.is_cuda:
+            return self._host_compute(s)
+        fr = self._rates(s.size(0), s.device)
+        out = torch.empty(s.size(0), *self._pooled(), device=s.device)
+        self._prop_into(s, out, rates=fr)
+        return out
+
+    def _prop_into(self, s, out, accumulate=False, rates=None) -> None:
+        fr = self._rates(s.size(0), s.device) if rates is None else rates
+        k, st, p, d = self._fields()
+        ops.prop_pool(fr, s.reshape(fr.shape).contiguous(), out.view(fr.shape[0], *self._pooled()), k, st, p, d, decay=float(self.decay),
+                      accumulate=accumulate)
+
+    def _describe(self, d, B, dev, scratch):
+        fr = self._rates(B, dev)
+        arrays, _ = ops.pool_geometry(self.source.shape[1:], *self._fields())
+        d.kind, d.w, d.firing_rates, d.pool_c, d.pool_decay = self._kind, None, dptr(fr), int(self.source.shape[0]), float(self.decay)
+        for name, arr in zip(("pool_in", "pool_k", "pool_stride", "pool_pad", "pool_dil"), arrays):
+            for a in range(3):
+                getattr(d, name)[a] = arr[a]
+        return [(self, "firing_rates")]
+
+    def update(self, **kwargs) -> None:
+        """Nothing learns; a mask has nothing to fill."""
+        if kwargs.get("mask", None) is not None:
+            raise self._run_refusal(kwargs["mask"], False)
+
+    def normalize(self) -> None:
+        """No weights -> no normalization."""
+
+    _host_normalize = normalize
+
+    def reset_state_variables(self) -> None:
+        """Zero rates for the source's batch size (reference: topology.py:1112-1121)."""
+        B = self.source.batch_size
+        if B is None:
+            return
+        if tuple(self.firing_rates.shape) == (B, *self.source.shape):
+            self.firing_rates.zero_()
+        else:
+            self.firing_rates = torch.zeros(B, *self.source.shape, device=self.source.s.device)
+
+
+class MaxPool1dConnection(_MaxPoolConnection):
+    """Max-pooling over a (C, N) source into a (C, L) target (reference: topology.py:1028-1121)."""
+    _ndim = 1
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: int, stride: int = 1, padding: int = 0, dilation: int = 1,
+                 **kwargs) -> None:
+        self._init_pool(source, target, kwargs)
+        self.kernel_size, self.stride, self.padding, self.dilation = kernel_size, stride, padding, dilation
+
+
+class MaxPool2dConnection(_MaxPoolConnection):
+    """Max-pooling over a (C, H, W) source into a (C, OH, OW) target (reference: topology.py:1124-1211)."""
+    _ndim = 2
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]],
+                 stride: Union[int, Tuple[int, int]] = 1, padding: Union[int, Tuple[int, int]] = 0,
+                 dilation: Union[int, Tuple[int, int]] = 1, **kwargs) -> None:
+        self._init_pool(source, target, kwargs)
+        self.kernel_size, self.stride = _pair(kernel_size), _pair(stride)
+        self.padding, self.dilation = _pair(padding), _pair(dilation)
+
+
+class MaxPoo3dConnection(_MaxPoolConnection):
+    """Max-pooling over a (C, D, H, W) source into a (C, OD, OH, OW) target (reference: topology.py:1214-1301, where the class
+    name lacks its "l"; `MaxPool3dConnection` is the same class)."""
+    _ndim = 3
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int, int]],
+                 stride: Union[int, Tuple[int, int, int]] = 1, padding: Union[int, Tuple[int, int, int]] = 0,
+                 dilation: Union[int, Tuple[int, int, int]] = 1, **kwargs) -> None:
+        self._init_pool(source, target, kwargs)
+        self.kernel_size, self.stride = _triple(kernel_size), _triple(stride)
+        self.padding, self.dilation = _triple(padding), _triple(dilation)
+
+
+MaxPool3dConnection = MaxPoo3dConnection
+
+
+class MeanFieldConnection(AbstractConnection):
+    """Mean-field synapses (reference: topology.py:1920-2006): `compute(s) = s.float().mean() * w`, the mean over the whole
+    [B, *source.shape] tensor, the batch included.  `w` is 0-dim (the default: one randn draw) or a tensor that broadcasts onto
+    [B, *target.shape]; a recurrent connection with a negative scalar `w` is global inhibition.  On the device the spikes are
+    counted as integers and the mean is f32(count) / f32(numel), which is the reference's mean up to 2^24 elements
+    (snn_prop_meanfield_f32); on the host the reference's expression.  Propagation only, in training and eval mode.
+
+    As the reference: the constructor hands `weight_decay` on in the `reduction` slot, so it never reaches the rule; a given `w`
+    is clamped only when a bound is infinite; a rule other than NoOp raises NotImplementedError at construction.  `norm=` raises
+    NotImplementedError before a run changes any state (the reference's normalize() raises TypeError behind the run: it assigns
+    a plain tensor to the Parameter `w`).  Masks, monitors, Dales_rule, a `w` that is not float32 and batch x source.n beyond
+    2^24 raise."""
+
+    _kind = _lib.CONN_MEANFIELD
+    _rules = frozenset(("NoOp",))
+    _host_compute, _host_update = host_path._propagate_meanfield, host_path._update_nothing
+
+    def __init__(self, source: Nodes, target: Nodes, nu=None, weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32,
+                 **kwargs) -> None:
+        super().__init__(source, target, nu, weight_decay, **kwargs)          # (sic: topology.py:1957)
+        if w_dtype != torch.float32:
+            raise NotImplementedError("bindsnet_amd computes in float32 only")
+        w = kwargs.get("w", None)
+        unbounded = bool((self.wmin == -np.inf).any() or (self.wmax == np.inf).any())
+        if w is None:
+            r = (torch.randn(1)[0] + 1) / 10
+            w = torch.clamp(r, self.wmin, self.wmax) if unbounded else self.wmin + r * (self.wmax - self.wmin)
+            w = w.to(dtype=w_dtype)
+        else:
+            if unbounded:
+                w = torch.clamp(w, self.wmin, self.wmax)
+            w = self.cast_dtype_if_needed(w, w_dtype)
+        self.w = Parameter(w, requires_grad=False)
+
+    def _w_refusal(self, B: int):
+        w = self.w
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+            return NotImplementedError(f"bindsnet_amd: MeanFieldConnection.w must be float32 (got {getattr(w, 'dtype', type(w))}); "
+                                       "bindsnet_amd computes in float32 only")
+        full = (int(B), *self.target.shape)
+        shape = tuple(w.shape)
+        while shape and shape[0] == 1:
+            shape = shape[1:]
+        if len(shape) > len(full) or shape != full[len(full) - len(shape):]:
+            return NotImplementedError(f"bindsnet_amd: MeanFieldConnection.w must have one element or the shape of a tail of "
+                                       f"[batch, *target.shape] = {list(full)}; got {list(w.shape)}")
+        return None
+
+    def _batch_refusal(self, B: int):
+        if int(B) * self.source.n > _lib.MEANFIELD_MAX:
+            return NotImplementedError(f"bindsnet_amd: MeanFieldConnection over batch x source.n = {int(B) * self.source.n} elements is "
+                                       "not supported (f32(count) / f32(numel) is the reference's mean up to 2^24 elements)")
+        return self._w_refusal(B)
+
+    def _run_refusal(self, mask, monitored: bool):
+        if self.norm is not None:
+            return NotImplementedError("MeanFieldConnection with `norm`: the reference's normalize() raises TypeError at the end of the "
+                                       "run (it assigns a plain tensor to the Parameter `w`); leave `norm` unset")
+        if mask is not None:
+            return NotImplementedError("bindsnet_amd: a mask on a MeanFieldConnection is not supported")
+        if monitored:
+            return NotImplementedError("bindsnet_amd: a monitor on a MeanFieldConnection is not supported (nothing changes `w`)")
+        return None
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        """A tensor of w's shape, as in the reference (Network.run broadcasts it onto the target)."""
+        if not self.w.is_cuda:
+            return self._host_compute(s)
+        err = self._batch_refusal(s.size(0))
+        if err is not None:
+            raise err
+        out = torch.empty_like(self.w.data)
+        ops.prop_meanfield(self.w.data.contiguous(), s.reshape(1, -1).contiguous(), out.view(1, -1), store=True)
+        return out
+
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        err = self._batch_refusal(s.size(0))
+        if err is not None:
+            raise err
+        ops.prop_meanfield(self.w.data.contiguous(), s.reshape(s.size(0), -1).contiguous(), out.view(s.size(0), -1), accumulate=accumulate)
+
+    def _describe(self, d, B, dev, scratch):
+        if self.w.device != dev:
+            raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
+        err = self._run_refusal(None, False) or self._batch_refusal(B)
+        if err is not None:
+            raise err
+        if not self.w.is_contiguous():
+            raise NotImplementedError("bindsnet_amd: connection weights must be contiguous float32")
+        d.kind, d.w, d.w_numel = self._kind, dptr(self.w.data), self.w.numel()
+        return [(self, "w")]
+
+    def update(self, **kwargs) -> None:
+        """Reference: topology.py:1983-1988 with NoOp, which leaves `w` as it is."""
+        if kwargs.get("mask", None) is not None:
+            raise self._run_refusal(kwargs["mask"], False)
+
+    def normalize(self) -> None:
+        if self.norm is not None:
+            raise self._run_refusal(None, False)
+
+    _host_normalize = normalize
 
 
 class LocalConnection(_DenseConnection):

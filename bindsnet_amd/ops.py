@@ -248,6 +248,48 @@ def _pv(vectors, N):
     return C.byref(pv), pv
 
 
+def pool_geometry(spatial, kernel_size, stride, padding, dilation):
+    """f11: the five int[3] arrays of snn_prop_pool_f32 for a pooling of rank len(spatial) <= 3 (the missing leading dimensions:
+    size 1, kernel 1, stride 1, padding 0, dilation 1) and the pooled sizes, out = (in + 2p - d(k - 1) - 1) // s + 1."""
+    nd = len(spatial)
+    tup = lambda v: tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v),) * nd       # noqa: E731
+    fields = [tuple(int(x) for x in spatial), tup(kernel_size), tup(stride), tup(padding), tup(dilation)]
+    if nd < 1 or nd > 3 or any(len(f) != nd for f in fields):
+        raise ValueError(f"pool_geometry: {nd} spatial dimensions need {nd} entries (or one int) per field")
+    unit = (1, 1, 1, 0, 1)
+    arrays = [(C.c_int * 3)(*((u,) * (3 - nd) + f)) for u, f in zip(unit, fields)]
+    out = tuple((i + 2 * p - d * (k - 1) - 1) // s + 1 for i, k, s, p, d in zip(*fields))
+    return arrays, out
+
+
+def prop_pool(fr, s, out, kernel_size, stride=1, padding=0, dilation=1, decay=0.0, accumulate=False):
+    """f11: one MaxPoolNdConnection.compute: fr [B, C, *spatial] <- fr - decay * fr + s; out [B, C, *pooled] (+)= s gathered at
+    the indices of F.max_poolNd(fr, ..., return_indices=True)."""
+    if fr.dim() < 3 or fr.dim() > 5 or tuple(s.shape) != tuple(fr.shape):
+        raise ValueError("prop_pool: firing rates and spikes must both be [B, C, *spatial] with 1 to 3 spatial dimensions")
+    arrays, pooled = pool_geometry(fr.shape[2:], kernel_size, stride, padding, dilation)
+    if min(pooled) <= 0 or tuple(out.shape) != tuple(fr.shape[:2]) + pooled:
+        raise ValueError(f"prop_pool: out must be {tuple(fr.shape[:2]) + pooled}, got {tuple(out.shape)}")
+    check(lib().snn_prop_pool_f32(_ptr(fr, F32), _ptr(s, "spike"), _ptr(out, F32), fr.shape[0], fr.shape[1], *arrays, float(decay),
+                                  int(accumulate), _stream()), "prop_pool")
+    return out
+
+
+def prop_meanfield(w, s, out, accumulate=False, store=False):
+    """f11: MeanFieldConnection.compute: out [B, n_tgt] (+)= s.float().mean() * w, the mean over the whole of s [B, n_src]; `w` has
+    one element or a shape that is a tail of out's.  store: out = mean * w itself (a zero keeps its sign) instead of 0 + mean * w."""
+    B = s.shape[0]
+    if s.numel() > _lib.MEANFIELD_MAX:
+        raise NotImplementedError(f"bindsnet_amd: MeanFieldConnection over {s.numel()} source elements (batch x source.n) is not "
+                                  f"supported: f32(count) / f32(numel) is the reference's mean up to 2^24 elements")
+    if out.shape[0] != B or w.numel() < 1 or out.numel() % w.numel() != 0:
+        raise ValueError("prop_meanfield: out must be [B, ...] and w's element count must divide out's")
+    mode = _lib.MEANFIELD_STORE if store else int(accumulate)
+    check(lib().snn_prop_meanfield_f32(_ptr(w, F32), w.numel(), _ptr(s, "spike"), _ptr(out, F32), B, s.numel() // B, out.numel() // B,
+                                       mode, _stream()), "prop_meanfield")
+    return out
+
+
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None, pv=None):
     """pv (here and in every step below): optional {quantity name (_lib.PERVEC): f32 [N] device tensor} of per-neuron
     parameters that take the place of the scalars (include/snnhip.h f10)."""

@@ -105,6 +105,35 @@ int snn_prop_dense_f32(const float *W, const float *bias, const uint8_t *s, floa
 int snn_prop_sparse_f32(const int *ptr, const uint8_t *col, const float *val, int nnz, const float *bias, const uint8_t *s,
                         float *out, int B, int Nin, int N, int accumulate, snn_stream_t stream);
 
+/* ---- f11: MaxPool1d / 2d / 3dConnection.compute -------------------------------------------------
+ * bindsnet/network/topology.py:1028-1301.  fr f32 [B, C, in[0], in[1], in[2]] is the connection's `firing_rates` (updated in
+ * place), s the source's spike bytes of the same shape, out f32 [B, C, out[0], out[1], out[2]] with
+ * out[a] = (in[a] + 2 pad[a] - dil[a] (k[a] - 1) - 1) / stride[a] + 1.  Per call:
+ *   fr = fr - decay * fr (one rounded multiply, one rounded subtract); fr = fr + float(s);
+ *   idx = the index F.max_poolNd(fr, ..., return_indices=True) returns: the window's in-bounds taps in row-major order, the
+ *         first in-bounds tap to begin with, replaced iff val > max || isnan(val) (first maximum, last NaN);
+ *   out (+)= float(s[idx]).
+ * in / k / stride / pad / dil are HOST arrays of three ints; a 1-D or 2-D pooling pads the leading dimensions with size 1,
+ * kernel 1, stride 1, padding 0, dilation 1.  A plane (in[0] * in[1] * in[2]) of at most SNN_POOL_STAGE elements is updated
+ * and pooled in LDS by ONE launch; a larger one takes two launches (rates, then pooling from global memory); both give the
+ * same bits.  2 * pad[a] > dil[a] (k[a] - 1) + 1 (torch refuses it) or an empty output is SNN_ERR_INVALID; planes, plane sizes
+ * or B * C beyond 2^30, or more than 2^40 elements, SNN_ERR_UNSUPPORTED.  (ABI 8, additive)                              */
+#define SNN_POOL_STAGE 8192
+int snn_prop_pool_f32(float *fr, const uint8_t *s, float *out, int B, int C, const int *in, const int *k, const int *stride,
+                      const int *pad, const int *dil, float decay, int accumulate, snn_stream_t stream);
+
+/* ---- f11: MeanFieldConnection.compute -------------------------------------------------------------
+ * bindsnet/network/topology.py:1972-1981: `s.float().mean() * w`, the mean over the WHOLE [B, n_src] tensor.  The spikes are
+ * counted as integers; mean = f32(count) / f32(B * n_src), one correctly rounded divide (exact operands: B * n_src <= 2^24,
+ * else SNN_ERR_UNSUPPORTED; pinned for spike bytes 0/1); out[o] (+)= mean * w[o % w_numel] for o < B * n_tgt: one rounded
+ * multiply, one rounded add.  w_numel is 1 (a 0-dim `w`) or the element count of a `w` whose shape is a tail of
+ * [B, n_tgt...]; it must divide B * n_tgt.  accumulate: 0 -- out = 0 + mean * w, the first term of a zeroed sum as in
+ * snn_prop_cascade_f32; 1 -- out = out + mean * w; SNN_MEANFIELD_STORE -- out = mean * w itself (compute()'s own value: a
+ * zero keeps its sign).  One launch, no host synchronisation.  (ABI 8, additive)                                          */
+#define SNN_MEANFIELD_STORE 2
+int snn_prop_meanfield_f32(const float *w, int w_numel, const uint8_t *s, float *out, int B, int n_src, int n_tgt,
+                           int accumulate, snn_stream_t stream);
+
 /* The same product on the f32 matrix cores (v_mfma_f32_16x16x4_f32): ONE k-ordered accumulator chain per output
  * tile, bit-identical to snn_prop_dense_f32 when every spike byte is 0 or 1 (products are then exact and gfx950's
  * f32 MFMA is a k-ordered fmaf chain).  Cost is Nin / 4 dependent MFMAs per tile regardless of sparsity; kept as an
@@ -453,7 +482,7 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
  * bindsnet/network/network.py:380-465 (the per-timestep loop and the post-loop normalisation),
  * for graphs built from {Input, LIFNodes, DiehlAndCookNodes / AdaptiveLIFNodes, McCullochPitts, IFNodes, BoostedLIFNodes,
  * CurrentLIFNodes, IzhikevichNodes} x {MulticompartmentConnection+Weight, Connection, SparseConnection, Conv1d / Conv2d /
- * Conv3dConnection, LocalConnection1D / 2D / 3D} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
+ * Conv3dConnection, LocalConnection1D / 2D / 3D, MaxPool1d / 2d / 3dConnection, MeanFieldConnection} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
  * with any other layer kind runs the generic plan.  The descriptors are HOST
  * structs holding DEVICE pointers; layers and connections are listed in network insertion
  * order, which fixes the evaluation order exactly as the reference's dict iteration does.   */
@@ -468,7 +497,11 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP =
 /* SNN_CONN_CONVND (Conv1dConnection / Conv3dConnection, rules NONE or POSTPRE, generic plan only) and the conv_* fields
  * after them were added the same way, again without changing SNN_ABI_VERSION.  So were SNN_CONN_SPARSE (SparseConnection:
  * propagation only -- any rule, norm, mask or weight monitor is SNN_ERR_INVALID --, generic plan only) and the sparse_* fields.  */
-enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5 };
+/* SNN_CONN_POOL (MaxPool1d / 2d / 3dConnection: no `w`; firing_rates and the pool_* fields) and SNN_CONN_MEANFIELD
+ * (MeanFieldConnection: `w` of w_numel elements) came the same way: propagation only -- a rule is SNN_ERR_UNSUPPORTED, a norm,
+ * mask, bias or weight monitor SNN_ERR_INVALID --, generic plan only, SNN_ABI_VERSION unchanged.  */
+enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5,
+       SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5 };
 
@@ -558,6 +591,13 @@ typedef struct {
     const uint8_t *sparse_col;
     const float *sparse_val;
     int sparse_nnz;
+    /* POOL: the arguments of snn_prop_pool_f32 -- firing_rates f32 [B, pool_c, pool_in...] (the connection's state, updated every
+     * timestep), three ints per geometry field (leading dimensions padded as there), pool_decay; `w` is NULL.  MEANFIELD: `w`
+     * holds w_numel elements (snn_prop_meanfield_f32).  Added like the fields above: SNN_ABI_VERSION stays. */
+    float *firing_rates;
+    int pool_c, pool_in[3], pool_k[3], pool_stride[3], pool_pad[3], pool_dil[3];
+    float pool_decay;
+    int w_numel;
 } snn_conn_desc;
 
 typedef struct {
