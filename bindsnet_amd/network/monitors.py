@@ -102,10 +102,14 @@ class NetworkMonitor(AbstractMonitor):
         """`layer`: a layer name or a connection's (source, target) key."""
         data = chunk.float()
         old = self.recording[layer][var]
+        # a recording never shares memory with the state it was taken from: torch.cat copies; where the chunk alone becomes the
+        # recording it is cloned if `.float()` handed it back as it was
+        def alone():
+            return data.clone() if data.data_ptr() == chunk.data_ptr() else data
         if self.time is None:
-            self.recording[layer][var] = data if old.numel() == 0 else torch.cat((old.to(data.device), data), 0)
+            self.recording[layer][var] = alone() if old.numel() == 0 else torch.cat((old.to(data.device), data), 0)
         else:
-            keep = torch.cat((old.to(data.device), data), 0) if old.shape[1:] == data.shape[1:] else data
+            keep = torch.cat((old.to(data.device), data), 0) if old.shape[1:] == data.shape[1:] else alone()
             self.recording[layer][var] = keep[-self.time:]
 
     def record(self) -> None:

@@ -19,6 +19,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 CASES = {
     "ref_hebbian": dict(rule="Hebbian", cin=1, hw=(10, 10), k=3, s=1, p=0, cout=32, B=1, T=40, n_in=3, density=0.3, nu=(1e-3, 1e-2),
                         wmin=None, wmax=None, wd=0.0, wscale=0.6, train=True, seed=0),
@@ -33,6 +35,9 @@ CASES = {
     "hebb_eval": dict(rule="Hebbian", cin=1, hw=(10, 10), k=3, s=1, p=0, cout=32, B=1, T=40, n_in=2, density=0.3, nu=(1e-3, 1e-2),
                       wmin=None, wmax=None, wd=0.0, wscale=0.6, train=False, seed=0),
 }
+# b3_wdpp at dt = 0.5 (default 1.0; `time = T * dt` is run): the refractory countdown and the decays of v and both traces, which the
+# rule reads.  `sibling`: the dt = 1 case it repeats.
+CASES["b3_wdpp_dt05"] = dict(CASES["b3_wdpp"], dt=0.5, T=56, sibling="b3_wdpp")     # (56 steps: three spikes ten steps of refractory period apart)
 
 
 def ns_from(nodes, topology, learning, network_cls):
@@ -53,7 +58,7 @@ def w0_of(name):
 
 def build(ns, name):
     c = CASES[name]
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     X = ns.Input(shape=[c["cin"], *c["hw"]], traces=True, tc_trace=20.0)
     Y = ns.LIFNodes(shape=[c["cout"], *out_hw(c)], traces=True, tc_trace=20.0)
     kw = dict(kernel_size=c["k"], stride=c["s"], padding=c["p"], nu=c["nu"], update_rule=getattr(ns, c["rule"]), w=w0_of(name),
@@ -102,7 +107,7 @@ def run_case(net, name, monitor_cls, device=None):
         x = torch.from_numpy(inputs(name, r))
         if device is not None:
             x = x.to(device)
-        net.run({"X": x}, time=c["T"])
+        net.run({"X": x}, time=run_time(c["T"], c.get("dt", 1.0)))
         raster = mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)
         out.append(snapshot(net, raster))
         del net.monitors["Y_s"]

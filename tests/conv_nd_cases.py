@@ -18,6 +18,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 CASES = {
     "a": dict(kind="c1", cin=1, shape=(784,), k=56, s=28, p=0, F=25, B=1, T=50, n_in=3, density=0.05, nu=(1e-4, 1e-2),
               wmin=None, norm=0.4 * 56, inh=100.0, train=True, seed=10),
@@ -34,6 +36,10 @@ CASES = {
     "g": dict(kind="c3", cin=1, shape=(28, 28, 28), k=16, s=4, p=0, F=12, B=1, T=50, n_in=2, density=0.03, nu=(1e-4, 1e-2),
               wmin=None, norm=0.4 * 16 ** 3, inh=100.0, train=False, seed=13),
 }
+# (e) at dt = 0.5 (default 1.0; `time = T * dt` is run): the refractory countdown and the decays of v / theta / both traces behind the
+# conv propagation and its PostPre.  DiehlAndCookNodes lets one neuron per sample fire in a step, so it takes 120 steps until ten of the
+# 81 neurons have fired three times (B = 1: with two samples the file outgrows its sibling).  `sibling`: the dt = 1 case it repeats.
+CASES["e_dt05"] = dict(CASES["e"], dt=0.5, T=120, B=1, sibling="e")
 BIG = ("a", "c", "d", "f", "g")          # w recorded as a sha256 per input, the final array once (not for g: learning off)
 
 
@@ -52,7 +58,7 @@ def build(ns, name):
     """The case's network (weights drawn from the global generator after torch.manual_seed(seed))."""
     c = CASES[name]
     torch.manual_seed(c["seed"])
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     X = ns.Input(shape=[c["cin"], *c["shape"]], traces=True)
     tshape = target_shape(c)
     Y = ns.DiehlAndCookNodes(shape=tshape, traces=True)
@@ -126,7 +132,7 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None):
         x = torch.from_numpy(inputs(name, r))
         if device is not None:
             x = x.to(device)
-        net.run({"X": x}, time=c["T"])
+        net.run({"X": x}, time=run_time(c["T"], c.get("dt", 1.0)))
         raster = mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)
         out.append(snapshot(net, raster))
         del net.monitors["Y_s"]

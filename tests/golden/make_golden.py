@@ -270,16 +270,16 @@ def dc_case(name, N, B, T, runs, full_w, inh=120.0, max_rate=0.0625, dt=1.0):
     save(name, N=N, B=B, T=T, runs=runs, inh=np.float32(inh), max_rate=np.float64(max_rate), **extra, **consts, **out)
 
 
-def two_layer_case(name, rule, Nin, N, B, T):
-    """Input -> Connection -> LIFNodes with learning.PostPre / MSTDP (dense family)."""
+def two_layer_case(name, rule, Nin, N, B, T, dt=1.0, max_rate=0.12, sibling=None):
+    """Input -> Connection -> LIFNodes with learning.PostPre / MSTDP (dense family).  T TIMESTEPS of length dt."""
     torch.manual_seed(0)
     W0 = synth.weights_q12(11, Nin, N)
     if rule == "postpre":
-        net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, reduction=torch.sum, norm=78.4 * Nin / 784)
+        net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, dt=dt, reduction=torch.sum, norm=78.4 * Nin / 784)
         conn = net.connections[("X", "Y")]
         conn.w.data.copy_(T_(W0))
     else:
-        net = Network(dt=1.0)
+        net = Network(dt=dt)
         net.add_layer(Input(n=Nin, traces=True), "X")
         net.add_layer(LIFNodes(n=N, traces=True), "Y")
         conn = Connection(net.layers["X"], net.layers["Y"], w=T_(W0).clone(), wmin=0, wmax=1, update_rule=MSTDP,
@@ -296,9 +296,10 @@ def two_layer_case(name, rule, Nin, N, B, T):
         return o
 
     conn.compute = capture
-    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.12)
+    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=max_rate)
     kw = {"reward": 1.0} if rule == "mstdp" else {}
-    net.run({"X": T_(spikes)}, time=T, **kw)
+    assert int(T * dt / dt) == T
+    net.run({"X": T_(spikes)}, time=T * dt, **kw)
     Y, X = net.layers["Y"], net.layers["X"]
     out = dict(sY=np.packbits(mon.get("s").numpy().astype(np.uint8)), W=conn.w.detach().numpy().copy(),
                I_forced=np.array(forced).astype(np.float32), vY=Y.v.numpy().copy(), xY=Y.x.numpy().copy(),
@@ -308,10 +309,22 @@ def two_layer_case(name, rule, Nin, N, B, T):
         ur = conn.update_rule
         out.update(p_plus=ur.p_plus.numpy().copy(), p_minus=ur.p_minus.numpy().copy(),
                    elig_sha=sha(ur.eligibility.numpy()),
-                   decay_plus=torch.exp(-torch.tensor(1.0) / ur.tc_plus).numpy(),
-                   decay_minus=torch.exp(-torch.tensor(1.0) / ur.tc_minus).numpy())
+                   decay_plus=torch.exp(-torch.tensor(dt) / ur.tc_plus).numpy(),
+                   decay_minus=torch.exp(-torch.tensor(dt) / ur.tc_minus).numpy())
     print(f"  {name}: Y spikes {int(mon.get('s').sum())}")
-    save(name, Nin=Nin, N=N, B=B, T=T, **out)
+    save_dt(name, dt, [mon.get("s").numpy().reshape(T, B, N)], max_rate, sibling, Nin=Nin, N=N, B=B, T=T, **out)
+
+
+def save_dt(name, dt, rasters, max_rate, sibling, **kw):
+    """save() for a case that may run at dt != 1.  Such a case adds the keys "dt" and "max_rate" of its input (the dt = 1 fixtures keep
+    their original key set and synth.spike_train's max_rate = 0.12) and is kept only if the reference's own record meets the conditions of
+    dt_cases.save_fixture.  rasters: one [T, B, N] array per run; sibling: the dt = 1 fixture it repeats, or None."""
+    if dt == 1.0:
+        return save(name, **kw)
+    from dt_cases import save_fixture
+    out = dict(kw, dt=np.float32(dt), max_rate=np.float64(max_rate))
+    save_fixture(os.path.join(HERE, name + ".npz"), out, name, rasters, None if sibling is None else os.path.join(HERE, sibling + ".npz"),
+                 refractory=True)
 
 
 if __name__ == "__main__":

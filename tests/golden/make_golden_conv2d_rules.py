@@ -29,6 +29,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology  # noq
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import conv2d_rule_cases as CC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def main():
@@ -50,7 +51,10 @@ def main():
             for k in ("v", "refrac", "xX", "xY", "w"):
                 out[f"r{r}_{k}"] = s[k]
         path = CC.gold_path(name)
-        np.savez_compressed(path, **out)
+        if "dt" in c:
+            save_fixture(path, out, name, [s["raster"] for s in snaps], CC.gold_path(c["sibling"]), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", spikes, "bytes:", os.path.getsize(path))
 
 

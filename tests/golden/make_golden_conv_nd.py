@@ -29,6 +29,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology  # noq
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import conv_nd_cases as CC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def main(names=None):
@@ -54,7 +55,10 @@ def main(names=None):
         if name in CC.BIG and CC.CASES[name]["train"]:
             out["final_w"] = snaps[-1]["w"]
         path = os.path.join(HERE, f"convnd_{name}.npz")
-        np.savez_compressed(path, **out)
+        if "dt" in CC.CASES[name]:
+            save_fixture(path, out, name, [s["raster"] for s in snaps], os.path.join(HERE, f"convnd_{CC.CASES[name]['sibling']}.npz"), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(s["raster"].sum()) for s in snaps], "bytes:", os.path.getsize(path))
 
 

@@ -28,6 +28,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology  # noq
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import local_cases as LC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 BIG = ("a", "e")
 
@@ -51,7 +52,10 @@ def main():
         if name in BIG:
             out["final_w"] = snaps[-1]["w"]
         path = os.path.join(HERE, f"local_{name}.npz")
-        np.savez_compressed(path, **out)
+        if "dt" in LC.CASES[name]:
+            save_fixture(path, out, name, [s["raster"] for s in snaps], os.path.join(HERE, f"local_{LC.CASES[name]['sibling']}.npz"), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(s["raster"].sum()) for s in snaps], "bytes:", os.path.getsize(path))
 
 

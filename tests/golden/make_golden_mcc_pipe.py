@@ -31,6 +31,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology, topol
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import mcc_pipe_cases as PC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def draws_between(state0, state1, limit):
@@ -84,7 +85,11 @@ def main():
         if total < PC.MIN_SPIKES:
             problems.append((name, "spikes", total))
         path = os.path.join(HERE, f"mccpipe_{name}.npz")
-        np.savez_compressed(path, **out)
+        if "dt" in c:
+            rasters = [v for s in snaps for k, v in s.items() if k.startswith("raster_")]
+            save_fixture(path, out, name, rasters, os.path.join(HERE, f"mccpipe_{c['sibling']}.npz"), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes:", {k: int(v) for k, v in out.items() if k.endswith("_sum")}, "draws:", [int(out[f"r{r}_draws"]) for r in range(len(snaps))],
               "bytes:", os.path.getsize(path))
     out = {}

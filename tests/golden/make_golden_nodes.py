@@ -29,6 +29,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology, topol
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import node_cases as NC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 VREC_WHOLE = 2500          # per-step v records of at most this many floats are stored whole
 
@@ -67,7 +68,11 @@ def main():
         if not 0.005 < total / cells < 0.7:                          # neither empty nor saturated
             problems.append((name, "spike rate", total / cells))
         path = os.path.join(HERE, f"nodes_{name}.npz")
-        np.savez_compressed(path, **out)
+        if "dt" in c:           # (McCullochPitts and IzhikevichNodes have no refractory period)
+            save_fixture(path, out, name, [s["raster"] for s in snaps], os.path.join(HERE, f"nodes_{c['sibling']}.npz"),
+                         refractory=c["kind"] in ("if", "boosted", "clif"), also=[s["vrec"] for s in snaps])
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(s["raster"].sum()) for s in snaps], "rate %.3f" % (total / cells),
               "per-step spike counts min/max:", int(counts.min()), int(counts.max()), "bytes:", os.path.getsize(path))
 

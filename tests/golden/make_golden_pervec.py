@@ -33,6 +33,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology, topol
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import pervec_cases as PC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def matrix(ns):
@@ -68,7 +69,12 @@ def main():
                 if k != "raster":
                     out[f"r{r}_{k}"] = v
         path = os.path.join(HERE, f"pervec_{name}.npz")
-        np.savez_compressed(path, **out)
+        c = PC.CASES[name]
+        if "dt" in c:           # (McCullochPitts and IzhikevichNodes have no refractory period)
+            save_fixture(path, out, name, [s["raster"] for s in snaps], os.path.join(HERE, f"pervec_{c['sibling']}.npz"),
+                         refractory=c["kind"] not in ("mcp", "izh"))
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(s["raster"].sum()) for s in snaps], "of", snaps[0]["raster"].size, "bytes:", os.path.getsize(path))
 
 

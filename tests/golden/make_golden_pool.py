@@ -36,6 +36,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology  # noq
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import pool_cases as PC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def watch(conn, geom, tally):
@@ -80,7 +81,12 @@ def main(names=None):
             out["share_nonfirst"], out["share_ties"] = tally[0] / tally[2], tally[1] / tally[2]
             assert out["share_nonfirst"] >= 0.10 and out["share_ties"] > 0.0, (name, tally)
         path = os.path.join(HERE, f"pool_{name}.npz")
-        np.savez_compressed(path, **out)
+        if name in PC.DT:
+            T, B = PC.steps_of(name), PC.batch_of(name)
+            rasters = [np.unpackbits(out[f"r{r}_raster"]).reshape(-1)[:T * B * net.layers["Y"].n].reshape(T, B, -1) for r in range(len(snaps))]
+            save_fixture(path, out, name, rasters, os.path.join(HERE, f"pool_{PC.base(name)}.npz"), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(np.unpackbits(out[f"r{r}_raster"]).sum()) for r in range(len(snaps))],
               "not-first / tie shares:", None if pool is None else (round(float(out["share_nonfirst"]), 3), round(float(out["share_ties"]), 3)),
               "bytes:", os.path.getsize(path))

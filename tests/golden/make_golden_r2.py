@@ -67,12 +67,12 @@ def mcc_mstdp_case(name, Nin, N, B, T):
     save(name, Nin=Nin, N=N, B=B, T=T, **out)
 
 
-def mcc_mstdpet_case(name, Nin, N, T):
+def mcc_mstdpet_case(name, Nin, N, T, dt=1.0, max_rate=0.12, sibling=None):
     """Input -> MulticompartmentConnection[Weight, MCC_learning.MSTDPET] -> LIFNodes at batch 1 (the rule flattens the
     spikes, MCC_learning.py:665-666), two consecutive runs with different rewards, no reset of the rule's P+ / P- in
     between (MSTDPET.reset_state_variables clears the eligibilities only, :731-734)."""
     W0 = synth.weights_q12(11, Nin, N)
-    net = Network(dt=1.0)
+    net = Network(dt=dt)
     X_, Y_ = Input(n=Nin, traces=True), LIFNodes(n=N, traces=True)
     feat = Weight("weight", T_(W0).clone(), range=[0.0, 1.0], norm=0.1 * Nin, nu=(1e-1, 1e-1), learning_rule=MCC_MSTDPET)
     conn = MulticompartmentConnection(X_, Y_, device="cpu", pipeline=[feat], tc_e_trace=25.0)
@@ -81,11 +81,13 @@ def mcc_mstdpet_case(name, Nin, N, T):
     net.add_connection(conn, "X", "Y")
     mon = Monitor(net.layers["Y"], ["s"], time=T)
     net.add_monitor(mon, "Y_s")
-    out = {}
+    out, rasters = {}, []
     rule = feat.learning_rule
     for r in range(2):
-        spikes = synth.spike_train(30 + r, T, 1, Nin, active=0.3, max_rate=0.12)
-        net.run({"X": T_(spikes)}, time=T, reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
+        spikes = synth.spike_train(30 + r, T, 1, Nin, active=0.3, max_rate=max_rate)
+        assert int(T * dt / dt) == T
+        net.run({"X": T_(spikes)}, time=T * dt, reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
+        rasters.append(mon.get("s").numpy().reshape(T, 1, N).copy())
         out[f"r{r}_sY"] = np.packbits(mon.get("s").numpy().astype(np.uint8))
         out[f"r{r}_W"] = feat.value.detach().numpy().copy()
         out[f"r{r}_vY"] = net.layers["Y"].v.numpy().copy()
@@ -97,10 +99,34 @@ def mcc_mstdpet_case(name, Nin, N, T):
         net.reset_state_variables()
     Y, X = net.layers["Y"], net.layers["X"]
     out.update(decay=Y.decay.numpy(), y_trace_decay=Y.trace_decay.numpy(), x_trace_decay=X.trace_decay.numpy(),
-               decay_plus=torch.exp(-torch.tensor(1.0) / rule.tc_plus).numpy(),
-               decay_minus=torch.exp(-torch.tensor(1.0) / rule.tc_minus).numpy(),
-               decay_e=torch.exp(-torch.tensor(1.0) / rule.tc_e_trace).numpy(), tc_e=rule.tc_e_trace.numpy())
-    save(name, Nin=Nin, N=N, B=1, T=T, **out)
+               decay_plus=torch.exp(-torch.tensor(dt) / rule.tc_plus).numpy(),
+               decay_minus=torch.exp(-torch.tensor(dt) / rule.tc_minus).numpy(),
+               decay_e=torch.exp(-torch.tensor(dt) / rule.tc_e_trace).numpy(), tc_e=rule.tc_e_trace.numpy())
+    mg.save_dt(name, dt, rasters, max_rate, sibling, Nin=Nin, N=N, B=1, T=T, **out)
+
+
+def mcc_postpre_case(name, Nin, N, B, T, dt, max_rate):
+    """Input -> MulticompartmentConnection[Weight, MCC_learning.PostPre] -> LIFNodes at dt != 1: the rule multiplies each reduced update by
+    connection.dt (MCC_learning.py:224-302).  Nin % 16 == 0: the one-launch plan's shape.  Everything on this path is ATen-ordered."""
+    W0 = synth.weights_q12(11, Nin, N)
+    net = Network(dt=dt)
+    X_, Y_ = Input(n=Nin, traces=True), LIFNodes(n=N, traces=True)
+    feat = Weight("weight", T_(W0).clone(), range=[0.0, 1.0], norm=78.4 * Nin / 784, nu=(1e-4, 1e-2), learning_rule=mg.MCCPostPre)
+    conn = MulticompartmentConnection(X_, Y_, device="cpu", pipeline=[feat])
+    net.add_layer(X_, "X")
+    net.add_layer(Y_, "Y")
+    net.add_connection(conn, "X", "Y")
+    mon = Monitor(net.layers["Y"], ["s"], time=T)
+    net.add_monitor(mon, "Y_s")
+    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=max_rate)
+    assert int(T * dt / dt) == T
+    net.run({"X": T_(spikes)}, time=T * dt)
+    Y, X = net.layers["Y"], net.layers["X"]
+    out = dict(sY=np.packbits(mon.get("s").numpy().astype(np.uint8)), W=feat.value.detach().numpy().copy(), vY=Y.v.numpy().copy(),
+               xY=Y.x.numpy().copy(), xX=X.x.numpy().copy(), rY=Y.refrac_count.numpy().copy(), decay=Y.decay.numpy(),
+               y_trace_decay=Y.trace_decay.numpy(), x_trace_decay=X.trace_decay.numpy())
+    assert not np.array_equal(out["W"], W0)
+    mg.save_dt(name, dt, [mon.get("s").numpy().reshape(T, B, N)], max_rate, None, Nin=Nin, N=N, B=B, T=T, **out)
 
 
 def conn_monitor_case():
@@ -420,12 +446,19 @@ def one_step_case():
 
 
 if __name__ == "__main__":
-    jobs = sys.argv[1:] or ["mstdp", "mstdpet", "dc_v2", "dc_dt", "conv_mstdp", "conn_monitor", "monitor", "rules", "extras", "one_step"]
+    jobs = sys.argv[1:] or ["mstdp", "mstdpet", "dc_v2", "dc_dt", "two_dt", "conv_mstdp", "conn_monitor", "monitor", "rules", "extras", "one_step"]
     if "dc_v2" in jobs:
         dc_v2_case()
         dc_v2_case("run_iin_n64_b4", "IncreasingInhibitionNetwork")
     if "dc_dt" in jobs:      # a D&C run at dt = 0.5 ms: decays, refractory counters and MCC PostPre's `* dt` all depend on it
         mg.dc_case("run_dc_n100_b3_dt05", 100, 3, 80, 2, False, max_rate=0.125, dt=0.5)
+    if "two_dt" in jobs:     # the two-layer graphs at dt != 1: the refractory countdown, every decay, MSTDPET's and MCC PostPre's `* dt`
+        mg.two_layer_case("run_two_postpre_b4_dt05", "postpre", 196, 64, 4, 50, dt=0.5, max_rate=0.3, sibling="run_two_postpre_b4")
+        # (MSTDP at nu = 0.1 depresses the weights after the first spikes: a third spike per neuron needs 80 steps, and 24 columns instead of
+        #  48 keep the recorded currents [T, B, N] inside the sibling's size)
+        mg.two_layer_case("run_two_mstdp_b4_dt05", "mstdp", 196, 24, 4, 80, dt=0.5, max_rate=0.3, sibling="run_two_mstdp_b4")
+        mcc_mstdpet_case("run_two_mcc_mstdpet_b1_dt05", 196, 48, 60, dt=0.5, max_rate=0.3, sibling="run_two_mcc_mstdpet_b1")
+        mcc_postpre_case("run_two_mcc_postpre_b4_dt03", 208, 40, 4, 100, dt=0.3, max_rate=0.3)
     if "conv_mstdp" in jobs:
         conv_mstdp_case()
     if "conn_monitor" in jobs:

@@ -27,6 +27,7 @@ from bindsnet.network import nodes as ref_nodes, topology as ref_topology  # noq
 from bindsnet.network.monitors import Monitor  # noqa: E402
 from bindsnet.network.network import Network  # noqa: E402
 import sparse_cases as SC  # noqa: E402
+from dt_cases import save_fixture  # noqa: E402
 
 
 def main(names=None):
@@ -46,7 +47,12 @@ def main(names=None):
                 else:
                     out[f"r{r}_{k}"] = v
         path = os.path.join(HERE, f"sparse_{name}.npz")
-        np.savez_compressed(path, **out)
+        c = SC.CASES[name]
+        if "dt" in c:
+            rasters = [np.unpackbits(out[f"r{r}_raster"])[:c["T"] * c["B"] * c["n"]].reshape(c["T"], c["B"], c["n"]) for r in range(len(snaps))]
+            save_fixture(path, out, name, rasters, os.path.join(HERE, f"sparse_{c['sibling']}.npz"), refractory=True)
+        else:
+            np.savez_compressed(path, **out)
         print(name, "spikes per input:", [int(np.unpackbits(out[f"r{r}_raster"]).sum()) for r in range(len(snaps))], "nnz:",
               out["w0_nnz"].tolist(), "bytes:", os.path.getsize(path))
 

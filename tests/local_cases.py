@@ -16,6 +16,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 CASES = {
     "a": dict(kind="lc2d", cin=1, shape=(20, 20), k=12, s=4, F=50, B=1, T=100, n_in=3, density=0.05, nu=(1e-4, 1e-2),
               norm=0.2 * 144, inh=25.0, train=True, seed=0),
@@ -29,6 +31,9 @@ CASES = {
               norm=0.2 * 144, inh=25.0, train=False, seed=0),
     "f": dict(kind="dense", cin=1, shape=(50,), F=30, B=2, T=60, n_in=2, density=0.2, train=True, seed=4),
 }
+# (b) at dt = 0.5 (default 1.0; `time = T * dt` is run): the refractory countdown, the decays of v / theta / both traces.  `sibling`:
+# the dt = 1 case it repeats.
+CASES["b_dt05"] = dict(CASES["b"], dt=0.5, sibling="b")
 
 
 def ns_from(nodes, topology, learning, network_cls):
@@ -54,7 +59,7 @@ def build(ns, name):
     """The case's network (weights drawn from the global generator after torch.manual_seed(seed))."""
     c = CASES[name]
     torch.manual_seed(c["seed"])
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     X = ns.Input(shape=[c["cin"], *c["shape"]], traces=True, tc_trace=20.0)
     if c["kind"] == "dense":
         Y = ns.AdaptiveLIFNodes(n=c["F"], traces=True, rest=-65.0, reset=-60.0, thresh=-58.0, refrac=3, tc_trace=20.0,
@@ -121,7 +126,7 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None):
         x = torch.from_numpy(inputs(name, r))
         if device is not None:
             x = x.to(device)
-        net.run({"X": x}, time=c["T"])
+        net.run({"X": x}, time=run_time(c["T"], c.get("dt", 1.0)))
         raster = mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)
         out.append(snapshot(net, raster))
         del net.monitors["Y_s"]

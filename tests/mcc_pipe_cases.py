@@ -19,6 +19,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 CASES = {
     "a": dict(graph="reservoir", S=36, N=20, B=1, T=30, pipe="PW", density=0.3, wscale=2.5, seed=31),
     "b": dict(graph="reservoir", S=36, N=20, B=3, T=30, pipe="PW", density=0.3, wscale=2.5, seed=32),
@@ -38,6 +40,9 @@ CASES = {
     "l_wide": dict(graph="ff", S=300, N=70, B=2, T=12, pipe="PMW", density=0.1, wscale=1.5, seed=45),          # S > 256, N > 64 and no multiple of 32
     "l_bias": dict(graph="ff", S=260, N=37, B=2, T=12, pipe="WB", density=0.1, wscale=1.0, seed=46),           # the dense walk past 256 terms
 }
+# (h) at dt = 0.5 (default 1.0; `time = T * dt` is run): the refractory countdown, the decays, and MCC PostPre's `* dt` behind a
+# Probability feature.  `sibling`: the dt = 1 case it repeats.
+CASES["h_dt05"] = dict(CASES["h"], dt=0.5, T=40, B=1, sibling="h")
 FEATURES = {"P": "Probability", "M": "Mask", "W": "Weight", "B": "Bias", "I": "Intensity"}
 MIN_SPIKES = 36            # "a few dozen": what the generator demands of the reference's own run of every case
 
@@ -92,7 +97,7 @@ def build(ns, name):
         feat.prime_feature(connection=conn, device="cpu")
         conn.feature_index["prob"] = feat
         return net
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     X = ns.Input(n=S, traces=True, tc_trace=20.0)
     if c["graph"] == "reservoir":
         thresh = (-52.0 + rng.standard_normal(N)).astype(np.float32)
@@ -158,7 +163,7 @@ def run_case(net, name, monitor_cls, device=None, n_in=2):
         x = torch.from_numpy(inputs(name, r).copy())
         if device is not None:
             x = x.to(device)
-        net.run({"X": x}, time=T, one_step=bool(c.get("one_step", False)))
+        net.run({"X": x}, time=run_time(T, c.get("dt", 1.0)), one_step=bool(c.get("one_step", False)))
         out.append(snapshot(net, {l: m.get("s").cpu().numpy().reshape(T, B, -1).astype(np.uint8) for l, m in mons.items()}))
         for l in mons:
             del net.monitors[l + "_mon"]

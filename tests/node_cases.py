@@ -15,6 +15,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time, tag
+
 KINDS = ("mcp", "if", "boosted", "clif", "izh")
 
 # per kind: constructor arguments that stay fixed, and the range [lo, hi) the uniform external current is drawn from
@@ -37,6 +39,25 @@ CASES["izh_mix_b1"] = dict(kind="izh", graph="direct", n=100, B=1, T=60, n_in=3,
 CASES["izh_mix_b4"] = dict(kind="izh", graph="direct", n=100, B=4, T=60, n_in=2, exc=0.8, lbound=None, additive=True, seed=24)
 CASES["izh_mcc"] = dict(kind="izh", graph="mcc", n=20, n_src=40, B=2, T=50, n_in=2, exc=0.8, lbound=None, additive=False, seed=25,
                         density=0.25)
+
+
+# dt != 1 (default 1.0): `time = T * dt` is run, so T stays the step count.  The refractory counter is `rc -= dt`, every decay
+# exp(-dt / tc), Izhikevich steps by dt / 2 twice and MCC PostPre multiplies by dt.  refrac 5 at dt 2.0 counts 5, 3, 1, -1 (no
+# multiple); refrac 1.0 at dt 0.1 is ten f32 subtractions of 0.1f.  0.5 and 2.0 scale exactly in f32, 0.1 and 0.3 do not.
+for kind in ("if", "boosted", "clif"):
+    for dt, refrac, T in ((0.5, 5, 80), (2.0, 5, 50), (0.1, 1.0, 120)):
+        CASES[f"{kind}_b4_{tag(dt)}"] = dict(kind=kind, graph="direct", n=37, B=4, T=T, n_in=2, refrac=refrac, lbound=True, additive=True,
+                                             seed=12, dt=dt, sibling=f"{kind}_b4")
+CASES["mcp_b4_dt05"] = dict(kind="mcp", graph="direct", n=37, B=4, T=50, n_in=2, refrac=0, lbound=True, additive=True, seed=12, dt=0.5,
+                            sibling="mcp_b4")
+CASES["izh_mix_b4_dt05"] = dict(kind="izh", graph="direct", n=100, B=4, T=60, n_in=2, exc=0.8, lbound=None, additive=True, seed=24, dt=0.5,
+                                sibling="izh_mix_b4")
+CASES["izh_e0_b1_dt03"] = dict(kind="izh", graph="direct", n=100, B=1, T=120, n_in=2, exc=0, lbound=True, additive=True, seed=22, dt=0.3,
+                               sibling="izh_e0_b4")
+CASES["if_mcc_dt03"] = dict(kind="if", graph="mcc", n=20, n_src=40, B=2, T=50, n_in=2, refrac=5, lbound=None, additive=False, seed=13,
+                            density=0.25, dt=0.3, sibling="if_mcc")
+CASES["izh_mcc_dt03"] = dict(kind="izh", graph="mcc", n=20, n_src=40, B=2, T=40, n_in=2, exc=0.8, lbound=None, additive=False, seed=25,
+                             density=0.25, dt=0.3, sibling="izh_mcc")
 
 LBOUND = {"if": -66.0, "clif": -65.25, "izh": -70.0}          # (McCullochPitts and BoostedLIFNodes have none)
 IZH_RANGE = {1: (0.0, 9.0), 0: (0.0, 30.0), 0.8: (0.0, 12.0)}  # external current per excitatory regime
@@ -81,7 +102,7 @@ def mcc_scale(c):
 def build(ns, name, izh=None):
     c = CASES[name]
     torch.manual_seed(c["seed"])
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     Y = make_layer(ns, c, izh)
     if c["graph"] == "mcc":
         X = ns.Input(n=c["n_src"], traces=True, tc_trace=20.0)
@@ -131,10 +152,10 @@ def sha(a):
 
 def run_case(net, name, monitor_cls, device=None, first=0, count=None, halves=False):
     """Run inputs [first, first+count) of the case (reset_state_variables() between them); one snapshot per input.
-    halves: every input as two run() calls of T/2 steps."""
+    halves: every input as two run() calls of T/2 steps.  A run of T steps lasts `T * dt`."""
     c = CASES[name]
     out = []
-    T = c["T"]
+    T, dt = c["T"], c.get("dt", 1.0)
     count = c["n_in"] - first if count is None else count
     for r in range(first, first + count):
         mon = monitor_cls(net.layers["Y"], ["s", "v"], time=T)
@@ -143,10 +164,10 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None, halves=Fa
         if device is not None:
             inp = {k: v.to(device) for k, v in inp.items()}
         if halves:
-            net.run({k: v[:T // 2] for k, v in inp.items()}, time=T // 2)
-            net.run({k: v[T // 2:] for k, v in inp.items()}, time=T - T // 2)
+            net.run({k: v[:T // 2] for k, v in inp.items()}, time=run_time(T // 2, dt))
+            net.run({k: v[T // 2:] for k, v in inp.items()}, time=run_time(T - T // 2, dt))
         else:
-            net.run(inp, time=T)
+            net.run(inp, time=run_time(T, dt))
         raster = mon.get("s").cpu().numpy().reshape(T, c["B"], -1).astype(np.uint8)
         vrec = mon.get("v").cpu().numpy().reshape(T, c["B"], -1).astype(np.float32)
         out.append(snapshot(net, raster, vrec))

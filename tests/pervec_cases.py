@@ -22,6 +22,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import again, run_time
+
 N_SRC = 40
 
 CASES = {
@@ -43,6 +45,16 @@ CASES = {
     "e_izh": dict(kind="izh", shape=[66], B=3, T=60, n_in=2, density=0.25, scale=3.0, seed=39, vec=("thresh",)),
     "f": dict(kind="lif", shape=[30], B=3, T=50, n_in=2, density=0.25, scale=0.5, seed=40, input_vec=True, postpre=True, vec=()),
 }
+
+# dt != 1 (default 1.0; `time = T * dt` is run): one case of each node class with per-neuron decays repeated at dt 0.5 -- exp(-dt / tc)
+# is then a per-neuron tensor made when the layer joins the network -- and (a) at dt 0.1 with refrac 1.0: ten f32 subtractions of 0.1f
+# per refractory period.  `sibling`: the dt = 1 case it repeats.
+for _name in ("a", "b3", "d", "e_clif", "e_izh"):
+    CASES[_name + "_dt05"] = dict(CASES[_name], dt=0.5, sibling=_name)
+CASES["b3_dt05"].update(T=120, B=2)             # (one_spike: at most one neuron fires per step and sample; 80 steps leave 7 neurons with three spikes;
+#                                            B = 2 keeps the file under its sibling's size)
+CASES["e_clif_dt05"]["scale"] = 0.2      # (at 0.5 every neuron fires as soon as each ten-step refractory period ends)
+CASES["a_dt01"] = dict(CASES["a"], dt=0.1, refrac=1.0, B=2, T=100, sibling="a")
 
 # per kind: the scalar constructor arguments, and per parameter the [lo, hi) range its per-neuron values are drawn from
 _KW = {
@@ -101,10 +113,12 @@ def build(ns, name):
     torch.manual_seed(c["seed"])
     rng = np.random.default_rng(c["seed"])
     yvec, xvec = vectors(name)
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     X = ns.Input(n=N_SRC, traces=True, traces_additive=bool(xvec), **{k: torch.from_numpy(v.copy()) for k, v in xvec.items()},
                  **({} if xvec else dict(tc_trace=20.0)))
     kw = dict(_KW[c["kind"]])
+    if "refrac" in c:
+        kw["refrac"] = c["refrac"]
     kw.update({k: torch.from_numpy(v.copy()) for k, v in yvec.items()})
     kw.setdefault("tc_trace", 20.0)
     shape = c["shape"]
@@ -193,7 +207,7 @@ def run_case(net, name, monitor_cls, device=None):
         x = torch.from_numpy(inputs(name, r))
         if device is not None:
             x = x.to(device)
-        net.run({"X": x}, time=c["T"])
+        net.run({"X": x}, time=run_time(c["T"], c.get("dt", 1.0)))
         raster = mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)
         out.append(snapshot(net, name, raster))
         del net.monitors["Y_mon"]
@@ -210,7 +224,10 @@ def conditions(name, rasters, thetas=None):
         assert total >= 50, f"case {name} input {r}: only {total} spikes"
         assert 2 * total < raster.size, f"case {name} input {r}: {total} of {raster.size} slots spike"
         assert len(set(counts.tolist())) >= 2, f"case {name} input {r}: every neuron spikes {counts[0]} times"
-    if name in ("b1", "b3") and thetas is not None:
+    if "dt" in CASES[name] and CASES[name]["kind"] not in ("mcp", "izh"):
+        for r, raster in enumerate(rasters):       # a refractory period ended and the neuron fired again, twice
+            assert again(raster) >= 10, f"case {name} input {r}: only {again(raster)} neurons spike three or more times"
+    if CASES[name].get("sibling", name) in ("b1", "b3") and thetas is not None:
         for r, th in enumerate(thetas):
             assert len(set(np.asarray(th).reshape(-1).tolist())) >= 2, f"case {name} input {r}: theta is the same for every neuron"
 

@@ -19,6 +19,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 POOL = {
     "a": dict(nd=2, shape=(2, 6, 6), k=2, s=2, p=0, d=1, B=3, decay=0.2),
     "b": dict(nd=2, shape=(2, 7, 5), k=(3, 2), s=(2, 1), p=(1, 1), d=1, B=2, decay=0.2),
@@ -34,17 +36,33 @@ MEAN = {
     "m2": dict(w=lambda: 4.0 * torch.rand(20, generator=torch.Generator().manual_seed(77)), kw={}),
     "m3": dict(w=None, kw=dict(wmin=2.0, wmax=40.0)),
 }
-CASES = sorted(POOL) + ["h"] + sorted(MEAN)
+# (h) -- the case with a learning rule -- at dt = 0.5 (`time = T * dt` is run): the refractory countdown (1 and 2 ms: two and four
+# steps) and the decays of both node layers and their traces.  A dt case is its sibling (the name before "_dt") at another timestep, with
+# the sibling's seed and input; listed last, so that seed_of() of the others stays.
+DT = {"h_dt05": dict(dt=0.5, rate=0.3, T=30, B=1)}     # (at the others' input rate of 0.4 the rule empties the weights and the second input is silent; B = 1 keeps the file under its sibling's size)
+CASES = sorted(POOL) + ["h"] + sorted(MEAN) + sorted(DT)
 T, N_IN, RATE = 30, 2, 0.4
 H = dict(shape=(1, 10, 10), filters=4, k=3, B=2, seed=58)
 
 
+def base(name):
+    return name.split("_dt")[0]
+
+
+def dt_of(name):
+    return DT[name]["dt"] if name in DT else 1.0
+
+
+def steps_of(name):
+    return DT[name]["T"] if name in DT else T
+
+
 def seed_of(name):
-    return 300 + CASES.index(name)
+    return 300 + CASES.index(base(name))
 
 
 def batch_of(name):
-    return POOL[name]["B"] if name in POOL else 2
+    return POOL[name]["B"] if name in POOL else DT[name]["B"] if name in DT else 2
 
 
 def ns_from(nodes, topology, network_cls, learning):
@@ -108,8 +126,8 @@ def build(ns, name):
         net.add_connection(conn, source="X", target="Y")
         net.train(False)                            # (the reference's pooling classes run in eval mode only)
         return net
-    if name == "h":
-        net = ns.Network(dt=1.0, batch_size=H["B"])
+    if base(name) == "h":
+        net = ns.Network(dt=dt_of(name), batch_size=batch_of(name))
         F, k = H["filters"], H["k"]
         side = H["shape"][1] - k + 1
         net.add_layer(ns.Input(shape=H["shape"], traces=True), name="X")
@@ -143,9 +161,9 @@ def pool_of(net):
 
 def inputs(name, r):
     """Input `r` of a case: [T, B, *shape] uint8 from numpy's generator."""
-    shape = POOL[name]["shape"] if name in POOL else H["shape"] if name == "h" else (50,)
+    shape = POOL[name]["shape"] if name in POOL else H["shape"] if base(name) == "h" else (50,)
     rng = np.random.default_rng(1000 * seed_of(name) + r)
-    return (rng.random((T, batch_of(name), *shape)) < RATE).astype(np.uint8)
+    return (rng.random((steps_of(name), batch_of(name), *shape)) < (DT[name]["rate"] if name in DT else RATE)).astype(np.uint8)
 
 
 def sha(a):
@@ -170,6 +188,7 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None, split=Fal
     input is run as two halves, with one monitor over both."""
     out = []
     count = N_IN - first if count is None else count
+    dt, T = dt_of(name), steps_of(name)
     for r in range(first, first + count):
         mon = monitor_cls(net.layers["Y"], ["s"], time=T)
         net.add_monitor(mon, name="Y_s")
@@ -177,10 +196,10 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None, split=Fal
         if device is not None:
             x = x.to(device)
         if split:
-            net.run({"X": x[:T // 2].clone()}, time=T // 2)
-            net.run({"X": x[T // 2:].clone()}, time=T - T // 2)
+            net.run({"X": x[:T // 2].clone()}, time=run_time(T // 2, dt))
+            net.run({"X": x[T // 2:].clone()}, time=run_time(T - T // 2, dt))
         else:
-            net.run({"X": x}, time=T)
+            net.run({"X": x}, time=run_time(T, dt))
         raster = mon.get("s").cpu().numpy().reshape(T, batch_of(name), -1).astype(np.uint8)
         out.append(snapshot(net, raster))
         del net.monitors["Y_s"]

@@ -22,6 +22,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from dt_cases import run_time
+
 CASES = {
     "a": dict(inputs={"X": 100}, n=50, node="lif", B=1, T=50, n_in=2, rate=0.1, seed=21,
               conns=[dict(src="X", dst="Y", density=0.2, scale=3.0)]),
@@ -41,6 +43,9 @@ CASES = {
     "g": dict(inputs={"X": 2500}, n=700, node="lif", B=2, T=20, n_in=2, rate=0.05, seed=27,
               conns=[dict(src="X", dst="Y", density=0.02, scale=3.0)]),
 }
+# (d) at dt = 0.5 (default 1.0; `time = T * dt` is run): the refractory countdown and the decays of the generic plan's LIF step behind
+# the sparse propagation.  `sibling`: the dt = 1 case it repeats.
+CASES["d_dt05"] = dict(CASES["d"], dt=0.5, sibling="d")
 
 
 def ns_from(nodes, topology, network_cls):
@@ -76,7 +81,7 @@ def build(ns, name):
     """The case's network (a connection without a given `w` draws it from the global generator after torch.manual_seed(seed))."""
     c = CASES[name]
     torch.manual_seed(c["seed"])
-    net = ns.Network(dt=1.0)
+    net = ns.Network(dt=c.get("dt", 1.0))
     sizes = dict(c["inputs"], Y=c["n"])
     for lname, n in c["inputs"].items():
         net.add_layer(ns.Input(n=n, traces=True), name=lname)
@@ -142,7 +147,7 @@ def run_case(net, name, monitor_cls, device=None, first=0, count=None):
         x = {k: torch.from_numpy(v) for k, v in inputs(name, r).items()}
         if device is not None:
             x = {k: v.to(device) for k, v in x.items()}
-        net.run(x, time=c["T"])
+        net.run(x, time=run_time(c["T"], c.get("dt", 1.0)))
         raster = mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)
         out.append(snapshot(net, raster))
         del net.monitors["Y_s"]

@@ -12,6 +12,7 @@ import torch
 
 import synth
 from conv_oracle_run import ConvOracleRun
+from dt_cases import again, run_time
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -20,10 +21,11 @@ FUSED, GENERIC, CONVLIF = "convpp-fused", "generic", "convlif-fused"
 
 
 def case(B, T, Cin, H, W, Cout, k, stride, pad, dens, w, plans, vmax=1, nu=(1e-4, 5e-4), wmin=None, wmax=None, wd=0.0, learning=True,
-         vmon=False):
-    """plans: the plan of (auto, 2, 4, 8 channels per workgroup), worked out from convpp_match / convpp_threads / convpp_lds."""
+         vmon=False, dt=1.0, refrac=None):
+    """plans: the plan of (auto, 2, 4, 8 channels per workgroup), worked out from convpp_match / convpp_threads / convpp_lds.
+    dt: the network's timestep (T steps are `time = T * dt`); refrac: the LIF layer's refractory period (None: the class default)."""
     return dict(B=B, T=T, Cin=Cin, H=H, W=W, Cout=Cout, k=k if isinstance(k, tuple) else (k, k), stride=stride, pad=pad, dens=dens,
-                w=w, plans=plans, vmax=vmax, nu=nu, wmin=wmin, wmax=wmax, wd=wd, learning=learning, vmon=vmon)
+                w=w, plans=plans, vmax=vmax, nu=nu, wmin=wmin, wmax=wmax, wd=wd, learning=learning, vmon=vmon, dt=dt, refrac=refrac)
 
 
 ALL_FUSED = (FUSED, FUSED, FUSED, FUSED)
@@ -59,9 +61,13 @@ CASES = {
                                wd=0.005),
     "k16_32x32_only_pre": case(2, 14, 1, 32, 32, 4, 16, 1, 0, 0.08, (-0.05, 0.18), ALL_FUSED, nu=(3e-4, 0.0)),
     "k16_32x32_only_post": case(2, 14, 1, 32, 32, 4, 16, 1, 0, 0.08, (-0.05, 0.18), ALL_FUSED, nu=(0.0, 1e-3)),
+    # dt != 1: both whole-run kernels keep the refractory counter in registers and step it by dt; the decays of v and of both traces
+    # are exp(-dt / tc).  k16_s1 over 50 steps: ten steps of refractory period at dt 0.5; at dt 2.0 with refrac 5 the counter runs 5, 3, 1, -1
+    "k16_s1_dt05": case(4, 50, 1, 28, 28, 6, 16, 1, 0, 0.08, (-0.05, 0.18), ALL_FUSED, vmon=True, dt=0.5),
+    "k16_s1_dt2_refrac5": case(4, 50, 1, 28, 28, 6, 16, 1, 0, 0.08, (-0.05, 0.18), ALL_FUSED, vmon=True, dt=2.0, refrac=5),
 }
 VARIANTS = {"auto": 0, "cc2": 1, "cc4": 2, "cc8": 3, "generic": None}
-CONVLIF_CASES = ["k16_s1", "rgb_k7_s2_p1", "k16_32x32", "full_rows_1024"]
+CONVLIF_CASES = ["k16_s1", "rgb_k7_s2_p1", "k16_32x32", "full_rows_1024", "k16_s1_dt05", "k16_s1_dt2_refrac5"]
 
 
 def geometry(c):
@@ -86,9 +92,9 @@ def build(c, rule=True):
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import Conv2dConnection
     OH, OW = geometry(c)
-    net = Network(dt=1.0, batch_size=c["B"], learning=c["learning"])
+    net = Network(dt=c["dt"], batch_size=c["B"], learning=c["learning"])
     net.add_layer(Input(shape=(c["Cin"], c["H"], c["W"]), traces=True), "X")
-    net.add_layer(LIFNodes(shape=(c["Cout"], OH, OW), traces=True), "Y")
+    net.add_layer(LIFNodes(shape=(c["Cout"], OH, OW), traces=True, **({} if c["refrac"] is None else {"refrac": c["refrac"]})), "Y")
     kw = dict(kernel_size=c["k"], stride=c["stride"], padding=c["pad"], w=torch.from_numpy(w0(c)))
     if rule:
         kw.update(update_rule=PostPre, nu=c["nu"], weight_decay=c["wd"])
@@ -125,7 +131,7 @@ def device_runs(name, rule=True, n_runs=2):
     net.to(DEV)
     out, plans = [], []
     for r in range(n_runs):
-        net.run({"X": torch.from_numpy(inputs(c, r)).to(DEV)}, time=T)
+        net.run({"X": torch.from_numpy(inputs(c, r)).to(DEV)}, time=run_time(T, c["dt"]))
         X, Y = net.layers["X"], net.layers["Y"]
         host = lambda t: t.detach().cpu().numpy().copy()
         st = dict(s=host(mons["s"].get("s")).astype(u8), v=host(Y.v), refrac_count=host(Y.refrac_count), sY=host(Y.s).astype(u8),
@@ -167,6 +173,10 @@ def compare(got, want, W0, what):
 def check_not_vacuous(name, runs, learning):
     c = CASES[name]
     assert sum(int(r["s"].sum()) for r in runs) > 0, f"{name}: no output spike in the oracle run"
+    if c["dt"] != 1.0:
+        # a refractory period ended and the neuron fired again, twice: neurons with three or more spikes in one sample of one run
+        n = max(again(r["s"].reshape(c["T"], c["B"], -1)) for r in runs)
+        assert n >= 10, f"{name}: only {n} neurons fire three times in the oracle run"
     if learning:
         # a frozen slice of filter elements could hide behind elements the oracle leaves alone: every channel's filter moves, in the first
         # and in the last half of its taps

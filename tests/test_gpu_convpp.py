@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import synth
+from dt_cases import again, run_time, tag
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -28,7 +29,7 @@ CASES = {
 }
 
 
-def run(mode, case, n_runs=2):
+def run(mode, case, n_runs=2, dt=1.0, refrac=None, steps=None):
     from bindsnet_amd import _lib
     from bindsnet_amd.learning import PostPre
     from bindsnet_amd.network import Network
@@ -36,12 +37,13 @@ def run(mode, case, n_runs=2):
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import Conv2dConnection
     B, T, Cin, H, W, Cout, k, stride, pad, dens, vmax, nu, wmin, wmax, wd, vmon, learning = case
+    T = T if steps is None else steps
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     _lib.lib().snn_set_plan_mode(mode)
     try:
-        net = Network(dt=1.0, batch_size=B, learning=learning)
+        net = Network(dt=dt, batch_size=B, learning=learning)
         net.add_layer(Input(shape=(Cin, H, W), traces=True), "X")
-        net.add_layer(LIFNodes(shape=(Cout, OH, OW), traces=True), "Y")
+        net.add_layer(LIFNodes(shape=(Cout, OH, OW), traces=True, **({} if refrac is None else {"refrac": refrac})), "Y")
         w = torch.from_numpy(synth.uniform_f32(7, (Cout, Cin, k, k), -0.1, 0.5))
         kw = dict(kernel_size=k, stride=stride, padding=pad, w=w, update_rule=PostPre, nu=nu, weight_decay=wd)
         if wmin is not None:
@@ -62,7 +64,7 @@ def run(mode, case, n_runs=2):
             sp = synth.dense_spikes(60 + r, (T, B, Cin, H, W), dens)
             if vmax > 1:
                 sp = (sp * rs.randint(1, vmax + 1, size=sp.shape)).astype(u8)
-            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=T)
+            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=run_time(T, dt))
             Y = net.layers["Y"]
             st = dict(s=mons["s"].get("s").cpu().numpy().copy(), v=Y.v.cpu().numpy().copy(), r=Y.refrac_count.cpu().numpy().copy(),
                       sl=Y.s.cpu().numpy().copy(), xY=Y.x.cpu().numpy().copy(), xX=net.layers["X"].x.cpu().numpy().copy(),
@@ -89,6 +91,24 @@ def test_convpp_fused_equals_generic(name):
     if CASES[name][-1]:
         w0 = synth.uniform_f32(7, fused[0]["w"].shape, -0.1, 0.5)
         assert not np.array_equal(fused[-1]["w"], w0), "the weights never moved: vacuous"
+
+
+@pytest.mark.parametrize("dt,refrac", [(0.5, None), (2.0, 5), (0.1, 1.0)], ids=lambda v: tag(v) if isinstance(v, float) and v != 1.0 else f"refrac{v}")
+def test_convpp_fused_equals_generic_at_dt(dt, refrac):
+    """stride2_pad1_b3 over 50 steps at dt != 1: the one-launch kernel keeps the refractory counter in registers and steps it by dt (ten steps
+    at dt 0.5; 5, 3, 1, -1 at dt 2.0; ten f32 subtractions of 0.1f at dt 0.1 with refrac 1.0); v and both traces decay by exp(-dt / tc)."""
+    case = CASES["stride2_pad1_b3"]
+    fused, plan = run(0, case, dt=dt, refrac=refrac, steps=50)
+    assert plan == "convpp-fused"
+    generic, plan_g = run(1, case, dt=dt, refrac=refrac, steps=50)
+    assert plan_g == "generic"
+    for r, (a, b) in enumerate(zip(fused, generic)):
+        for k in a:
+            np.testing.assert_array_equal(a[k].view(u8), b[k].view(u8), err_msg=f"dt {dt} run {r}: {k}")
+    n = again(generic[0]["s"].reshape(50, case[0], -1))
+    assert n >= 10, f"only {n} neurons fire three times: no refractory period is seen to end twice"
+    one, _ = run(1, case, n_runs=1, steps=50)
+    assert not np.array_equal(one[0]["s"], generic[0]["s"]), "dt changes nothing: vacuous"
 
 
 @pytest.mark.parametrize("cc", [2, 4, 8])

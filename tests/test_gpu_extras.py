@@ -51,6 +51,51 @@ def test_run_keyword_arguments_match_reference():
     assert (W[mask.numpy()] == 0).all()
 
 
+def test_run_keyword_arguments_at_dt05_equal_the_host_path():
+    """The same clamp / unclamp / injects_v / masks run at dt = 0.5, device against the host path with the dense family's criterion
+    (the host's `s @ w` is an MKL sgemm: rasters identical, v within 2e-4 and weights within 1e-5, as above), with a Monitor(time=T)
+    and a NetworkMonitor on both sides: T steps are `time = T * dt`, and every record holds int(time / dt) of them."""
+    from dt_cases import again, run_time
+    from bindsnet_amd.models import TwoLayerNetwork
+    from bindsnet_amd.network.monitors import Monitor, NetworkMonitor
+    Nin, N, B, T, dt = 196, 48, 3, 40, 0.5
+    time = run_time(T, dt)
+    assert time == 20.0 and int(time / dt) == T
+    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.3)
+    clamp = T_(synth.dense_spikes(51, (T, N), 0.03)).bool()
+    unclamp = T_(synth.dense_spikes(52, (N,), 0.2)).bool()
+    inject = T_(synth.uniform_f32(53, (N,), 0.0, 0.6))
+    mask = T_(synth.dense_spikes(54, (Nin, N), 0.3)).bool()
+    out = {}
+    for dev, plan in (("cpu", "host-torch"), (DEV, "generic")):
+        torch.manual_seed(0)
+        net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, dt=dt, reduction=torch.sum, norm=78.4 * Nin / 784)
+        conn = net.connections[("X", "Y")]
+        conn.w.data.copy_(T_(synth.weights_q12(11, Nin, N)))
+        mon = Monitor(net.layers["Y"], ["s", "v"], time=T)
+        nm = NetworkMonitor(net, layers=["Y"], connections=[], state_vars=["s", "v"])
+        net.add_monitor(mon, "Y"); net.add_monitor(nm, "all")
+        net.to(dev)
+        net.run({"X": T_(spikes).to(dev)}, time=time, clamp={"Y": clamp}, unclamp={"Y": unclamp}, injects_v={"Y": inject},
+                masks={("X", "Y"): mask})
+        assert net.last_plan == plan
+        rec = nm.get()
+        assert mon.get("s").shape[0] == mon.get("v").shape[0] == rec["Y"]["s"].shape[0] == rec["Y"]["v"].shape[0] == int(time / dt) == T
+        out[dev] = dict(s=host(mon.get("s")).reshape(T, B, N).astype(u8), v=host(mon.get("v")).reshape(T, B, N), W=host(conn.w),
+                        nm_s=host(rec["Y"]["s"]).reshape(T, B, N).astype(u8), nm_v=host(rec["Y"]["v"]).reshape(T, B, N),
+                        rc=host(net.layers["Y"].refrac_count), x=host(net.layers["Y"].x))
+    h, d = out["cpu"], out[DEV]
+    assert again(h["s"]) >= 10, "no refractory period (ten steps) is seen to end twice"
+    np.testing.assert_array_equal(d["s"], h["s"])
+    np.testing.assert_array_equal(d["nm_s"], h["s"])
+    np.testing.assert_array_equal(d["nm_v"].view(np.uint32), d["v"].view(np.uint32))
+    np.testing.assert_allclose(d["v"], h["v"], rtol=0, atol=2e-4)
+    np.testing.assert_allclose(d["W"], h["W"], rtol=0, atol=1e-5)
+    for k in ("rc", "x"):                                   # functions of the raster alone: bit for bit
+        np.testing.assert_array_equal(d[k].view(np.uint32), h[k].view(np.uint32), err_msg=k)
+    assert (d["W"][mask.numpy()] == 0).all()
+
+
 def test_local_connection_postpre_matches_reference():
     from bindsnet_amd.learning import PostPre
     from bindsnet_amd.network import Network

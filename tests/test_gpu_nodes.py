@@ -58,7 +58,8 @@ def test_device_reproduces_reference_fixture(name):
     check_snapshots(name, snaps)               # raster and v record come from the device monitors
 
 
-@pytest.mark.parametrize("name", ["mcp_b4", "if_b4", "boosted_mcc", "clif_b4", "clif_mcc", "izh_mix_b4", "izh_e0_b4", "izh_mcc"])
+@pytest.mark.parametrize("name", ["mcp_b4", "if_b4", "boosted_mcc", "clif_b4", "clif_mcc", "izh_mix_b4", "izh_e0_b4", "izh_mcc", "if_b4_dt01", "clif_b4_dt2",
+                                  "izh_e0_b1_dt03", "if_mcc_dt03"])
 def test_two_half_runs_equal_one_whole_run(name):
     from bindsnet_amd.network.monitors import Monitor
     net = build(name).to(DEV)

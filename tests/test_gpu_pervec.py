@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import pervec_cases as PC
+from dt_cases import run_time
 from test_pervec_host import _bits, check_snapshots, gold, matrix, ns
 
 pytestmark = pytest.mark.gpu
@@ -70,7 +71,7 @@ def test_second_input_runs_on_the_kept_descriptors(name, monkeypatch):
         Y.reset_state_variables = lambda: (Y.s.zero_(), Y.x.zero_(), Y.v.fill_(float(Y.rest)), Y.u.copy_(Y.b * Y.v))
     torch.manual_seed(100 + c["seed"])
     for r in range(c["n_in"]):
-        net.run({"X": torch.from_numpy(PC.inputs(name, r)).to(DEV)}, time=c["T"])
+        net.run({"X": torch.from_numpy(PC.inputs(name, r)).to(DEV)}, time=run_time(c["T"], c.get("dt", 1.0)))
         assert net.last_plan == "generic"
         kept.append(net.__dict__["_run_cache"])
         snaps.append(PC.snapshot(net, name, mon.get("s").cpu().numpy().reshape(c["T"], c["B"], -1).astype(np.uint8)))

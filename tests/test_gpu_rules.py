@@ -9,7 +9,8 @@ import torch
 import oracle
 import synth
 from cases import f32, u8, gold
-from test_oracle_golden import RULE_VARIANTS, rule_inputs
+from dt_cases import again, run_time, tag
+from test_oracle_golden import RULE_VARIANTS, rule_inputs, two_dt, two_input
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -94,17 +95,30 @@ def test_outer_rules_row_major_form_one_sided_rates_and_partial_tiles(rule, N, B
     _run_rule_vs_oracle(rule, 208, N, B, "twolayer-fused", nu=nu)
 
 
-def _run_rule_vs_oracle(rule, Nin, N, B, plan, nu=None):
+DT_RUNS = [("hebbian", 196, 48, 6, "generic", 0.3, None), ("wdpp", 196, 48, 6, "generic", 0.3, None), ("mstdpet", 196, 48, 1, "generic", 0.3, None),
+           ("hebbian", 208, 48, 6, "twolayer-fused", 0.5, None), ("wdpp", 208, 48, 6, "twolayer-fused", 0.5, None),
+           ("hebbian", 208, 48, 6, "twolayer-fused", 2.0, None), ("wdpp", 208, 48, 6, "twolayer-fused", 2.0, None),
+           # refrac 1.0 at dt 0.1: a period is ten f32 subtractions of 0.1f; last tile of 4 columns, two batch-mask words
+           ("wdpp", 208, 44, 40, "twolayer-fused", 0.1, 1.0)]
+
+
+@pytest.mark.parametrize("rule,Nin,N,B,plan,dt,refrac", DT_RUNS, ids=[f"{r[0]}-{r[1]}-{r[2]}-{r[3]}-{r[4]}-{tag(r[5])}" for r in DT_RUNS])
+def test_network_run_with_the_rule_vs_oracle_at_dt(rule, Nin, N, B, plan, dt, refrac):
+    """dt != 1: the network is built with Network(dt=dt) and runs `time = T * dt`; the oracle gets P.dt = dt and the decays of the built
+    layers; 80 steps at max_rate 0.3, so that every neuron fires three times or more.  0.3 and 0.1 are no powers of two (MSTDPET's `nu * dt * reward` rounds); at 2.0 the counter of refrac 5 runs 5, 3, 1, -1."""
+    _run_rule_vs_oracle(rule, Nin, N, B, plan, dt=dt, refrac=refrac, T=80, max_rate=0.3)
+
+
+def _run_rule_vs_oracle(rule, Nin, N, B, plan, nu=None, dt=1.0, refrac=None, T=40, max_rate=0.12):
     from bindsnet_amd.learning import Hebbian, MSTDPET, WeightDependentPostPre
     from bindsnet_amd.network import Network
     from bindsnet_amd.network.monitors import Monitor
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import Connection
-    T = 40
     W0 = synth.weights_q12(11, Nin, N)
-    net = Network(dt=1.0)
+    net = Network(dt=dt)
     net.add_layer(Input(n=Nin, traces=True), "X")
-    net.add_layer(LIFNodes(n=N, traces=True), "Y")
+    net.add_layer(LIFNodes(n=N, traces=True, **({} if refrac is None else {"refrac": refrac})), "Y")
     cls = {"hebbian": Hebbian, "wdpp": WeightDependentPostPre, "mstdpet": MSTDPET}[rule]
     if nu is None:
         nu = (1e-1, 1e-1) if rule == "mstdpet" else (1e-4, 1e-3)
@@ -114,15 +128,15 @@ def _run_rule_vs_oracle(rule, Nin, N, B, plan, nu=None):
     mon = Monitor(net.layers["Y"], ["s"], time=T)
     net.add_monitor(mon, "Y_s")
     net.to(DEV)
-    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.12)
+    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=max_rate)
     kw = {"reward": 0.8} if rule == "mstdpet" else {}
-    net.run({"X": torch.from_numpy(spikes).to(DEV)}, time=T, **kw)
+    net.run({"X": torch.from_numpy(spikes).to(DEV)}, time=run_time(T, dt), **kw)
     assert net.last_plan == plan
     P = oracle.TwoParams()
-    P.B, P.Nin, P.N, P.T, P.dt = B, Nin, N, T, 1.0
+    P.B, P.Nin, P.N, P.T, P.dt = B, Nin, N, T, dt
     P.rule = {"hebbian": 3, "wdpp": 4, "mstdpet": 5}[rule]
     P.x_trace_decay = float(net.layers["X"].trace_decay); P.x_trace_scale = 1.0; P.x_traces = 1
-    P.decay = float(net.layers["Y"].decay); P.rest, P.reset, P.thresh, P.refrac = -65.0, -65.0, -52.0, 5.0
+    P.decay = float(net.layers["Y"].decay); P.rest, P.reset, P.thresh, P.refrac = -65.0, -65.0, -52.0, 5.0 if refrac is None else refrac
     P.y_traces = 1; P.y_trace_decay = float(net.layers["Y"].trace_decay); P.y_trace_scale = 1.0
     P.nu0, P.nu1 = nu
     P.has_min = P.has_max = 1; P.wmin, P.wmax = 0.0, 1.0; P.has_norm = 1; P.norm = 0.1 * Nin; P.learning = 1
@@ -135,6 +149,8 @@ def _run_rule_vs_oracle(rule, Nin, N, B, plan, nu=None):
         st.update(elig=np.zeros((Nin, N), f32), e_trace=np.zeros((Nin, N), f32), p_plus=np.zeros(Nin, f32), p_minus=np.zeros(N, f32))
     ras = oracle.run_two_layer(P, st, spikes)
     assert ras.sum() > 20
+    if dt != 1.0:       # a refractory period ended and the neuron fired again, twice (80 steps of a denser input than at dt = 1)
+        assert again(ras) >= 10, "no refractory period is seen to end"
     np.testing.assert_array_equal(host(mon.get("s")).reshape(T, B, N).astype(u8), ras)
     np.testing.assert_array_equal(bits(host(conn.w)), bits(st["W"]))
     if rule == "mstdpet":
@@ -145,6 +161,15 @@ def test_mcc_mstdpet_matches_reference():
     """MulticompartmentConnection + Weight with MCC_learning.MSTDPET (MCC_learning.py:554-733, batch 1): two consecutive
     Network.run() calls (different reward / a_plus, layers reset in between, the rule's state kept) bit for bit against
     the reference fixture, plus single update() calls through the rule object afterwards against the oracle."""
+    _mcc_mstdpet("run_two_mcc_mstdpet_b1")
+
+
+def test_mcc_mstdpet_matches_reference_at_dt05():
+    """The same at dt = 0.5 (snn_mstdpet_step takes dt as an argument; the rule's decays are exp(-dt / tc))."""
+    _mcc_mstdpet("run_two_mcc_mstdpet_b1_dt05")
+
+
+def _mcc_mstdpet(name):
     from cases import unpack
     from bindsnet_amd.learning.MCC_learning import MSTDPET
     from bindsnet_amd.network import Network
@@ -152,9 +177,9 @@ def test_mcc_mstdpet_matches_reference():
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import MulticompartmentConnection
     from bindsnet_amd.network.topology_features import Weight
-    g = gold("run_two_mcc_mstdpet_b1")
-    Nin, N, T = int(g["Nin"]), int(g["N"]), int(g["T"])
-    net = Network(dt=1.0)
+    g = gold(name)
+    Nin, N, T, dt = int(g["Nin"]), int(g["N"]), int(g["T"]), two_dt(g)
+    net = Network(dt=dt)
     X_, Y_ = Input(n=Nin, traces=True), LIFNodes(n=N, traces=True)
     feat = Weight("weight", torch.from_numpy(synth.weights_q12(11, Nin, N)), range=[0.0, 1.0], norm=0.1 * Nin, nu=(1e-1, 1e-1),
                   learning_rule=MSTDPET)
@@ -166,8 +191,8 @@ def test_mcc_mstdpet_matches_reference():
     net.to(DEV)
     rule = feat.learning_rule
     for r in range(2):
-        spikes = synth.spike_train(30 + r, T, 1, Nin, active=0.3, max_rate=0.12)
-        net.run({"X": torch.from_numpy(spikes).to(DEV)}, time=T, reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
+        spikes = two_input(g, 30 + r)
+        net.run({"X": torch.from_numpy(spikes).to(DEV)}, time=run_time(T, dt), reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
         assert net.last_plan == "generic"
         np.testing.assert_array_equal(host(mon.get("s")).reshape(T, 1, N).astype(u8), unpack(g[f"r{r}_sY"], (T, 1, N)))
         for got, key in ((feat.value, "W"), (net.layers["Y"].v, "vY"), (rule.p_plus, "p_plus"), (rule.p_minus, "p_minus"),
@@ -182,7 +207,7 @@ def test_mcc_mstdpet_matches_reference():
         s_src, s_tgt = synth.dense_spikes(960 + t, (1, Nin), 0.2), synth.dense_spikes(970 + t, (1, N), 0.2)
         X_.s, Y_.s = dev(s_src), dev(s_tgt)
         rule.update(reward=0.3, a_minus=-0.5)
-        oracle.mstdpet(W, el, et, pp, pm, s_src.reshape(-1), s_tgt.reshape(-1), reward=0.3, nu0=np.float32(1e-1), a_minus=-0.5,
+        oracle.mstdpet(W, el, et, pp, pm, s_src.reshape(-1), s_tgt.reshape(-1), reward=0.3, nu0=np.float32(1e-1), dt=dt, a_minus=-0.5,
                        decay_plus=dp, decay_minus=dm, decay_e=de, tc_e=25.0, wmin=0.0, wmax=1.0)
     for got, want, key in ((feat.value, W, "W"), (rule.eligibility_trace, et, "e_trace"), (rule.eligibility, el, "elig"),
                            (rule.p_plus, pp, "p_plus"), (rule.p_minus, pm, "p_minus")):

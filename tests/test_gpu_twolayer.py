@@ -5,12 +5,13 @@ import pytest
 import torch
 
 import synth
+from dt_cases import again, run_time, tag
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def build(kind, Nin, N, rule, bias):
+def build(kind, Nin, N, rule, bias, dt=1.0):
     from bindsnet_amd.learning import PostPre
     from bindsnet_amd.learning.MCC_learning import PostPre as MCCPostPre
     from bindsnet_amd.network import Network
@@ -19,7 +20,7 @@ def build(kind, Nin, N, rule, bias):
     from bindsnet_amd.network.topology import Connection, MulticompartmentConnection
     from bindsnet_amd.network.topology_features import Weight
     torch.manual_seed(0)
-    net = Network(dt=1.0)
+    net = Network(dt=dt)
     net.add_layer(Input(n=Nin, traces=True), "X")
     net.add_layer(LIFNodes(n=N, traces=True, lbound=-70.0 if bias else None), "Y")
     W0 = torch.from_numpy(synth.weights_q12(11, Nin, N))
@@ -35,12 +36,12 @@ def build(kind, Nin, N, rule, bias):
     return net
 
 
-def run(generic, kind, Nin, N, B, T, rule=True, bias=False, n_inputs=2, dens=0.03, learning=True, additive=False):
+def run(generic, kind, Nin, N, B, T, rule=True, bias=False, n_inputs=2, dens=0.03, learning=True, additive=False, dt=1.0):
     from bindsnet_amd import _lib
     from bindsnet_amd.network.monitors import Monitor
     _lib.lib().snn_set_plan_mode(1 if generic else 0)
     try:
-        net = build(kind, Nin, N, rule, bias)
+        net = build(kind, Nin, N, rule, bias, dt)
         ms, mv = Monitor(net.layers["Y"], ["s"], time=T), Monitor(net.layers["Y"], ["v"], time=T)
         net.add_monitor(ms, "s"); net.add_monitor(mv, "v")
         net.train(learning)
@@ -52,7 +53,7 @@ def run(generic, kind, Nin, N, B, T, rule=True, bias=False, n_inputs=2, dens=0.0
         out = []
         for r in range(n_inputs):
             sp = synth.dense_spikes(40 + r, (T, B, Nin), dens)
-            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=T)
+            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=run_time(T, dt))
             conn = net.connections[("X", "Y")]
             W = (conn.w if kind == "dense" else conn.pipeline[0].value).detach().cpu().numpy().copy()
             out.append(dict(s=ms.get("s").cpu().numpy().copy(), v=mv.get("v").cpu().numpy().copy(), W=W,
@@ -100,6 +101,28 @@ def test_twolayer_fused_equals_generic(name):
     assert sum(int(x["s"].sum()) for x in f) > 0, "silent network: vacuous"
 
 
+# dt != 1: the one-launch kernel keeps the refractory counter, the decays and (MCC) PostPre's `* dt` in its own parameter block.  Inputs dense and long
+# enough that neurons fire again after a refractory period of 10 (dt 0.5), 3 (dt 2.0: 5, 3, 1, -1) or 17 (dt 0.3) steps.
+DT_CASES = [("dense_postpre_b16", 0.5, 40, 0.03), ("dense_postpre_b16", 2.0, 40, 0.03), ("mcc_postpre_b5_tailcols", 0.3, 60, 0.03),
+            ("mcc_postpre_b5_tailcols", 2.0, 40, 0.03), ("dense_postpre_b33_bias", 0.1, 120, 0.05)]      # (name, dt, steps, input density)
+
+
+@pytest.mark.parametrize("name,dt,T,dens", DT_CASES, ids=[f"{c[0]}-{tag(c[1])}" for c in DT_CASES])
+def test_twolayer_fused_equals_generic_at_dt(name, dt, T, dens):
+    kind, Nin, N, B, _, rule, bias = CASES[name]
+    f, plan = run(False, kind, Nin, N, B, T, rule, bias, dens=dens, dt=dt)
+    assert plan == "twolayer-fused"
+    g, plan_g = run(True, kind, Nin, N, B, T, rule, bias, dens=dens, dt=dt)
+    assert plan_g == "generic"
+    for r, (a, b) in enumerate(zip(f, g)):
+        for k in a:
+            np.testing.assert_array_equal(a[k].view(np.uint8), b[k].view(np.uint8), err_msg=f"{name} dt {dt} input {r}: {k}")
+    n = again(g[0]["s"].reshape(T, B, N))
+    assert n >= 10, f"only {n} neurons fire three times: no refractory period is seen to end twice"
+    one, _ = run(True, kind, Nin, N, B, T, rule, bias, n_inputs=1, dens=dens)
+    assert not np.array_equal(one[0]["s"], g[0]["s"]) and not np.array_equal(one[0]["W"], g[0]["W"]), "dt changes nothing: vacuous"
+
+
 def test_twolayer_learning_off_and_big_batch_fallback():
     f, plan = run(False, "dense", 784, 64, 8, 25, learning=False)
     g, _ = run(True, "dense", 784, 64, 8, 25, learning=False)
@@ -112,7 +135,7 @@ def test_twolayer_learning_off_and_big_batch_fallback():
 
 
 # ------------------------------------------------------------------------------------------------ MSTDP
-def run_mstdp(generic, Nin, N, B, T, reward, n_inputs=3, dens=0.05, vmax=1, learning=True):
+def run_mstdp(generic, Nin, N, B, T, reward, n_inputs=3, dens=0.05, vmax=1, learning=True, dt=1.0):
     """Input -> Connection(MSTDP) -> LIF (the cfg5 graph): fused plan vs generic plan, incl. the rule's state."""
     from bindsnet_amd import _lib
     from bindsnet_amd.learning import MSTDP
@@ -123,7 +146,7 @@ def run_mstdp(generic, Nin, N, B, T, reward, n_inputs=3, dens=0.05, vmax=1, lear
     _lib.lib().snn_set_plan_mode(1 if generic else 0)
     try:
         torch.manual_seed(0)
-        net = Network(dt=1.0)
+        net = Network(dt=dt)
         net.add_layer(Input(n=Nin, traces=True), "X")
         net.add_layer(LIFNodes(n=N, traces=True), "Y")
         W0 = torch.from_numpy(synth.weights_q12(11, Nin, N))
@@ -141,7 +164,7 @@ def run_mstdp(generic, Nin, N, B, T, reward, n_inputs=3, dens=0.05, vmax=1, lear
             if vmax > 1:
                 sp = (sp * rs.randint(1, vmax + 1, size=sp.shape)).astype(np.uint8)
             rw = reward if not isinstance(reward, str) else torch.from_numpy(synth.uniform_f32(17 + r, (B,), -1.0, 1.0)).to(DEV)
-            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=T, reward=rw)
+            net.run({"X": torch.from_numpy(sp).to(DEV)}, time=run_time(T, dt), reward=rw)
             rule = conn.update_rule
             st = dict(s=ms.get("s").cpu().numpy().copy(), W=conn.w.detach().cpu().numpy().copy(),
                       vY=net.layers["Y"].v.cpu().numpy().copy(), xX=net.layers["X"].x.cpu().numpy().copy(),
@@ -187,6 +210,21 @@ def test_twolayer_mstdp_fused_equals_generic(name):
             np.testing.assert_array_equal(a[k].view(np.uint8), b[k].view(np.uint8), err_msg=f"{name} input {r}: {k}")
     assert sum(int(x["s"].sum()) for x in f) > 0, "silent network: vacuous"
     assert np.abs(f[-1]["pm"]).max() > 0 and not np.array_equal(f[0]["W"], f[-1]["W"])
+
+
+@pytest.mark.parametrize("dt", [0.5, 0.3], ids=tag)
+def test_twolayer_mstdp_fused_equals_generic_at_dt(dt):
+    """b5_reward_vector_tailcols at dt != 1: P+ / P- decay by exp(-dt / tc), the refractory counter steps by dt."""
+    Nin, N, B, T, reward, dens, vmax = MSTDP_CASES["b5_reward_vector_tailcols"]
+    f, plan = run_mstdp(False, Nin, N, B, T, reward, dens=dens, vmax=vmax, dt=dt)
+    assert plan == "twolayer-fused"
+    g, plan_g = run_mstdp(True, Nin, N, B, T, reward, dens=dens, vmax=vmax, dt=dt)
+    assert plan_g == "generic"
+    for r, (a, b) in enumerate(zip(f, g)):
+        for k in a:
+            np.testing.assert_array_equal(a[k].view(np.uint8), b[k].view(np.uint8), err_msg=f"dt {dt} input {r}: {k}")
+    one, _ = run_mstdp(True, Nin, N, B, T, reward, n_inputs=1, dens=dens, vmax=vmax)
+    assert f[0]["s"].sum() > 0 and not np.array_equal(one[0]["pp"], g[0]["pp"]), "dt changes nothing: vacuous"
 
 
 @pytest.mark.parametrize("name", ["b16_scalar_reward", "wide_tile4_b12_reward_vector", "wide_tile2_b16_long", "cfg5_shape_short"])

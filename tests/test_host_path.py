@@ -8,6 +8,8 @@ import torch
 
 import synth
 from cases import gold, sha, unpack
+from dt_cases import run_time
+from test_oracle_golden import two_dt, two_input
 
 u8 = np.uint8
 
@@ -51,18 +53,27 @@ def test_two_layer_postpre_on_the_host_matches_reference():
     """TwoLayerNetwork (dense Connection + PostPre): rasters identical to the reference; weights / state within the dense
     family's tolerance (Connection.compute is an MKL sgemm whose summation order depends on the thread count of the
     machine the fixture was made on -- SURVEY.md finding 5)."""
+    _two_layer_postpre("run_two_postpre_b4")
+
+
+def test_two_layer_postpre_on_the_host_at_dt05_matches_reference():
+    """The same graph at dt = 0.5: T steps are `time = T * dt`, decays are exp(-dt / tc), a refractory period lasts ten steps."""
+    _two_layer_postpre("run_two_postpre_b4_dt05")
+
+
+def _two_layer_postpre(name):
     from bindsnet_amd.models import TwoLayerNetwork
     from bindsnet_amd.network.monitors import Monitor
-    g = gold("run_two_postpre_b4")
-    Nin, N, B, T = int(g["Nin"]), int(g["N"]), int(g["B"]), int(g["T"])
+    g = gold(name)
+    Nin, N, B, T, dt = int(g["Nin"]), int(g["N"]), int(g["B"]), int(g["T"]), two_dt(g)
     torch.manual_seed(0)
-    net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, reduction=torch.sum, norm=78.4 * Nin / 784)
+    net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, dt=dt, reduction=torch.sum, norm=78.4 * Nin / 784)
     conn = net.connections[("X", "Y")]
     conn.w.data.copy_(T_(synth.weights_q12(11, Nin, N)))
     mon = Monitor(net.layers["Y"], ["s"], time=T)
     net.add_monitor(mon, "Y_s")
-    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.12)
-    net.run({"X": T_(spikes)}, time=T)
+    spikes = two_input(g)
+    net.run({"X": T_(spikes)}, time=run_time(T, dt))
     np.testing.assert_array_equal(mon.get("s").numpy().reshape(T, B, N).astype(u8), unpack(g["sY"], (T, B, N)))
     np.testing.assert_allclose(conn.w.detach().numpy(), g["W"], rtol=0, atol=1e-5)
     np.testing.assert_allclose(net.layers["Y"].v.numpy(), g["vY"], rtol=0, atol=1e-4)
@@ -111,14 +122,23 @@ def test_external_currents_and_one_step_clamp_on_the_host():
 def test_mstdp_on_the_host_matches_reference():
     """Input -> Connection(MSTDP) -> LIF (the cfg5 graph, small): rasters and the rule's traces identical to the reference,
     weights within the dense family's tolerance (MKL propagation)."""
+    _two_layer_mstdp("run_two_mstdp_b4")
+
+
+def test_two_layer_mstdp_on_the_host_at_dt05_matches_reference():
+    """The same graph at dt = 0.5: P+ / P- decay by exp(-dt / tc)."""
+    _two_layer_mstdp("run_two_mstdp_b4_dt05")
+
+
+def _two_layer_mstdp(name):
     from bindsnet_amd.learning import MSTDP
     from bindsnet_amd.network import Network
     from bindsnet_amd.network.monitors import Monitor
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import Connection
-    g = gold("run_two_mstdp_b4")
-    Nin, N, B, T = int(g["Nin"]), int(g["N"]), int(g["B"]), int(g["T"])
-    net = Network(dt=1.0)
+    g = gold(name)
+    Nin, N, B, T, dt = int(g["Nin"]), int(g["N"]), int(g["B"]), int(g["T"]), two_dt(g)
+    net = Network(dt=dt)
     net.add_layer(Input(n=Nin, traces=True), "X")
     net.add_layer(LIFNodes(n=N, traces=True), "Y")
     conn = Connection(net.layers["X"], net.layers["Y"], w=T_(synth.weights_q12(11, Nin, N)).clone(), wmin=0, wmax=1, update_rule=MSTDP,
@@ -126,8 +146,8 @@ def test_mstdp_on_the_host_matches_reference():
     net.add_connection(conn, "X", "Y")
     mon = Monitor(net.layers["Y"], ["s"], time=T)
     net.add_monitor(mon, "Y_s")
-    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.12)
-    net.run({"X": T_(spikes)}, time=T, reward=1.0)
+    spikes = two_input(g)
+    net.run({"X": T_(spikes)}, time=run_time(T, dt), reward=1.0)
     assert net.last_plan == "host-torch"
     np.testing.assert_array_equal(mon.get("s").numpy().reshape(T, B, N).astype(u8), unpack(g["sY"], (T, B, N)))
     np.testing.assert_allclose(conn.w.detach().numpy(), g["W"], rtol=0, atol=1e-5)
@@ -211,15 +231,50 @@ def test_mcc_mstdp_on_the_host_matches_reference(name):
 def test_mcc_mstdpet_on_the_host_matches_reference():
     """MCC_learning.MSTDPET (batch 1): two runs with different reward / a_plus, layers reset in between, the rule's state
     kept -- everything bit for bit against the reference fixture."""
+    _mcc_mstdpet("run_two_mcc_mstdpet_b1")
+
+
+def test_mcc_mstdpet_on_the_host_at_dt05_matches_reference():
+    """The same at dt = 0.5: `nu * dt * reward` and exp(-dt / tc) of the eligibility trace."""
+    _mcc_mstdpet("run_two_mcc_mstdpet_b1_dt05")
+
+
+def test_mcc_postpre_on_the_host_at_dt03_matches_reference():
+    """Input -> MulticompartmentConnection[Weight, MCC PostPre] -> LIF at dt = 0.3: the rule's `update * dt` with a dt that is no power of
+    two, a refractory period of 17 steps that ends on accumulated f32 subtractions of 0.3 -- everything bit for bit."""
+    from bindsnet_amd.learning.MCC_learning import PostPre
+    from bindsnet_amd.network import Network
+    from bindsnet_amd.network.monitors import Monitor
+    from bindsnet_amd.network.nodes import Input, LIFNodes
+    from bindsnet_amd.network.topology import MulticompartmentConnection
+    from bindsnet_amd.network.topology_features import Weight
+    g = gold("run_two_mcc_postpre_b4_dt03")
+    Nin, N, B, T, dt = int(g["Nin"]), int(g["N"]), int(g["B"]), int(g["T"]), two_dt(g)
+    net = Network(dt=dt)
+    X_, Y_ = Input(n=Nin, traces=True), LIFNodes(n=N, traces=True)
+    feat = Weight("weight", T_(synth.weights_q12(11, Nin, N)), range=[0.0, 1.0], norm=78.4 * Nin / 784, nu=(1e-4, 1e-2), learning_rule=PostPre)
+    conn = MulticompartmentConnection(X_, Y_, device="cpu", pipeline=[feat])
+    net.add_layer(X_, "X"); net.add_layer(Y_, "Y")
+    net.add_connection(conn, "X", "Y")
+    mon = Monitor(Y_, ["s"], time=T)
+    net.add_monitor(mon, "Y_s")
+    net.run({"X": T_(two_input(g))}, time=run_time(T, dt))
+    assert net.last_plan == "host-torch"
+    np.testing.assert_array_equal(mon.get("s").numpy().reshape(T, B, N).astype(u8), unpack(g["sY"], (T, B, N)))
+    for got, key in ((feat.value, "W"), (Y_.v, "vY"), (Y_.x, "xY"), (X_.x, "xX"), (Y_.refrac_count, "rY")):
+        np.testing.assert_array_equal(bits(got.detach().numpy()), bits(g[key]), err_msg=key)
+
+
+def _mcc_mstdpet(name):
     from bindsnet_amd.learning.MCC_learning import MSTDPET
     from bindsnet_amd.network import Network
     from bindsnet_amd.network.monitors import Monitor
     from bindsnet_amd.network.nodes import Input, LIFNodes
     from bindsnet_amd.network.topology import MulticompartmentConnection
     from bindsnet_amd.network.topology_features import Weight
-    g = gold("run_two_mcc_mstdpet_b1")
-    Nin, N, T = int(g["Nin"]), int(g["N"]), int(g["T"])
-    net = Network(dt=1.0)
+    g = gold(name)
+    Nin, N, T, dt = int(g["Nin"]), int(g["N"]), int(g["T"]), two_dt(g)
+    net = Network(dt=dt)
     X_, Y_ = Input(n=Nin, traces=True), LIFNodes(n=N, traces=True)
     feat = Weight("weight", T_(synth.weights_q12(11, Nin, N)), range=[0.0, 1.0], norm=0.1 * Nin, nu=(1e-1, 1e-1), learning_rule=MSTDPET)
     conn = MulticompartmentConnection(X_, Y_, device="cpu", pipeline=[feat], tc_e_trace=25.0)
@@ -229,8 +284,8 @@ def test_mcc_mstdpet_on_the_host_matches_reference():
     net.add_monitor(mon, "Y_s")
     rule = feat.learning_rule
     for r in range(2):
-        spikes = synth.spike_train(30 + r, T, 1, Nin, active=0.3, max_rate=0.12)
-        net.run({"X": T_(spikes)}, time=T, reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
+        spikes = two_input(g, 30 + r)
+        net.run({"X": T_(spikes)}, time=run_time(T, dt), reward=0.8 if r == 0 else -0.5, a_plus=1.0 if r == 0 else 0.75)
         np.testing.assert_array_equal(mon.get("s").numpy().reshape(T, 1, N).astype(u8), unpack(g[f"r{r}_sY"], (T, 1, N)))
         for got, key in ((feat.value, "W"), (Y_.v, "vY"), (rule.p_plus, "p_plus"), (rule.p_minus, "p_minus"), (rule.eligibility, "elig"),
                          (rule.eligibility_trace, "e_trace")):
@@ -609,3 +664,24 @@ def test_encoder_thread_cap_is_reentrant_and_skips_worker_threads():
         assert torch.get_num_threads() == 8 and E._cap_depth == 0
     finally:
         torch.set_num_threads(n0)
+
+
+@pytest.mark.parametrize("dt", [1.0, 0.5, 0.3])
+def test_monitor_records_hold_int_time_over_dt_steps_and_agree_with_each_other(dt):
+    """A Monitor(time=T) and a growing NetworkMonitor over one run with injects_v (an in-place `v += inject` every step): both hold
+    int(time / dt) steps and the same voltages -- the NetworkMonitor's first record is a copy, not a view of the layer's state."""
+    from bindsnet_amd.models import TwoLayerNetwork
+    from bindsnet_amd.network.monitors import Monitor, NetworkMonitor
+    Nin, N, B, T = 196, 48, 3, 31                      # (31 * 0.3 / 0.3 falls short of 31: run_time adds the half step)
+    time = run_time(T, dt)
+    torch.manual_seed(0)
+    net = TwoLayerNetwork(n_inpt=Nin, n_neurons=N, dt=dt, reduction=torch.sum, norm=78.4 * Nin / 784)
+    mon = Monitor(net.layers["Y"], ["s", "v"], time=T)
+    nm = NetworkMonitor(net, layers=["Y"], connections=[], state_vars=["s", "v"])
+    net.add_monitor(mon, "Y"); net.add_monitor(nm, "all")
+    spikes = synth.spike_train(30, T, B, Nin, active=0.3, max_rate=0.3)
+    net.run({"X": T_(spikes)}, time=time, injects_v={"Y": torch.full((N,), 0.3)})
+    rec = nm.get()["Y"]
+    assert mon.get("s").shape[0] == mon.get("v").shape[0] == rec["s"].shape[0] == rec["v"].shape[0] == int(time / dt) == T
+    np.testing.assert_array_equal(bits(rec["v"].numpy().reshape(-1)), bits(mon.get("v").numpy().reshape(-1)))
+    assert mon.get("s").sum() > 0

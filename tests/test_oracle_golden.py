@@ -240,11 +240,26 @@ def test_increasing_inhibition_network_run_matches_reference():
         np.testing.assert_array_equal(bits(st["theta"]), bits(g[f"r{r}_theta"]))
 
 
+def two_dt(g):
+    """The timestep of a two-layer fixture (the dt = 1 fixtures carry no key for it)."""
+    return float(g["dt"]) if "dt" in g.files else 1.0
+
+
+def two_input(g, seed=30, B=None):
+    """Input of a two-layer fixture: synth.spike_train at the fixture's shape and, for the dt != 1 repeats, their own max_rate."""
+    max_rate = float(g["max_rate"]) if "max_rate" in g.files else 0.12
+    return synth.spike_train(seed, int(g["T"]), int(g["B"]) if B is None else B, int(g["Nin"]), active=0.3, max_rate=max_rate)
+
+
+DENSE_TWO = [("run_two_postpre_b4", "postpre"), ("run_two_postpre_b32", "postpre"), ("run_two_mstdp_b4", "mstdp"),
+             ("run_two_postpre_b4_dt05", "postpre"), ("run_two_mstdp_b4_dt05", "mstdp")]
+
+
 def two_params(g, rule):
     P = oracle.TwoParams()
     P.B, P.Nin, P.N, P.T = int(g["B"]), int(g["Nin"]), int(g["N"]), int(g["T"])
     P.rule = 1 if rule == "postpre" else 2
-    P.dt = 1.0
+    P.dt = two_dt(g)
     P.x_trace_decay = float(g["x_trace_decay"]); P.x_trace_scale = 1.0; P.x_traces = 1
     P.decay = float(g["decay"]); P.rest, P.reset, P.thresh, P.refrac = -65.0, -65.0, -52.0, 5.0
     P.y_traces = 1; P.y_trace_decay = float(g["y_trace_decay"]); P.y_trace_scale = 1.0
@@ -271,12 +286,11 @@ def two_state(P):
     return st
 
 
-@pytest.mark.parametrize("name,rule", [("run_two_postpre_b4", "postpre"), ("run_two_postpre_b32", "postpre"),
-                                       ("run_two_mstdp_b4", "mstdp")])
+@pytest.mark.parametrize("name,rule", DENSE_TWO)
 def test_dense_family_run_matches_reference(name, rule):
     g = gold(name)
     P = two_params(g, rule)
-    spikes = synth.spike_train(30, P.T, P.B, P.Nin, active=0.3, max_rate=0.12)
+    spikes = two_input(g)
     # (1) teacher-forced with the reference's own MKL currents: everything else bit-exact
     st = two_state(P)
     ras = oracle.run_two_layer(P, st, spikes, I_forced=np.ascontiguousarray(g["I_forced"]))
@@ -295,18 +309,32 @@ def test_dense_family_run_matches_reference(name, rule):
 
 
 # --------------------------------------------------------------------------- MCC MSTDP
-def mcc_mstdp_params(g):
+def mcc_two_params(g):
+    """What every MulticompartmentConnection two-layer fixture shares: shape, dt, the layers' constants and decays, the weight bounds."""
     P = oracle.TwoParams()
     P.B, P.Nin, P.N, P.T = int(g["B"]), int(g["Nin"]), int(g["N"]), int(g["T"])
-    P.rule, P.mcc, P.dt = 2, 1, 1.0
+    P.mcc, P.dt = 1, two_dt(g)
     P.x_trace_decay = float(g["x_trace_decay"]); P.x_trace_scale = 1.0; P.x_traces = 1
     P.decay = float(g["decay"]); P.rest, P.reset, P.thresh, P.refrac = -65.0, -65.0, -52.0, 5.0
     P.y_traces = 1; P.y_trace_decay = float(g["y_trace_decay"]); P.y_trace_scale = 1.0
-    P.has_min = P.has_max = 1; P.wmin, P.wmax = 0.0, 1.0; P.has_norm = 1; P.norm = 0.1 * P.Nin
+    P.has_min = P.has_max = 1; P.wmin, P.wmax = 0.0, 1.0; P.has_norm = 1
+    P.learning = 1
+    return P
+
+
+def mcc_mstdp_params(g):
+    P = mcc_two_params(g)
+    P.rule, P.norm = 2, 0.1 * P.Nin
     P.nu0 = P.nu1 = 1e-1
     P.a_plus, P.a_minus = 1.0, -1.0
     P.decay_plus, P.decay_minus = float(g["decay_plus"]), float(g["decay_minus"])
-    P.learning = 1
+    return P
+
+
+def mcc_postpre_params(g):
+    """The MCC PostPre two-layer fixture (run_two_mcc_postpre_b4_dt03): rule 1 with the connection's `* dt`."""
+    P = mcc_two_params(g)
+    P.rule, P.nu0, P.nu1, P.norm = 1, 1e-4, 1e-2, 78.4 * P.Nin / 784
     return P
 
 
@@ -333,14 +361,37 @@ def test_mcc_mstdpet_run_matches_reference():
     """Input -> MulticompartmentConnection[Weight, MCC MSTDPET] -> LIF at batch 1 (MCC_learning.py:554-733): two runs with
     different rewards / a_plus; the layers are reset in between, the rule's state is not (Weight.reset_state_variables is
     empty, topology_features.py:630-631).  Everything on this path is ATen-ordered: bit-exact."""
-    g = gold("run_two_mcc_mstdpet_b1")
+    _mcc_mstdpet_run("run_two_mcc_mstdpet_b1")
+
+
+def test_mcc_mstdpet_run_at_dt05_matches_reference():
+    """The same at dt = 0.5: the rule's `nu * dt * reward`, exp(-dt / tc) of P+ / P- / the eligibility trace, a refractory period of
+    ten steps."""
+    _mcc_mstdpet_run("run_two_mcc_mstdpet_b1_dt05")
+
+
+def test_mcc_postpre_run_at_dt03_matches_reference():
+    """Input -> MulticompartmentConnection[Weight, MCC PostPre] -> LIF at dt = 0.3 (not a power of two: `update * dt` rounds): ATen-ordered
+    throughout, so everything is bit-exact."""
+    g = gold("run_two_mcc_postpre_b4_dt03")
+    P = mcc_postpre_params(g)
+    assert abs(P.dt - 0.3) < 1e-6
+    st = two_state(P)
+    ras = oracle.run_two_layer(P, st, two_input(g))
+    np.testing.assert_array_equal(ras, unpack(g["sY"], (P.T, P.B, P.N)))
+    for key in ("W", "vY", "xY", "xX", "rY"):
+        np.testing.assert_array_equal(bits(st[key]), bits(g[key]), err_msg=key)
+
+
+def _mcc_mstdpet_run(name):
+    g = gold(name)
     P = mcc_mstdp_params(g)
     P.rule, P.decay_e, P.tc_e = 5, float(g["decay_e"]), float(g["tc_e"])
     st = two_state(P)
     Nin, N = P.Nin, P.N
     st.update(elig=np.zeros((Nin, N), f32), e_trace=np.zeros((Nin, N), f32), p_plus=np.zeros(Nin, f32), p_minus=np.zeros(N, f32))
     for r in range(2):
-        spikes = synth.spike_train(30 + r, P.T, 1, Nin, active=0.3, max_rate=0.12)
+        spikes = two_input(g, 30 + r)
         P.reward, P.a_plus = (0.8, 1.0) if r == 0 else (-0.5, 0.75)
         ras = oracle.run_two_layer(P, st, spikes)
         assert ras.sum() > 20

@@ -121,7 +121,7 @@ def test_per_neuron_update_text_reproduces_reference_fixture(host, name):
                 host.hostcheck_pv_trace(_p(xs), _p(X.x), B, PC.N_SRC, C.byref(xp), C.byref(xvec))
                 _step_layer(host, c, Y, cur, B, n)
                 if c.get("postpre"):
-                    host_path._postpre_mcc(rule, conn._weight().value.data, xs, X.x.view(B, -1), Y.s.view(B, -1), Y.x.view(B, -1), 1.0)
+                    host_path._postpre_mcc(rule, conn._weight().value.data, xs, X.x.view(B, -1), Y.s.view(B, -1), Y.x.view(B, -1), c.get("dt", 1.0))
                 raster[t] = Y.s.view(B, n).numpy().astype(np.uint8)
             snaps.append(PC.snapshot(net, name, raster))
             net.reset_state_variables()

@@ -51,7 +51,7 @@ def test_reference_names_resolve():
 def test_fixtures_decide_the_index_rule():
     """What the generator measured: in every pooling fixture at least a tenth of the window decisions picked a tap other than the
     window's first in-bounds one, and ties occurred."""
-    for name in sorted(PC.POOL) + ["h"]:
+    for name in sorted(PC.POOL) + ["h"] + sorted(PC.DT):
         g = cases.gold("pool_" + name)
         assert float(g["share_nonfirst"]) >= 0.10 and float(g["share_ties"]) > 0.0, name
 
