@@ -96,7 +96,9 @@ class LayerDesc(C.Structure):
                 ("ext_current", C.c_void_p), ("thresh_vec", C.c_void_p),
                 ("aux", C.c_void_p), ("aux_decay", C.c_float),
                 ("izh_a", C.c_void_p), ("izh_b", C.c_void_p), ("izh_c", C.c_void_p), ("izh_d", C.c_void_p),
-                ("izh_St", C.c_void_p), ("pv", PerVec)]
+                ("izh_St", C.c_void_p), ("pv", PerVec),
+                ("srm_eps0", C.c_float), ("srm_rho0", C.c_float), ("srm_dthresh", C.c_float),
+                ("srm_sprob", C.c_void_p), ("srm_rho", C.c_void_p)]
 
 
 class ConnDesc(C.Structure):
@@ -122,7 +124,7 @@ class ConnDesc(C.Structure):
                 ("sparse_ptr", C.c_void_p), ("sparse_col", C.c_void_p), ("sparse_val", C.c_void_p), ("sparse_nnz", C.c_int),
                 ("firing_rates", C.c_void_p), ("pool_c", C.c_int), ("pool_in", C.c_int * 3), ("pool_k", C.c_int * 3),
                 ("pool_stride", C.c_int * 3), ("pool_pad", C.c_int * 3), ("pool_dil", C.c_int * 3), ("pool_decay", C.c_float),
-                ("w_numel", C.c_int)]
+                ("w_numel", C.c_int), ("rmax_tc_c", C.c_float)]
 
 
 class MccOp(C.Structure):
@@ -143,7 +145,7 @@ class FillSegment(C.Structure):
 
 MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
-LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH = 3, 4, 5, 6, 7
+LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH, LAYER_SRM0 = 3, 4, 5, 6, 7, 8
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
 CONN_POOL, CONN_MEANFIELD = 6, 7
@@ -153,7 +155,7 @@ MEANFIELD_MAX = 1 << 24   # B * source.n up to which f32(count) / f32(numel) is 
 SPARSE_TJ = 256           # SNN_SPARSE_TJ: the column-tile width of SparseConnection's compiled form
 MCC_MAX_PIPE = 8          # SNN_MCC_MAX_PIPE
 MCC_OP_MUL_DRAW, MCC_OP_MUL_MASK, MCC_OP_MUL_F32, MCC_OP_ADD_F32 = 1, 2, 3, 4
-RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET = 0, 1, 2, 3, 4, 5
+RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET, RULE_RMAX = 0, 1, 2, 3, 4, 5, 6
 
 _lib = None
 
@@ -187,6 +189,9 @@ _SIGS = {
     "snn_clif_step_pv": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _f, C.POINTER(PerVec), _vp, _vp, _vp], _i),
     "snn_izh_step_pv": ([_vp] * 10 + [_i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
     "snn_dc_step_pv": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(DcParams), C.POINTER(PerVec), _vp, _ll, _vp, _vp, _vp, _vp, _vp], _i),
+    "snn_srm0_step_pv": ([_vp] * 8 + [_i, _i, C.POINTER(LifParams), _f, _f, _f, C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_srm0_step": ([_vp] * 8 + [_i, _i, C.POINTER(LifParams), _f, _f, _f, _vp, _vp, _vp], _i),
+    "snn_rmax_step": ([_vp] * 5 + [_i, _i] + [_f] * 6 + [_i, _f, _i, _f, _vp], _i),
     "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_boosted_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),

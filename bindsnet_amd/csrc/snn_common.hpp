@@ -170,6 +170,70 @@ __host__ __device__ __forceinline__ uint8_t izh_update(float &v, float &u, uint8
     return izh_update(v, u, s_in, cur, a, b, c, d, p, p.thresh);
 }
 
+// SRM0Nodes.forward, bindsnet/network/nodes.py:1647-1669.  `u`: this element's uniform draw (:1661 torch.rand_like, one 32-bit
+// generator output: srm0_uniform).  `ex`: the exponential -- expf on the device, the host's in tests/hostcheck/srm0_host.hip;
+// everything else is this text.  rho and s_prob are the layer's attributes of the same names (rho is taken BEFORE the reset).
+__host__ __device__ __forceinline__ float srm0_uniform(uint32_t tempered) {
+    return (float)(tempered & 0xFFFFFFu) * 5.9604644775390625e-08f;       // (r & (2^24 - 1)) * 2^-24, exact in f32
+}
+template <class EXP>
+__host__ __device__ __forceinline__ uint8_t srm0_update(float &v, float &rc, float cur, float u, float &s_prob, float &rho,
+                                                        const snn_lif_params &p, float thresh, float decay, float eps_0,
+                                                        float rho_0, float d_thresh, EXP ex) {
+    float vv = v - p.rest;              // :1647  decay * (v - rest) + rest, three roundings
+    vv = decay * vv;
+    vv = vv + p.rest;
+    const float gate = (rc <= 0.f) ? 1.0f : 0.0f;            // :1650 ((refrac_count <= 0).float() * eps_0) * x
+    const float ge = gate * eps_0;
+    const float gx = ge * cur;
+    vv = vv + gx;
+    float a = vv - thresh;              // :1654 rho_0 * exp((v - thresh) / d_thresh)
+    a = a / d_thresh;
+    const float r = rho_0 * ex(a);
+    float b = -r;                       // :1655 1.0 - exp(-rho * dt)
+    b = b * p.dt;
+    const float sp_ = 1.0f - ex(b);
+    rho = r; s_prob = sp_;
+    rc = rc - p.dt;                     // :1658
+    const uint8_t sp = u < sp_;         // :1661
+    if (sp) { rc = p.refrac; vv = p.reset; }                 // :1664-1665
+    if (p.has_lbound && vv < p.lbound) vv = p.lbound;        // :1668-1669
+    v = vv;
+    return sp;
+}
+
+// Rmax._connection_update, bindsnet/learning/learning.py:2948-2958 (+ LearningRule.update :87-104), batch 1.
+// rmax_term: the per-target factor s_j - p_j / (1 + (tc_c / dt) * p_j), q = tc_c / dt.  rmax_update: one synapse --
+// e = e * k + term_j * x_i (k = 1 - dt / tc_e_trace), w += (nu0 * reward) * e, w *= wdecay, clamp.
+struct rmax_consts { float k, q, scale; };
+__host__ __device__ __forceinline__ rmax_consts rmax_constants(float reward, float nu0, float dt, float tc_c, float tc_e) {
+    rmax_consts c;
+    c.k = dt / tc_e;                    // :2948  1 - dt / tc_e_trace: a Python float over a 0-dim f32 tensor, evaluated in f32
+    c.k = 1.0f - c.k;
+    c.q = tc_c / dt;                    // :2951
+    c.scale = nu0 * reward;             // :2955  (nu[0] * reward) * eligibility_trace
+    return c;
+}
+__host__ __device__ __forceinline__ float rmax_term(uint8_t s, float p, float q) {
+    float d = q * p;
+    d = 1.0f + d;
+    d = p / d;
+    return (float)s - d;
+}
+__host__ __device__ __forceinline__ void rmax_update(float &w, float &e, float term, float x, float k, float scale, float wdecay,
+                                                     int has_min, float wmin, int has_max, float wmax) {
+    float ee = e * k;                   // :2948
+    const float tx = term * x;          // :2949-2952
+    ee = ee + tx;
+    e = ee;
+    const float up = scale * ee;        // :2955
+    float ww = w + up;                  // :2958
+    ww = ww * wdecay;                   // :93-94
+    if (has_min && ww < wmin) ww = wmin;                     // :104
+    if (has_max && ww > wmax) ww = wmax;
+    w = ww;
+}
+
 // One neuron's seven parameters: the scalars of the layer's parameter block, or -- PV, the instance a launch with vectors selects --
 // row j of whichever snn_pervec vectors are given.  The scalar instance reads no pointer and indexes nothing.
 struct node_row { float thresh, decay, trace_decay, trace_scale, theta_decay, theta_plus, i_decay; };

@@ -120,6 +120,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 case SNN_LAYER_DC: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvTheta; break;
                 case SNN_LAYER_MCP: case SNN_LAYER_IF: case SNN_LAYER_IZH: allowed = snn::kPvTrace | snn::kPvThresh; break;
                 case SNN_LAYER_CURRENT: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvIDecay; break;
+                case SNN_LAYER_SRM0: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay; break;
                 default: return SNN_ERR_INVALID;
             }
             const snn_pervec pv = layer_pervec(d);
@@ -127,7 +128,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if ((pv.v[SNN_PV_TRACE_DECAY] || pv.v[SNN_PV_TRACE_SCALE]) && !d.p.lif.traces) return SNN_ERR_INVALID;
             if (pv.v[SNN_PV_TRACE_SCALE] && !d.p.lif.traces_additive) return SNN_ERR_INVALID;   // (masked_fill_ takes a 0-dim value)
             // (the per-neuron instances put the sample into the grid's second dimension; an LIF layer with thresh_vec alone keeps snn_lif_step_vth)
-            if (R->B > 65535 && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
+            if (R->B > 65535 && d.kind != SNN_LAYER_SRM0 && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
         }
         switch (d.kind) {
             case SNN_LAYER_INPUT:
@@ -147,6 +148,11 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             case SNN_LAYER_IZH:               // nodes.py:1147: u in aux, a .. d and the transposed lateral matrix
                 if (!d.aux || !d.izh_a || !d.izh_b || !d.izh_c || !d.izh_d || !d.izh_St) return SNN_ERR_INVALID;
                 if (d.n > SNN_IZH_MAX_N) return SNN_ERR_UNSUPPORTED;
+                if (!d.v || !d.s || !d.current) return SNN_ERR_INVALID;
+                if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
+                break;
+            case SNN_LAYER_SRM0:              // nodes.py:1555: draws from the run's generator; s_prob and rho are outputs
+                if (!R->rng || !d.srm_sprob || !d.srm_rho || !d.refrac) return SNN_ERR_INVALID;
                 if (!d.v || !d.s || !d.current) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
                 break;
@@ -188,7 +194,12 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_MSTDP || d.rule == SNN_RULE_MSTDPET) && !conv_mstdp && (!d.p_plus || !d.p_minus || !d.s_src_prev || !d.s_tgt_prev)) return SNN_ERR_INVALID;
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
-        if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_MSTDPET) return SNN_ERR_INVALID;
+        if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_RMAX) return SNN_ERR_INVALID;
+        if (d.rule == SNN_RULE_RMAX) {         // learning.py:2858-2960: a dense matrix into an SRM0 layer, additive source traces, batch 1
+            if (d.kind != SNN_CONN_DENSE) return SNN_ERR_UNSUPPORTED;
+            if (L[d.dst].kind != SNN_LAYER_SRM0 || !L[d.src].x || !L[d.src].p.lif.traces_additive || !d.e_trace) return SNN_ERR_INVALID;
+            if (R->B != 1) return SNN_ERR_UNSUPPORTED;
+        }
         if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_MEANFIELD) return SNN_ERR_INVALID;
         if (d.kind == SNN_CONN_POOL || d.kind == SNN_CONN_MEANFIELD) {     // MaxPoolNdConnection / MeanFieldConnection: propagation only (NoOp)
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
@@ -324,6 +335,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step_pv(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, pv, rs, rv, st));
             else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step_pv(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
                                                                  &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_SRM0) TRY(snn_srm0_step_pv(R->rng, d.v, d.refrac, d.s, d.x, d.current, d.srm_sprob, d.srm_rho, B, d.n, &d.p.lif,
+                                                                   d.srm_eps0, d.srm_rho0, d.srm_dthresh, pv, rs, rv, st));
             else if (R->rng && d.p.one_spike) {   // device generator: membrane -> draws for this step -> arbitration
                 TRY(snn_launch_dc_membrane(d.v, d.refrac, d.s, d.theta, d.current, B, d.n, d.p, R->cursor, rv, st, pv));
                 TRY(snn_launch_rng_fill(R->rng, d.s, B, d.n, R->qbuf, R->cursor, st));
@@ -367,6 +380,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE)
                     TRY(snn_stdp_hebbian(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
                                          d.has_min, d.wmin, d.has_max, d.wmax, st));
+                else if (d.rule == SNN_RULE_RMAX)
+                    TRY(snn_rmax_step(d.w, d.e_trace, D.s, D.srm_sprob, S.x, S.n, D.n, d.reward, d.nu0, R->dt, d.rmax_tc_c, d.tc_e, d.wdecay,
+                                      d.has_min, d.wmin, d.has_max, d.wmax, st));
                 else if (d.rule == SNN_RULE_MSTDPET)
                     TRY(snn_mstdpet_step(d.w, d.e_trace, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, S.n, D.n, d.reward,
                                          d.nu0, R->dt, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.decay_e, d.tc_e, d.wdecay,
@@ -448,7 +464,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (has_pervec(L[l])) mode = 1;     // per-neuron parameters: generic plan
-    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes: generic plan only
+    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection) plan only; no fused plan is offered the graph

@@ -1,6 +1,6 @@
 """Learning rules for dense `Connection`s: API mirror of bindsnet/learning/learning.py for `LearningRule`, `NoOp`,
-`PostPre`, `WeightDependentPostPre`, `Hebbian`, `MSTDP`, `MSTDPET`.  Updates run in snn_stdp_postpre /
-snn_stdp_hebbian / snn_mstdp_step / snn_mstdpet_step (on a Conv2dConnection: snn_conv2d_postpre / snn_conv2d_hebbian /
+`PostPre`, `WeightDependentPostPre`, `Hebbian`, `MSTDP`, `MSTDPET`, `Rmax`.  Updates run in snn_stdp_postpre /
+snn_stdp_hebbian / snn_mstdp_step / snn_mstdpet_step / snn_rmax_step (on a Conv2dConnection: snn_conv2d_postpre / snn_conv2d_hebbian /
 snn_conv2d_mstdp_step)."""
 import warnings
 from typing import Optional, Sequence, Union
@@ -292,3 +292,71 @@ class MSTDPET(LearningRule):
                          float(self.nu[0]), float(self.connection.dt), float(kwargs.get("a_plus", 1.0)),
                          float(kwargs.get("a_minus", -1.0)), dp, dm, de, float(self.tc_e_trace),
                          wdecay=float(self.weight_decay), wmin=lo, wmax=hi)
+
+
+class Rmax(LearningRule):
+    """Reward-modulated rule derived from reward maximisation for stochastically firing neurons (reference: learning.py:2858-2960).
+    Defined for `Connection` and `LocalConnection` into an `SRM0Nodes` layer, from a source with additive traces, at batch size
+    1 (the reference flattens the target's state with `view(-1)`).  `eligibility_trace` is the rule's dense [source.n, target.n]
+    state, created on first use."""
+
+    _rule_code = _lib.RULE_RMAX
+    _B1 = ("Rmax is defined for batch size 1 (learning.py:2940-2942: `target_s = self.target.s.view(-1).float()`, "
+           "`target_s_prob = self.target.s_prob.view(-1)`, `source_x = self.source.x.view(-1)`)")
+
+    def __init__(self, connection, nu=None, reduction=None, weight_decay: float = 0.0, **kwargs) -> None:
+        if not _descriptor.accepts(connection, self) and not getattr(connection, "_rules_only", None):
+            # (a family without the dense connections' attributes -- MulticompartmentConnection -- cannot reach the base constructor)
+            raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
+        from ..network.nodes import SRM0Nodes
+        assert self.source.traces and self.source.traces_additive, "Pre-synaptic nodes must use additive spike traces."
+        assert isinstance(self.target, SRM0Nodes), "R-max needs stochastically firing neurons, use SRM0Nodes."
+        self._require_accepted()
+        self.tc_c = torch.tensor(kwargs.get("tc_c", 5.0))
+        self.tc_e_trace = torch.tensor(kwargs.get("tc_e_trace", 25.0))
+
+    def _batch_refusal(self, B: int):
+        """What Network.run asks before the run changes any state."""
+        return NotImplementedError(self._B1) if B != 1 else None
+
+    def _ensure_state(self) -> None:
+        w = self.connection.w
+        t = self.__dict__.get("eligibility_trace")
+        if t is None:
+            self.eligibility_trace = torch.zeros(*w.shape, device=w.device)
+        elif t.device != w.device:
+            self.eligibility_trace = t.to(w.device)
+
+    @staticmethod
+    def _reward(kwargs) -> float:
+        r = _descriptor.reward(kwargs)
+        if isinstance(r, torch.Tensor):
+            if r.numel() != 1:
+                raise NotImplementedError("bindsnet_amd: Rmax takes a scalar reward (the rule is defined for batch size 1)")
+            return float(r.reshape(()).item())
+        if not isinstance(r, (int, float)):
+            raise NotImplementedError(f"bindsnet_amd: Rmax takes a scalar reward, got {type(r).__name__}")
+        return float(r)
+
+    def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
+        if B != 1:
+            raise NotImplementedError(self._B1)
+        reward = self._reward(kwargs)
+        self._ensure_state()
+        _descriptor.fill_update(d, self, self.weight_decay)
+        d.rule, d.reward = self._rule_code, reward
+        d.tc_e, d.rmax_tc_c = float(self.tc_e_trace), float(self.tc_c)
+        d.e_trace = _lib.dptr(self.eligibility_trace)
+
+    def update(self, **kwargs) -> None:
+        from .. import ops
+        if self.source.batch_size != 1:
+            raise NotImplementedError(self._B1)
+        reward = self._reward(kwargs)
+        self._ensure_state()
+        lo, hi = self._bounds()
+        c = self.connection
+        ops.rmax_step(c.w.data.view(self.source.n, self.target.n), self.eligibility_trace, self.target.s.reshape(-1).contiguous(),
+                      self.target.s_prob.reshape(-1), self.source.x.reshape(-1), reward, float(self.nu[0]), float(c.dt),
+                      float(self.tc_c), float(self.tc_e_trace), wdecay=float(self.weight_decay), wmin=lo, wmax=hi)

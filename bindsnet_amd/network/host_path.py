@@ -5,8 +5,8 @@ package still constructs and runs where there is no GPU (SURVEY.md 8(b) fallback
 second, independent statement of the same semantics: tests/test_host_path.py pins it to the reference-generated fixtures
 the GPU tests use.  It is selected by Network.run only when the network's tensors are CPU tensors; it never touches
 libsnnhip and has nothing to do with oracle/ (test infrastructure).  Supported on this path: Input / LIFNodes /
-DiehlAndCookNodes / AdaptiveLIFNodes / McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
-rule / PostPre / MSTDP / Hebbian / WeightDependentPostPre / MSTDPET), Conv2dConnection (no rule / PostPre / MSTDP at batch 1);
+DiehlAndCookNodes / AdaptiveLIFNodes / McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes / SRM0Nodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
+rule / PostPre / MSTDP / Hebbian / WeightDependentPostPre / MSTDPET / Rmax), Conv2dConnection (no rule / PostPre / MSTDP at batch 1);
 clamp / unclamp / injects_v / masks / one_step / reward; Monitor / NetworkMonitor.
 
 What each function states (paths inside BindsNET): network.py:211-250,380-465 (loop, `zeros + c1 + c2` accumulation,
@@ -181,6 +181,21 @@ def _step_izh(layer, x) -> None:
     if layer.lbound is not None:
         layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
     layer.s = layer.v >= layer.thresh
+    _trace(layer, layer.s)
+
+
+def _step_srm0(layer, x) -> None:
+    """nodes.py:1639-1671, the reference's statements in its order; the draw is torch.rand_like on the global generator."""
+    layer.v = layer.decay * (layer.v - layer.rest) + layer.rest
+    layer.v += (layer.refrac_count <= 0).float() * layer.eps_0 * x
+    layer.rho = layer.rho_0 * torch.exp((layer.v - layer.thresh) / layer.d_thresh)
+    layer.s_prob = 1.0 - torch.exp(-layer.rho * layer.dt)
+    layer.refrac_count -= layer.dt
+    layer.s = torch.rand_like(layer.s_prob) < layer.s_prob
+    layer.refrac_count.masked_fill_(layer.s, layer.refrac)
+    layer.v.masked_fill_(layer.s, layer.reset)
+    if layer.lbound is not None:
+        layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
     _trace(layer, layer.s)
 
 
@@ -391,6 +406,21 @@ def _mstdpet(rule, W, dt, src_s, tgt_s, kwargs) -> None:
     _advance_p(rule, dp, dm, src_s, tgt_s, kwargs)
 
 
+def _rmax(rule, W, dt, kwargs) -> None:
+    """learning.py:2923-2958 (batch 1), the reference's statements in its order."""
+    if rule.source.batch_size != 1:
+        raise NotImplementedError(rule._B1)
+    rule._reward(kwargs)                               # (a reward the rule does not take raises before anything changes)
+    rule._ensure_state()
+    target_s = rule.target.s.view(-1).float()
+    target_s_prob = rule.target.s_prob.view(-1)
+    source_x = rule.source.x.view(-1)
+    reward = kwargs["reward"]
+    rule.eligibility_trace *= 1 - dt / rule.tc_e_trace
+    rule.eligibility_trace += (target_s - (target_s_prob / (1.0 + rule.tc_c / dt * target_s_prob))) * source_x[:, None]
+    W += rule.nu[0] * reward * rule.eligibility_trace
+
+
 def _conv_postpre(conn, rule) -> None:
     """learning.py:457-497: im2col of the source's spikes / traces, one bmm per term, reduced over the batch."""
     from ..utils import im2col_indices
@@ -540,6 +570,8 @@ def _update_dense(conn, kwargs, mask) -> None:
     nu0, nu1 = float(rule.nu[0]), float(rule.nu[1])
     if isinstance(rule, rules.MSTDPET):
         _mstdpet(rule, W, conn.dt, conn.source.s.view(-1).float(), conn.target.s.view(-1).float(), kwargs)
+    elif isinstance(rule, rules.Rmax):
+        _rmax(rule, W, conn.dt, kwargs)
     else:
         rule._check_reduction()
         src_s, tgt_s = conn.source.s.view(B, -1).float(), conn.target.s.view(B, -1).float()

@@ -329,6 +329,12 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             err = conn._batch_refusal(B) if hasattr(conn, "_batch_refusal") else None
             if err is not None:
                 raise err
+        if self.learning and T > 0:
+            for conn in self.connections.values():         # ... nor its rule (Rmax is defined for batch size 1)
+                rule = conn._rule() if hasattr(conn, "_rule") else None
+                err = rule._batch_refusal(B) if hasattr(rule, "_batch_refusal") else None
+                if err is not None:
+                    raise err
         dev = self._device()
         if dev.type != "cuda":
             # A network whose tensors live on the host: the plain-PyTorch step loop with the reference's semantics
@@ -538,7 +544,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
+            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
                 t = getattr(layer, attr, None)
                 if isinstance(t, torch.Tensor):
                     ptrs.append((layer, attr, t.data_ptr()))

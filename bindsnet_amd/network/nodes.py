@@ -1,7 +1,7 @@
 """Neuron groups: API mirror of bindsnet/network/nodes.py for the layer types on the hot path
 (`Nodes`, `Input`, `McCullochPitts`, `IFNodes`, `LIFNodes`, `BoostedLIFNodes`, `CurrentLIFNodes`, `AdaptiveLIFNodes`,
-`DiehlAndCookNodes`, `IzhikevichNodes`); the arithmetic lives in libsnnhip (snn_input_step / snn_lif_step / snn_dc_step /
-snn_mcp_step / snn_if_step / snn_boosted_step / snn_clif_step / snn_izh_step).  Each class fills its own snn_layer_desc
+`DiehlAndCookNodes`, `IzhikevichNodes`, `SRM0Nodes`); the arithmetic lives in libsnnhip (snn_input_step / snn_lif_step / snn_dc_step /
+snn_mcp_step / snn_if_step / snn_boosted_step / snn_clif_step / snn_izh_step / snn_srm0_step).  Each class fills its own snn_layer_desc
 (`_describe`), so Network._build_descriptors needs no table of layer types.
 
 State is held in the same attributes as the reference (`s`, `x`, `v`, `refrac_count`, `theta`,
@@ -182,7 +182,7 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         the layer may consume."""
         raise NotImplementedError(f"bindsnet_amd: layer type {type(self).__name__} is outside the accelerated path (Input, "
                                   "McCullochPitts, IFNodes, LIFNodes, BoostedLIFNodes, CurrentLIFNodes, AdaptiveLIFNodes, "
-                                  "DiehlAndCookNodes, IzhikevichNodes)")
+                                  "DiehlAndCookNodes, IzhikevichNodes, SRM0Nodes)")
 
     def _host_step(self, x: torch.Tensor) -> None:
         """One step on the host path (network/host_path.py)."""
@@ -725,3 +725,94 @@ class IzhikevichNodes(Nodes):
         pv = {}
         p = self._node_params(pv)
         ops.izh_step(self.v, self.u, self.s, self.x if self.traces else None, x, a, b, c, d, self._St(), p, pv=pv)
+
+
+class SRM0Nodes(Nodes):
+    """Simplified spike response model neurons with a stochastic threshold -- escape noise (reference: nodes.py:1555-1701).  Each
+    step draws one uniform number per neuron and sample from torch's GLOBAL CPU generator (`torch.rand_like(s_prob) < s_prob`);
+    on the device the step kernel (snn_srm0_step) consumes that generator's stream in the same positions (rng.DeviceGenerator),
+    so the spikes are the reference's.  `rho` and `s_prob` are attributes after a step, as in the reference; on the device the
+    kernel writes both (`rho` is taken from the voltage before the reset, so it cannot be recomputed from `v`).  The two
+    exponentials are the device's expf, a 1-ulp function like torch's own: `rho` and `s_prob` agree with the reference to a few
+    ulp, everything else bit for bit whenever the spikes do."""
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay")
+    _SCALAR_ONLY = ("eps_0", "rho_0", "d_thresh", "rest", "reset")      # refused as tensors on the device, by name
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, thresh: Scalar = -50.0, rest: Scalar = -70.0, reset: Scalar = -70.0,
+                 refrac: Union[int, torch.Tensor] = 5, tc_decay: Scalar = 10.0, lbound: float = None, eps_0: Scalar = 1.0,
+                 rho_0: Scalar = 1.0, d_thresh: Scalar = 5.0, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("rest", _buf(rest))
+        self.register_buffer("reset", _buf(reset))
+        self.register_buffer("thresh", _buf(thresh))
+        self.register_buffer("refrac", _buf(refrac))
+        self.register_buffer("tc_decay", _buf(tc_decay))
+        self.register_buffer("decay", _buf(tc_decay))      # (set in compute_decays, as in the reference)
+        self.register_buffer("eps_0", _buf(eps_0))
+        self.register_buffer("rho_0", _buf(rho_0))
+        self.register_buffer("d_thresh", _buf(d_thresh))
+        self.register_buffer("v", torch.FloatTensor())
+        self.register_buffer("refrac_count", torch.FloatTensor())
+        self.lbound = lbound
+
+    def compute_decays(self, dt) -> None:
+        super().compute_decays(dt=dt)
+        self.decay = torch.exp(-self.dt / self.tc_decay.cpu()).to(self.tc_decay.device)
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        dev = self.v.device
+        self.v = self.rest.to(dev) * torch.ones(batch_size, *self.shape, device=dev)
+        self.refrac_count = torch.zeros_like(self.v, device=self.refrac_count.device)
+
+    def reset_state_variables(self) -> None:
+        super().reset_state_variables()
+        self.v.fill_(_f(self.rest))
+        self.refrac_count.zero_()
+
+    def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
+        for name in self._SCALAR_ONLY:
+            t = getattr(self, name)
+            if isinstance(t, torch.Tensor) and t.numel() != 1:
+                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on SRM0Nodes is not supported on the device")
+        return self._node_params(pv, decay=self.decay, rest=self.rest, reset=self.reset, refrac=self.refrac)
+
+    def _prob_buffers(self):
+        """`s_prob` and `rho` as the step kernel writes them: f32 tensors beside `v`, created on first use (plain attributes, as in
+        the reference)."""
+        for name in ("s_prob", "rho"):
+            t = self.__dict__.get(name)
+            if not isinstance(t, torch.Tensor) or t.shape != self.v.shape or t.device != self.v.device or t.dtype != torch.float32 \
+                    or not t.is_contiguous():
+                setattr(self, name, torch.zeros_like(self.v))
+        return self.s_prob, self.rho
+
+    def _describe(self, d, keep, scalars) -> int:
+        pv = {}
+        d.kind, d.p.lif = _lib.LAYER_SRM0, self._params(pv)
+        d.srm_eps0, d.srm_rho0, d.srm_dthresh = _f(self.eps_0), _f(self.rho_0), _f(self.d_thresh)
+        s_prob, rho = self._prob_buffers()
+        d.srm_sprob, d.srm_rho = _lib.dptr(s_prob), _lib.dptr(rho)
+        self._fill_pv(d, pv, keep)
+        return 1                                          # (> 0: the run takes the host generator to the device; no Exp(1) draws)
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_srm0(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:1639-1671); the draw consumes the global CPU generator exactly as torch.rand_like does there."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        from ..rng import DeviceGenerator
+        self._own_spikes()
+        pv = {}
+        p = self._params(pv)                              # (before the draws: a refused parameter leaves the generator alone)
+        eps_0, rho_0, d_thresh = _f(self.eps_0), _f(self.rho_0), _f(self.d_thresh)
+        s_prob, rho = self._prob_buffers()
+        with DeviceGenerator(self.v.device, 1) as g:
+            ops.srm0_step(g.state, self.v, self.refrac_count, self.s, self.x if self.traces else None, x, s_prob, rho, p,
+                          eps_0, rho_0, d_thresh, pv=pv)
+            g.finish()

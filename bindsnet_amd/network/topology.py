@@ -197,7 +197,7 @@ class _DenseConnection(AbstractConnection):
 
     _kind, _norm_by, _norm_abs = _lib.CONN_DENSE, "columns", True
     _takes_mask = _multi_device = True
-    _rules = frozenset(("NoOp", "PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET"))
+    _rules = frozenset(("NoOp", "PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET", "Rmax"))
     _host_compute, _host_update = host_path._propagate_dense, host_path._update_dense
 
     def _prop_into(self, s, out, accumulate=False) -> None:

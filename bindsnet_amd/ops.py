@@ -358,6 +358,28 @@ def clif_step(v, refrac, i, s, x, I, p: LifParams, i_decay, raster_s=None, raste
                                  C.byref(p), i_decay, arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "clif_step")
 
 
+def srm0_step(rng_state, v, refrac, s, x, I, s_prob, rho, p: LifParams, eps_0, rho_0, d_thresh, raster_s=None, raster_v=None, pv=None):
+    """SRM0Nodes.forward (nodes.py:1639-1671), the draw included.  rng_state: the int32 image of a device generator state
+    (rng.DeviceGenerator.state) holding the HOST generator; it is advanced in place by B * N 32-bit outputs.  s_prob, rho: f32
+    [B, N] outputs."""
+    B, N = _node_args(v)
+    arg, _keep = _pv(pv, N)
+    if s_prob.numel() != B * N or rho.numel() != B * N or I.numel() != B * N:
+        raise ValueError("srm0_step: I, s_prob and rho must have the shape of v")
+    check(lib().snn_srm0_step_pv(_ptr(rng_state, torch.int32), _ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True),
+                                 _ptr(I, F32), _ptr(s_prob, F32), _ptr(rho, F32), B, N, C.byref(p), eps_0, rho_0, d_thresh, arg,
+                                 _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "srm0_step")
+
+
+def rmax_step(W, e_trace, s_tgt, s_prob, x_src, reward, nu0, dt, tc_c, tc_e, wdecay=1.0, wmin=None, wmax=None):
+    """Rmax._connection_update (learning.py:2923-2960), batch 1: W, e_trace [Nin, N]; s_tgt, s_prob [N]; x_src [Nin]."""
+    Nin, N = W.shape
+    if e_trace.numel() != Nin * N or s_tgt.numel() != N or s_prob.numel() != N or x_src.numel() != Nin:
+        raise ValueError("rmax_step: operand sizes do not match the weights")
+    check(lib().snn_rmax_step(_ptr(W, F32), _ptr(e_trace, F32), _ptr(s_tgt, "spike"), _ptr(s_prob, F32), _ptr(x_src, F32), Nin, N,
+                              reward, nu0, dt, tc_c, tc_e, wdecay, *_bounds(wmin, wmax), _stream()), "rmax_step")
+
+
 def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """IzhikevichNodes.forward (nodes.py:1265-1296) in one launch; s holds the previous step's spikes at entry; St is the
     lateral matrix transposed ([N, N], St[i, j] = S[j, i]); the lateral sum is added to I in place."""

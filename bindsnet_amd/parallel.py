@@ -93,12 +93,27 @@ def _reject_pervec(network, mode: str, lif_thresh_ok: bool = False) -> None:
                                       "the multi-device modes do not support; run the network on one device")
 
 
+def _reject_stochastic(network, mode: str) -> None:
+    """None of the multi-device modes runs SRM0Nodes or Rmax: the layer draws from the ONE host generator in the global batch's
+    row-major order, which no shard of the batch or of the columns reproduces, and the rule is defined for batch size 1."""
+    from .network.nodes import SRM0Nodes
+    for key, conn in network.connections.items():      # (the rule first: its target is always an SRM0 layer)
+        if type(conn._rule()).__name__ == "Rmax":
+            raise NotImplementedError(f"{mode}: Rmax on connection {key} is not supported by the multi-device modes (the rule is defined for "
+                                      "batch size 1 and reads a layer that draws from the host generator); run the network on one device")
+    for name, layer in network.layers.items():
+        if isinstance(layer, SRM0Nodes):
+            raise NotImplementedError(f"{mode}: layer '{name}' (SRM0Nodes) draws from the host generator in the global batch's order, which "
+                                      "the multi-device modes do not reproduce; run the network on one device")
+
+
 def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, **kwargs) -> None:
     """network.run on this rank's batch shard, then merge learning across ranks (see module doc): the weights and
     thresholds become  before + sum_over_ranks(after - before), are clamped, and only then normalised.  The post-run
     normalisation inside run() is switched off through the network's `_defer_norm` flag (part of the key of the kept
     descriptor arrays, so consecutive sharded runs re-use them like plain runs do)."""
     _reject_local(network, "sharded_run")
+    _reject_stochastic(network, "sharded_run")
     _reject_pervec(network, "sharded_run", lif_thresh_ok=True)
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
@@ -163,6 +178,7 @@ def column_shard(network, rank: int, world: int):
     from .network import Network
     from .network.nodes import Input, LIFNodes
     _reject_local(network, "column_shard")
+    _reject_stochastic(network, "column_shard")
     _reject_pervec(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
@@ -253,6 +269,7 @@ def gather_columns(local: torch.Tensor, n_columns: int, group=None) -> torch.Ten
 # =====================================================================================================
 def _exact_check(network):
     _reject_local(network, "exact_run")
+    _reject_stochastic(network, "exact_run")
     _reject_pervec(network, "exact_run")
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes
     for name, layer in network.layers.items():

@@ -266,6 +266,27 @@ int snn_izh_step(float *v, float *u, uint8_t *s, float *x, float *I, const float
                  const float *d, const float *St, int B, int N, const snn_lif_params *h_p, uint8_t *raster_s,
                  float *raster_v, snn_stream_t stream);
 
+/* ---- f12: SRM0Nodes.forward and Rmax --------------------------------------------------------------
+ * bindsnet/network/nodes.py:1639-1671.  The layer's whole step in one launch, the draw included: *rng holds the HOST generator
+ * (see snn_rng_state below); element e of the row-major [B,N] range takes its e-th next 32-bit output, u = (r & 0xFFFFFF) * 2^-24
+ * -- what torch.rand_like(s_prob) draws -- and *rng is left advanced by B*N outputs (rng->consumed is not touched).  Order:
+ * v = decay*(v-rest)+rest;  v += ((refrac <= 0) * eps_0) * I;  rho = rho_0 * exp((v - thresh) / d_thresh);
+ * s_prob = 1 - exp(-rho * dt);  refrac -= dt;  s = u < s_prob;  where s: refrac = h_p->refrac, v = reset;  lbound;  trace.
+ * s_prob, rho [B,N] f32 out (rho from the voltage BEFORE the reset, as the reference's attribute).  The two exp are the
+ * device's expf, a 1-ulp function like torch's: rho and s_prob agree with the reference to a few ulp, everything else to the
+ * bit whenever the spikes do.  pv may name thresh, decay, trace_decay, trace_scale.  One workgroup (the stream is serial).
+ * (ABI 8, additive)                                                                                                       */
+struct snn_rng_state_s;
+int snn_srm0_step(struct snn_rng_state_s *rng, float *v, float *refrac, uint8_t *s, float *x, const float *I, float *s_prob,
+                  float *rho, int B, int N, const snn_lif_params *h_p, float eps_0, float rho_0, float d_thresh,
+                  uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+/* bindsnet/learning/learning.py:2923-2960 (+ :87-104), batch 1.  e_trace [Nin,N] in/out, s_tgt / s_prob [N] the target's spikes
+ * and spike probabilities of this step, x_src [Nin] the source's (additive) trace.  With k = 1 - dt / tc_e and q = tc_c / dt, both
+ * formed in f32:  e = e*k + (s_j - p_j / (1 + q*p_j)) * x_i;  W += (nu0 * reward) * e;  W *= wdecay;  clamp.               */
+int snn_rmax_step(float *W, float *e_trace, const uint8_t *s_tgt, const float *s_prob, const float *x_src, int Nin, int N,
+                  float reward, float nu0, float dt, float tc_c, float tc_e, float wdecay, int has_min, float wmin,
+                  int has_max, float wmax, snn_stream_t stream);
+
 /* ---- a4: DiehlAndCookNodes.forward ----------------------------------------------------------
  * bindsnet/network/nodes.py:1069-1111.  theta [N] shared by the batch.  one_spike winner
  * selection reproduces torch.multinomial on the CPU generator: noise_q is the pre-drawn
@@ -326,6 +347,9 @@ int snn_izh_step_pv(float *v, float *u, uint8_t *s, float *x, float *I, const fl
 int snn_dc_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *theta, const float *I, int B, int N,
                    const snn_dc_params *h_p, const snn_pervec *pv, const float *noise_q, long long q_len, long long *cursor,
                    int *status, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_srm0_step_pv(struct snn_rng_state_s *rng, float *v, float *refrac, uint8_t *s, float *x, const float *I, float *s_prob,
+                     float *rho, int B, int N, const snn_lif_params *h_p, float eps_0, float rho_0, float d_thresh,
+                     const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
 
 /* ---- device-resident emulation of torch's CPU generator --------------------------------------
  * Replaces the pre-drawn noise_q stream: the library reproduces the draws torch.multinomial
@@ -334,7 +358,7 @@ int snn_dc_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *theta, 
  * (parsed from torch.get_rng_state()).  pos: index of the next output inside the current 624-word
  * block, 624 = "twist before the next output" (at::mt19937's left_ == 1).  consumed counts draws.
  * After the run the host downloads the struct and writes it back with torch.set_rng_state(). */
-typedef struct {
+typedef struct snn_rng_state_s {
     uint32_t mt[624];
     int32_t pos;
     int32_t reserved;
@@ -489,7 +513,10 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
 /* SNN_LAYER_MCP .. SNN_LAYER_IZH (nodes.py:231, :308, :562, :681, :1147; generic plan only) and the aux / izh_* fields at the
  * end of snn_layer_desc were added without changing SNN_ABI_VERSION, like the additive connection kinds below.  */
 enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP = 3, SNN_LAYER_IF = 4, SNN_LAYER_BOOSTED = 5,
-       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7 };
+       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7, SNN_LAYER_SRM0 = 8 };
+/* SNN_LAYER_SRM0 (nodes.py:1555; generic plan only, needs snn_run_desc.rng) with the srm_* fields at the end of snn_layer_desc, and
+ * SNN_RULE_RMAX (learning.py:2858; a DENSE connection into an SRM0 layer, batch 1) with rmax_tc_c at the end of snn_conn_desc,
+ * were added the same way: SNN_ABI_VERSION unchanged.  */
 /* SNN_CONN_LOCAL (LocalConnection1D / 2D / 3D, rules NONE or POSTPRE, generic plan only) and the local_* fields at the end of
  * snn_conn_desc were added without changing SNN_ABI_VERSION: the change is purely additive.  A library built before it is
  * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
@@ -503,7 +530,7 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP =
 enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5,
        SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
-       SNN_RULE_MSTDPET = 5 };
+       SNN_RULE_MSTDPET = 5, SNN_RULE_RMAX = 6 };
 
 typedef struct {
     int kind;                   /* SNN_LAYER_* */
@@ -536,6 +563,10 @@ typedef struct {
      * A layer with any of them sends the graph to the generic plan, as thresh_vec does; a vector its kind does not read is
      * SNN_ERR_INVALID.  Added at the end without changing SNN_ABI_VERSION, like the fields above. */
     snn_pervec pv;
+    /* SRM0: eps_0, rho_0, d_thresh and the layer's s_prob / rho [B,n] f32 outputs (snn_srm0_step).  The layer draws from
+     * snn_run_desc.rng, within a timestep behind the Probability masks of the input gathering and in layer order. */
+    float srm_eps0, srm_rho0, srm_dthresh;
+    float *srm_sprob, *srm_rho;
 } snn_layer_desc;
 
 typedef struct {
@@ -598,6 +629,9 @@ typedef struct {
     int pool_c, pool_in[3], pool_k[3], pool_stride[3], pool_pad[3], pool_dil[3];
     float pool_decay;
     int w_numel;
+    /* RMAX (snn_rmax_step): e_trace is the rule's dense eligibility trace [Nin,N], tc_e its tc_e_trace, rmax_tc_c its tc_c; the
+     * target's s_prob is read from the target layer's srm_sprob, the source's trace from its x. */
+    float rmax_tc_c;
 } snn_conn_desc;
 
 typedef struct {
