@@ -98,7 +98,9 @@ class LayerDesc(C.Structure):
                 ("izh_a", C.c_void_p), ("izh_b", C.c_void_p), ("izh_c", C.c_void_p), ("izh_d", C.c_void_p),
                 ("izh_St", C.c_void_p), ("pv", PerVec),
                 ("srm_eps0", C.c_float), ("srm_rho0", C.c_float), ("srm_dthresh", C.c_float),
-                ("srm_sprob", C.c_void_p), ("srm_rho", C.c_void_p)]
+                ("srm_sprob", C.c_void_p), ("srm_rho", C.c_void_p),
+                ("csrm_xwin", C.c_void_p), ("csrm_last", C.c_void_p), ("csrm_resk", C.c_void_p), ("csrm_refk", C.c_void_p),
+                ("csrm_wres", C.c_int), ("csrm_wref", C.c_int)]
 
 
 class ConnDesc(C.Structure):
@@ -124,7 +126,8 @@ class ConnDesc(C.Structure):
                 ("sparse_ptr", C.c_void_p), ("sparse_col", C.c_void_p), ("sparse_val", C.c_void_p), ("sparse_nnz", C.c_int),
                 ("firing_rates", C.c_void_p), ("pool_c", C.c_int), ("pool_in", C.c_int * 3), ("pool_k", C.c_int * 3),
                 ("pool_stride", C.c_int * 3), ("pool_pad", C.c_int * 3), ("pool_dil", C.c_int * 3), ("pool_decay", C.c_float),
-                ("w_numel", C.c_int), ("rmax_tc_c", C.c_float)]
+                ("w_numel", C.c_int), ("rmax_tc_c", C.c_float),
+                ("window", C.c_int), ("win_ring", C.c_void_p), ("win_head", C.c_int), ("win_size", C.c_int)]
 
 
 class MccOp(C.Structure):
@@ -146,6 +149,8 @@ class FillSegment(C.Structure):
 MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH, LAYER_SRM0 = 3, 4, 5, 6, 7, 8
+LAYER_CSRM = 9
+CSRM_MAX_WINDOW = 1024    # SNN_CSRM_MAX_WINDOW: the largest res_window_size / ref_window_size of a CSRMNodes layer
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
 CONN_POOL, CONN_MEANFIELD = 6, 7
@@ -191,6 +196,8 @@ _SIGS = {
     "snn_dc_step_pv": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(DcParams), C.POINTER(PerVec), _vp, _ll, _vp, _vp, _vp, _vp, _vp], _i),
     "snn_srm0_step_pv": ([_vp] * 8 + [_i, _i, C.POINTER(LifParams), _f, _f, _f, C.POINTER(PerVec), _vp, _vp, _vp], _i),
     "snn_srm0_step": ([_vp] * 8 + [_i, _i, C.POINTER(LifParams), _f, _f, _f, _vp, _vp, _vp], _i),
+    "snn_prop_window_f32": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "snn_csrm_step": ([_vp] * 7 + [_i, _vp, _i, _i, _i, C.POINTER(DcParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
     "snn_rmax_step": ([_vp] * 5 + [_i, _i] + [_f] * 6 + [_i, _f, _i, _f, _vp], _i),
     "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),

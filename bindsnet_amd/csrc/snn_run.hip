@@ -121,6 +121,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 case SNN_LAYER_MCP: case SNN_LAYER_IF: case SNN_LAYER_IZH: allowed = snn::kPvTrace | snn::kPvThresh; break;
                 case SNN_LAYER_CURRENT: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvIDecay; break;
                 case SNN_LAYER_SRM0: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay; break;
+                case SNN_LAYER_CSRM: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvTheta; break;
                 default: return SNN_ERR_INVALID;
             }
             const snn_pervec pv = layer_pervec(d);
@@ -128,7 +129,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if ((pv.v[SNN_PV_TRACE_DECAY] || pv.v[SNN_PV_TRACE_SCALE]) && !d.p.lif.traces) return SNN_ERR_INVALID;
             if (pv.v[SNN_PV_TRACE_SCALE] && !d.p.lif.traces_additive) return SNN_ERR_INVALID;   // (masked_fill_ takes a 0-dim value)
             // (the per-neuron instances put the sample into the grid's second dimension; an LIF layer with thresh_vec alone keeps snn_lif_step_vth)
-            if (R->B > 65535 && d.kind != SNN_LAYER_SRM0 && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
+            if (R->B > 65535 && d.kind != SNN_LAYER_SRM0 && d.kind != SNN_LAYER_CSRM && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
         }
         switch (d.kind) {
             case SNN_LAYER_INPUT:
@@ -156,6 +157,14 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (!d.v || !d.s || !d.current) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
                 break;
+            case SNN_LAYER_CSRM:              // nodes.py:1319: a window of currents in, its own last spikes; no reset, no refractory counter
+                if (!d.csrm_xwin || !d.csrm_last || !d.csrm_resk || !d.csrm_refk || !d.theta || d.csrm_wres <= 0 || d.csrm_wref <= 0) return SNN_ERR_INVALID;
+                if (!d.v || !d.s) return SNN_ERR_INVALID;
+                if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
+                if (d.ext_current) return SNN_ERR_UNSUPPORTED;
+                if (d.csrm_wres > SNN_CSRM_MAX_WINDOW || d.csrm_wref > SNN_CSRM_MAX_WINDOW || R->B > 65535) return SNN_ERR_UNSUPPORTED;
+                if ((long long)R->B * d.csrm_wres * d.n > 2147483647LL || (long long)R->B * d.csrm_wref * d.n > 2147483647LL) return SNN_ERR_UNSUPPORTED;
+                break;
             case SNN_LAYER_CURRENT:           // nodes.py:681: the synaptic current i in aux
                 if (!d.aux) return SNN_ERR_INVALID;
                 /* fallthrough */
@@ -182,6 +191,11 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
         } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
+        if ((L[d.dst].kind == SNN_LAYER_CSRM) != (d.window != 0)) return SNN_ERR_INVALID;      // topology.py:348: compute_window, and only there
+        if (d.window) {                        // network.py:232-246: only Connection has a compute_window that runs
+            if (d.kind != SNN_CONN_DENSE || !d.win_ring || d.win_size != L[d.dst].csrm_wres || d.win_head < 0 || d.win_head >= d.win_size) return SNN_ERR_INVALID;
+            if ((long long)R->B * d.win_size * L[d.src].n > 2147483647LL) return SNN_ERR_UNSUPPORTED;
+        }
         const bool conv_mstdp = d.kind == SNN_CONN_CONV2D && d.rule == SNN_RULE_MSTDP;      // learning.py:1942-2015, batch 1
         // (the three outer-product rules share the per-sample partial sums in rule_ws: learning.py:457-497, :920-976, :1348-1380; MSTDPET's conv2d
         //  form never feeds its eligibility trace, :2654-2745 -- it cannot learn and is not offered)
@@ -283,6 +297,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                     TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, D.current, B, S.n, D.n, acc, st));
                 }
                 else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
+                else if (d.window) TRY(snn_prop_window_f32(d.w, d.bias, d.win_ring, (d.win_head + t) % d.win_size, sp, D.csrm_xwin, B, d.win_size,
+                                                           S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_SPARSE) TRY(snn_prop_sparse_f32(d.sparse_ptr, d.sparse_col, d.sparse_val, d.sparse_nnz, d.bias, sp,
                                                                             D.current, B, S.n, D.n, acc, st));
@@ -314,7 +330,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                       d.p.lif.trace_decay, d.p.lif.trace_scale, d.p.lif.traces_additive, pv, rs, st));
                 continue;
             }
-            if (!fed[l]) TRY(snn_check(hipMemsetAsync(d.current, 0, sizeof(float) * (size_t)B * d.n, st)));  // :409-413
+            if (!fed[l] && d.kind == SNN_LAYER_CSRM) TRY(snn_check(hipMemsetAsync(d.csrm_xwin, 0, sizeof(float) * (size_t)B * d.csrm_wres * d.n, st)));
+            else if (!fed[l]) TRY(snn_check(hipMemsetAsync(d.current, 0, sizeof(float) * (size_t)B * d.n, st)));  // :409-413
             // an external current for this layer: added behind the connections' sums (:386-392).  With one_step the reference
             // OVERWRITES it for a layer that has an incoming connection: `current_inputs[l] = inputs[l][t]` is followed by
             // `current_inputs.update(self._get_inputs(layers=[l]))` (:388-393), which replaces the entry -- the current survives
@@ -335,6 +352,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step_pv(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, pv, rs, rv, st));
             else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step_pv(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
                                                                  &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_CSRM) TRY(snn_csrm_step(d.v, d.s, d.x, d.theta, d.csrm_xwin, d.csrm_last, d.csrm_resk, d.csrm_wres, d.csrm_refk,
+                                                                d.csrm_wref, B, d.n, &d.p, pv, rs, rv, st));
             else if (d.kind == SNN_LAYER_SRM0) TRY(snn_srm0_step_pv(R->rng, d.v, d.refrac, d.s, d.x, d.current, d.srm_sprob, d.srm_rho, B, d.n, &d.p.lif,
                                                                    d.srm_eps0, d.srm_rho0, d.srm_dthresh, pv, rs, rv, st));
             else if (R->rng && d.p.one_spike) {   // device generator: membrane -> draws for this step -> arbitration
@@ -464,7 +483,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (has_pervec(L[l])) mode = 1;     // per-neuron parameters: generic plan
-    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes: generic plan only
+    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes, CSRMNodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection) plan only; no fused plan is offered the graph

@@ -5,7 +5,7 @@ package still constructs and runs where there is no GPU (SURVEY.md 8(b) fallback
 second, independent statement of the same semantics: tests/test_host_path.py pins it to the reference-generated fixtures
 the GPU tests use.  It is selected by Network.run only when the network's tensors are CPU tensors; it never touches
 libsnnhip and has nothing to do with oracle/ (test infrastructure).  Supported on this path: Input / LIFNodes /
-DiehlAndCookNodes / AdaptiveLIFNodes / McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes / SRM0Nodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
+DiehlAndCookNodes / AdaptiveLIFNodes / McCullochPitts / IFNodes / BoostedLIFNodes / CurrentLIFNodes / IzhikevichNodes / SRM0Nodes / CSRMNodes; MulticompartmentConnection + Weight (no rule / PostPre / MSTDP / MSTDPET), Connection and LocalConnection (no
 rule / PostPre / MSTDP / Hebbian / WeightDependentPostPre / MSTDPET / Rmax), Conv2dConnection (no rule / PostPre / MSTDP at batch 1);
 clamp / unclamp / injects_v / masks / one_step / reward; Monitor / NetworkMonitor.
 
@@ -199,6 +199,23 @@ def _step_srm0(layer, x) -> None:
     _trace(layer, layer.s)
 
 
+def _step_csrm(layer, x) -> None:
+    """nodes.py:1427-1464, the reference's statements in its order; `x` is the window [B, res_window_size, *shape]."""
+    layer.v *= layer.decay
+    if layer.learning:
+        layer.theta *= layer.theta_decay
+    v = torch.einsum("i,kij->kj", layer.resKernel, x)
+    v += torch.einsum("i,kij->kj", layer.refKernel, layer.last_spikes)
+    layer.v += v.view(x.size(0), *layer.shape)
+    layer.s = layer.v >= layer.thresh + layer.theta
+    if layer.learning:
+        layer.theta += layer.theta_plus * layer.s.float().sum(0)
+    layer.last_spikes = torch.cat((layer.last_spikes[:, 1:, :], layer.s[:, None, :]), 1)
+    if layer.lbound is not None:
+        layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
+    _trace(layer, layer.s)
+
+
 def _dc_membrane(layer, x) -> None:
     """nodes.py:1069-1092: everything up to the threshold crossings (left in layer.s) and their reset."""
     layer.v = layer.decay * (layer.v - layer.rest) + layer.rest
@@ -283,6 +300,21 @@ def _propagate_dense(conn, s):
     if getattr(conn, "b", None) is not None:
         post = post + conn.b
     return post.view(B, *conn.target.shape)
+
+
+def _propagate_window(conn, s):
+    """Connection.compute_window (topology.py:348-374): the window shifted by one slot, times the current weights."""
+    s_w = conn.s_w
+    if s_w is None:
+        s_w = torch.zeros(conn.target.batch_size, conn.target.res_window_size, *conn.source.shape)
+    s_w = torch.cat((s_w[:, 1:, :], s[:, None, :]), 1)
+    # (the window is state, not a parameter: written past the `s_w` setter, which would invalidate every network's kept descriptors each step)
+    conn.__dict__["_win"] = {"host": s_w, "ring": None, "head": 0}
+    if conn.b is None:
+        post = s_w.view(s_w.size(0), s_w.size(1), -1).float() @ conn.w
+    else:
+        post = s_w.view(s_w.size(0), s_w.size(1), -1).float() @ conn.w + conn.b
+    return post.view(s_w.size(0), conn.target.res_window_size, *conn.target.shape)
 
 
 def _propagate_sparse(conn, s):
@@ -605,7 +637,7 @@ def _update_dense(conn, kwargs, mask) -> None:
 
 
 def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs) -> None:
-    from .nodes import Input, Nodes
+    from .nodes import CSRMNodes, Input, Nodes
     clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
     injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
     if isinstance(kwargs.get("a_plus"), dict) or isinstance(kwargs.get("a_minus"), dict):
@@ -628,9 +660,10 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
             if only is not None and dst != only:
                 continue
             tgt = network.layers[dst]
+            window = isinstance(tgt, CSRMNodes)          # network.py:232-246: a CSRM layer gathers windows
             if dst not in cur:
-                cur[dst] = torch.zeros(network.batch_size, *tgt.shape)
-            cur[dst] += conn._host_compute(network.layers[src].s)
+                cur[dst] = torch.zeros(network.batch_size, tgt.res_window_size, *tgt.shape) if window else torch.zeros(network.batch_size, *tgt.shape)
+            cur[dst] += conn.compute_window(network.layers[src].s) if window else conn._host_compute(network.layers[src].s)
         return cur
 
     for t in range(T):
@@ -649,7 +682,9 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
                 # `current_inputs.update(self._get_inputs(layers=[l]))` (:388-393) REPLACES the entry it has just set for a
                 # layer with an incoming connection: the current survives only where no connection feeds the layer
                 if name in inputs and not fed_now:
-                    ext = inputs[name][t].float().view(network.batch_size, *layer.shape)
+                    ext = inputs[name][t].float()
+                    if not (isinstance(layer, CSRMNodes) and x is not None):     # (a window: `+=` broadcasts the current over its slots, as there)
+                        ext = ext.view(network.batch_size, *layer.shape)
                     x = ext.clone() if x is None else x + ext
                 if x is None:
                     x = torch.zeros(network.batch_size, *layer.shape)

@@ -18,7 +18,7 @@ from .._lib import dptr as _dptr
 from ..rng import DeviceGenerator
 from . import host_path
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
-from .nodes import AdaptiveLIFNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
+from .nodes import AdaptiveLIFNodes, CSRMNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
 
 
 def load(file_name: str, map_location: str = "cpu", learning: bool = None) -> "Network":
@@ -315,6 +315,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 inputs[key] = inputs[key].unsqueeze(0).unsqueeze(0)
             elif inputs[key].dim() == 2:
                 inputs[key] = inputs[key].unsqueeze(1)
+        self._csrm_refusals(inputs)                        # what a CSRMNodes layer cannot run: before the run changes any state
         for key in inputs:
             if inputs[key].size(1) != self.batch_size:
                 self.batch_size = inputs[key].size(1)
@@ -400,6 +401,11 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             else:
                 self.__dict__["resident_retries"] = self.__dict__.get("resident_retries", 0) + 1
                 R.plan = 2
+        # (reached only behind a run that was enqueued whole: a run that raises leaves the layers' state and the windows undefined, as it
+        #  does v and w)
+        for k, conn in built["windows"]:               # every timestep overwrote the oldest slot of the ring
+            win = conn.__dict__["_win"]
+            win["head"] = (win["head"] + T) % win["ring"].shape[1]
         if not self.__dict__.get("_defer_norm", False):     # network.py:463-465 for the connections snn_net_run does not normalise itself
             for conn in self.connections.values():
                 if conn._norm_by == "after" and conn.norm is not None:
@@ -417,6 +423,39 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         for kept in (built, self.__dict__.get("_reset_cache")):    # the assignments just made are this call's own
             if kept is not None and kept["epoch"] == before:
                 kept["epoch"] = _lib.epoch()
+
+    def _csrm_refusals(self, inputs) -> None:
+        """CSRMNodes layers (nodes.py:1319): what the reference's first step would raise half-way through it -- kernels that do not
+        fit the windows, a window made at another batch size --, a connection class without a working compute_window, and what
+        the device path leaves out (external currents, tensor-valued parameters), all raised before anything changes."""
+        if not any(isinstance(l, CSRMNodes) for l in self.layers.values()):
+            return
+        B = self.batch_size
+        for key in inputs:
+            B = inputs[key].size(1)
+            break
+        on_device = self._device().type == "cuda"
+        from .topology import Connection
+        for name, layer in self.layers.items():
+            if not isinstance(layer, CSRMNodes):
+                continue
+            err = layer._run_refusal(B)
+            if err is not None:
+                raise err
+            if on_device:
+                if name in inputs:
+                    raise NotImplementedError(f"bindsnet_amd: `inputs['{name}']`, an external current into a CSRMNodes layer, is not "
+                                              "supported on the device")
+                layer._csrm_params({})
+        for (src, dst), conn in self.connections.items():
+            if not isinstance(self.layers[dst], CSRMNodes):
+                continue
+            if type(conn) is not Connection:
+                raise NotImplementedError(f"bindsnet_amd: {type(conn).__name__} into a CSRMNodes layer is not supported: only Connection "
+                                          "has a compute_window (topology.py:348) that runs in the reference")
+            err = conn._window_refusal(B)
+            if err is not None:
+                raise err
 
     # ------------------------------------------------------------------ descriptors
     def _cache_valid(self, built, T, B, dev) -> bool:
@@ -511,7 +550,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     if lname not in self.layers or isinstance(self.layers[lname], Input):
                         raise NotImplementedError(f"bindsnet_amd: {what}['{lname}'] must name a non-Input layer of the network")
             Cn = (_lib.ConnDesc * max(1, len(self.connections)))()
-            lists, dyn_conns, described = [], [], []
+            lists, dyn_conns, described, windows = [], [], [], []
             for k, ((src, dst), conn) in enumerate(self.connections.items()):
                 described += self._fill_conn(Cn[k], conn, index[src], index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
                 if self.__dict__.get("_defer_norm", False):    # parallel.sharded_run normalises the MERGED weights itself
@@ -519,6 +558,8 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 wanted = self._conn_monitor_requests(conn, (src, dst))
                 if wanted:
                     dyn_conns.append((k, conn, wanted))
+                if Cn[k].window:
+                    windows.append((k, conn))
                 nu = getattr(conn._rule(), "nu", None)
                 if isinstance(nu, torch.Tensor):
                     lists.append((nu, nu._version))
@@ -544,7 +585,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
+            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho", "last_spikes", "resKernel", "refKernel") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
                 t = getattr(layer, attr, None)
                 if isinstance(t, torch.Tensor):
                     ptrs.append((layer, attr, t.data_ptr()))
@@ -569,7 +610,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     self._scratch("rng_qbuf", (max(max_draws, 1),), torch.float32, dev), pool["rng_host"])
         # (assignments made while building -- a state tensor re-created by _check_state, a rule's lazily allocated
         #  memory -- belong to this build: the descriptors already point at the new objects)
-        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns,
+        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows,
                 "max_draws": max_draws, "gen_bufs": gen_bufs, "T": T, "B": B, "dev": dev, "scalars": scalars,
                 "lists": lists, "epoch": _lib.epoch(), "n_objects": (len(self.layers), len(self.connections), len(self.monitors)),
                 "epoch0": epoch0, "defer_norm": bool(self.__dict__.get("_defer_norm", False)), "ptrs": ptrs}
@@ -631,6 +672,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                         mon_v = torch.empty(T, B, *layer.shape, device=dev)
                     rasters.append((m, key, mon_v))
             L[i].raster_s, L[i].raster_v = _dptr(mon_s), _dptr(mon_v)
+        for k, conn in built["windows"]:           # a connection into a CSRM layer: its ring and where the oldest entry stands now
+            win = conn._window_ring(B, dev)
+            built["Cn"][k].win_ring, built["Cn"][k].win_head = _dptr(win["ring"]), win["head"]
         for k, conn, wanted in built["conns"]:     # weights at the end of every timestep (monitors.py:94-111, 222-262)
             mon_w = torch.empty(T, *conn.w.shape, device=dev)
             built["Cn"][k].raster_w = _dptr(mon_w)

@@ -1,7 +1,7 @@
 """Neuron groups: API mirror of bindsnet/network/nodes.py for the layer types on the hot path
 (`Nodes`, `Input`, `McCullochPitts`, `IFNodes`, `LIFNodes`, `BoostedLIFNodes`, `CurrentLIFNodes`, `AdaptiveLIFNodes`,
-`DiehlAndCookNodes`, `IzhikevichNodes`, `SRM0Nodes`); the arithmetic lives in libsnnhip (snn_input_step / snn_lif_step / snn_dc_step /
-snn_mcp_step / snn_if_step / snn_boosted_step / snn_clif_step / snn_izh_step / snn_srm0_step).  Each class fills its own snn_layer_desc
+`DiehlAndCookNodes`, `IzhikevichNodes`, `SRM0Nodes`, `CSRMNodes`); the arithmetic lives in libsnnhip (snn_input_step / snn_lif_step / snn_dc_step /
+snn_mcp_step / snn_if_step / snn_boosted_step / snn_clif_step / snn_izh_step / snn_srm0_step / snn_csrm_step).  Each class fills its own snn_layer_desc
 (`_describe`), so Network._build_descriptors needs no table of layer types.
 
 State is held in the same attributes as the reference (`s`, `x`, `v`, `refrac_count`, `theta`,
@@ -182,7 +182,7 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         the layer may consume."""
         raise NotImplementedError(f"bindsnet_amd: layer type {type(self).__name__} is outside the accelerated path (Input, "
                                   "McCullochPitts, IFNodes, LIFNodes, BoostedLIFNodes, CurrentLIFNodes, AdaptiveLIFNodes, "
-                                  "DiehlAndCookNodes, IzhikevichNodes, SRM0Nodes)")
+                                  "DiehlAndCookNodes, IzhikevichNodes, SRM0Nodes, CSRMNodes)")
 
     def _host_step(self, x: torch.Tensor) -> None:
         """One step on the host path (network/host_path.py)."""
@@ -816,3 +816,205 @@ class SRM0Nodes(Nodes):
             ops.srm0_step(g.state, self.v, self.refrac_count, self.s, self.x if self.traces else None, x, s_prob, rho, p,
                           eps_0, rho_0, d_thresh, pv=pv)
             g.finish()
+
+
+class CSRMNodes(Nodes):
+    """Cumulative spike response model neurons (reference: nodes.py:1319-1552).  Unlike every other layer its input is a WINDOW,
+    `[B, res_window_size, n]`: the last `res_window_size` spike vectors of its sources, each multiplied by the current weights
+    (Connection.compute_window).  A step contracts that window with the response kernel and the layer's own last
+    `ref_window_size` spikes (`last_spikes`) with the refractory kernel.  There is no reset and no refractory counter, `theta` is
+    shared by the batch, and reset_state_variables() clears neither `last_spikes` nor the connections' windows -- all as in the
+    reference.  `resKernel` and `refKernel` are made on the host with the reference's own expressions.
+
+    On the device the step is snn_csrm_step: the two contractions run in ascending slot order, product then add, which is not the
+    order of torch's einsum -- `v` agrees with the reference to rounding, everything that depends on `v` only through the spikes
+    bit for bit whenever the spikes do."""
+    _STATE = ("v",)
+    _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
+    # refused as tensors on the device, by name
+    _SCALAR_ONLY = ("rest", "tau", "reset_const")
+
+    def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
+                 sum_input=False, rest: Scalar = -65.0, thresh: Scalar = -52.0, responseKernel: str = "ExponentialKernel",
+                 refractoryKernel: str = "EtaKernel", tau: Scalar = 1, res_window_size: Scalar = 20, ref_window_size: Scalar = 10,
+                 reset_const: Scalar = 50, tc_decay: Scalar = 100.0, theta_plus: Scalar = 0.05, tc_theta_decay: Scalar = 1e7,
+                 lbound: float = None, **kwargs) -> None:
+        super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,
+                         trace_scale=trace_scale, sum_input=sum_input)
+        self.register_buffer("rest", _buf(rest))
+        self.register_buffer("thresh", _buf(thresh))
+        self.register_buffer("tau", _buf(tau))
+        self.register_buffer("reset_const", _buf(reset_const))
+        self.register_buffer("res_window_size", _buf(res_window_size))
+        self.register_buffer("ref_window_size", _buf(ref_window_size))
+        self.register_buffer("tc_decay", _buf(tc_decay))
+        self.register_buffer("decay", torch.empty_like(self.tc_decay, dtype=torch.float32))
+        self.register_buffer("theta_plus", _buf(theta_plus))
+        self.register_buffer("tc_theta_decay", _buf(tc_theta_decay))
+        self.register_buffer("theta_decay", torch.empty_like(self.tc_theta_decay))
+        self.register_buffer("v", torch.FloatTensor())
+        self.register_buffer("last_spikes", torch.ByteTensor())
+        self.register_buffer("theta", torch.zeros(*self.shape))
+        self.lbound = lbound
+        self.responseKernel = responseKernel
+        self.refractoryKernel = refractoryKernel
+        self.register_buffer("resKernel", torch.FloatTensor())
+        self.register_buffer("refKernel", torch.FloatTensor())
+
+    def compute_decays(self, dt) -> None:
+        super().compute_decays(dt=dt)
+        dev = self.tc_decay.device
+        self.decay = torch.exp(-self.dt / self.tc_decay.cpu()).to(dev)
+        self.theta_decay = torch.exp(-self.dt / self.tc_theta_decay.cpu()).to(dev)
+
+    def set_batch_size(self, batch_size) -> None:
+        super().set_batch_size(batch_size=batch_size)
+        dev = self.v.device
+        self.v = self.rest.to(dev) * torch.ones(batch_size, *self.shape, device=dev)
+        self.last_spikes = torch.zeros(batch_size, self.ref_window_size.cpu(), *self.shape).to(dev)   # (a float size: TypeError, as there)
+        resKernels = {"AlphaKernel": self.AlphaKernel, "AlphaKernelSLAYER": self.AlphaKernelSLAYER, "LaplacianKernel": self.LaplacianKernel,
+                      "ExponentialKernel": self.ExponentialKernel, "RectangularKernel": self.RectangularKernel,
+                      "TriangularKernel": self.TriangularKernel}
+        if self.responseKernel not in resKernels.keys():
+            raise Exception(" The given response Kernel is not implemented")
+        self.resKernel = resKernels[self.responseKernel](self.dt).to(dev)
+        refKernels = {"EtaKernel": self.EtaKernel}
+        if self.refractoryKernel not in refKernels.keys():
+            raise Exception(" The given refractory Kernel is not implemented")
+        self.refKernel = refKernels[self.refractoryKernel](self.dt).to(dev)
+
+    # The kernels, nodes.py:1519-1552: the reference's expressions, evaluated on the host (the last bit of exp belongs to it).
+    def AlphaKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)
+        kernelVec = (1 / (tau**2)) * t * torch.exp(-t / tau)
+        return torch.flip(kernelVec, [0])
+
+    def AlphaKernelSLAYER(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)
+        kernelVec = (1 / tau) * t * torch.exp(1 - t / tau)
+        return torch.flip(kernelVec, [0])
+
+    def LaplacianKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)
+        kernelVec = (1 / (tau * 2)) * torch.exp(-1 * torch.abs(t / tau))
+        return torch.flip(kernelVec, [0])
+
+    def ExponentialKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)
+        kernelVec = (1 / tau) * torch.exp(-t / tau)
+        return torch.flip(kernelVec, [0])
+
+    def RectangularKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)        # noqa: F841 (the reference forgets to use it: the kernel is 0-dim)
+        kernelVec = 1 / (tau * 2)
+        return torch.flip(kernelVec, [0])
+
+    def TriangularKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.res_window_size.cpu(), dt)
+        kernelVec = (1 / tau) * (1 - (t / tau))
+        return torch.flip(kernelVec, [0])
+
+    def EtaKernel(self, dt):
+        tau = self.tau.cpu()
+        t = torch.arange(0, self.ref_window_size.cpu(), dt)
+        kernelVec = -self.reset_const.cpu() * torch.exp(-t / tau)
+        return torch.flip(kernelVec, [0])
+
+    def reset_state_variables(self) -> None:      # last_spikes is NOT cleared (nodes.py:1466-1472)
+        super().reset_state_variables()
+        self.v.fill_(_f(self.rest))
+
+    def _window_sizes(self):
+        """(res_window_size, ref_window_size) as ints; a non-integer res_window_size raises the TypeError the reference's
+        torch.zeros(batch, res_window_size, ...) raises in the first step."""
+        for name in ("res_window_size", "ref_window_size"):
+            t = getattr(self, name)
+            if t.is_floating_point() or t.numel() != 1:
+                raise TypeError(f"zeros(): argument 'size' must be tuple of ints, but CSRMNodes.{name} is {t.dtype} with {t.numel()} element(s)")
+        return int(self.res_window_size), int(self.ref_window_size)
+
+    def _run_refusal(self, B: int):
+        """What the reference's first step raises for this layer, found before a run changes any state: a response kernel that is
+        not a vector (RectangularKernel: einsum on a 0-dim operand), kernels whose length is not the window's (dt != 1)."""
+        try:
+            wres, wref = self._window_sizes()
+        except TypeError as e:
+            return e
+        if self.resKernel.dim() != 1 or self.refKernel.dim() != 1:
+            return RuntimeError(f"einsum(): CSRMNodes.{self.responseKernel} gives a {self.resKernel.dim()}-dimensional response kernel, "
+                                "the step contracts a vector over the window")
+        if self.resKernel.numel() != wres or self.refKernel.numel() != wref:
+            return RuntimeError(f"einsum(): the kernels of CSRMNodes have {self.resKernel.numel()} / {self.refKernel.numel()} entries at dt = "
+                                f"{float(self.dt)}, the windows {wres} / {wref} slots (only dt = 1 runs)")
+        if self.last_spikes.dim() < 2 or self.last_spikes.shape[1] != wref:
+            return RuntimeError(f"CSRMNodes.last_spikes has shape {list(self.last_spikes.shape)}, the refractory window {wref} slots")
+        return None
+
+    def _csrm_params(self, pv: Optional[dict] = None) -> _lib.DcParams:
+        for name in self._SCALAR_ONLY:
+            t = getattr(self, name)
+            if isinstance(t, torch.Tensor) and t.numel() != 1:
+                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on CSRMNodes is not supported on the device")
+        p = _lib.DcParams()
+        pv = {} if pv is None else pv
+        p.lif = self._node_params(pv, decay=self.decay)
+        p.theta_decay, p.theta_plus = self._sv("theta_decay", pv), self._sv("theta_plus", pv)
+        p.learning, p.one_spike = int(self.learning), 0
+        return p
+
+    def _device_state(self, B: int):
+        """The tensors snn_csrm_step reads beside `v`: (window-current buffer [B, Wres, n], last_spikes, resKernel, refKernel,
+        Wres, Wref), each a contiguous f32 tensor on the layer's device.  Sizes beyond the kernels' limits raise.  The window-current
+        buffer is scratch the layer keeps for itself (made anew for another batch size or device, never pickled), not state."""
+        wres, wref = self._window_sizes()
+        dev = self.v.device
+        if max(wres, wref) > _lib.CSRM_MAX_WINDOW or B > 65535 or B * max(wres, wref) * self.n >= 1 << 31:
+            raise NotImplementedError(f"bindsnet_amd: CSRMNodes with windows {wres} / {wref}, batch {B} and {self.n} neurons is beyond the device "
+                                      f"kernels' limits (windows <= {_lib.CSRM_MAX_WINDOW}, batch <= 65535, batch * window * n < 2^31)")
+        for name, shape in (("last_spikes", (B, wref, self.n)), ("resKernel", (wres,)), ("refKernel", (wref,))):
+            t = getattr(self, name)
+            if t.device != dev or t.dtype != torch.float32 or t.numel() != shape[0] * (shape[1] * shape[2] if len(shape) == 3 else 1) \
+                    or not t.is_contiguous():
+                raise ValueError(f"CSRMNodes.{name} must be a contiguous float32 tensor of {list(shape)} elements on {dev}")
+        xwin = self.__dict__.get("_xwin")
+        if xwin is None or xwin.device != dev or tuple(xwin.shape) != (B, wres, self.n):
+            xwin = self.__dict__["_xwin"] = torch.zeros(B, wres, self.n, device=dev)
+        return xwin, self.last_spikes, self.resKernel, self.refKernel, wres, wref
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_xwin", None)                          # device scratch, not model state
+        return state
+
+    def _describe(self, d, keep, scalars) -> int:
+        pv = {}
+        d.kind, d.p, d.theta = _lib.LAYER_CSRM, self._csrm_params(pv), _lib.dptr(self.theta)
+        xwin, last, resk, refk, d.csrm_wres, d.csrm_wref = self._device_state(self.v.shape[0])
+        d.csrm_xwin, d.csrm_last, d.csrm_resk, d.csrm_refk = _lib.dptr(xwin), _lib.dptr(last), _lib.dptr(resk), _lib.dptr(refk)
+        keep.append(xwin)
+        self._fill_pv(d, pv, keep)
+        return 0
+
+    def _host_step(self, x: torch.Tensor) -> None:
+        from . import host_path
+        host_path._step_csrm(self, x)
+
+    def forward(self, x: torch.Tensor) -> None:
+        """One step (nodes.py:1427-1464); `x` is the window of currents [B, res_window_size, *shape]."""
+        if not self.v.is_cuda:
+            return self._host_step(x)
+        self._own_spikes()
+        pv = {}
+        p = self._csrm_params(pv)
+        B = self.v.shape[0]
+        _, last, resk, refk, wres, wref = self._device_state(B)
+        x = x.to(torch.float32).contiguous()
+        if x.numel() != B * wres * self.n:
+            raise RuntimeError(f"CSRMNodes.forward: the input has shape {list(x.shape)}, the layer needs [{B}, {wres}, {self.n}]")
+        ops.csrm_step(self.v, self.s, self.x if self.traces else None, self.theta, x, last, resk, refk, p, pv=pv)

@@ -18,7 +18,7 @@ from torch.nn.modules.utils import _pair, _triple
 from .. import _lib, ops
 from .._lib import dptr
 from . import host_path
-from .nodes import Nodes
+from .nodes import CSRMNodes, Nodes
 
 
 def _rand_weights(conn, shape, bias_n, w_dtype, kwargs) -> None:
@@ -219,6 +219,88 @@ class Connection(_DenseConnection):
                  w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
         super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
         self.w, self.b = _matrix_weights(self, w_dtype, kwargs)
+
+    # -- the window of a connection into a CSRMNodes layer (topology.py:329-330, :348-374) ---------------------------------
+    # `s_w` reads as the reference's attribute: None until first use, then float32 [B, res_window_size, *source.shape], oldest
+    # slot first; it is a plain attribute, not a buffer.  On the device the window is a ring of bytes [B, Wres, source.n] with a
+    # head index (snn_prop_window_f32 overwrites the oldest slot); both live in self.__dict__["_win"], which .to() carries along.
+    @property
+    def s_w(self):
+        if not isinstance(self.target, CSRMNodes):
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 's_w'")
+        win = self.__dict__.get("_win")
+        if win is None:
+            return None
+        if win["ring"] is None:
+            return win["host"]
+        ring, head = win["ring"], win["head"]
+        return torch.cat((ring[:, head:], ring[:, :head]), 1).float().view(ring.shape[0], ring.shape[1], *self.source.shape)
+
+    @s_w.setter
+    def s_w(self, value) -> None:
+        self.__dict__["_win"] = None if value is None else {"host": value, "ring": None, "head": 0}
+        _lib.touch()
+
+    def _apply(self, fn, *args, **kwargs):
+        """nn.Module.to() / cuda() hook: an existing window moves with the weights (the reference leaves it behind)."""
+        out = super()._apply(fn, *args, **kwargs)
+        win = self.__dict__.get("_win")
+        if win is not None:
+            for key in ("host", "ring"):
+                if win[key] is not None:
+                    win[key] = fn(win[key])
+        return out
+
+    def _window_ring(self, B: int, dev):
+        """The window as snn_prop_window_f32 keeps it, made from `s_w` where that was last written on the host: the "_win" entry
+        with a u8 ring [B, Wres, source.n] on `dev`.  A window made for another batch size raises like the reference's cat()."""
+        wres = self.target._window_sizes()[0]
+        win = self.__dict__.get("_win")
+        if win is not None and win["ring"] is not None and win["ring"].device == dev and tuple(win["ring"].shape) == (B, wres, self.source.n):
+            return win
+        cur = None if win is None else self.s_w
+        if cur is None:
+            ring = torch.zeros(B, wres, self.source.n, dtype=torch.uint8, device=dev)
+        else:
+            err = self._window_refusal(B)
+            if err is not None:
+                raise err
+            ring = cur.reshape(B, wres, self.source.n).ne(0).to(dev, torch.uint8).contiguous()
+        win = self.__dict__["_win"] = {"host": None, "ring": ring, "head": 0}
+        return win
+
+    def _window_refusal(self, B: int):
+        """A window made at another batch size or window length: the RuntimeError of the reference's torch.cat (topology.py:359)."""
+        win = self.__dict__.get("_win")
+        cur = None if win is None else (win["ring"] if win["ring"] is not None else win["host"])
+        if cur is None:
+            return None
+        wres = self.target._window_sizes()[0]
+        if cur.shape[0] != B or cur.shape[1] != wres or cur[0, 0].numel() != self.source.n:
+            return RuntimeError(f"Sizes of tensors must match except in dimension 1: the window s_w of {type(self).__name__} was made as "
+                                f"{[cur.shape[0], cur.shape[1], cur[0, 0].numel()]}, the step needs [{B}, {wres}, {self.source.n}]")
+        return None
+
+    def compute_window(self, s: torch.Tensor) -> torch.Tensor:
+        """Reference: topology.py:348-374 -- push `s` into the window, return the window times the CURRENT weights (+ b) as
+        [B, res_window_size, *target.shape].  On the device snn_prop_window_f32 sums every slot over its spiking sources in
+        ascending order."""
+        if not self.w.is_cuda:
+            return host_path._propagate_window(self, s)
+        B = s.size(0)
+        win = self._window_ring(B, self.w.device)
+        out = torch.empty(B, win["ring"].shape[1], *self.target.shape, device=self.w.device)
+        ops.prop_window(self.w.data.view(self.source.n, self.target.n), win["ring"], win["head"], s.reshape(B, -1).contiguous(), out,
+                        bias=None if self.b is None else self.b.data)
+        win["head"] = (win["head"] + 1) % win["ring"].shape[1]
+        return out
+
+    def _describe(self, d, B: int, dev, scratch) -> list:
+        described = super()._describe(d, B, dev, scratch)
+        if isinstance(self.target, CSRMNodes):
+            win = self._window_ring(B, dev)
+            d.window, d.win_ring, d.win_head, d.win_size = 1, dptr(win["ring"]), win["head"], win["ring"].shape[1]
+        return described
 
     def _column_slice(self, source, target, lo, hi):
         def scalar(t) -> float:

@@ -380,6 +380,32 @@ def rmax_step(W, e_trace, s_tgt, s_prob, x_src, reward, nu0, dt, tc_c, tc_e, wde
                               reward, nu0, dt, tc_c, tc_e, wdecay, *_bounds(wmin, wmax), _stream()), "rmax_step")
 
 
+def prop_window(W, ring, head, s, out, bias=None, accumulate=False):
+    """Connection.compute_window (topology.py:348-374) on a ring: ring u8 [B, Wres, Nin] with its oldest entry in physical slot
+    `head`; the call overwrites that slot with s [B, Nin] and writes out [B, Wres, N] (+)= window @ W (+ b), slot 0 the oldest,
+    each sum over the spiking sources in ascending order.  The caller's next head is (head + 1) % Wres."""
+    B, Wres, Nin = ring.shape
+    N = W.shape[1]
+    if W.shape[0] != Nin or s.numel() != B * Nin or out.numel() != B * Wres * N or not 0 <= head < Wres:
+        raise ValueError("prop_window: operand sizes do not match")
+    check(lib().snn_prop_window_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(ring, torch.uint8), int(head), _ptr(s, "spike"),
+                                    _ptr(out, F32), B, Wres, Nin, N, int(accumulate), _stream()), "prop_window")
+    return out
+
+
+def csrm_step(v, s, x, theta, xwin, last, resK, refK, p, raster_s=None, raster_v=None, pv=None):
+    """CSRMNodes.forward (nodes.py:1427-1464) in one launch: xwin f32 [B, Wres, N] the window of currents, last f32 [B, Wref, N]
+    the layer's last spikes (shifted in place, the new spikes appended), resK / refK the kernels, p an snn_dc_params."""
+    B, N = _node_args(v)
+    arg, _keep = _pv(pv, N)
+    Wres, Wref = resK.numel(), refK.numel()
+    if xwin.numel() != B * Wres * N or last.numel() != B * Wref * N or theta.numel() != N:
+        raise ValueError("csrm_step: xwin, last and theta must be [B, Wres, N], [B, Wref, N] and [N]")
+    check(lib().snn_csrm_step(_ptr(v, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(theta, F32), _ptr(xwin, F32), _ptr(last, F32),
+                              _ptr(resK, F32), Wres, _ptr(refK, F32), Wref, B, N, C.byref(p), arg, _ptr(raster_s, "spike", True),
+                              _ptr(raster_v, F32, True), _stream()), "csrm_step")
+
+
 def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """IzhikevichNodes.forward (nodes.py:1265-1296) in one launch; s holds the previous step's spikes at entry; St is the
     lateral matrix transposed ([N, N], St[i, j] = S[j, i]); the lateral sum is added to I in place."""

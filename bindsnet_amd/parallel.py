@@ -96,7 +96,11 @@ def _reject_pervec(network, mode: str, lif_thresh_ok: bool = False) -> None:
 def _reject_stochastic(network, mode: str) -> None:
     """None of the multi-device modes runs SRM0Nodes or Rmax: the layer draws from the ONE host generator in the global batch's
     row-major order, which no shard of the batch or of the columns reproduces, and the rule is defined for batch size 1."""
-    from .network.nodes import SRM0Nodes
+    from .network.nodes import CSRMNodes, SRM0Nodes
+    for name, layer in network.layers.items():
+        if isinstance(layer, CSRMNodes):
+            raise NotImplementedError(f"{mode}: layer '{name}' (CSRMNodes) takes a window of currents and shares its threshold adaptation over the "
+                                      "global batch, which the multi-device modes do not reproduce; run the network on one device")
     for key, conn in network.connections.items():      # (the rule first: its target is always an SRM0 layer)
         if type(conn._rule()).__name__ == "Rmax":
             raise NotImplementedError(f"{mode}: Rmax on connection {key} is not supported by the multi-device modes (the rule is defined for "

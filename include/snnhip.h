@@ -287,6 +287,27 @@ int snn_rmax_step(float *W, float *e_trace, const uint8_t *s_tgt, const float *s
                   float reward, float nu0, float dt, float tc_c, float tc_e, float wdecay, int has_min, float wmin,
                   int has_max, float wmax, snn_stream_t stream);
 
+/* ---- f13: CSRMNodes.forward and Connection.compute_window ---------------------------------------------
+ * bindsnet/network/nodes.py:1427-1464, topology.py:348-374.  The layer's input is a WINDOW: the last Wres spike vectors of
+ * every source, each multiplied by the CURRENT weights.
+ * snn_prop_window_f32: ring u8 [B,Wres,Nin] is the connection's window kept as a ring; `head` the physical slot of its oldest
+ * entry.  The call overwrites that slot with s [B,Nin] (the push), after which logical slot i (0 = oldest, Wres-1 = s) is
+ * physical slot (head + 1 + i) mod Wres, and writes  out[b,i,j] (+)= (((0 + W[s1,j]) + W[s2,j]) + ...) (+ bias[j])  over the
+ * sources s1 < s2 < ... that spiked in slot i: ascending source index from 0.0f, one rounded f32 add per term, bias (nullable)
+ * last; accumulate as in snn_prop_dense_f32 (0: out = sum, 1: out = out + sum).  out f32 [B,Wres,N].  Event-driven: the work
+ * is (spikes in the window) x N, a silent source's row of W is never loaded.  The next call's head is (head + 1) mod Wres.
+ * snn_csrm_step, one launch, in this order per (b,j):  v = v * decay;  res = sum_i resK[i] * xwin[b,i,j];  ref = sum_i refK[i]
+ * * last[b,i,j]  (both: i ascending from 0.0f, product then add, each one rounding);  v = v + (res + ref);  s = v >= thresh +
+ * theta[j]  (theta shared by the batch; while learning it is decayed before the comparison and grows by theta_plus * (the
+ * neuron's spike count over the batch) after it, as in snn_dc_step);  last[b] shifted by one slot, s appended;  lbound;  trace.
+ * There is no reset and no refractory counter.  pv may name thresh, decay, theta_decay, theta_plus, trace_decay, trace_scale.
+ * Limits: Wres, Wref <= SNN_CSRM_MAX_WINDOW, B <= 65535 (snn_prop_window_f32), B*Wres*N, B*Wres*Nin, B*Wref*N < 2^31; beyond
+ * them SNN_ERR_UNSUPPORTED.  (ABI 8, additive)                                                                          */
+#define SNN_CSRM_MAX_WINDOW 1024
+int snn_prop_window_f32(const float *W, const float *bias, uint8_t *ring, int head, const uint8_t *s, float *out,
+                        int B, int Wres, int Nin, int N, int accumulate, snn_stream_t stream);
+/* (snn_csrm_step takes snn_dc_params and snn_pervec: declared behind them, below) */
+
 /* ---- a4: DiehlAndCookNodes.forward ----------------------------------------------------------
  * bindsnet/network/nodes.py:1069-1111.  theta [N] shared by the batch.  one_spike winner
  * selection reproduces torch.multinomial on the CPU generator: noise_q is the pre-drawn
@@ -350,6 +371,9 @@ int snn_dc_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *theta, 
 int snn_srm0_step_pv(struct snn_rng_state_s *rng, float *v, float *refrac, uint8_t *s, float *x, const float *I, float *s_prob,
                      float *rho, int B, int N, const snn_lif_params *h_p, float eps_0, float rho_0, float d_thresh,
                      const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_csrm_step(float *v, uint8_t *s, float *x, float *theta, const float *xwin, float *last, const float *resK, int Wres,
+                  const float *refK, int Wref, int B, int N, const snn_dc_params *h_p, const snn_pervec *pv, uint8_t *raster_s,
+                  float *raster_v, snn_stream_t stream);
 
 /* ---- device-resident emulation of torch's CPU generator --------------------------------------
  * Replaces the pre-drawn noise_q stream: the library reproduces the draws torch.multinomial
@@ -513,10 +537,13 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
 /* SNN_LAYER_MCP .. SNN_LAYER_IZH (nodes.py:231, :308, :562, :681, :1147; generic plan only) and the aux / izh_* fields at the
  * end of snn_layer_desc were added without changing SNN_ABI_VERSION, like the additive connection kinds below.  */
 enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP = 3, SNN_LAYER_IF = 4, SNN_LAYER_BOOSTED = 5,
-       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7, SNN_LAYER_SRM0 = 8 };
+       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7, SNN_LAYER_SRM0 = 8, SNN_LAYER_CSRM = 9 };
 /* SNN_LAYER_SRM0 (nodes.py:1555; generic plan only, needs snn_run_desc.rng) with the srm_* fields at the end of snn_layer_desc, and
  * SNN_RULE_RMAX (learning.py:2858; a DENSE connection into an SRM0 layer, batch 1) with rmax_tc_c at the end of snn_conn_desc,
  * were added the same way: SNN_ABI_VERSION unchanged.  */
+/* SNN_LAYER_CSRM (nodes.py:1319; generic plan only) with the csrm_* fields at the end of snn_layer_desc, and the win_* fields at
+ * the end of snn_conn_desc -- a DENSE connection into a CSRM layer propagates its window: snn_prop_window_f32 --, were added the
+ * same way: SNN_ABI_VERSION unchanged.  */
 /* SNN_CONN_LOCAL (LocalConnection1D / 2D / 3D, rules NONE or POSTPRE, generic plan only) and the local_* fields at the end of
  * snn_conn_desc were added without changing SNN_ABI_VERSION: the change is purely additive.  A library built before it is
  * still refused at load, because the Python binding looks up every symbol declared here and such a library lacks
@@ -567,6 +594,13 @@ typedef struct {
      * snn_run_desc.rng, within a timestep behind the Probability masks of the input gathering and in layer order. */
     float srm_eps0, srm_rho0, srm_dthresh;
     float *srm_sprob, *srm_rho;
+    /* CSRM (snn_csrm_step): csrm_xwin the layer's window-current buffer f32 [B, csrm_wres, n] -- what its incoming connections'
+     * snn_prop_window_f32 calls sum into, in place of `current` --, csrm_last its last_spikes f32 [B, csrm_wref, n] (oldest slot
+     * first, updated in place), csrm_resk / csrm_refk the response and refractory kernels f32 [csrm_wres] / [csrm_wref]; theta [n]
+     * and p (thresh, decay, lbound, traces, theta_decay, theta_plus, learning) as for DC.  ext_current is SNN_ERR_UNSUPPORTED. */
+    float *csrm_xwin, *csrm_last;
+    const float *csrm_resk, *csrm_refk;
+    int csrm_wres, csrm_wref;
 } snn_layer_desc;
 
 typedef struct {
@@ -632,6 +666,13 @@ typedef struct {
     /* RMAX (snn_rmax_step): e_trace is the rule's dense eligibility trace [Nin,N], tc_e its tc_e_trace, rmax_tc_c its tc_c; the
      * target's s_prob is read from the target layer's srm_sprob, the source's trace from its x. */
     float rmax_tc_c;
+    /* A DENSE connection into a CSRM layer: `window` = 1, win_ring the connection's window of source spikes u8 [B, win_size, Nin]
+     * kept as a ring, win_head the physical slot holding its OLDEST entry at the start of the run (the run leaves the oldest
+     * entry in slot (win_head + T) mod win_size); win_size == the target's csrm_wres.  Any other kind into a CSRM layer, or
+     * `window` on a connection into another layer kind, is SNN_ERR_INVALID. */
+    int window;
+    uint8_t *win_ring;
+    int win_head, win_size;
 } snn_conn_desc;
 
 typedef struct {
