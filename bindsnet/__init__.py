@@ -42,7 +42,7 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 sys.meta_path.insert(0, _AliasFinder())
 __path__ = []            # a package without files of its own: every submodule comes from the finder above
 
-_SUBPACKAGES = ("network", "learning", "models", "encoding", "evaluation", "datasets", "analysis", "utils", "parallel")
+_SUBPACKAGES = ("network", "learning", "models", "encoding", "evaluation", "datasets", "analysis", "utils", "parallel", "conversion")
 
 
 def __getattr__(name):

@@ -100,7 +100,7 @@ class LayerDesc(C.Structure):
                 ("srm_eps0", C.c_float), ("srm_rho0", C.c_float), ("srm_dthresh", C.c_float),
                 ("srm_sprob", C.c_void_p), ("srm_rho", C.c_void_p),
                 ("csrm_xwin", C.c_void_p), ("csrm_last", C.c_void_p), ("csrm_resk", C.c_void_p), ("csrm_refk", C.c_void_p),
-                ("csrm_wres", C.c_int), ("csrm_wref", C.c_int)]
+                ("csrm_wres", C.c_int), ("csrm_wref", C.c_int), ("summed", C.c_void_p)]
 
 
 class ConnDesc(C.Structure):
@@ -127,7 +127,8 @@ class ConnDesc(C.Structure):
                 ("firing_rates", C.c_void_p), ("pool_c", C.c_int), ("pool_in", C.c_int * 3), ("pool_k", C.c_int * 3),
                 ("pool_stride", C.c_int * 3), ("pool_pad", C.c_int * 3), ("pool_dil", C.c_int * 3), ("pool_decay", C.c_float),
                 ("w_numel", C.c_int), ("rmax_tc_c", C.c_float),
-                ("window", C.c_int), ("win_ring", C.c_void_p), ("win_head", C.c_int), ("win_size", C.c_int)]
+                ("window", C.c_int), ("win_ring", C.c_void_p), ("win_head", C.c_int), ("win_size", C.c_int),
+                ("gat_out", C.c_int * 3), ("gat_src", C.c_int * 3), ("gat_stride", C.c_int * 3), ("gat_off", C.c_int * 3)]
 
 
 class MccOp(C.Structure):
@@ -150,10 +151,12 @@ MAX_FILL_SEGMENTS = 32
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH, LAYER_SRM0 = 3, 4, 5, 6, 7, 8
 LAYER_CSRM = 9
+LAYER_SIF, LAYER_PASS = 10, 11     # bindsnet.conversion: SubtractiveResetIFNodes, PassThroughNodes
 CSRM_MAX_WINDOW = 1024    # SNN_CSRM_MAX_WINDOW: the largest res_window_size / ref_window_size of a CSRMNodes layer
 IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the lateral sum's order is pinned against torch
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
 CONN_POOL, CONN_MEANFIELD = 6, 7
+CONN_PERMUTE, CONN_PAD = 8, 9      # bindsnet.conversion: PermuteConnection, ConstantPad2dConnection (snn_prop_gather_f32)
 POOL_STAGE = 8192         # SNN_POOL_STAGE: the largest (b, c) plane snn_prop_pool_f32 updates and pools in LDS, in one launch
 MEANFIELD_STORE = 2       # SNN_MEANFIELD_STORE: snn_prop_meanfield_f32 writes mean * w itself
 MEANFIELD_MAX = 1 << 24   # B * source.n up to which f32(count) / f32(numel) is the reference's mean
@@ -198,6 +201,10 @@ _SIGS = {
     "snn_srm0_step": ([_vp] * 8 + [_i, _i, C.POINTER(LifParams), _f, _f, _f, _vp, _vp, _vp], _i),
     "snn_prop_window_f32": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "snn_csrm_step": ([_vp] * 7 + [_i, _vp, _i, _i, _i, C.POINTER(DcParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_sif_step": ([_vp] * 6 + [_i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
+    "snn_sif_step_pv": ([_vp] * 6 + [_i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
+    "snn_pass_step": ([_vp, _vp, _i, _i, _vp, _vp], _i),
+    "snn_prop_gather_f32": ([_vp, _vp, _i, _i] + [C.POINTER(_i)] * 4 + [_i, _vp], _i),
     "snn_rmax_step": ([_vp] * 5 + [_i, _i] + [_f] * 6 + [_i, _f, _i, _f, _vp], _i),
     "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),

@@ -1,0 +1,187 @@
+"""`ann_to_snn`: a trained torch.nn model as a spiking Network (reference: bindsnet/conversion/conversion.py).  Host code; the
+network it returns runs on the device after `network.to("cuda")`: every layer and connection it is made of has a kernel.
+
+What it builds, child by child of the model (a top-level Sequential is opened up, one level):
+    Linear          -> `node_type` layer of out_features neurons behind a Connection with w = weight.t() and b = bias (zeros without)
+    Conv2d          -> `node_type` layer (out_channels, OH, OW) behind a Conv2dConnection with the module's w and b
+    MaxPool2d       -> PassThroughNodes behind a MaxPool2dConnection(decay=1)
+    Permute         -> PassThroughNodes behind a PermuteConnection
+    ConstantPad2d   -> PassThroughNodes behind a ConstantPad2dConnection
+    anything else   -> skipped (ReLU is what the spiking neurons themselves stand for)
+The layers are named "Input", "1", "2", ... after the child's position, so a skipped child leaves a gap, and a connection's key
+is (str(i - 1), str(i)) whether or not a layer of that name exists.  Every `node_type` layer gets reset=0, thresh=1, refrac=0;
+the last one sum_input=True -- its `summed` is the network's readout.  Only SubtractiveResetIFNodes takes sum_input here, so any
+other `node_type` raises NotImplementedError at the last layer.
+
+Kept from the reference as it is, not repaired: the output shape of a Permute child is looked up in the previous layer's shape
+with the batch-inclusive dims; a Conv2d without bias gets zeros(layer.shape[1]), one per output ROW; a ConstantPad2d's height
+grows by padding[0] + padding[1], the left and right pads.  Where the resulting graph cannot run, the run raises before it
+changes any state.  `torch.load` of a path is called as the reference calls it.
+
+On the device the limits of the parts apply: Conv2d with at most 16 input channels, dilation 1, symmetric stride and padding;
+uint8 / bool input spikes; no fused plan (`network.last_plan == "generic"`); no monitor on `summed`."""
+import warnings
+from copy import deepcopy
+from typing import Dict, Optional, Sequence, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.nn.modules.utils import _pair
+
+from ..network import Network
+from ..network import nodes, topology
+from .nodes import PassThroughNodes, SubtractiveResetIFNodes
+from .topology import ConstantPad2dConnection, PermuteConnection
+
+
+class Permute(nn.Module):
+    """`x.permute(*dims)` as a module, so that a Sequential (and `ann_to_snn`) can see it."""
+
+    def __init__(self, dims):
+        super().__init__()
+        self.dims = dims
+
+    def forward(self, x):
+        return x.permute(*self.dims).contiguous()
+
+
+class FeatureExtractor(nn.Module):
+    """Runs `submodule`'s children one after the other and keeps every child's output: {"input": x, child name: activation}.
+    The input of a Linear child is flattened to [-1, in_features] first."""
+
+    def __init__(self, submodule):
+        super().__init__()
+        self.submodule = submodule
+
+    def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        seen = {"input": x}
+        for name, child in self.submodule._modules.items():
+            if isinstance(child, nn.Linear):
+                x = x.view(-1, child.in_features)
+            x = child(x)
+            seen[name] = x
+        return seen
+
+
+def _is_weighted(module) -> bool:
+    return isinstance(module, (nn.Linear, nn.Conv2d))
+
+
+def data_based_normalization(ann: Union[nn.Module, str], data: torch.Tensor, percentile: float = 99.9):
+    """Rescale the weights and biases of `ann` IN PLACE so that the `percentile`-th percentile of every ReLU's activations on
+    `data` becomes 1, and return it.  A path is read with torch.load.
+
+    The control flow is the reference's, quirks included: the model's top-level children are walked once; inside a Sequential
+    child every ReLU rescales the weighted layer seen last (by `previous factor / this factor`, the bias by `1 / this factor`);
+    a top-level Linear is rescaled like a ReLU would rescale -- with whatever activations were looked at last -- and never
+    becomes the "weighted layer seen last" itself; a top-level ReLU or Conv2d behaves as inside a Sequential."""
+    if isinstance(ann, str):
+        ann = torch.load(ann)
+    assert isinstance(ann, nn.Module)
+    for param in ann.parameters():
+        param.requires_grad = False
+    outer = FeatureExtractor(ann).forward(data)
+
+    state = {"last": None, "factor": 1}
+
+    def rescale(acts) -> None:
+        last = state["last"]
+        if last is None:
+            return
+        scale = np.percentile(acts.cpu(), percentile)
+        last.weight *= state["factor"] / scale
+        last.bias /= scale
+        state["factor"] = scale
+
+    for name, module in ann._modules.items():
+        if isinstance(module, nn.Sequential):
+            inner = FeatureExtractor(module).forward(data)
+            for inner_name, module in module.named_children():      # (`module` is the LAST inner child behind this loop, as there)
+                activations = inner[inner_name]
+                if isinstance(module, nn.ReLU):
+                    rescale(activations)
+                elif _is_weighted(module):
+                    state["last"] = module
+        if isinstance(module, nn.Linear):
+            if state["last"] is not None:
+                rescale(activations)                               # (the activations looked at last, whichever child's they were)
+        else:
+            activations = outer[name]
+            if isinstance(module, nn.ReLU):
+                rescale(activations)
+            elif _is_weighted(module):
+                state["last"] = module
+    return ann
+
+
+def _conv_output(prev, module):
+    """(rows, columns) of a Conv2d / MaxPool2d output as the reference computes them: float division, then int()."""
+    k, p, s = module.kernel_size, module.padding, module.stride
+    return (int((prev.shape[1] - k[0] + 2 * p[0]) / s[0] + 1), int((prev.shape[2] - k[1] + 2 * p[1]) / s[1] + 1))
+
+
+def _ann_to_snn_helper(prev, current, node_type, last=False, **kwargs):
+    """(layer, connection) for the ANN module `current` behind the spiking layer `prev`, or (None, None) for a module that has no
+    spiking counterpart."""
+    spiking = dict(reset=0, thresh=1, refrac=0, sum_input=last, **kwargs)
+    if isinstance(current, nn.Linear):
+        layer = node_type(n=current.out_features, **spiking)
+        bias = current.bias if current.bias is not None else torch.zeros(layer.n)
+        # (a transposed view, as in the reference -- on the host MKL is then handed the same operand; Connection stores it contiguously
+        #  once it moves to the device, where the kernels read [in, out] row-major)
+        return layer, topology.Connection(source=prev, target=layer, w=current.weight.t(), b=bias)
+    if isinstance(current, nn.Conv2d):
+        layer = node_type(shape=(current.out_channels, *_conv_output(prev, current)), **spiking)
+        bias = current.bias if current.bias is not None else torch.zeros(layer.shape[1])
+        return layer, topology.Conv2dConnection(source=prev, target=layer, kernel_size=current.kernel_size, stride=current.stride,
+                                                padding=current.padding, dilation=current.dilation, w=current.weight, b=bias)
+    if isinstance(current, nn.MaxPool2d):
+        current.kernel_size, current.padding, current.stride = _pair(current.kernel_size), _pair(current.padding), _pair(current.stride)
+        layer = PassThroughNodes(shape=(prev.shape[0], *_conv_output(prev, current)))
+        return layer, topology.MaxPool2dConnection(source=prev, target=layer, kernel_size=current.kernel_size, stride=current.stride,
+                                                   padding=current.padding, dilation=current.dilation, decay=1)
+    if isinstance(current, Permute):
+        layer = PassThroughNodes(shape=[prev.shape[current.dims[k]] for k in range(3)])
+        return layer, PermuteConnection(source=prev, target=layer, dims=current.dims)
+    if isinstance(current, nn.ConstantPad2d):
+        pad = current.padding
+        layer = PassThroughNodes(shape=[prev.shape[0], pad[0] + pad[1] + prev.shape[1], pad[2] + pad[3] + prev.shape[2]])
+        return layer, ConstantPad2dConnection(source=prev, target=layer, padding=pad)
+    return None, None
+
+
+def ann_to_snn(ann: Union[nn.Module, str], input_shape: Sequence[int], data: Optional[torch.Tensor] = None, percentile: float = 99.9,
+               node_type: Optional[nodes.Nodes] = SubtractiveResetIFNodes, **kwargs) -> Network:
+    """The spiking Network of the module docstring for `ann` (a deep copy is converted; a path is read with torch.load).  With
+    `data` the copy's weights are rescaled by data_based_normalization first; without it a RuntimeWarning says they are not.
+    `kwargs` go to every `node_type` layer."""
+    ann = torch.load(ann) if isinstance(ann, str) else deepcopy(ann)
+    assert isinstance(ann, nn.Module)
+    if data is None:
+        warnings.warn("Data is None. Weights will not be scaled.", RuntimeWarning)
+    else:
+        ann = data_based_normalization(ann=ann, data=data.detach(), percentile=percentile)
+
+    snn = Network()
+    prev = nodes.Input(shape=input_shape)
+    snn.add_layer(prev, name="Input")
+
+    children = []
+    for child in ann.children():
+        children += list(child.children()) if isinstance(child, nn.Sequential) else [child]
+
+    for i, current in enumerate(children[:-1], start=1):
+        layer, connection = _ann_to_snn_helper(prev, current, node_type, **kwargs)
+        if layer is None or connection is None:
+            continue
+        snn.add_layer(layer, name=str(i))
+        snn.add_connection(connection, source=str(i - 1), target=str(i))
+        prev = layer
+
+    i = len(children)                                  # (the reference counts the last child too, a one-child model included)
+    layer, connection = _ann_to_snn_helper(prev, children[-1], node_type, last=True, **kwargs)
+    if layer is not None or connection is not None:
+        snn.add_layer(layer, name=str(i))
+        snn.add_connection(connection, source=str(i - 1), target=str(i))
+    return snn

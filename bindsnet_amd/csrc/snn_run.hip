@@ -12,6 +12,7 @@
 #include "../../include/snnhip.h"
 #include "snn_common.hpp"
 #include "snn_pool.hpp"
+#include "snn_conversion.hpp"
 
 static thread_local const char *g_plan = "none";
 static int g_plan_mode = 0;
@@ -122,6 +123,8 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 case SNN_LAYER_CURRENT: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvIDecay; break;
                 case SNN_LAYER_SRM0: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay; break;
                 case SNN_LAYER_CSRM: allowed = snn::kPvTrace | snn::kPvThresh | snn::kPvDecay | snn::kPvTheta; break;
+                case SNN_LAYER_SIF: allowed = snn::kPvTrace; break;      // (conversion/nodes.py:93: `v[s] - thresh` takes a scalar threshold)
+                case SNN_LAYER_PASS: allowed = 0; break;
                 default: return SNN_ERR_INVALID;
             }
             const snn_pervec pv = layer_pervec(d);
@@ -131,7 +134,16 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             // (the per-neuron instances put the sample into the grid's second dimension; an LIF layer with thresh_vec alone keeps snn_lif_step_vth)
             if (R->B > 65535 && d.kind != SNN_LAYER_SRM0 && d.kind != SNN_LAYER_CSRM && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
         }
+        if (d.summed && d.kind != SNN_LAYER_SIF) return SNN_ERR_INVALID;       // sum_input: SubtractiveResetIFNodes only
         switch (d.kind) {
+            case SNN_LAYER_PASS:              // conversion/nodes.py:122: s = x, nothing else; x must be 0 or 1 (checked per connection below)
+                if (!d.s || !d.current) return SNN_ERR_INVALID;
+                if (d.inject_v || d.ext_current) return SNN_ERR_UNSUPPORTED;
+                break;
+            case SNN_LAYER_SIF:               // conversion/nodes.py:8
+                if (!d.v || !d.refrac || !d.s || !d.current) return SNN_ERR_INVALID;
+                if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
+                break;
             case SNN_LAYER_INPUT:
                 if (!d.ext_spikes || !d.s) return SNN_ERR_INVALID;
                 if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
@@ -179,6 +191,16 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             default: return SNN_ERR_INVALID;
         }
     }
+    for (int l = 0; l < nL; ++l) {             // a PassThroughNodes layer: exactly one feeder, and one whose outputs are 0 or 1
+        if (L[l].kind != SNN_LAYER_PASS) continue;
+        int feeders = 0;
+        for (int c = 0; c < nC; ++c) {
+            if (C[c].dst != l) continue;
+            ++feeders;
+            if (C[c].kind != SNN_CONN_POOL && C[c].kind != SNN_CONN_PERMUTE && C[c].kind != SNN_CONN_PAD) return SNN_ERR_UNSUPPORTED;
+        }
+        if (feeders != 1) return SNN_ERR_UNSUPPORTED;
+    }
     for (int c = 0; c < nC; ++c) {
         const snn_conn_desc &d = C[c];
         if (d.src < 0 || d.src >= nL || d.dst < 0 || d.dst >= nL) return SNN_ERR_INVALID;
@@ -189,7 +211,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW && (!d.pipe_bits[k] || !R->rng)) return SNN_ERR_INVALID;
             }
             if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
-        } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL) return SNN_ERR_INVALID;
+        } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL && d.kind != SNN_CONN_PERMUTE && d.kind != SNN_CONN_PAD) return SNN_ERR_INVALID;
         if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
         if ((L[d.dst].kind == SNN_LAYER_CSRM) != (d.window != 0)) return SNN_ERR_INVALID;      // topology.py:348: compute_window, and only there
         if (d.window) {                        // network.py:232-246: only Connection has a compute_window that runs
@@ -214,7 +236,15 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if (L[d.dst].kind != SNN_LAYER_SRM0 || !L[d.src].x || !L[d.src].p.lif.traces_additive || !d.e_trace) return SNN_ERR_INVALID;
             if (R->B != 1) return SNN_ERR_UNSUPPORTED;
         }
-        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_MEANFIELD) return SNN_ERR_INVALID;
+        if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_PAD) return SNN_ERR_INVALID;
+        if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) {        // PermuteConnection / ConstantPad2dConnection: a gather, propagation only
+            if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
+            if (d.has_norm || d.mask || d.raster_w || d.bias || d.w) return SNN_ERR_INVALID;
+            snn::GatherGeom g;
+            for (int a = 0; a < 3; ++a) { g.out[a] = d.gat_out[a]; g.src[a] = d.gat_src[a]; g.stride[a] = d.gat_stride[a]; g.off[a] = d.gat_off[a]; }
+            if (!snn::gather_valid(g, L[d.src].n, L[d.dst].n)) return SNN_ERR_INVALID;
+            continue;
+        }
         if (d.kind == SNN_CONN_POOL || d.kind == SNN_CONN_MEANFIELD) {     // MaxPoolNdConnection / MeanFieldConnection: propagation only (NoOp)
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
             if (d.has_norm || d.mask || d.raster_w || d.bias) return SNN_ERR_INVALID;
@@ -304,6 +334,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                                                             D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_POOL) TRY(snn_prop_pool_f32(d.firing_rates, sp, D.current, B, d.pool_c, d.pool_in, d.pool_k, d.pool_stride,
                                                                         d.pool_pad, d.pool_dil, d.pool_decay, acc, st));
+                else if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) TRY(snn_prop_gather_f32(sp, D.current, B, S.n, d.gat_out, d.gat_src, d.gat_stride,
+                                                                                                        d.gat_off, acc, st));
                 else if (d.kind == SNN_CONN_MEANFIELD) TRY(snn_prop_meanfield_f32(d.w, d.w_numel, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_CONVND) TRY(snn_prop_convnd_f32(d.w, d.bias, sp, D.current, B, d.cin, d.conv_d, d.h, d.wd, d.cout,
                                                                              d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
@@ -352,6 +384,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             else if (d.kind == SNN_LAYER_CURRENT) TRY(snn_clif_step_pv(d.v, d.refrac, d.aux, d.s, d.x, d.current, B, d.n, &d.p.lif, d.aux_decay, pv, rs, rv, st));
             else if (d.kind == SNN_LAYER_IZH) TRY(snn_izh_step_pv(d.v, d.aux, d.s, d.x, d.current, d.izh_a, d.izh_b, d.izh_c, d.izh_d, d.izh_St, B, d.n,
                                                                  &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_SIF) TRY(snn_sif_step_pv(d.v, d.refrac, d.s, d.x, d.summed, d.current, B, d.n, &d.p.lif, pv, rs, rv, st));
+            else if (d.kind == SNN_LAYER_PASS) TRY(snn_pass_step(d.s, d.current, B, d.n, rs, st));
             else if (d.kind == SNN_LAYER_CSRM) TRY(snn_csrm_step(d.v, d.s, d.x, d.theta, d.csrm_xwin, d.csrm_last, d.csrm_resk, d.csrm_wres, d.csrm_refk,
                                                                 d.csrm_wref, B, d.n, &d.p, pv, rs, rv, st));
             else if (d.kind == SNN_LAYER_SRM0) TRY(snn_srm0_step_pv(R->rng, d.v, d.refrac, d.s, d.x, d.current, d.srm_sprob, d.srm_rho, B, d.n, &d.p.lif,
@@ -483,10 +517,10 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (has_pervec(L[l])) mode = 1;     // per-neuron parameters: generic plan
-    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes, CSRMNodes: generic plan only
+    bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes, CSRMNodes, SubtractiveResetIFNodes, PassThroughNodes: generic plan only
     for (int l = 0; l < nL; ++l) if (L[l].kind > SNN_LAYER_DC) other_nodes = true;
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
-    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection) plan only; no fused plan is offered the graph
+    for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection, PermuteConnection, ConstantPad2dConnection) plan only; no fused plan is offered the graph
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {

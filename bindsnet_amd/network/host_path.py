@@ -145,6 +145,20 @@ def _step_if(layer, x) -> None:
     _trace(layer, layer.s)
 
 
+def _step_sif(layer, x) -> None:
+    """SubtractiveResetIFNodes.forward (conversion/nodes.py:73-99), then the base class's trace and `summed` (nodes.py:96-107)."""
+    layer.v += (layer.refrac_count == 0).float() * x
+    layer.refrac_count = (layer.refrac_count > 0).float() * (layer.refrac_count - layer.dt)
+    layer.s = layer.v >= layer.thresh
+    layer.refrac_count.masked_fill_(layer.s, layer.refrac)
+    layer.v[layer.s] = layer.v[layer.s] - layer.thresh
+    if layer.lbound is not None:
+        layer.v.masked_fill_(layer.v < layer.lbound, layer.lbound)
+    _trace(layer, layer.s)
+    if layer.sum_input:
+        layer.summed += x.float()
+
+
 def _step_boosted(layer, x) -> None:
     """nodes.py:621-648."""
     layer.v *= layer.decay
@@ -337,6 +351,16 @@ def _propagate_pool(conn, s):
     pool = getattr(torch.nn.functional, f"max_pool{conn._ndim}d")
     _, idx = pool(fr, kernel_size=k, stride=stride, padding=pad, dilation=dil, return_indices=True)
     return s.reshape(B, fr.shape[1], -1).gather(2, idx.flatten(2)).view_as(idx).float()
+
+
+def _propagate_permute(conn, s):
+    """PermuteConnection.compute (conversion/topology.py:48-56)."""
+    return s.permute(conn.dims).float()
+
+
+def _propagate_pad(conn, s):
+    """ConstantPad2dConnection.compute (conversion/topology.py:100-108): F.pad's default fill, 0."""
+    return F.pad(s, conn.padding).float()
 
 
 def _propagate_meanfield(conn, s):
@@ -663,7 +687,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
             window = isinstance(tgt, CSRMNodes)          # network.py:232-246: a CSRM layer gathers windows
             if dst not in cur:
                 cur[dst] = torch.zeros(network.batch_size, tgt.res_window_size, *tgt.shape) if window else torch.zeros(network.batch_size, *tgt.shape)
-            cur[dst] += conn.compute_window(network.layers[src].s) if window else conn._host_compute(network.layers[src].s)
+            cur[dst] += conn.compute_window(conn.source.s) if window else conn._host_compute(conn.source.s)     # (the connection's own source, as network.py:227)
         return cur
 
     for t in range(T):

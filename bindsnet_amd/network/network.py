@@ -316,6 +316,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             elif inputs[key].dim() == 2:
                 inputs[key] = inputs[key].unsqueeze(1)
         self._csrm_refusals(inputs)                        # what a CSRMNodes layer cannot run: before the run changes any state
+        self._layer_refusals(inputs, injects_v)            # ... and what a layer knows it cannot run on the device
         for key in inputs:
             if inputs[key].size(1) != self.batch_size:
                 self.batch_size = inputs[key].size(1)
@@ -423,6 +424,17 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         for kept in (built, self.__dict__.get("_reset_cache")):    # the assignments just made are this call's own
             if kept is not None and kept["epoch"] == before:
                 kept["epoch"] = _lib.epoch()
+
+    def _layer_refusals(self, inputs, injects_v) -> None:
+        """Layers with a `_run_refusal` (PassThroughNodes: which connections may feed it on the device), asked before anything changes."""
+        if self._device().type != "cuda":
+            return
+        for name, layer in self.layers.items():
+            if hasattr(layer, "_run_refusal") and not isinstance(layer, CSRMNodes):
+                feeders = [conn for (_, dst), conn in self.connections.items() if dst == name]
+                err = layer._run_refusal(name, feeders, name in inputs, injects_v.get(name) is not None)
+                if err is not None:
+                    raise err
 
     def _csrm_refusals(self, inputs) -> None:
         """CSRMNodes layers (nodes.py:1319): what the reference's first step would raise half-way through it -- kernels that do not
@@ -552,7 +564,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             Cn = (_lib.ConnDesc * max(1, len(self.connections)))()
             lists, dyn_conns, described, windows = [], [], [], []
             for k, ((src, dst), conn) in enumerate(self.connections.items()):
-                described += self._fill_conn(Cn[k], conn, index[src], index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
+                described += self._fill_conn(Cn[k], conn, self._source_index(names, index, src, conn), index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
                 if self.__dict__.get("_defer_norm", False):    # parallel.sharded_run normalises the MERGED weights itself
                     Cn[k].has_norm = 0
                 wanted = self._conn_monitor_requests(conn, (src, dst))
@@ -585,7 +597,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho", "last_spikes", "resKernel", "refKernel") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
+            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho", "last_spikes", "resKernel", "refKernel", "summed") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
                 t = getattr(layer, attr, None)
                 if isinstance(t, torch.Tensor):
                     ptrs.append((layer, attr, t.data_ptr()))
@@ -706,6 +718,16 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             return l.s.device
         return torch.device("cpu")
 
+    def _source_index(self, names, index, src, conn) -> int:
+        """The layer a connection reads: its own `source` object, as in the reference (network.py:227), whatever name the
+        connection was filed under -- ann_to_snn files a connection behind a skipped child under a name no layer has."""
+        if self.layers.get(src) is conn.source:
+            return index[src]
+        for i, name in enumerate(names):
+            if self.layers[name] is conn.source:
+                return i
+        raise KeyError(f"the source layer of connection {(src,)} is not a layer of the network")
+
     @staticmethod
     def _check_state(layer, B, dev):
         for nm in layer._STATE + (("x",) if layer.traces else ()):
@@ -729,7 +751,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     raise NotImplementedError("bindsnet_amd: monitors on objects other than the network's layers and "
                                               "connections (features, ...) are not supported")
         for m, key, var in requests:
-            if var != "s" and not (var == "v" and hasattr(layer, "v")):
+            if var != "s" and not (var == "v" and "v" in layer._STATE):
                 raise NotImplementedError(f"bindsnet_amd: monitoring '{var}' of {type(layer).__name__} is "
                                           "outside the accelerated path (supported: 's', 'v')")
         return requests

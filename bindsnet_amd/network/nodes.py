@@ -63,8 +63,9 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         self.n = reduce(mul, shape) if n is None else n
         self.shape = [self.n] if shape is None else shape
         assert self.n == reduce(mul, self.shape), "No. of neurons and shape do not match"
-        if sum_input:
-            raise NotImplementedError("bindsnet_amd: sum_input=True is outside the accelerated path")
+        if sum_input and not self._SUMS_INPUT:
+            raise NotImplementedError("bindsnet_amd: sum_input=True is outside the accelerated path (only "
+                                      "bindsnet.conversion.SubtractiveResetIFNodes takes it)")
         self.traces, self.traces_additive, self.sum_input = traces, traces_additive, sum_input
         self.register_buffer("s", torch.ByteTensor())
         if traces:
@@ -72,6 +73,8 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
             self.register_buffer("tc_trace", _buf(tc_trace))
             self.register_buffer("trace_scale", _buf(trace_scale))
             self.register_buffer("trace_decay", torch.empty_like(self.tc_trace))
+        if sum_input:
+            self.register_buffer("summed", torch.FloatTensor())      # (behind the trace buffers, as in the reference: nodes.py:80-81)
         self.dt = None
         self.batch_size = None
         self.learning = learning
@@ -88,11 +91,15 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         self.s = torch.zeros(batch_size, *self.shape, device=dev, dtype=torch.bool)
         if self.traces:
             self.x = torch.zeros(batch_size, *self.shape, device=dev)
+        if self.sum_input:
+            self.summed = torch.zeros(batch_size, *self.shape, device=self.summed.device)
 
     def reset_state_variables(self) -> None:
         self.s.zero_()
         if self.traces:
             self.x.zero_()
+        if self.sum_input:
+            self.summed.zero_()
 
     def train(self, mode: bool = True) -> "Nodes":
         self.learning = mode
@@ -103,6 +110,8 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
     # value per neuron -- the pairs the reference itself runs (INTEGRATION.md section 3 has the table).  `trace_scale` only with
     # additive traces.  The tc_* constants reach the kernels through compute_decays(), as in the reference.
     _PERVEC = ("trace_decay", "trace_scale")
+    # whether the class takes sum_input=True (nodes.py:105-107: `summed += x` behind every step); every class without it raises
+    _SUMS_INPUT = False
 
     def _state_device(self) -> torch.device:
         v = getattr(self, "v", None)
@@ -182,7 +191,7 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
         the layer may consume."""
         raise NotImplementedError(f"bindsnet_amd: layer type {type(self).__name__} is outside the accelerated path (Input, "
                                   "McCullochPitts, IFNodes, LIFNodes, BoostedLIFNodes, CurrentLIFNodes, AdaptiveLIFNodes, "
-                                  "DiehlAndCookNodes, IzhikevichNodes, SRM0Nodes, CSRMNodes)")
+                                  "DiehlAndCookNodes, IzhikevichNodes, SRM0Nodes, CSRMNodes, SubtractiveResetIFNodes, PassThroughNodes)")
 
     def _host_step(self, x: torch.Tensor) -> None:
         """One step on the host path (network/host_path.py)."""

@@ -244,6 +244,8 @@ class Connection(_DenseConnection):
     def _apply(self, fn, *args, **kwargs):
         """nn.Module.to() / cuda() hook: an existing window moves with the weights (the reference leaves it behind)."""
         out = super()._apply(fn, *args, **kwargs)
+        if self.w.is_cuda and not self.w.is_contiguous():      # (ann_to_snn's `weight.t()`: same values and shape, row-major for the kernels)
+            self.w.data = self.w.data.contiguous()
         win = self.__dict__.get("_win")
         if win is not None:
             for key in ("host", "ring"):
@@ -296,6 +298,10 @@ class Connection(_DenseConnection):
         return out
 
     def _describe(self, d, B: int, dev, scratch) -> list:
+        if self.w.numel() != self.source.n * self.target.n or (self.b is not None and self.b.numel() != self.target.n):
+            # (what torch's matmul / broadcast raises in the first step of the reference; here before the run changes state)
+            raise RuntimeError(f"Connection: w {tuple(self.w.shape)} and b {None if self.b is None else tuple(self.b.shape)} do not fit "
+                               f"{self.source.n} source and {self.target.n} target neurons")
         described = super()._describe(d, B, dev, scratch)
         if isinstance(self.target, CSRMNodes):
             win = self._window_ring(B, dev)
@@ -818,6 +824,8 @@ class Conv2dConnection(AbstractConnection):
                         accumulate=accumulate)
 
     def _describe(self, d, B, dev, scratch):
+        if self.b.numel() != self.out_channels:       # (F.conv2d's RuntimeError in the first step of the reference; here before the run changes state)
+            raise RuntimeError(f"Conv2dConnection: the bias has {self.b.numel()} entries, the convolution {self.out_channels} output channels")
         described = super()._describe(d, B, dev, scratch)
         d.cin, d.h, d.wd = self.in_channels, self.source.shape[1], self.source.shape[2]
         d.cout, d.kh, d.kw = self.out_channels, self.kernel_size[0], self.kernel_size[1]

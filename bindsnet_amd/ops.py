@@ -406,6 +406,65 @@ def csrm_step(v, s, x, theta, xwin, last, resK, refK, p, raster_s=None, raster_v
                               _ptr(raster_v, F32, True), _stream()), "csrm_step")
 
 
+def sif_step(v, refrac, s, x, I, p: LifParams, summed=None, raster_s=None, raster_v=None, pv=None):
+    """f14: SubtractiveResetIFNodes.forward (conversion/nodes.py:73-99); summed f32 [B, N] (sum_input) takes the raw input."""
+    B, N = _node_args(v)
+    arg, _keep = _pv(pv, N)
+    if I.numel() != B * N or (summed is not None and summed.numel() != B * N):
+        raise ValueError("sif_step: the input and `summed` must have the layer's [B, N] elements")
+    check(lib().snn_sif_step_pv(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(summed, F32, True), _ptr(I, F32),
+                                B, N, C.byref(p), arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "sif_step")
+
+
+def pass_step(s, I, raster_s=None):
+    """f14: PassThroughNodes.forward (conversion/nodes.py:161-169) with the spikes kept as bytes: s [B, N] = (I != 0)."""
+    B = s.shape[0]
+    if I.numel() != s.numel():
+        raise ValueError("pass_step: the input must have the layer's [B, N] elements")
+    check(lib().snn_pass_step(_ptr(s, "spike"), _ptr(I, F32), B, s.numel() // B, _ptr(raster_s, "spike", True), _stream()), "pass_step")
+
+
+def gather_geometry(src_shape, out_shape, strides, offsets):
+    """f14: the four int[3] arrays of snn_prop_gather_f32 (output extents, source extents in the output's order, source strides,
+    leading offsets) for a gather of rank <= 3; missing leading dimensions are 1 / 1 / 0 / 0."""
+    nd = len(out_shape)
+    fields = [tuple(int(v) for v in f) for f in (out_shape, src_shape, strides, offsets)]
+    if nd < 1 or nd > 3 or any(len(f) != nd for f in fields):
+        raise ValueError("gather_geometry: one to three dimensions, the same number in every field")
+    return [(C.c_int * 3)(*((u,) * (3 - nd) + f)) for u, f in zip((1, 1, 0, 0), fields)]
+
+
+def permute_geometry(src_shape, dims):
+    """The gather of `s.permute(0, *[d + 1 for d in dims])` over a sample of shape src_shape: (arrays, permuted shape)."""
+    src_shape = tuple(int(v) for v in src_shape)
+    row_major = [1] * len(src_shape)
+    for a in range(len(src_shape) - 2, -1, -1):
+        row_major[a] = row_major[a + 1] * src_shape[a + 1]
+    out = tuple(src_shape[d] for d in dims)
+    return gather_geometry(out, out, [row_major[d] for d in dims], (0,) * len(dims)), out
+
+
+def pad_geometry(src_shape, before, after):
+    """The gather of a zero padding of `before[a]` / `after[a]` elements around every dimension of a sample: (arrays, padded shape)."""
+    src_shape = tuple(int(v) for v in src_shape)
+    row_major = [1] * len(src_shape)
+    for a in range(len(src_shape) - 2, -1, -1):
+        row_major[a] = row_major[a + 1] * src_shape[a + 1]
+    out = tuple(n + int(b) + int(e) for n, b, e in zip(src_shape, before, after))
+    return gather_geometry(src_shape, out, row_major, before), out
+
+
+def prop_gather(s, out, arrays, accumulate=False):
+    """f14: PermuteConnection / ConstantPad2dConnection.compute: out f32 [B, *out shape] (+)= float(s[b, gathered index]), 0 in the
+    padding; `arrays` from permute_geometry / pad_geometry."""
+    B = s.shape[0]
+    n_out = arrays[0][0] * arrays[0][1] * arrays[0][2]
+    if out.shape[0] != B or out.numel() != B * n_out:
+        raise ValueError(f"prop_gather: out must hold [{B}, {n_out}] elements, got {tuple(out.shape)}")
+    check(lib().snn_prop_gather_f32(_ptr(s, "spike"), _ptr(out, F32), B, s.numel() // B, *arrays, int(accumulate), _stream()), "prop_gather")
+    return out
+
+
 def izh_step(v, u, s, x, I, a, b, c, d, St, p: LifParams, raster_s=None, raster_v=None, pv=None):
     """IzhikevichNodes.forward (nodes.py:1265-1296) in one launch; s holds the previous step's spikes at entry; St is the
     lateral matrix transposed ([N, N], St[i, j] = S[j, i]); the lateral sum is added to I in place."""

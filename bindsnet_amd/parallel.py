@@ -101,6 +101,10 @@ def _reject_stochastic(network, mode: str) -> None:
         if isinstance(layer, CSRMNodes):
             raise NotImplementedError(f"{mode}: layer '{name}' (CSRMNodes) takes a window of currents and shares its threshold adaptation over the "
                                       "global batch, which the multi-device modes do not reproduce; run the network on one device")
+    for name, layer in network.layers.items():          # bindsnet.conversion's layers: generic plan of one device only
+        if type(layer).__name__ in ("SubtractiveResetIFNodes", "PassThroughNodes"):
+            raise NotImplementedError(f"{mode}: layer '{name}' ({type(layer).__name__}) is not supported by the multi-device modes; "
+                                      "run the network on one device")
     for key, conn in network.connections.items():      # (the rule first: its target is always an SRM0 layer)
         if type(conn._rule()).__name__ == "Rmax":
             raise NotImplementedError(f"{mode}: Rmax on connection {key} is not supported by the multi-device modes (the rule is defined for "

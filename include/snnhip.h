@@ -375,6 +375,31 @@ int snn_csrm_step(float *v, uint8_t *s, float *x, float *theta, const float *xwi
                   const float *refK, int Wref, int B, int N, const snn_dc_params *h_p, const snn_pervec *pv, uint8_t *raster_s,
                   float *raster_v, snn_stream_t stream);
 
+/* ---- f14: bindsnet.conversion -- SubtractiveResetIFNodes, PassThroughNodes, PermuteConnection, ConstantPad2dConnection ----
+ * snn_sif_step      bindsnet/conversion/nodes.py:73-99, one launch, state streamed once.  Per element, every operation one
+ *                   rounded f32 operation:  v += float(refrac == 0) * I;  refrac = float(refrac > 0) * (refrac - dt);
+ *                   s = v >= thresh;  where s: refrac = h_p->refrac, v = v - thresh (reset by subtraction: `reset` is only
+ *                   the value reset_state_variables() fills in);  lbound;  trace;  summed += I (the raw input; `summed`
+ *                   f32 [B,N] nullable -- Nodes(sum_input=True) -- and free when NULL: a kernel instance of its own).
+ *                   Uses thresh, refrac, dt, lbound and the trace fields.  pv (the _pv form) may name trace_decay and
+ *                   trace_scale only: the reference's `v[s] - thresh` cannot broadcast a tensor-valued threshold either.
+ * snn_pass_step     bindsnet/conversion/nodes.py:161-169: s = I, kept as a spike byte (I != 0; what feeds such a layer
+ *                   emits 0.0 or 1.0), plus the raster_s slice.  No voltage, no trace, no summed.
+ * snn_prop_gather_f32  PermuteConnection.compute (`s.permute(dims).float()`, dims[0] == 0) and ConstantPad2dConnection
+ *                   .compute (`F.pad(s, padding).float()`, fill 0) as one gather: out f32 [B, out[0], out[1], out[2]],
+ *                   s spike bytes [B, n_src];  out[b, i0, i1, i2] (+)= float(s[b, sum_a (i_a - off[a]) * stride[a]]) where
+ *                   every i_a - off[a] lies in [0, src[a]), else (+)= 0.  out / src / stride / off are HOST arrays of three
+ *                   ints (missing leading dimensions: extent 1, stride 0, offset 0); there is no index table.  A geometry
+ *                   that could read outside [0, n_src) or that crops (off[a] + src[a] > out[a]) is SNN_ERR_INVALID.
+ *                   accumulate as snn_prop_pool_f32.  (ABI 8, additive)                                                    */
+int snn_sif_step(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, int B, int N,
+                 const snn_lif_params *h_p, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_sif_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, int B, int N,
+                    const snn_lif_params *h_p, const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
+int snn_pass_step(uint8_t *s, const float *I, int B, int N, uint8_t *raster_s, snn_stream_t stream);
+int snn_prop_gather_f32(const uint8_t *s, float *out, int B, int n_src, const int *out_ext, const int *src_ext,
+                        const int *stride, const int *off, int accumulate, snn_stream_t stream);
+
 /* ---- device-resident emulation of torch's CPU generator --------------------------------------
  * Replaces the pre-drawn noise_q stream: the library reproduces the draws torch.multinomial
  * (bindsnet/network/nodes.py:1100-1102) would consume -- mt19937 -> random64 -> u in [0,1) ->
@@ -529,15 +554,21 @@ int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream
 /* ---- a1: Network.run ------------------------------------------------------------------------
  * bindsnet/network/network.py:380-465 (the per-timestep loop and the post-loop normalisation),
  * for graphs built from {Input, LIFNodes, DiehlAndCookNodes / AdaptiveLIFNodes, McCullochPitts, IFNodes, BoostedLIFNodes,
- * CurrentLIFNodes, IzhikevichNodes} x {MulticompartmentConnection+Weight, Connection, SparseConnection, Conv1d / Conv2d /
- * Conv3dConnection, LocalConnection1D / 2D / 3D, MaxPool1d / 2d / 3dConnection, MeanFieldConnection} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
+ * CurrentLIFNodes, IzhikevichNodes, SRM0Nodes, CSRMNodes, SubtractiveResetIFNodes, PassThroughNodes} x {MulticompartmentConnection+Weight,
+ * Connection, SparseConnection, Conv1d / Conv2d / Conv3dConnection, LocalConnection1D / 2D / 3D, MaxPool1d / 2d / 3dConnection,
+ * MeanFieldConnection, PermuteConnection, ConstantPad2dConnection} x {no rule, PostPre, MSTDP, ...}.  The fused plans match Input / LIF / DC graphs only; a graph
  * with any other layer kind runs the generic plan.  The descriptors are HOST
  * structs holding DEVICE pointers; layers and connections are listed in network insertion
  * order, which fixes the evaluation order exactly as the reference's dict iteration does.   */
 /* SNN_LAYER_MCP .. SNN_LAYER_IZH (nodes.py:231, :308, :562, :681, :1147; generic plan only) and the aux / izh_* fields at the
  * end of snn_layer_desc were added without changing SNN_ABI_VERSION, like the additive connection kinds below.  */
 enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP = 3, SNN_LAYER_IF = 4, SNN_LAYER_BOOSTED = 5,
-       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7, SNN_LAYER_SRM0 = 8, SNN_LAYER_CSRM = 9 };
+       SNN_LAYER_CURRENT = 6, SNN_LAYER_IZH = 7, SNN_LAYER_SRM0 = 8, SNN_LAYER_CSRM = 9, SNN_LAYER_SIF = 10, SNN_LAYER_PASS = 11 };
+/* SNN_LAYER_SIF (conversion/nodes.py:8, SubtractiveResetIFNodes; `summed` at the end of snn_layer_desc) and SNN_LAYER_PASS
+ * (conversion/nodes.py:122, PassThroughNodes: `s` and `current` only -- inject_v and ext_current are SNN_ERR_UNSUPPORTED, and
+ * every connection into it must be POOL, PERMUTE or PAD, whose outputs are 0 or 1), with SNN_CONN_PERMUTE / SNN_CONN_PAD
+ * (conversion/topology.py: no `w`; the gat_* fields at the end of snn_conn_desc; propagation only, refused like POOL), were added
+ * the same way: generic plan only, SNN_ABI_VERSION unchanged.  */
 /* SNN_LAYER_SRM0 (nodes.py:1555; generic plan only, needs snn_run_desc.rng) with the srm_* fields at the end of snn_layer_desc, and
  * SNN_RULE_RMAX (learning.py:2858; a DENSE connection into an SRM0 layer, batch 1) with rmax_tc_c at the end of snn_conn_desc,
  * were added the same way: SNN_ABI_VERSION unchanged.  */
@@ -555,7 +586,7 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP =
  * (MeanFieldConnection: `w` of w_numel elements) came the same way: propagation only -- a rule is SNN_ERR_UNSUPPORTED, a norm,
  * mask, bias or weight monitor SNN_ERR_INVALID --, generic plan only, SNN_ABI_VERSION unchanged.  */
 enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5,
-       SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7 };
+       SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7, SNN_CONN_PERMUTE = 8, SNN_CONN_PAD = 9 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5, SNN_RULE_RMAX = 6 };
 
@@ -601,6 +632,9 @@ typedef struct {
     float *csrm_xwin, *csrm_last;
     const float *csrm_resk, *csrm_refk;
     int csrm_wres, csrm_wref;
+    /* SIF (snn_sif_step): the layer's `summed` f32 [B,n] -- Nodes(sum_input=True): every step adds the layer's raw input --, NULL
+     * without sum_input.  Any other kind with it is SNN_ERR_INVALID.  Added like the fields above: SNN_ABI_VERSION stays. */
+    float *summed;
 } snn_layer_desc;
 
 typedef struct {
@@ -673,6 +707,10 @@ typedef struct {
     int window;
     uint8_t *win_ring;
     int win_head, win_size;
+    /* PERMUTE / PAD: the geometry of snn_prop_gather_f32 -- output extents, source extents in the output's dimension order, the
+     * source stride and the leading offset per output dimension (three ints each, missing leading dimensions 1 / 1 / 0 / 0).
+     * prod(gat_out) == the target's n; `w` is NULL.  Added like the fields above: SNN_ABI_VERSION stays. */
+    int gat_out[3], gat_src[3], gat_stride[3], gat_off[3];
 } snn_conn_desc;
 
 typedef struct {
