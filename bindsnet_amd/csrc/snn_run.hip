@@ -237,6 +237,12 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if (R->B != 1) return SNN_ERR_UNSUPPORTED;
         }
         if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_PAD) return SNN_ERR_INVALID;
+        if (d.w_dtype != SNN_W_F32) {          // a float16 / bfloat16 Weight: MCC with that one feature, no rule or PostPre, nothing that reads `w` as f32
+            if (d.w_dtype != SNN_W_F16 && d.w_dtype != SNN_W_BF16) return SNN_ERR_INVALID;
+            if (d.kind != SNN_CONN_MCC || d.pipe_n != 0 || (d.rule != SNN_RULE_NONE && d.rule != SNN_RULE_POSTPRE) || d.raster_w || d.mask)
+                return SNN_ERR_UNSUPPORTED;
+            if (d.rule == SNN_RULE_POSTPRE && R->B > 256) return SNN_ERR_UNSUPPORTED;
+        }
         if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) {        // PermuteConnection / ConstantPad2dConnection: a gather, propagation only
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
             if (d.has_norm || d.mask || d.raster_w || d.bias || d.w) return SNN_ERR_INVALID;
@@ -326,6 +332,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                     }
                     TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, D.current, B, S.n, D.n, acc, st));
                 }
+                else if (d.kind == SNN_CONN_MCC && d.w_dtype != SNN_W_F32) TRY(snn_prop_cascade_h16(d.w, d.w_dtype, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
                 else if (d.window) TRY(snn_prop_window_f32(d.w, d.bias, d.win_ring, (d.win_head + t) % d.win_size, sp, D.csrm_xwin, B, d.win_size,
                                                            S.n, D.n, acc, st));
@@ -427,6 +434,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && d.kind == SNN_CONN_CONV2D)
                     TRY(snn_conv2d_hebbian(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
                                            d.rule == SNN_RULE_WDPOSTPRE, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
+                else if (d.rule == SNN_RULE_POSTPRE && d.w_dtype != SNN_W_F32)
+                    TRY(snn_stdp_postpre_h16(d.w, d.w_dtype, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
+                                             d.has_min, d.wmin, d.has_max, d.wmax, st));
                 else if (d.rule == SNN_RULE_POSTPRE)
                     TRY(snn_stdp_postpre(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                          d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, st));
@@ -522,6 +532,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     bool local = false;                                                // LocalConnection1D / 2D / 3D, Conv1d / Conv3dConnection: generic
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection, PermuteConnection, ConstantPad2dConnection) plan only; no fused plan is offered the graph
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
+    for (int c = 0; c < nC; ++c) if (C[c].w_dtype != SNN_W_F32) local = true;   // ... and float16 / bfloat16 weights (the fused plans keep f32 tiles)
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));
@@ -538,6 +549,8 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c)
         if (C[c].has_norm && C[c].kind == SNN_CONN_LOCAL)     // topology.py:1601 / :1748-1759 / :1898: every [kernel_prod] row to sum `norm`
             TRY(snn_normalize_conv2d(C[c].w, C[c].cin * C[c].local_F * C[c].local_conv_prod, C[c].local_kernel_prod, C[c].norm, st));
+        else if (C[c].has_norm && C[c].w_dtype != SNN_W_F32)
+            TRY(snn_normalize_h16(C[c].w, C[c].w_dtype, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_ws, st));
         else if (C[c].has_norm && !((normalized >> c) & 1u))
             TRY(snn_normalize(C[c].w, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_abs, C[c].norm_ws, st));
     return SNN_OK;

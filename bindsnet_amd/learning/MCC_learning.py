@@ -1,6 +1,7 @@
 """Learning rules for MulticompartmentConnection features: API mirror of
 bindsnet/learning/MCC_learning.py for `MCC_LearningRule`, `NoOp`, `PostPre`, `MSTDP`, `MSTDPET`.
-The updates themselves are snn_stdp_postpre (use_dt = 1) / snn_mstdp_step / snn_mstdpet_step."""
+The updates themselves are snn_stdp_postpre (use_dt = 1; snn_stdp_postpre_h16 on a float16 / bfloat16 Weight) / snn_mstdp_step /
+snn_mstdpet_step."""
 import warnings
 from typing import Optional, Sequence, Union
 
@@ -39,6 +40,13 @@ class MCC_LearningRule(_lib.Touching):
             reduction = torch.squeeze if self.source.batch_size == 1 else torch.sum
         self.reduction = reduction
         self.decay = 1.0 - decay if decay else 1.0
+
+    def _float32_only(self) -> None:
+        """The reward-modulated rules keep float32 state beside the weights: a float16 / bfloat16 Weight is refused by name."""
+        dtype = getattr(self.feature_value, "dtype", torch.float32)
+        if dtype in (torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"bindsnet_amd: MCC {type(self).__name__} on a {dtype} Weight is not supported "
+                                      "(NoOp and PostPre are)")
 
     def _bounds(self):
         def one(v):
@@ -136,6 +144,7 @@ class MSTDP(MCC_LearningRule):
         from ..network.topology import MulticompartmentConnection
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        self._float32_only()
         if kwargs.get("average_update", 0):
             raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         if self.reduction not in (torch.sum, torch.squeeze):
@@ -195,6 +204,7 @@ class MSTDPET(MCC_LearningRule):
         from ..network.topology import MulticompartmentConnection
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
+        self._float32_only()
         if kwargs.get("average_update", 0):
             raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))

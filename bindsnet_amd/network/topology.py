@@ -1162,7 +1162,9 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
     """Feature-pipeline connection (reference: topology.py:402-537).  A pipeline of exactly one `Weight` is
     snn_prop_cascade_f32; every other ordered pipeline of up to 8 features out of Probability / Mask / Weight / Bias /
     Intensity is a feature program evaluated per synapse (snn_mcc_bernoulli + snn_prop_mcc_pipe_f32 on the device,
-    host_path._propagate_mcc_pipe on the host)."""
+    host_path._propagate_mcc_pipe on the host).  The single Weight may be float16 or bfloat16 (DiehlAndCook2015(w_dtype=...)):
+    snn_prop_cascade_h16 / snn_stdp_postpre_h16 / snn_normalize_h16 with the reference's roundings (csrc/snn_half.hpp), NoOp or
+    PostPre only; plain torch on the host."""
 
     _kind = _lib.CONN_MCC
     _norm_by = "columns"               # the Weight's SIGNED column sums (topology_features.py:250-266), by snn_net_run
@@ -1221,6 +1223,31 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
                                       "(a single Weight is)")
         return self.pipeline[0]
 
+    def _half_dtype(self):
+        """torch.float16 / torch.bfloat16 if a feature's value has that dtype, else None."""
+        for f in self.pipeline:
+            if isinstance(f.value, torch.Tensor) and f.value.dtype in ops.HALF:
+                return f.value.dtype
+        return None
+
+    def _run_refusal(self, mask, monitored: bool):
+        """What a float16 / bfloat16 Weight cannot run, asked by Network.run before anything changes: it is supported as the single
+        feature of the pipeline, without a rule or with PostPre, unmonitored."""
+        half = self._half_dtype()
+        if half is None:
+            return None
+        from ..learning import MCC_learning
+        if monitored:
+            return NotImplementedError(f"bindsnet_amd: a Monitor on a MulticompartmentConnection with a {half} Weight is not supported")
+        if self._single():
+            feat = self.pipeline[0]
+            if isinstance(feat.learning_rule, (MCC_learning.MSTDP, MCC_learning.MSTDPET)):
+                return NotImplementedError(f"bindsnet_amd: MCC {type(feat.learning_rule).__name__} on a {half} Weight is not supported "
+                                           "(NoOp and PostPre are)")
+            if isinstance(feat.norm, torch.Tensor):
+                return NotImplementedError(f"bindsnet_amd: tensor norms are not supported on a {half} Weight")
+        return None
+
     def _on_host(self) -> bool:
         return bool(self.pipeline) and all(isinstance(f.value, torch.Tensor) and not f.value.is_cuda for f in self.pipeline)
 
@@ -1237,6 +1264,9 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         dev = self.pipeline[0].value.device
         out = torch.empty(B, self.target.n, device=dev)
         self._prop_into(s.reshape(B, -1).contiguous(), out)
+        half = self._half_dtype() if self._single() else None
+        if half is not None:                    # the reference returns the sum in the Weight's dtype; the values already are
+            out = out.to(half)
         return out.view(B, *self.target.shape)
 
     def _host_compute(self, s):
@@ -1332,11 +1362,16 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         if feat.value.device != dev:
             feat.to(dev)
         val = feat.value
-        if val.dtype != torch.float32 or not val.is_contiguous() or tuple(val.shape) != (self.source.n, self.target.n):
-            raise NotImplementedError(f"bindsnet_amd: Weight.value must be a contiguous float32 [{self.source.n}, "
+        if (val.dtype != torch.float32 and val.dtype not in ops.HALF) or not val.is_contiguous() or \
+                tuple(val.shape) != (self.source.n, self.target.n):
+            raise NotImplementedError(f"bindsnet_amd: Weight.value must be a contiguous float32, float16 or bfloat16 [{self.source.n}, "
                                       f"{self.target.n}] tensor (got {val.dtype}, shape {tuple(val.shape)}, "
                                       f"contiguous={val.is_contiguous()})")
-        d.kind, d.w = self._kind, dptr(val.data)
+        err = self._run_refusal(None, False)
+        if err is not None:
+            raise err
+        # (float16 / bfloat16: `w` points at 2-byte elements and the run takes the generic plan's *_h16 kernels, csrc/snn_half.hip)
+        d.kind, d.w, d.w_dtype = self._kind, dptr(val.data), ops.HALF.get(val.dtype, _lib.W_F32)
         if feat.norm is not None:
             if isinstance(feat.norm, torch.Tensor):
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")

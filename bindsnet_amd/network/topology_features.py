@@ -79,7 +79,8 @@ class AbstractFeature(_lib.Touching):
         self.learning_rule.update(**kwargs)
 
     def normalize(self) -> None:
-        """Reference: topology_features.py:250-266 (signed column sums) -> snn_normalize(use_abs=0)."""
+        """Reference: topology_features.py:250-266 (signed column sums) -> snn_normalize(use_abs=0); a float16 / bfloat16 value ->
+        snn_normalize_h16 (the reference's three roundings: csrc/snn_half.hpp)."""
         if self.norm is None:
             return
         if isinstance(self.norm, torch.Tensor):
@@ -111,6 +112,8 @@ class Weight(AbstractFeature):
         if norm_frequency != "sample":
             raise NotImplementedError("bindsnet_amd: norm_frequency='time step' is outside the accelerated path")
         self.norm_frequency, self.enforce_polarity = norm_frequency, enforce_polarity
+        if value_dtype in (torch.float16, torch.bfloat16) and isinstance(norm, torch.Tensor):
+            raise NotImplementedError(f"bindsnet_amd: tensor norms are not supported on a {value_dtype} Weight")
         super().__init__(name=name, value=value, value_dtype=value_dtype,
                          range=[-torch.inf, +torch.inf] if range is None else range, norm=norm,
                          learning_rule=learning_rule, nu=nu, reduction=reduction, decay=decay, sparse=sparse,

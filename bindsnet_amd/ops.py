@@ -34,6 +34,8 @@ def _ptr(t, dtype=None, allow_none=False):
 
 
 F32 = torch.float32
+# Weight.value dtypes beside float32 and their snn_conn_desc.w_dtype codes: the *_h16 entry points (csrc/snn_half.hip)
+HALF = {torch.float16: _lib.W_F16, torch.bfloat16: _lib.W_BF16}
 
 
 def _bounds(wmin, wmax):
@@ -46,6 +48,10 @@ def prop_cascade(W, s, out, accumulate=False):
     B = s.shape[0]
     Nin, N = W.shape
     assert s.numel() == B * Nin and out.numel() == B * N
+    if W.dtype in HALF:                 # a float16 / bfloat16 Weight: the f32 sum, rounded once to W's dtype, into the f32 current
+        check(lib().snn_prop_cascade_h16(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate),
+                                         _stream()), "prop_cascade_h16")
+        return out
     check(lib().snn_prop_cascade_f32(_ptr(W, F32), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate),
                                      _stream()), "prop_cascade")
     return out
@@ -507,6 +513,11 @@ def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=
                  assume_clamped=False):
     B = s_src.shape[0]
     Nin, N = W.shape
+    if W.dtype in HALF:                 # (every element is visited: assume_clamped has nothing to skip)
+        check(lib().snn_stdp_postpre_h16(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
+                                         _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax), _stream()),
+              "stdp_postpre_h16")
+        return
     check(lib().snn_stdp_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                  _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay,
                                  *_bounds(wmin, wmax), int(assume_clamped), _stream()), "stdp_postpre")
@@ -578,6 +589,11 @@ def normalize(W, norm, use_abs, ws=None):
     Nin, N = W.shape
     if ws is None:
         ws = torch.empty(N, dtype=F32, device=W.device)
+    if W.dtype in HALF:
+        if use_abs:
+            raise NotImplementedError(f"bindsnet_amd: normalisation by absolute column sums computes in float32 only (got {W.dtype})")
+        check(lib().snn_normalize_h16(_ptr(W, W.dtype), HALF[W.dtype], Nin, N, norm, _ptr(ws, F32), _stream()), "normalize_h16")
+        return
     check(lib().snn_normalize(_ptr(W, F32), Nin, N, norm, int(use_abs), _ptr(ws, F32), _stream()), "normalize")
 
 

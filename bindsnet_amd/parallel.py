@@ -72,6 +72,10 @@ def _reject_local(network, mode: str) -> None:
     weights are not [source.n, target.n] matrices): such a graph raises instead of being routed through a mode built for other
     layouts."""
     for key, conn in network.connections.items():
+        half = conn._half_dtype() if hasattr(conn, "_half_dtype") else None
+        if half is not None:               # the modes merge, slice and gather float32 matrices
+            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a {half} Weight; the multi-device modes compute in "
+                                      "float32 only; run the network on one device")
         if not conn._multi_device:
             if hasattr(conn, "pipeline"):
                 raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "
@@ -526,6 +530,7 @@ def exact_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, c
     from .network.monitors import Monitor
     from .network.nodes import DiehlAndCookNodes, Input
     assert type(inputs) == dict, "'inputs' must be a dict of names of layers (str) and relevant input tensors."
+    _reject_local(network, "exact_run")                       # (before the batch size below is taken from the inputs)
     if comm is not None:
         world, rank = comm.world, comm.rank
     else:

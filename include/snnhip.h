@@ -519,6 +519,25 @@ int snn_normalize(float *W, int Nin, int N, float norm, int use_abs, float *cols
  * row_sum, leftovers, then the lanes), no zero guard like the reference.  (ABI 6)                                  */
 int snn_normalize_conv2d(float *W, int n_filters, int taps, float norm, snn_stream_t stream);
 
+/* ---- f12: float16 / bfloat16 Weight features --------------------------------------------------
+ * A MulticompartmentConnection whose single Weight has value_dtype torch.float16 or torch.bfloat16 (w_dtype 1 / 2, SNN_W_*): W is
+ * the [Nin, N] value as 2-byte elements; neuron state, traces and currents stay f32.  All arithmetic is f32 on exactly widened
+ * values, with one round-to-nearest-even conversion to the weight dtype ("->h", overflow to +-inf) where the reference stores
+ * into or produces a tensor of that dtype (csrc/snn_half.hpp):
+ *   snn_prop_cascade_h16   snn_prop_cascade_f32's sum over the widened weights, ->h, widened, stored (0 + r) or added to out;
+ *   snn_stdp_postpre_h16   MCC_learning.py:224-302 + :86-110: w = (w - pre*dt)->h if nu0 != 0; w = (w + post*dt)->h if
+ *                          nu1 != 0; w = (w * decay)->h; clamp.  pre / post: f32 batch sums (B = 1: squeeze).  Limits: B <= 256;
+ *   snn_normalize_h16      topology_features.py:250-266: cs = colsum->h (0 -> 1), r = (1/cs)->h, f = (r*norm)->h, w = (w*f)->h;
+ *                          colsum_ws: device scratch of N floats.
+ * Spike bytes are 0 or 1.  Added without changing SNN_ABI_VERSION: purely additive.                              */
+enum { SNN_W_F32 = 0, SNN_W_F16 = 1, SNN_W_BF16 = 2 };
+int snn_prop_cascade_h16(const void *W, int w_dtype, const uint8_t *s, float *out, int B, int Nin, int N, int accumulate,
+                         snn_stream_t stream);
+int snn_stdp_postpre_h16(void *W, int w_dtype, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                         const float *x_tgt, int B, int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay,
+                         int has_min, float wmin, int has_max, float wmax, snn_stream_t stream);
+int snn_normalize_h16(void *W, int w_dtype, int Nin, int N, float norm, float *colsum_ws, snn_stream_t stream);
+
 /* ---- f2: spike encoders on the device ---------------------------------------------------------
  * bindsnet/encoding/encodings.py:51-98 (bernoulli): out [steps, n] u8 = what torch.bernoulli(max_prob *
  * datum.repeat([steps, 1])) draws from the HOST generator whose state is in *rng -- one 32-bit mt19937 output
@@ -711,6 +730,11 @@ typedef struct {
      * source stride and the leading offset per output dimension (three ints each, missing leading dimensions 1 / 1 / 0 / 0).
      * prod(gat_out) == the target's n; `w` is NULL.  Added like the fields above: SNN_ABI_VERSION stays. */
     int gat_out[3], gat_src[3], gat_stride[3], gat_off[3];
+    /* The element type of `w` (SNN_W_*): 0 float32, as ever; 1 float16 / 2 bfloat16 -- `w` then points at 2-byte elements and the
+     * connection runs snn_prop_cascade_h16 / snn_stdp_postpre_h16 / snn_normalize_h16.  MCC with one Weight only (pipe_n 0), rule
+     * NONE or POSTPRE, no weight monitor, no mask: anything else is SNN_ERR_UNSUPPORTED.  A non-zero w_dtype sends the graph to the
+     * generic plan, as per-neuron parameters do.  Added like the fields above: SNN_ABI_VERSION stays. */
+    int w_dtype;
 } snn_conn_desc;
 
 typedef struct {
