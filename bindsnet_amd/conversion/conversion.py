@@ -18,8 +18,10 @@ with the batch-inclusive dims; a Conv2d without bias gets zeros(layer.shape[1]),
 grows by padding[0] + padding[1], the left and right pads.  Where the resulting graph cannot run, the run raises before it
 changes any state.  `torch.load` of a path is called as the reference calls it.
 
-On the device the limits of the parts apply: Conv2d with at most 16 input channels, dilation 1, symmetric stride and padding;
-uint8 / bool input spikes; no fused plan (`network.last_plan == "generic"`); no monitor on `summed`."""
+On the device the limits of the parts apply: Conv2d with dilation 1, symmetric stride and padding; uint8 / bool input spikes; no
+fused plan (`network.last_plan == "generic"`); no monitor on `summed`.  A Conv2d with more than 16 input channels runs in the stated
+order of snn_prop_conv2d_f32 (include/snnhip.h): equal to the reference bit for bit where every partial sum is exact, else up to
+summation rounding."""
 import warnings
 from copy import deepcopy
 from typing import Dict, Optional, Sequence, Union

@@ -627,6 +627,7 @@ bool convpp_match(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int n
     if (d.kind != SNN_CONN_CONV2D || d.src != 0 || d.dst != 1 || d.has_norm || d.mask || d.raster_w) return false;
     if (d.rule != SNN_RULE_POSTPRE && d.rule != SNN_RULE_HEBBIAN && d.rule != SNN_RULE_WDPOSTPRE) return false;      // the outer-product rules: same two sums
     if (d.rule == SNN_RULE_WDPOSTPRE && !(d.has_min && d.has_max)) return false;                                     // (the generic plan reports it)
+    if (d.cin > 16) return false;                                                                                    // wide convolutions: the generic plan (snn_conv_wide.hip)
     if (R->T < 1 || R->one_step || R->B < 1 || R->B > 256) return false;
     if (L[0].clamp || L[0].unclamp || L[0].inject_v || L[0].ext_current || L[1].clamp || L[1].unclamp || L[1].inject_v || L[1].ext_current || L[1].thresh_vec) return false;
     memset(&c, 0, sizeof(c));
@@ -657,6 +658,7 @@ int snn_try_fused_convlif(const snn_layer_desc *L, int nL, const snn_conn_desc *
     if (L[0].kind != SNN_LAYER_INPUT || L[1].kind != SNN_LAYER_LIF) return SNN_OK;
     const snn_conn_desc &d = C[0];
     if (d.kind != SNN_CONN_CONV2D || d.src != 0 || d.dst != 1 || d.rule != SNN_RULE_NONE || d.has_norm) return SNN_OK;
+    if (d.cin > 16) return SNN_OK;                                  // wide convolutions: the generic plan (snn_conv_wide.hip)
     if (R->T < 1) return SNN_OK;
     ConvCtx c;
     memset(&c, 0, sizeof(c));

@@ -146,6 +146,9 @@ __global__ __launch_bounds__(256) void k_conv2d(const float *__restrict__ W, con
     }
 }
 
+int snn_conv_wide_launch(const float *W, const float *bias, const uint8_t *s, float *out, int B, int Cin, int H, int Wd, int Cout,
+                         int KH, int KW, int stride, int pad, int OH, int OW, int accumulate, hipStream_t stream);      // snn_conv_wide.hip
+
 extern "C" int snn_prop_conv2d_f32(const float *W, const float *bias, const uint8_t *s, float *out, int B,
                                    int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad,
                                    int accumulate, snn_stream_t stream) {
@@ -154,9 +157,9 @@ extern "C" int snn_prop_conv2d_f32(const float *W, const float *bias, const uint
         return SNN_ERR_INVALID;
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1;
     if (OH <= 0 || OW <= 0) return SNN_ERR_INVALID;
-    if (Cin > 16) return SNN_ERR_UNSUPPORTED;      // the reference's accumulation order is only characterised up to 16 channels
     size_t lds = sizeof(float) * (size_t)Cout * Cin * KH * KW;
-    if (lds > 64 * 1024) return SNN_ERR_UNSUPPORTED;
+    if (Cin > 16 || lds > 64 * 1024)               // more channels than k_conv2d was written for, or a bank beyond its LDS: the same order, slab by slab (snn_conv_wide.hip)
+        return snn_conv_wide_launch(W, bias, s, out, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, accumulate, (hipStream_t)stream);
     const long npix = (long)B * OH * OW;
     // a block of 256 consecutive output pixels touches at most 255 / (OH * OW) + 2 samples: their input images go to LDS when they fit 32 KB
     int nstage = 255 / (OH * OW) + 2;

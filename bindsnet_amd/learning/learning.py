@@ -24,6 +24,9 @@ class LearningRule(_lib.Touching):
         if getattr(connection, "_rules_only", None) and not _descriptor.accepts(connection, self):
             raise NotImplementedError(f"bindsnet_amd: {type(self).__name__} on {type(connection).__name__} is not supported "
                                       f"({connection._rules_only})")
+        refusal = getattr(connection, "_rule_refusal", None)        # a family's own reason against this rule (Conv2dConnection: wide inputs)
+        if refusal is not None and refusal(self) is not None:
+            raise NotImplementedError(refusal(self))
         self.connection = connection
         self.source, self.target = connection.source, connection.target
         self.wmin, self.wmax = connection.wmin, connection.wmax

@@ -787,7 +787,12 @@ class LocalConnection(_DenseConnection):
 class Conv2dConnection(AbstractConnection):
     """2-D convolutional synapses (reference: topology.py:686-844): propagation, PostPre, Hebbian, WeightDependentPostPre, and MSTDP
     at batch 1.  MSTDPET is not offered: the reference's conv2d form (learning.py:2654-2745) never adds the point eligibility to its
-    eligibility trace, so it leaves the weights as they are at batch 1 and fails at larger batches."""
+    eligibility trace, so it leaves the weights as they are at batch 1 and fails at larger batches.
+
+    Propagation takes any number of input channels.  On the device every output is the sequential f32 sum over (kh, kw, cin), input
+    channels innermost, bias last: up to 16 channels that is the reference's own order; beyond, the reference's oneDNN order depends
+    on the host, and the device equals it bit for bit where every partial sum is exact, else up to summation rounding (INTEGRATION.md
+    section 3).  The host path calls F.conv2d itself.  The learning rules stop at 16 input channels (`_rule_refusal`)."""
 
     _kind, _ndim = _lib.CONN_CONV2D, 2
     _norm_by = "after"      # every [KH*KW] filter to sum `norm` (topology.py:824-837): not snn_net_run's column step
@@ -807,9 +812,6 @@ class Conv2dConnection(AbstractConnection):
         if self.dilation != (1, 1) or self.stride[0] != self.stride[1] or self.padding[0] != self.padding[1]:
             raise NotImplementedError("bindsnet_amd: conv2d supports dilation 1 and symmetric stride/padding only")
         self.in_channels, ih, iw = source.shape[0], source.shape[1], source.shape[2]
-        if self.in_channels > 16:
-            raise NotImplementedError("bindsnet_amd: Conv2dConnection with more than 16 input channels is not supported (the "
-                                      "reference's oneDNN accumulation order is only characterised up to 16)")
         self.out_channels = target.shape[0]
         oh = int((ih - self.kernel_size[0] + 2 * self.padding[0]) / self.stride[0] + 1)
         ow = int((iw - self.kernel_size[1] + 2 * self.padding[1]) / self.stride[1] + 1)
@@ -818,6 +820,16 @@ class Conv2dConnection(AbstractConnection):
             "(input_height - filter_height + 2 * padding_height) / stride_height + 1,"
             "(input_width - filter_width + 2 * padding_width) / stride_width + 1")
         _rand_weights(self, (self.out_channels, self.in_channels, *self.kernel_size), self.out_channels, w_dtype, kwargs)
+
+    def _rule_refusal(self, rule):
+        """Why `rule` must not be constructed on this connection, or None: asked by LearningRule.__init__ (the connection's own
+        constructor has not run yet, so the channel count is the source's)."""
+        cin = self.source.shape[0]
+        if cin > 16 and type(rule).__name__ != "NoOp":
+            return (f"bindsnet_amd: {type(rule).__name__} on a Conv2dConnection with {cin} input channels is not supported: the "
+                    f"reference reduces the update with torch.bmm over an operand in_channels * KH * KW wide, whose summation "
+                    f"order has not been characterised beyond 16 input channels (propagation runs at any width; use NoOp or no rule)")
+        return None
 
     def _prop_into(self, s, out, accumulate=False) -> None:
         ops.prop_conv2d(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0],

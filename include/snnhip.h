@@ -143,9 +143,20 @@ int snn_prop_dense_mfma_f32(const float *W, const float *bias, const uint8_t *s,
 
 /* ---- a7: Conv2dConnection.compute ---------------------------------------------------------
  * bindsnet/network/topology.py:799-815 (F.conv2d).  s [B,Cin,H,W] u8, W [Cout,Cin,KH,KW],
- * out [B,Cout,OH,OW]; accumulated sequentially in (kh,kw,cin) order -- taps row-major, input channels
- * innermost: what the reference's oneDNN kernel does for Cin <= 16 (bit-exact against reference fixtures for Cin =
- * 1, 3, 8, 16) --, then bias.  Cin > 16: SNN_ERR_UNSUPPORTED (oneDNN switches kernels, order not characterised). */
+ * out [B,Cout,OH,OW].  Stated order, any Cin: every output element is ONE bias-free sequential f32 sum over (kh,kw,cin) --
+ * taps row-major, input channels innermost, out-of-image taps skipped, one rounding per multiply and per add --, then + bias;
+ * out (+)= that.  The device equals this order (oracle: orc_prop_conv2d) bit for bit for any weights.  Against the reference:
+ * Cin <= 16 -- it is what the reference's oneDNN kernel does (bit-exact against reference fixtures for Cin = 1, 3, 8, 16);
+ * Cin > 16 -- oneDNN takes blocked kernels whose order depends on the host's ISA: equal bit for bit whenever every partial sum
+ * is exactly representable (fixtures with weights on a 1/64 grid), else equal up to summation rounding: per element at most
+ * 2 * gamma_m * sum |t_i| over the m active taps and the bias, gamma_m = m u / (1 - m u), u = 2^-24.
+ * Cin <= 16 with a filter bank Cout*Cin*KH*KW*4 <= 64 KiB: the whole bank in LDS (k_conv2d); every other shape: the ordered
+ * taps in slabs of 512, 8 output channels per workgroup, the block's images staged channels-last in LDS where they fit 48 KiB
+ * (csrc/snn_conv_wide.hip).  Any Cin, Cout, KH, KW, stride >= 1, pad >= 0, B.  SNN_ERR_UNSUPPORTED only where an index leaves
+ * its int: Cin*KH*KW > SNN_CONV2D_MAX_TAPS, Cin*H*Wd or OH*OW > SNN_CONV2D_MAX_IMAGE, or more than 2^31 - 1 blocks of 256
+ * output pixels (B*OH*OW).                                                                                                  */
+#define SNN_CONV2D_MAX_TAPS 0x7fff0000
+#define SNN_CONV2D_MAX_IMAGE 0x7fff0000
 int snn_prop_conv2d_f32(const float *W, const float *bias, const uint8_t *s, float *out,
                         int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
                         int stride, int pad, int accumulate, snn_stream_t stream);
