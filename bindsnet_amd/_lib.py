@@ -330,7 +330,7 @@ def profile_run(net, inputs, time, stride=4, repeats=5, pipelined=False):
 
 
 def graph_stats():
-    """(plain, captured, replayed) run counts of the fused plan."""
+    """(plain, captured, replayed) run counts of the fused plan; the last two are always 0 (no run is captured any more)."""
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
     lib().snn_graph_stats(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value

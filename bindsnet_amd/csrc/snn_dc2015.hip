@@ -679,7 +679,7 @@ uint8_t *snn_input_raster_request(int layer);      // snn_run.hip: a spike monit
 void snn_input_raster_done(int layer);
 unsigned long long snn_twolayer_workspace_bytes(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC,
                                                 const snn_run_desc *R);
-int g_graph_stats[3] = {0, 0, 0};   // runs enqueued as plain launches / captured / replayed
+int g_graph_stats[3] = {0, 0, 0};   // runs enqueued as plain launches / captured / replayed (the last two: always 0, no run is captured any more)
 
 extern "C" void snn_graph_stats(int *h_plain, int *h_captured, int *h_replayed) {
     if (h_plain) *h_plain = g_graph_stats[0];
@@ -811,8 +811,7 @@ int snn_try_fused_dc2015(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     }
     // One run = memset of the exchange words (pad bytes for columns >= N are never written by a workgroup),
     // T+1 launches, and up to two small copies (final X trace sits in xX[(T-1)&1], final generator in rng[T&1]).
-    hipStream_t qs = st;           // stream the run is enqueued on (a private one when graphs are in play)
-    auto enqueue = [&](bool with_events) -> int {
+    auto enqueue = [&]() -> int {
         int rc0;
         if (resident) {
             // memset of the exchange granules (epochs restart at 1 every run), input-only pre-passes, ONE launch
@@ -838,26 +837,24 @@ int snn_try_fused_dc2015(const snn_layer_desc *L, int nL, const snn_conn_desc *C
             key |= 1ull;
             const bool clean = chain && g_ws_key_in == key;
             if (!clean) {
-                if ((rc0 = snn_check(hipMemsetAsync(c.ex, 0, exbytes, qs)))) return rc0;
-                if (chain && (rc0 = snn_check(hipMemsetAsync(sec0, 0, 2 * secbytes, qs)))) return rc0;
+                if ((rc0 = snn_check(hipMemsetAsync(c.ex, 0, exbytes, st)))) return rc0;
+                if (chain && (rc0 = snn_check(hipMemsetAsync(sec0, 0, 2 * secbytes, st)))) return rc0;
             }
             // input-only pre-passes: launches of their own -- unless the third generation runs them on producer workgroups INSIDE its
             // launch (c.NP > 0).  (Both in ONE launch was measured: 38 us against 10 + 22 -- the X-trace walk wants 256-thread workgroups.)
             if (!(lean == 3 && c.NP > 0)) {
-                hipLaunchKernelGGL(k_dc2015_prep, dim3(R->T + 1), dim3(NT), dc_prep_lds_bytes(B, Nin, NT), qs, c);
-                if (c.x_traces) hipLaunchKernelGGL(k_dc2015_xtrace, dim3((B * Nin + 255) / 256), dim3(256), 0, qs, c);
+                hipLaunchKernelGGL(k_dc2015_prep, dim3(R->T + 1), dim3(NT), dc_prep_lds_bytes(B, Nin, NT), st, c);
+                if (c.x_traces) hipLaunchKernelGGL(k_dc2015_xtrace, dim3((B * Nin + 255) / 256), dim3(256), 0, st, c);
             }
-            const bool prof = with_events && snn_prof_begin(0, qs);
+            const bool prof = snn_prof_begin(0, st);
             // A pipelined caller's launches are ORDINARY ones: a cooperative launch costs ~20 us of dispatch latency each (it goes through a
             // queue of its own: 0.989 -> 0.946 ms per step with both launches of a run ordinary, profiles/NOTES_r05.md).  What the cooperative
             // launch guarantees beyond the capacity check made above -- that no kernel of ANOTHER stream of this process holds CUs meanwhile --
             // is part of what a section asks of its caller anyway (a grid that is not co-resident in time ends with SNN_ERR_TIMEOUT, which
-            // a section reports as an error); synchronous runs keep the cooperative launch.  SNN_DC_GATED_COOP / SNN_DC_SECTION_COOP=1: measurement switches.
-            static const bool section_coop = getenv("SNN_DC_SECTION_COOP") && atoi(getenv("SNN_DC_SECTION_COOP")) != 0;
-            const bool ordinary = chain && !section_coop;
-            int rcl = lean == 3 ? snn_dc2015_async_launch(c, snn_dc2015_async_lds(B, Nin, N), qs, ordinary)
-                                : snn_dc2015_resident_launch(c, rcw, rnt, lean == 2 ? snn_dc2015_spec_lds(B, Nin, N) : snn_dc2015_resident_lds(B, Nin, N, rcw), lean, qs);
-            if (prof) snn_prof_end(qs);
+            // a section reports as an error); synchronous runs keep the cooperative launch.  The gated second attempt is an ordinary launch either way.
+            int rcl = lean == 3 ? snn_dc2015_async_launch(c, snn_dc2015_async_lds(B, Nin, N), st, chain)
+                                : snn_dc2015_resident_launch(c, rcw, rnt, lean == 2 ? snn_dc2015_spec_lds(B, Nin, N) : snn_dc2015_resident_lds(B, Nin, N, rcw), lean, st);
+            if (prof) snn_prof_end(st);
             if (rcl == SNN_OK && lean && R->status2) {
                 // A pipelined caller does not read the status word back between two runs, so the second attempt of an input the lean form
                 // gives up on (SNN_ERR_RETRY: nothing written) is enqueued right behind the first: the general resident kernel on the same
@@ -872,92 +869,33 @@ int snn_try_fused_dc2015(const snn_layer_desc *L, int nL, const snn_conn_desc *C
                     c2.exs = (unsigned long long *)(mine + al(resident_gran_bytes(B, N)));
                     c2.zeroA = (uint4 *)c.ex; c2.zeroA_n16 = (unsigned)(exbytes >> 4);
                     c2.zeroG = (uint4 *)other; c2.zeroG_n16 = (unsigned)(secbytes >> 4);
-                } else if ((rc0 = snn_check(hipMemsetAsync(c.ex, 0, exbytes, qs)))) return rc0;
-                static const bool gated_coop = getenv("SNN_DC_GATED_COOP") && atoi(getenv("SNN_DC_GATED_COOP")) != 0;
-                rcl = snn_dc2015_resident_launch(c2, rcw, rnt, snn_dc2015_resident_lds(B, Nin, N, rcw), 0, qs, !gated_coop && !section_coop);
+                } else if ((rc0 = snn_check(hipMemsetAsync(c.ex, 0, exbytes, st)))) return rc0;
+                rcl = snn_dc2015_resident_launch(c2, rcw, rnt, snn_dc2015_resident_lds(B, Nin, N, rcw), 0, st, true);
                 if (rcl == SNN_OK && chain) { R->host_state[0] = key; R->host_state[1] += 1; }
             }
             if (rcl == SNN_OK && lean == 3 && c.rasX) snn_input_raster_done(0);
             return rcl;                                     // SNN_ERR_UNSUPPORTED: the runtime refused the cooperative grid
         }
-        rc0 = snn_check(hipMemsetAsync(ws, 0, 4 * wb, qs));
+        rc0 = snn_check(hipMemsetAsync(ws, 0, 4 * wb, st));
         if (rc0) return rc0;
-        hipLaunchKernelGGL(k_dc2015_prep, dim3(R->T + 1), dim3(NT), dc_prep_lds_bytes(B, Nin, NT), qs, c);
+        hipLaunchKernelGGL(k_dc2015_prep, dim3(R->T + 1), dim3(NT), dc_prep_lds_bytes(B, Nin, NT), st, c);
         for (int t = 0; t <= R->T; ++t) {
-            const bool prof = with_events && snn_prof_begin(t, qs);
-            hipLaunchKernelGGL(k_dc2015_step, dim3(c.G), dim3(NT), lds, qs, c, t);
-            if (prof) snn_prof_end(qs);
+            const bool prof = snn_prof_begin(t, st);
+            hipLaunchKernelGGL(k_dc2015_step, dim3(c.G), dim3(NT), lds, st, c, t);
+            if (prof) snn_prof_end(st);
         }
         if ((rc0 = snn_check_launch())) return rc0;
         if (c.x_traces && ((R->T - 1) & 1) == 0)
-            if ((rc0 = snn_check(hipMemcpyAsync(L[0].x, xscratch, sizeof(float) * (size_t)B * Nin, hipMemcpyDeviceToDevice, qs)))) return rc0;
+            if ((rc0 = snn_check(hipMemcpyAsync(L[0].x, xscratch, sizeof(float) * (size_t)B * Nin, hipMemcpyDeviceToDevice, st)))) return rc0;
         if (L[1].p.one_spike && (R->T & 1))
-            if ((rc0 = snn_check(hipMemcpyAsync(R->rng, rng2, sizeof(snn_rng_state), hipMemcpyDeviceToDevice, qs)))) return rc0;
+            if ((rc0 = snn_check(hipMemcpyAsync(R->rng, rng2, sizeof(snn_rng_state), hipMemcpyDeviceToDevice, st)))) return rc0;
         return SNN_OK;
     };
 
-
-    // hipGraph replay (opt-in, SNN_GRAPH=1): the launch sequence of a run is fully determined by the context (pointers + sizes), and
-    // training loops present the same contexts again and again (same network, recycled input / monitor buffers).
-    // First sight of a context: plain launches.  Second sight: capture + instantiate.  Afterwards: one
-    // hipGraphLaunch per run instead of T+1 kernel launches (the host stops being the bottleneck).
-    struct GraphEntry { DcCtx key; hipGraphExec_t exec; unsigned long long stamp; };
-    static std::vector<GraphEntry> cache;
-    static unsigned long long clock_ = 0;
-    static const bool graphs_on = getenv("SNN_GRAPH") != nullptr;   // opt-in: replay measured no faster than eager launches
-    int rc = SNN_OK;
-    if (!graphs_on || resident || c.dbg || snn_prof_active()) {
-        rc = enqueue(true); g_graph_stats[0]++;
-        if (rc == SNN_ERR_UNSUPPORTED && resident)          // grid refused by the runtime: the same run, one launch per timestep
-            return snn_try_fused_dc2015(L, nL, C, nC, R, st, -1, 0, handled, normalized);
-    } else {
-        // capture is not allowed on the legacy default stream torch usually runs on: fork to a private
-        // non-blocking stream (event edge in, event edge out), so `st` still orders everything around the run
-        static hipStream_t side = nullptr;
-        static hipEvent_t ev_in = nullptr, ev_out = nullptr;
-        if (!side) {
-            if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) != hipSuccess) { side = nullptr; (void)hipGetLastError(); }
-        }
-        GraphEntry *hit = nullptr;
-        for (auto &e : cache) if (memcmp(&e.key, &c, sizeof(DcCtx)) == 0) { hit = &e; break; }
-        if (!side) {
-            rc = enqueue(false); g_graph_stats[0]++;
-        } else if (hit) {
-            if ((rc = snn_check(hipEventRecord(ev_in, st))) || (rc = snn_check(hipStreamWaitEvent(side, ev_in, 0)))) return rc;
-            qs = side;
-            if (!hit->exec) {
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t exec = nullptr;
-                bool ok = hipStreamBeginCapture(side, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    const int rce = enqueue(false);
-                    ok = hipStreamEndCapture(side, &graph) == hipSuccess && rce == SNN_OK && graph;
-                }
-                if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (graph) (void)hipGraphDestroy(graph);
-                if (ok) { hit->exec = exec; g_graph_stats[1]++; }
-                else { (void)hipGetLastError(); hit->exec = nullptr; }
-            } else {
-                g_graph_stats[2]++;
-            }
-            hit->stamp = ++clock_;
-            if (hit->exec) rc = snn_check(hipGraphLaunch(hit->exec, side));
-            else { rc = enqueue(false); g_graph_stats[0]++; }
-            if (rc) return rc;
-            if ((rc = snn_check(hipEventRecord(ev_out, side))) || (rc = snn_check(hipStreamWaitEvent(st, ev_out, 0)))) return rc;
-        } else {
-            if (cache.size() >= 16) {           // evict the least recently used context
-                size_t v = 0;
-                for (size_t k = 1; k < cache.size(); ++k) if (cache[k].stamp < cache[v].stamp) v = k;
-                if (cache[v].exec) (void)hipGraphExecDestroy(cache[v].exec);
-                cache.erase(cache.begin() + v);
-            }
-            cache.push_back(GraphEntry{c, nullptr, ++clock_});
-            rc = enqueue(false); g_graph_stats[0]++;
-        }
-    }
+    const int rc = enqueue();
+    g_graph_stats[0]++;
+    if (rc == SNN_ERR_UNSUPPORTED && resident)              // grid refused by the runtime: the same run, one launch per timestep
+        return snn_try_fused_dc2015(L, nL, C, nC, R, st, -1, 0, handled, normalized);
     if (rc) return rc;
     g_last_form = resident ? lean : -1;
     if (c.dbg && resident && lean == 3) {   // developer aid, third-generation lean kernel

@@ -1573,8 +1573,7 @@ int snn_dc2015_async_launch(const DcCtx &c, size_t lds, hipStream_t st, bool ord
     DcCtx arg = c;
     void *args[1] = {(void *)&arg};
     const unsigned grid = (unsigned)(c.G + 1 + c.NRW + c.NP);
-    static const bool ft_env = !(getenv("SNN_DC_FULLTILE") && atoi(getenv("SNN_DC_FULLTILE")) == 0);      // (measurement switch: 0 = the general instance)
-    const bool ft = ft_env && c.B == MAXB && c.N % ACW == 0;
+    const bool ft = c.B == MAXB && c.N % ACW == 0;
     const void *fn = c.dbg ? (const void *)k_dc2015_async<true, false>                                     // (the timing marks are compiled out of the ordinary instances)
                            : (ft ? (const void *)k_dc2015_async<false, true> : (const void *)k_dc2015_async<false, false>);
     if (!coop) return snn_check(hipLaunchKernel(fn, dim3(grid), dim3(ANT), args, lds, st));

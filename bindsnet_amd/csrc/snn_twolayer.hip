@@ -36,7 +36,7 @@ namespace {
 constexpr int NT = 1024;
 constexpr int MAXB = 128;       // samples per run: sample masks are MW = ceil(B / 32) words wide (one word up to batch 32)
 constexpr int META = 136;       // [0] list entries, [1] active rows, [2] flags (1: spike byte > 1, 2: list overflow), [3] longest per-sample list, [4..4+B] CSR offsets
-constexpr int kDigestRegs = 16 * 1024;   // words of a digest entry the run kernel's prefetch registers hold (PF * NT, either workgroup size)
+constexpr int kDigestRegs = 16 * 1024;   // words of a digest entry the run kernel's prefetch registers hold (PF * NT)
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -53,16 +53,12 @@ struct TwoCtx {
     int cascade;                                         // 1: MCC (ATen sum order), 0: dense Connection (ascending sequential)
     int rule; float nu0, nu1; int use_dt; float wdecay; int has_min; float wmin; int has_max; float wmax;
     uint32_t *dig; int DW, LCAP, o_ent, o_am, o_ar, o_ab, o_xw, o_ri;   // digest: words per entry, list capacity, word offsets (o_ri: u16 row -> index in the active-row list)
-    int late_events;                                     // PostPre family, two event areas: the next entry's events asked for behind phase A (with the row tables) instead of at the top (SNN_TWO_LATE_EVENTS)
-    int late_rows;                                       // MSTDP: the row tables asked for behind the first chunk of the dense current phase instead of at the top (SNN_TWO_LATE_ROWS)
     int ent2;                                            // two [meta | event list] areas in LDS (learning instances, where it fits)
     float inv_hwps;
     int prodw;                                           // floats of LDS for the staged products of the dense dot (0: off)
-    int mstdp_rows;                                      // MSTDP in its row-per-thread forms (developer switch SNN_TWO_MSTDP_ROWS=0: off)
     int mstdp_burst;                                     // MSTDP burst update (developer switch SNN_TWO_MSTDP_BURST): 2 sample-major where it applies (default), 1 the row walk in its packed forms, 0 the row walk as round 5 left it
-    int rowmajor;                                        // PostPre in its row-major form (developer switch SNN_TWO_ROWMAJOR=0: off)
-    int use_xsl;                                         // stage the source traces of spiking columns in LDS (fits + Nin <= nt)
-    int nt;                                              // threads per workgroup of the run kernel: 1024, or 512 (256 VGPRs per lane: nothing spills)
+    int rowmajor;                                        // PostPre family, learning: the row-major form
+    int use_xsl;                                         // stage the source traces of spiking columns in LDS (fits + Nin <= NT)
     // MSTDP (learning.py:1504-1574), factored eligibility: p_plus / p_minus traces, previous-step spike factors
     float *p_plus, *p_minus; uint8_t *s_src_prev, *s_tgt_prev;
     float *pall;                                         // [T+1][B][Nin] p_plus at entry / after every step
@@ -224,20 +220,7 @@ __global__ __launch_bounds__(NT) void k_two_prep(const TwoCtx c) {
 }
 
 // ---------------------------------------------------------------------------------------------- the run
-#define TWO_NS nt1024
-#define TWO_NT 1024
-#define TWO_PF 16
 #include "snn_twolayer_run.inc"
-#undef TWO_NS
-#undef TWO_NT
-#undef TWO_PF
-#define TWO_NS nt512
-#define TWO_NT 512
-#define TWO_PF 32
-#include "snn_twolayer_run.inc"
-#undef TWO_NS
-#undef TWO_NT
-#undef TWO_PF
 
 int digest_layout(TwoCtx &c) {
     c.o_ent = META;
@@ -280,9 +263,7 @@ bool plan(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const
     c.MW = (B + 31) / 32; c.BC = 32 * c.MW;
     c.dt = R->dt; c.learning = R->learning;
     c.rule = C[0].rule;
-    c.rowmajor = (c.rule == SNN_RULE_POSTPRE || c.rule == SNN_RULE_HEBBIAN || c.rule == SNN_RULE_WDPOSTPRE) && c.learning &&
-                 !(getenv("SNN_TWO_ROWMAJOR") && atoi(getenv("SNN_TWO_ROWMAJOR")) == 0);
-    c.mstdp_rows = !(getenv("SNN_TWO_MSTDP_ROWS") && atoi(getenv("SNN_TWO_MSTDP_ROWS")) == 0);
+    c.rowmajor = (c.rule == SNN_RULE_POSTPRE || c.rule == SNN_RULE_HEBBIAN || c.rule == SNN_RULE_WDPOSTPRE) && c.learning;
     c.mstdp_burst = getenv("SNN_TWO_MSTDP_BURST") ? atoi(getenv("SNN_TWO_MSTDP_BURST")) : 2;
     // list capacity: all events of a step in LDS (u16 each), up to 24 KiB
     c.LCAP = (int)((((size_t)B * Nin < 12288 ? (size_t)B * Nin : 12288) + 7) & ~(size_t)7);
@@ -293,22 +274,13 @@ bool plan(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const
         if (B * cw <= 1024 && run_lds(c) <= 140 * 1024) break;
         cw >>= 1;
     }
-    if (const char *e = getenv("SNN_TWO_CW")) {          // (measurement switch: a narrower tile than the widest that fits)
-        const int want = atoi(e);
-        if ((want == 1 || want == 2 || want == 4) && want < cw) cw = want;
-    }
     c.CW = cw;
     if (B * cw > 1024 || run_lds(c) > 140 * 1024) return false;
-    // Workgroup size of the run kernel.  At 1024 threads every learning instantiation sits at the 128-VGPR cap with 59 .. 139 spilled registers;
-    // at 512 threads (256 VGPRs per lane) nothing spills -- and the kernel is SLOWER all the same (round 6, same box, bit-exact both ways:
+    // Workgroup size of the run kernel: NT = 1024.  Every learning instantiation sits at the 128-VGPR cap with 59 .. 139 spilled registers;
+    // a 512-thread form (256 VGPRs per lane, nothing spills) was SLOWER all the same (round 6, same box, bit-exact both ways:
     // cfg5 MSTDP 28.3 against 24.7 us per timestep, cfg3 PostPre B=16 / 32 7.64 / 8.50 against 7.06 / 7.40, Hebbian 8.60 against 7.46): the
     // phases are issue-bound loops over rows / events that 1024 threads walk in half the trips, and the spilled registers are touched outside
-    // them.  So 1024 it stays; SNN_TWO_NT=512 runs the other instantiation where the tile (B * CW pairs) fits 512 threads.
-    c.nt = 1024;
-    {
-        const char *e = getenv("SNN_TWO_NT");
-        if (e && atoi(e) == 512 && B * cw <= 512) c.nt = 512;
-    }
+    // them.  That form was removed (profiles/NOTES_r06.md section 4 has its numbers).
     c.G = (N + cw - 1) / cw;
     if (c.T + 1 > 4096) return false;
     c.prodw = 0;
@@ -316,14 +288,11 @@ bool plan(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const
         const int sizes[9] = {16384, 12288, 8192, 6144, 5120, 4096, 3072, 2048, 0};
         for (int k = 0; k < 9; ++k) { c.prodw = sizes[k]; if (run_lds(c) <= 140 * 1024) break; }
         if (c.prodw / (B * cw) < 36) c.prodw = 0;           // (a chunk of at least 32 terms per pair)
-        if (getenv("SNN_TWO_PRODW")) { c.prodw = atoi(getenv("SNN_TWO_PRODW")); if (run_lds(c) > 150 * 1024) c.prodw = 0; }
     }
     c.use_xsl = 0;
-    if (Nin <= c.nt && (c.rule == SNN_RULE_POSTPRE || c.rule == SNN_RULE_HEBBIAN || c.rule == SNN_RULE_WDPOSTPRE) && !(c.rowmajor && ((size_t)Nin * N) % 32 == 0)) { c.use_xsl = 1; if (run_lds(c) > 140 * 1024) c.use_xsl = 0; }
-    c.late_events = getenv("SNN_TWO_LATE_EVENTS") ? atoi(getenv("SNN_TWO_LATE_EVENTS")) : 1;   // (same box, cfg3 B=128: 83.9 against 82.9 k timesteps/s)
-    c.late_rows = getenv("SNN_TWO_LATE_ROWS") ? atoi(getenv("SNN_TWO_LATE_ROWS")) : 1;     // (same box, cfg5: 71.1 against 67.8 k timesteps/s)
+    if (Nin <= NT && (c.rule == SNN_RULE_POSTPRE || c.rule == SNN_RULE_HEBBIAN || c.rule == SNN_RULE_WDPOSTPRE) && !(c.rowmajor && ((size_t)Nin * N) % 32 == 0)) { c.use_xsl = 1; if (run_lds(c) > 140 * 1024) c.use_xsl = 0; }
     c.ent2 = 0;
-    if (c.rule != SNN_RULE_NONE && c.rule != SNN_RULE_MSTDP && c.MW > 1 && !(getenv("SNN_TWO_ENT2") && atoi(getenv("SNN_TWO_ENT2")) == 0)) { c.ent2 = 1; if (run_lds(c) > 140 * 1024) c.ent2 = 0; }
+    if (c.rule != SNN_RULE_NONE && c.rule != SNN_RULE_MSTDP && c.MW > 1) { c.ent2 = 1; if (run_lds(c) > 140 * 1024) c.ent2 = 0; }
     // the per-step digest copy must fit the prefetch registers
     if (META + c.LCAP / 2 + Nin * c.MW + (Nin + 1) / 2 + c.NinW > kDigestRegs) return false;
     return true;
@@ -378,18 +347,17 @@ int snn_try_fused_twolayer(const snn_layer_desc *L, int nL, const snn_conn_desc 
     c.has_min = C[0].has_min; c.wmin = C[0].wmin; c.has_max = C[0].has_max; c.wmax = C[0].wmax;
     static bool attr = false;
     if (!attr) {
-#define TWO_VARIANTS(NS) \
-            (const void *)NS::k_two_run<false, SNN_RULE_HEBBIAN, 1>, (const void *)NS::k_two_run<false, SNN_RULE_WDPOSTPRE, 1>, \
-            (const void *)NS::k_two_run<false, SNN_RULE_HEBBIAN, 4>, (const void *)NS::k_two_run<false, SNN_RULE_WDPOSTPRE, 4>, \
-            (const void *)NS::k_two_run<true, SNN_RULE_NONE, 1>, (const void *)NS::k_two_run<true, SNN_RULE_POSTPRE, 1>, \
-            (const void *)NS::k_two_run<false, SNN_RULE_NONE, 1>, (const void *)NS::k_two_run<false, SNN_RULE_POSTPRE, 1>, \
-            (const void *)NS::k_two_run<false, SNN_RULE_MSTDP, 1>, (const void *)NS::k_two_run<true, SNN_RULE_MSTDP, 1>, \
-            (const void *)NS::k_two_run<true, SNN_RULE_NONE, 4>, (const void *)NS::k_two_run<true, SNN_RULE_POSTPRE, 4>, \
-            (const void *)NS::k_two_run<false, SNN_RULE_NONE, 4>, (const void *)NS::k_two_run<false, SNN_RULE_POSTPRE, 4>, \
-            (const void *)NS::k_two_run<false, SNN_RULE_MSTDP, 4>, (const void *)NS::k_two_run<true, SNN_RULE_MSTDP, 4>
-        const void *variants[34] = {TWO_VARIANTS(nt1024), TWO_VARIANTS(nt512),
-                                    (const void *)nt1024::k_two_run<false, SNN_RULE_POSTPRE, 1, 16>, (const void *)nt1024::k_two_run<false, SNN_RULE_POSTPRE, 1, 32>};
-#undef TWO_VARIANTS
+        using namespace nt1024;
+        const void *variants[18] = {
+            (const void *)k_two_run<false, SNN_RULE_HEBBIAN, 1>, (const void *)k_two_run<false, SNN_RULE_WDPOSTPRE, 1>,
+            (const void *)k_two_run<false, SNN_RULE_HEBBIAN, 4>, (const void *)k_two_run<false, SNN_RULE_WDPOSTPRE, 4>,
+            (const void *)k_two_run<true, SNN_RULE_NONE, 1>, (const void *)k_two_run<true, SNN_RULE_POSTPRE, 1>,
+            (const void *)k_two_run<false, SNN_RULE_NONE, 1>, (const void *)k_two_run<false, SNN_RULE_POSTPRE, 1>,
+            (const void *)k_two_run<false, SNN_RULE_MSTDP, 1>, (const void *)k_two_run<true, SNN_RULE_MSTDP, 1>,
+            (const void *)k_two_run<true, SNN_RULE_NONE, 4>, (const void *)k_two_run<true, SNN_RULE_POSTPRE, 4>,
+            (const void *)k_two_run<false, SNN_RULE_NONE, 4>, (const void *)k_two_run<false, SNN_RULE_POSTPRE, 4>,
+            (const void *)k_two_run<false, SNN_RULE_MSTDP, 4>, (const void *)k_two_run<true, SNN_RULE_MSTDP, 4>,
+            (const void *)k_two_run<false, SNN_RULE_POSTPRE, 1, 16>, (const void *)k_two_run<false, SNN_RULE_POSTPRE, 1, 32>};
         for (const void *f : variants)
             if (snn_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))) return SNN_ERR_LAUNCH;
         if (snn_check(hipFuncSetAttribute((const void *)k_two_prep, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))) return SNN_ERR_LAUNCH;
@@ -406,26 +374,25 @@ int snn_try_fused_twolayer(const snn_layer_desc *L, int nL, const snn_conn_desc 
         if (c.T + 1 <= 4096) { (void)hipMemsetAsync(dbg, 0, sizeof(long long) * 24 * 4096, st); c.dbg = dbg; }
     }
     {
-        const dim3 grid(c.G), blk(c.nt);
+        using namespace nt1024;
+        const dim3 grid(c.G), blk(NT);
         const size_t lds = run_lds(c);
-#define TWO_LAUNCH(NS, MWV) do { \
-        if (c.cascade && c.rule == SNN_RULE_POSTPRE) hipLaunchKernelGGL((NS::k_two_run<true, SNN_RULE_POSTPRE, MWV>), grid, blk, lds, st, c); \
-        else if (c.cascade && c.rule == SNN_RULE_MSTDP) hipLaunchKernelGGL((NS::k_two_run<true, SNN_RULE_MSTDP, MWV>), grid, blk, lds, st, c); \
-        else if (c.cascade) hipLaunchKernelGGL((NS::k_two_run<true, SNN_RULE_NONE, MWV>), grid, blk, lds, st, c); \
-        else if (c.rule == SNN_RULE_POSTPRE) hipLaunchKernelGGL((NS::k_two_run<false, SNN_RULE_POSTPRE, MWV>), grid, blk, lds, st, c); \
-        else if (c.rule == SNN_RULE_MSTDP) hipLaunchKernelGGL((NS::k_two_run<false, SNN_RULE_MSTDP, MWV>), grid, blk, lds, st, c); \
-        else if (c.rule == SNN_RULE_HEBBIAN) hipLaunchKernelGGL((NS::k_two_run<false, SNN_RULE_HEBBIAN, MWV>), grid, blk, lds, st, c); \
-        else if (c.rule == SNN_RULE_WDPOSTPRE) hipLaunchKernelGGL((NS::k_two_run<false, SNN_RULE_WDPOSTPRE, MWV>), grid, blk, lds, st, c); \
-        else hipLaunchKernelGGL((NS::k_two_run<false, SNN_RULE_NONE, MWV>), grid, blk, lds, st, c); } while (0)
-        // (same-box A/B, round 6: B = 16 / 32 PostPre 143.1 -> 145.8 k / 136.2 -> 137.6 k timesteps/s; B = 128 unchanged and MSTDP at B = 16 18 % SLOWER
-        //  -- 210 spilled registers against 94 -- so those two instances are not built)
-        static const bool bk_env = !(getenv("SNN_TWO_BCONST") && atoi(getenv("SNN_TWO_BCONST")) == 0);       // (measurement switch: 0 = the general instances)
-        const bool bk = bk_env && c.nt == 1024 && !c.cascade;
-        if (bk && c.rule == SNN_RULE_POSTPRE && c.MW == 1 && c.B == 16) hipLaunchKernelGGL((nt1024::k_two_run<false, SNN_RULE_POSTPRE, 1, 16>), grid, blk, lds, st, c);
-        else if (bk && c.rule == SNN_RULE_POSTPRE && c.MW == 1 && c.B == 32) hipLaunchKernelGGL((nt1024::k_two_run<false, SNN_RULE_POSTPRE, 1, 32>), grid, blk, lds, st, c);
-        else
-        if (c.nt == 512) { if (c.MW == 1) TWO_LAUNCH(nt512, 1); else TWO_LAUNCH(nt512, 4); }
-        else { if (c.MW == 1) TWO_LAUNCH(nt1024, 1); else TWO_LAUNCH(nt1024, 4); }
+#define TWO_LAUNCH(MWV) do { \
+        if (c.cascade && c.rule == SNN_RULE_POSTPRE) hipLaunchKernelGGL((k_two_run<true, SNN_RULE_POSTPRE, MWV>), grid, blk, lds, st, c); \
+        else if (c.cascade && c.rule == SNN_RULE_MSTDP) hipLaunchKernelGGL((k_two_run<true, SNN_RULE_MSTDP, MWV>), grid, blk, lds, st, c); \
+        else if (c.cascade) hipLaunchKernelGGL((k_two_run<true, SNN_RULE_NONE, MWV>), grid, blk, lds, st, c); \
+        else if (c.rule == SNN_RULE_POSTPRE) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_POSTPRE, MWV>), grid, blk, lds, st, c); \
+        else if (c.rule == SNN_RULE_MSTDP) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_MSTDP, MWV>), grid, blk, lds, st, c); \
+        else if (c.rule == SNN_RULE_HEBBIAN) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_HEBBIAN, MWV>), grid, blk, lds, st, c); \
+        else if (c.rule == SNN_RULE_WDPOSTPRE) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_WDPOSTPRE, MWV>), grid, blk, lds, st, c); \
+        else hipLaunchKernelGGL((k_two_run<false, SNN_RULE_NONE, MWV>), grid, blk, lds, st, c); } while (0)
+        // The batch as a constant of the instance for the dense PostPre baseline shapes (same-box A/B, round 6: B = 16 / 32 PostPre 143.1 -> 145.8 k /
+        // 136.2 -> 137.6 k timesteps/s; B = 128 unchanged and MSTDP at B = 16 18 % SLOWER -- 210 spilled registers against 94 -- so those two instances are not built)
+        const bool bk = !c.cascade && c.rule == SNN_RULE_POSTPRE && c.MW == 1;
+        if (bk && c.B == 16) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_POSTPRE, 1, 16>), grid, blk, lds, st, c);
+        else if (bk && c.B == 32) hipLaunchKernelGGL((k_two_run<false, SNN_RULE_POSTPRE, 1, 32>), grid, blk, lds, st, c);
+        else if (c.MW == 1) TWO_LAUNCH(1);
+        else TWO_LAUNCH(4);
 #undef TWO_LAUNCH
     }
     int rc = snn_check_launch();

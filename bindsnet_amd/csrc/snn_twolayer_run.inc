@@ -1,10 +1,9 @@
-// snn_twolayer_run.inc -- the run kernel of the fused plan "twolayer-fused" and its device helpers, included by snn_twolayer.hip ONCE PER
-// WORKGROUP SIZE (TWO_NS / TWO_NT / TWO_PF): the 1024-thread form (a tile thread per (sample, column) pair up to batch 128 x 8 columns: 128
-// VGPRs per lane, which every learning instantiation exceeds -- 59 .. 139 spilled registers) and, round 6, a 512-thread form (256 VGPRs per
-// lane: nothing spills) for the graphs whose tile fits 512 threads.  Same statements; NT is the only difference.
-namespace TWO_NS {
-constexpr int NT = TWO_NT;      // threads per workgroup
-constexpr int PF = TWO_PF;      // digest words prefetched per thread per step (PF * NT words hold one entry)
+// snn_twolayer_run.inc -- the run kernel of the fused plan "twolayer-fused" and its device helpers, included by snn_twolayer.hip.  Workgroups
+// of NT = 1024 threads (a tile thread per (sample, column) pair up to batch 128 x 8 columns): 128 VGPRs per lane, which every learning
+// instantiation exceeds -- 59 .. 139 spilled registers.  (The namespace is named after the workgroup size: kernel names in profiles.)
+namespace nt1024 {
+constexpr int PF = 16;          // digest words prefetched per thread per step (PF * NT words hold one entry)
+static_assert(PF * NT == kDigestRegs, "plan() admits the digests that fit the prefetch registers");
 
 template <class SUM>
 __device__ __forceinline__ float list_dot(const float *wt, int CW, int jj, const uint16_t *ent, int n0, int n1,
@@ -879,10 +878,12 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
     // prefetch registers, the sixteen words per thread were the first thing these 128-register kernels spilled: every load was followed by
     // `vmcnt(0)` and a scratch store -- up to sixteen memory round trips in a row ("issue" 3.5 us + "commit" 2.3 us of cfg5's 23.6 us step).
     // An LDS area takes the next entry as soon as its last reader is past a barrier:
-    //   MSTDP            [meta | event list] behind the barrier that ends phase B (lands during the update), the row tables at the top of the
-    //                    iteration whose END needs them (they land during phase B);
-    //   PostPre family   the row tables (+ the row -> index table the digest now carries) behind the barrier that ends phase A, [meta | event
-    //                    list] into the OTHER of two areas at the top of the iteration before (one area where LDS is short: behind phase B).
+    //   MSTDP            [meta | event list] behind the barrier that ends phase B (lands during the update), the row tables in phase B of the
+    //                    iteration whose END needs them, behind the first chunk of the dense current phase (at the top of the iteration they
+    //                    shared the LDS with that chunk's staging: same box, cfg5 67.8 -> 71.1 k timesteps/s);
+    //   PostPre family   the row tables (+ the row -> index table the digest now carries) behind the barrier that ends phase A, and with them
+    //                    [meta | event list] into the OTHER of two areas (asked for at the top of the iteration: cfg3 B=128 82.9 against 83.9 k
+    //                    timesteps/s; one area where LDS is short: behind phase B).
     // The loads are issued from inline asm: the compiler, which puts `vmcnt(0)` in front of every LDS read that follows an LDS-DMA it knows
     // of, does not see them; the waits are the explicit ones at the top of the iteration and in front of the update.
     // Where: MSTDP (cfg5 42.1 -> 51.3 k timesteps/s, same box) and the batch-128 instances of the PostPre family (82.5 -> 84.9 k).  The
@@ -944,7 +945,6 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
     issue(0);
     if constexpr (DIRECT) { dma_events(0); if (RULE != SNN_RULE_MSTDP) dma_rows(0); }
 
-    const bool late_rows = c.late_rows != 0;
     for (int t = 0; t <= c.T; ++t) {
         TMARK(0);
         // ---- stage the digest of step t-1 (entry t) from the prefetch registers
@@ -997,11 +997,7 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
         }
         lds_barrier();
         TMARK(1);
-        if constexpr (DIRECT) {
-            if (RULE == SNN_RULE_MSTDP) { if (t < c.T && !late_rows) dma_rows(t); }   // wanted by the update at the END of this iteration (none behind the last)
-            else if (c.ent2 && !c.late_events && t + 1 <= c.T) dma_events(t + 1);   // the other area: its last reader was phase B of iteration t - 1
-        } else
-        if (t + 1 <= c.T) issue(t + 1);                  // next step's digest: in flight behind this step's work
+        if (t + 1 <= c.T) issue(t + 1);                  // next step's digest: in flight behind this step's work (DIRECT: nothing, see above)
         TMARK(2);
         const int tot = meta[0], nact = meta[1], flags = meta[2];
         const bool overflow = (flags & 2) != 0;          // more events than the LDS list holds: walk bit words from global
@@ -1027,7 +1023,7 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
         lds_barrier();
         TMARK(4);
         if (t == c.T) break;
-        if constexpr (DIRECT && RULE != SNN_RULE_MSTDP) { dma_rows(t + 1); if (c.ent2 && c.late_events) dma_events(t + 1); }   // (phase A was the row tables' last reader)
+        if constexpr (DIRECT && RULE != SNN_RULE_MSTDP) { dma_rows(t + 1); if (c.ent2) dma_events(t + 1); }   // (phase A was the row tables' last reader, phase B of iteration t - 1 the other event area's)
 
         // ================================================== phase B: step t
         uint32_t *cmn = colmask + (t & 1) * CMS;
@@ -1039,7 +1035,7 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
         // adds as the reference (topology.py:332-346), without a memory access in the dependency chain.
         const bool wave_dot = !CASC && !overflow && c.prodw > 0 && tot >= 48 * B;
         float r_dot = 0.f;
-        if constexpr (DIRECT) { if (RULE == SNN_RULE_MSTDP && late_rows && !(!CASC && wave_dot)) dma_rows(t); }
+        if constexpr (DIRECT) { if (RULE == SNN_RULE_MSTDP && !(!CASC && wave_dot)) dma_rows(t); }   // wanted by the update at the END of this iteration
         if constexpr (DIRECT) { if (!CASC && wave_dot) {
             // (round 6, the instances whose digest left the registers)  The same two phases as below, each made of less: P -- a thread keeps one
             // pair and takes FOUR items per turn: index reads, then weight reads, then stores (one item per turn was a chain of three LDS
@@ -1091,9 +1087,9 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
                 }
                 SMARK(e0 == 0 ? 4 : 8);
                 if (e0 + CH < maxn) lds_barrier();
-                if (e0 == 0) { SMARK(5); if (RULE == SNN_RULE_MSTDP && late_rows) dma_rows(t); }   // (behind the first chunk: the first chunk's staging does not share the LDS with 22 KB of arriving tables)
+                if (e0 == 0) { SMARK(5); if (RULE == SNN_RULE_MSTDP) dma_rows(t); }   // (behind the first chunk: the first chunk's staging does not share the LDS with 22 KB of arriving tables)
             }
-            if (RULE == SNN_RULE_MSTDP && late_rows && maxn <= 0) dma_rows(t);
+            if (RULE == SNN_RULE_MSTDP && maxn <= 0) dma_rows(t);
         } } else
         if (!CASC && wave_dot) {
             // Phase P: all threads stage the products w[i,j] * s[b,i] of a chunk of every (sample, column) pair's event
@@ -1185,7 +1181,7 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
             sp_prev = sp;
         }
         TMARK(5);
-        // this wave's share of the row tables has landed (asked for at the top of the iteration).  In FRONT of the raster stores: on gfx950
+        // this wave's share of the row tables has landed (asked for earlier in this phase).  In FRONT of the raster stores: on gfx950
         // `vmcnt` counts stores too, and behind them the tile wave -- and with it the barrier below -- waited for its own stores every step.
         if constexpr (DIRECT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (mine) {
@@ -1234,13 +1230,13 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
             uint32_t anycol = 0;                             // did any column of the tile spike in the step this update pairs with?
             for (int k = 0; k < CMS; ++k) anycol |= cm[k];
             if (c.dbg && blockIdx.x == 0 && tid == 0 && anycol) c.dbg[(size_t)8 * 4096 + (size_t)16 * 4096 - 1 - t] = 1;
-            if (Etot == Emain && !full && !sb && c.mstdp_rows && !__builtin_amdgcn_readfirstlane(anycol)) {
+            if (Etot == Emain && !full && !sb && !__builtin_amdgcn_readfirstlane(anycol)) {
                 if (CW == 8) two_mstdp_rows<MWT, 8>(c, wt, ar, am, zl, na, c0, tid);
                 else if (CW == 4) two_mstdp_rows<MWT, 4>(c, wt, ar, am, zl, na, c0, tid);
                 else if (CW == 2) two_mstdp_rows<MWT, 2>(c, wt, ar, am, zl, na, c0, tid);
                 else two_mstdp_rows<MWT, 1>(c, wt, ar, am, zl, na, c0, tid);
             }
-            else if (Etot == Emain && !full && !sb && c.mstdp_rows && CW >= 2) {
+            else if (Etot == Emain && !full && !sb && CW >= 2) {
                 const int SB_ = (Nin + NT - 1) / NT;
                 if (MWT == 1 && B <= 16 && c.mstdp_burst == 2 && CW <= 4 && SB_ <= 7) {
                     const uint16_t *rig = (const uint16_t *)(c.dig + (size_t)(t == 0 ? c.T + 1 : t) * c.DW + c.o_ri);   // (the entry the row tables are of)
@@ -1316,4 +1312,4 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
     }
 }
 
-}  // namespace TWO_NS
+}  // namespace nt1024

@@ -699,8 +699,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
 
     # ------------------------------------------------------------------ helpers
     def _scratch(self, key, shape, dtype, dev):
-        """Persistent device scratch: the same addresses run after run keep the library's captured launch
-        graphs valid (csrc/snn_dc2015.hip) and avoid allocator traffic."""
+        """Persistent device scratch: the same addresses run after run avoid allocator traffic."""
         pool = self.__dict__.setdefault("_scratch_pool", {})
         t = pool.get(key)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev:

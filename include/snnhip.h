@@ -800,7 +800,8 @@ int snn_dc2015_last_form(void);
  * milliseconds and the sample count, and clears the samples.                                 */
 void snn_profile_enable(int stride);
 int snn_profile_collect(double *h_sum_ms, int *h_samples);
-/* Fused-plan bookkeeping: runs issued as plain launches / captured into a hipGraph / replayed from one. */
+/* Fused-plan bookkeeping: runs of the dc2015 plans issued as plain launches.  The hipGraph capture-and-replay path these
+ * counters were made for has been removed: *h_captured and *h_replayed are always 0 (kept: the ABI is additive-only). */
 void snn_graph_stats(int *h_plain, int *h_captured, int *h_replayed);
 /* Force a plan for testing: 0 = automatic, 1 = generic per-operator launches only,
  * 2 = fused plans in their one-launch-per-timestep form (no resident kernel), 3 = no lean forms. */
