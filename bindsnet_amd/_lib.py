@@ -103,6 +103,14 @@ class LayerDesc(C.Structure):
                 ("csrm_wres", C.c_int), ("csrm_wref", C.c_int), ("summed", C.c_void_p)]
 
 
+class SynParams(C.Structure):
+    """snn_synparams: the per-synapse constants of a rule (include/snnhip.h f13) -- device pointers, element strides against [S, N]."""
+    _fields_ = [("nu0", C.c_void_p), ("nu1", C.c_void_p), ("wmin", C.c_void_p), ("wmax", C.c_void_p),
+                ("nu0_rs", C.c_int), ("nu0_cs", C.c_int), ("nu1_rs", C.c_int), ("nu1_cs", C.c_int),
+                ("wmin_rs", C.c_int), ("wmin_cs", C.c_int), ("wmax_rs", C.c_int), ("wmax_cs", C.c_int),
+                ("nu0_any", C.c_int), ("nu1_any", C.c_int)]
+
+
 class ConnDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("src", C.c_int), ("dst", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p),
                 ("cin", C.c_int), ("h", C.c_int), ("wd", C.c_int), ("cout", C.c_int), ("kh", C.c_int),
@@ -129,7 +137,7 @@ class ConnDesc(C.Structure):
                 ("w_numel", C.c_int), ("rmax_tc_c", C.c_float),
                 ("window", C.c_int), ("win_ring", C.c_void_p), ("win_head", C.c_int), ("win_size", C.c_int),
                 ("gat_out", C.c_int * 3), ("gat_src", C.c_int * 3), ("gat_stride", C.c_int * 3), ("gat_off", C.c_int * 3),
-                ("w_dtype", C.c_int)]
+                ("w_dtype", C.c_int), ("syn", SynParams), ("norm_vec", C.c_void_p)]
 
 
 class MccOp(C.Structure):
@@ -223,6 +231,11 @@ _SIGS = {
     "snn_mstdpet_step": ([_vp] * 8 + [_i, _i] + [_f] * 10 + [_i, _f, _i, _f, _vp], _i),
     "snn_mstdp_step": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _vp], _i),
     "snn_normalize": ([_vp, _i, _i, _f, _i, _vp, _vp], _i),
+    "snn_stdp_postpre_pv": ([_vp] * 5 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _i, C.POINTER(SynParams), _vp], _i),
+    "snn_stdp_hebbian_pv": ([_vp] * 5 + [_i, _i, _i, _f, _f, _i, _f, _i, _f, _i, _f, C.POINTER(SynParams), _vp], _i),
+    "snn_mstdpet_step_pv": ([_vp] * 8 + [_i, _i] + [_f] * 10 + [_i, _f, _i, _f, C.POINTER(SynParams), _vp], _i),
+    "snn_mstdp_step_pv": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, C.POINTER(SynParams), _vp], _i),
+    "snn_normalize_pv": ([_vp, _i, _i, _vp, _i, _vp, _vp], _i),
     "snn_normalize_conv2d": ([_vp, _i, _i, _f, _vp], _i),
     "snn_prop_cascade_h16": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_stdp_postpre_h16": ([_vp, _i] + [_vp] * 4 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _vp], _i),

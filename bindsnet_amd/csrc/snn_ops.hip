@@ -12,6 +12,7 @@
 #include "snn_order.hpp"
 #include "snn_common.hpp"
 #include "snn_rng.hpp"
+#include "snn_synparams.hpp"
 
 using namespace snn;
 
@@ -549,146 +550,13 @@ struct StdpArgs {
 
 constexpr int kTI = 16;
 
-template <int TJ>
-__global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int B = a.B, Nin = a.Nin, N = a.N;
-    const int MW = (B + 31) / 32;                       // mask words per row / column
-    float *xt = (float *)smem;                          // [B][TJ]  target-side float factor
-    float *xs = xt + (size_t)B * TJ;                    // [B][kTI] source-side float factor
-    uint32_t *mT = (uint32_t *)(xs + (size_t)B * kTI);  // [TJ][MW] target spike masks
-    uint32_t *mS = mT + (size_t)TJ * MW;                // [kTI][MW]
-    uint8_t *vT = (uint8_t *)(mS + (size_t)kTI * MW);   // [B][TJ] target spike values
-    uint8_t *vS = vT + (size_t)B * TJ;                  // [B][kTI]
-    __shared__ int any_flag;
-
-    const int tid = threadIdx.x;
-    const int j0 = blockIdx.x * TJ, i0 = blockIdx.y * kTI;
-    if (tid == 0) any_flag = 0;
-    __syncthreads();
-    int local_any = 0;
-    for (int k = tid; k < B * TJ; k += 256) {
-        const int b = k / TJ, jj = k - b * TJ, j = j0 + jj;
-        float f = 0.f; uint8_t sv = 0;
-        if (j < N) {
-            sv = a.s_tgt[(size_t)b * N + j];
-            f = a.x_tgt[(size_t)b * N + j];
-            if (a.mode == 0) f = f * a.nu0;             // target_x * nu[0]  (MCC_learning.py:235)
-        }
-        xt[k] = f; vT[k] = sv; local_any |= sv;
-    }
-    for (int k = tid; k < B * kTI; k += 256) {
-        const int b = k / kTI, ii = k - b * kTI, i = i0 + ii;
-        float f = 0.f; uint8_t sv = 0;
-        if (i < Nin) { sv = a.s_src[(size_t)b * Nin + i]; f = a.x_src[(size_t)b * Nin + i]; }
-        xs[k] = f; vS[k] = sv; local_any |= sv;
-    }
-    if (local_any) any_flag = 1;
-    __syncthreads();
-    if (a.assume_clamped && !any_flag) return;          // nothing in this tile can change
-    for (int k = tid; k < (TJ + kTI) * MW; k += 256) {
-        const bool tgt = k < TJ * MW;
-        const int kk = tgt ? k : k - TJ * MW;
-        const int col = kk / MW, w = kk - col * MW;
-        uint32_t m = 0;
-        for (int bit = 0; bit < 32; ++bit) {
-            const int b = w * 32 + bit;
-            if (b < B && (tgt ? vT[(size_t)b * TJ + col] : vS[(size_t)b * kTI + col])) m |= 1u << bit;
-        }
-        (tgt ? mT : mS)[kk] = m;
-    }
-    __syncthreads();
-
-    const long E = (long)Nin * N, Emain = (E / 32) * 32;
-    constexpr int RG = 256 / TJ;                        // row groups handled concurrently
-    const int jj = tid % TJ, rg = tid / TJ, j = j0 + jj;
-    if (j >= N) return;
-    for (int ii = rg; ii < kTI; ii += RG) {
-        const int i = i0 + ii;
-        if (i >= Nin) break;
-        uint32_t anyS = 0, anyT = 0;
-        for (int w = 0; w < MW; ++w) { anyS |= mS[ii * MW + w]; anyT |= mT[jj * MW + w]; }
-        if (a.assume_clamped && !anyS && !anyT) continue;
-        const long e = (long)i * N + j;
-        const bool tail = e >= Emain;
-        float w_ = a.W[e];
-        if (a.mode == 0) {
-            if (a.nu0 != 0.f) {                         // pre: sum_b s_src[b,i] * (x_tgt[b,j]*nu0)
-                OuterSum acc; acc.init(tail);
-                for (int w = 0; w < MW; ++w) {
-                    uint32_t m = mS[ii * MW + w];
-                    while (m) {
-                        const int b = w * 32 + __ffs(m) - 1; m &= m - 1;
-                        acc.add(b, (float)vS[(size_t)b * kTI + ii] * xt[(size_t)b * TJ + jj], B);
-                    }
-                }
-                float u = acc.finish(B);
-                if (a.use_dt) u = u * a.dt;
-                w_ = w_ - u;
-            }
-            if (a.nu1 != 0.f) {                         // post: sum_b x_src[b,i] * (s_tgt[b,j]*nu1)
-                OuterSum acc; acc.init(tail);
-                for (int w = 0; w < MW; ++w) {
-                    uint32_t m = mT[jj * MW + w];
-                    while (m) {
-                        const int b = w * 32 + __ffs(m) - 1; m &= m - 1;
-                        const float st = (float)vT[(size_t)b * TJ + jj] * a.nu1;
-                        acc.add(b, xs[(size_t)b * kTI + ii] * st, B);
-                    }
-                }
-                float u = acc.finish(B);
-                if (a.use_dt) u = u * a.dt;
-                w_ = w_ + u;
-            }
-        } else if (a.mode == 2 || a.mode == 3) {
-            float u1 = 0.f, u2 = 0.f;
-            {   // U1 = sum_b s_src[b,i] * x_tgt[b,j]
-                OuterSum acc; acc.init(tail);
-                for (int w = 0; w < MW; ++w) {
-                    uint32_t m = mS[ii * MW + w];
-                    while (m) { const int b = w * 32 + __ffs(m) - 1; m &= m - 1; acc.add(b, (float)vS[(size_t)b * kTI + ii] * xt[(size_t)b * TJ + jj], B); }
-                }
-                u1 = acc.finish(B);
-            }
-            {   // U2 = sum_b x_src[b,i] * s_tgt[b,j]
-                OuterSum acc; acc.init(tail);
-                for (int w = 0; w < MW; ++w) {
-                    uint32_t m = mT[jj * MW + w];
-                    while (m) { const int b = w * 32 + __ffs(m) - 1; m &= m - 1; acc.add(b, xs[(size_t)b * kTI + ii] * (float)vT[(size_t)b * TJ + jj], B); }
-                }
-                u2 = acc.finish(B);
-            }
-            if (a.mode == 2) {                          // w += nu0 * U1; w += nu1 * U2
-                w_ = w_ + a.nu0 * u1;
-                w_ = w_ + a.nu1 * u2;
-            } else {                                    // update = 0 - (nu0 U1)(w - wmin) + (nu1 U2)(wmax - w); w += update
-                float upd = 0.f; bool have = false;
-                if (a.nu0 != 0.f) { upd = 0.0f - (a.nu0 * u1) * (w_ - a.wmin); have = true; }
-                if (a.nu1 != 0.f) { const float y = (a.nu1 * u2) * (a.wmax - w_); upd = have ? upd + y : y; have = true; }
-                if (have) w_ = w_ + upd;
-            }
-        } else {                                        // MSTDP: sum_b reward * elig[b][i,j]
-            OuterSum acc; acc.init(tail);
-            for (int w = 0; w < MW; ++w) {
-                uint32_t m = mS[ii * MW + w] | mT[jj * MW + w];
-                while (m) {
-                    const int b = w * 32 + __ffs(m) - 1; m &= m - 1;
-                    const float e1 = xs[(size_t)b * kTI + ii] * (float)vT[(size_t)b * TJ + jj];   // p_plus (x) s_tgt
-                    const float e2 = (float)vS[(size_t)b * kTI + ii] * xt[(size_t)b * TJ + jj];   // s_src (x) p_minus
-                    const float el = e1 + e2;
-                    const float r = a.reward_vec ? a.reward_vec[b] : a.reward;
-                    acc.add(b, r * el, B);
-                }
-            }
-            const float u = acc.finish(B);
-            w_ = w_ + a.nu0 * u;                        // learning.py:1561
-        }
-        w_ = w_ * a.decay;
-        if (a.has_min && w_ < a.wmin) w_ = a.wmin;
-        if (a.has_max && w_ > a.wmax) w_ = a.wmax;
-        a.W[e] = w_;
-    }
-}
+// k_plasticity<TJ> (scalar rates and bounds) and k_plasticity_pv<TJ> (per-synapse: snn_synparams) are one text compiled twice
+#define SNN_PLASTICITY_PV 0
+#include "snn_plasticity.inc"
+#undef SNN_PLASTICITY_PV
+#define SNN_PLASTICITY_PV 1
+#include "snn_plasticity.inc"
+#undef SNN_PLASTICITY_PV
 
 static int launch_plasticity(const StdpArgs &a, hipStream_t st) {
     const int B = a.B, MW = (B + 31) / 32;
@@ -717,6 +585,56 @@ static int launch_plasticity(const StdpArgs &a, hipStream_t st) {
         return SNN_ERR_UNSUPPORTED;
     }
     return snn_check_launch();
+}
+
+// The same tiles and LDS layout for the per-synapse instance (k_plasticity_pv).
+static int launch_plasticity_pv(const StdpArgs &a, const snn_synparams &q, hipStream_t st) {
+    const int B = a.B, MW = (B + 31) / 32;
+    auto lds = [&](int TJ) {
+        return (size_t)B * TJ * 4 + (size_t)B * kTI * 4 + (size_t)(TJ + kTI) * MW * 4 + (size_t)B * TJ + (size_t)B * kTI;
+    };
+    const dim3 blk(256);
+    const unsigned gy = (a.Nin + kTI - 1) / kTI;
+    constexpr size_t kSmall = 64 * 1024, kBig = 144 * 1024;
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (snn_check(hipFuncSetAttribute((const void *)k_plasticity_pv<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBig)))
+            return SNN_ERR_LAUNCH;
+        attr_set = true;
+    }
+    if (lds(256) <= kSmall) {
+        hipLaunchKernelGGL(k_plasticity_pv<256>, dim3((a.N + 255) / 256, gy), blk, lds(256), st, a, q);
+    } else if (lds(128) <= kSmall) {
+        hipLaunchKernelGGL(k_plasticity_pv<128>, dim3((a.N + 127) / 128, gy), blk, lds(128), st, a, q);
+    } else if (lds(64) <= kSmall) {
+        hipLaunchKernelGGL(k_plasticity_pv<64>, dim3((a.N + 63) / 64, gy), blk, lds(64), st, a, q);
+    } else if (lds(32) <= kBig) {
+        hipLaunchKernelGGL(k_plasticity_pv<32>, dim3((a.N + 31) / 32, gy), blk, lds(32), st, a, q);
+    } else {
+        return SNN_ERR_UNSUPPORTED;
+    }
+    return snn_check_launch();
+}
+
+// The scalar fields of StdpArgs for the per-synapse instance: a rate given as a tensor leaves "any entry non-zero" in its place.
+static void syn_rates(StdpArgs &a, const snn_synparams &q) {
+    if (q.nu0) a.nu0 = q.nu0_any ? 1.f : 0.f;
+    if (q.nu1) a.nu1 = q.nu1_any ? 1.f : 0.f;
+}
+
+extern "C" int snn_stdp_postpre_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                   int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
+                                   int has_max, float wmax, int assume_clamped, const snn_synparams *sp, snn_stream_t stream) {
+    if (!syn_any(sp))
+        return snn_stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax,
+                                assume_clamped, stream);
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
+    if ((sp->nu0 && sp->nu0_rs != 0) || (sp->nu1 && sp->nu1_rs != 0)) return SNN_ERR_INVALID;     // learning.py:401-402
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max,
+               wmax, (assume_clamped && decay == 1.0f) ? 1 : 0, 0, 0.f, nullptr};
+    syn_rates(a, *sp);
+    return launch_plasticity_pv(a, *sp, (hipStream_t)stream);
 }
 
 extern "C" int snn_stdp_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
@@ -1026,6 +944,81 @@ extern "C" int snn_stdp_hebbian(float *W, const uint8_t *s_src, const float *x_s
     return launch_plasticity(a, (hipStream_t)stream);
 }
 
+extern "C" int snn_stdp_hebbian_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                   int Nin, int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin,
+                                   int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
+    if (!syn_any(sp))
+        return snn_stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax,
+                                stream);
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
+    if (weight_dependent && !((has_min || sp->wmin) && (has_max || sp->wmax))) return SNN_ERR_INVALID;   // learning.py:600-602
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, 0, 1.f, decay, has_min, wmin, has_max, wmax, 0,
+               weight_dependent ? 3 : 2, 0.f, nullptr};
+    syn_rates(a, *sp);
+    return launch_plasticity_pv(a, *sp, (hipStream_t)stream);
+}
+
+// The per-synapse instance of k_mstdpet: the element's own nu0 inside ((nu0 * dt) * reward), its own bounds in the clamp.
+__global__ __launch_bounds__(256) void k_mstdpet_pv(float *__restrict__ W, float *__restrict__ e_trace, const float *__restrict__ p_plus,
+                                                    const float *__restrict__ p_minus, const uint8_t *__restrict__ s_src_prev,
+                                                    const uint8_t *__restrict__ s_tgt_prev, int Nin, int N, float nu0, float dt, float reward,
+                                                    float decay_e, float tc_e, float wdecay, int has_min, float wmin, int has_max,
+                                                    float wmax, snn_synparams q) {
+    const long E = (long)Nin * N;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (long)gridDim.x * blockDim.x) {
+        const int i = (int)(e / N), j = (int)(e - (long)i * N);
+        const SynElem c = syn_elem(q, nu0, 0.f, has_min, wmin, has_max, wmax, i, j);
+        const float el = p_plus[i] * (float)s_tgt_prev[j] + (float)s_src_prev[i] * p_minus[j];    // :2241-2243
+        const float w = syn_mstdpet(W[e], &e_trace[e], el, decay_e, tc_e, c.nu0, dt, reward);
+        W[e] = syn_finish(w, wdecay, c.lo, c.hi);
+    }
+}
+
+extern "C" int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
+                                   const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt,
+                                   float a_plus, float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e,
+                                   float wdecay, int has_min, float wmin, int has_max, float wmax, const snn_synparams *sp,
+                                   snn_stream_t stream) {
+    if (!syn_any(sp))
+        return snn_mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, Nin, N, reward, nu0, dt, a_plus, a_minus,
+                                decay_plus, decay_minus, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, stream);
+    if (!W || !e_trace || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
+        return SNN_ERR_INVALID;
+    const long E = (long)Nin * N;
+    const unsigned grid = (unsigned)((E + 255) / 256 < 4096 ? (E + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_mstdpet_pv, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev,
+                       Nin, N, nu0, dt, reward, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, *sp);
+    int rc = snn_check_launch();
+    if (rc) return rc;
+    const long n = (long)Nin + N;
+    hipLaunchKernelGGL(k_mstdp_traces, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
+                       s_tgt_prev, s_src, s_tgt, (long)Nin, (long)N, a_plus, a_minus, decay_plus, decay_minus);
+    return snn_check_launch();
+}
+
+extern "C" int snn_mstdp_step_pv(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                                 const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                                 float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                                 int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
+    if (!syn_any(sp))
+        return snn_mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                              decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, stream);
+    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
+        return SNN_ERR_INVALID;
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{W, s_src_prev, p_plus, s_tgt_prev, p_minus, B, Nin, N, nu0, 0.f, 0, 1.f, wdecay, has_min, wmin,
+               has_max, wmax, 0, 1, reward, reward_vec};
+    int rc = launch_plasticity_pv(a, *sp, (hipStream_t)stream);
+    if (rc) return rc;
+    const long n = (long)B * (Nin + N);
+    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
+                       s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
+                       decay_minus);
+    return snn_check_launch();
+}
+
 // MSTDPET (learning.py:2187-2248, batch 1): the eligibility TRACE is genuinely dense state; the point eligibility is the
 // rank-2 expression of the previous step's factors and is formed on the fly.
 __global__ __launch_bounds__(256) void k_mstdpet(float *__restrict__ W, float *__restrict__ e_trace, const float *__restrict__ p_plus,
@@ -1098,8 +1091,10 @@ extern "C" int snn_mstdp_step(float *W, float *p_plus, float *p_minus, uint8_t *
 // thread sums one block per round (coalesced 64-byte row segments), one thread per column (or per lane) folds the
 // round's block sums in block order.
 constexpr int kCsCols = 16, kCsBlk = 64;
-__global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum(const float *__restrict__ W, int Nin, int N, float norm,
-                                                             int use_abs, float *__restrict__ scale) {
+// NV: the per-target form (snn_normalize_pv): scale[j] = norm_vec[j] / colsum, one division (syn_norm_scale).
+template <bool NV>
+__device__ __forceinline__ void colsum_body(const float *__restrict__ W, int Nin, int N, float norm, const float *__restrict__ norm_vec,
+                                            int use_abs, float *__restrict__ scale) {
     __shared__ float bs[kCsBlk][kCsCols + 1];          // block sums of one round: [block thread][column]
     __shared__ float lanes[4][kCsCols + 1];
     const int tid = threadIdx.x, cl = tid % kCsCols, bt = tid / kCsCols;
@@ -1134,6 +1129,7 @@ __global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum(const float *__rest
             float a0 = 0.f;                            // rows past the last complete block
             for (int i = nfull * 16; i < Nin; ++i) { const float w = W[(size_t)i * N + jc]; a0 += use_abs ? fabsf(w) : w; }
             float cs = ((a0 + a1) + a2) + a3;
+            if (NV) { scale[j] = syn_norm_scale(norm_vec[j], cs); return; }
             if (cs == 0.f) cs = 1.0f;                   // topology_features.py:265
             scale[j] = (1.0f / cs) * norm;              // torch: python_scalar / tensor == reciprocal * scalar
         }
@@ -1174,9 +1170,20 @@ __global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum(const float *__rest
     __syncthreads();
     if (bt == 0 && valid) {
         float cs = ((lanes[0][cl] + lanes[1][cl]) + lanes[2][cl]) + lanes[3][cl];
+        if (NV) { scale[j] = syn_norm_scale(norm_vec[j], cs); return; }
         if (cs == 0.f) cs = 1.0f;
         scale[j] = (1.0f / cs) * norm;
     }
+}
+
+__global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum(const float *__restrict__ W, int Nin, int N, float norm,
+                                                             int use_abs, float *__restrict__ scale) {
+    colsum_body<false>(W, Nin, N, norm, nullptr, use_abs, scale);
+}
+__global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum_nv(const float *__restrict__ W, int Nin, int N,
+                                                                const float *__restrict__ norm_vec, int use_abs,
+                                                                float *__restrict__ scale) {
+    colsum_body<true>(W, Nin, N, 0.f, norm_vec, use_abs, scale);
 }
 
 __global__ __launch_bounds__(256) void k_scale_cols(float *__restrict__ W, long E, int N,
@@ -1191,6 +1198,19 @@ extern "C" int snn_normalize(float *W, int Nin, int N, float norm, int use_abs, 
     if (Nin > kMaxTerms) return SNN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_colsum, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
                        norm, use_abs, colsum_ws);
+    int rc = snn_check_launch();
+    if (rc) return rc;
+    const long E = (long)Nin * N;
+    const unsigned grid = (unsigned)((E + 255) / 256 < 4096 ? (E + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_scale_cols, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, E, N, colsum_ws);
+    return snn_check_launch();
+}
+
+extern "C" int snn_normalize_pv(float *W, int Nin, int N, const float *norm_vec, int use_abs, float *colsum_ws, snn_stream_t stream) {
+    if (!W || !norm_vec || !colsum_ws || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
+    if (Nin > kMaxTerms) return SNN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_colsum_nv, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
+                       norm_vec, use_abs, colsum_ws);
     int rc = snn_check_launch();
     if (rc) return rc;
     const long E = (long)Nin * N;

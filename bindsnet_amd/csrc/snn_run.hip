@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/snnhip.h"
 #include "snn_common.hpp"
+#include "snn_synparams.hpp"
 #include "snn_pool.hpp"
 #include "snn_conversion.hpp"
 
@@ -243,6 +244,13 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
                 return SNN_ERR_UNSUPPORTED;
             if (d.rule == SNN_RULE_POSTPRE && R->B > 256) return SNN_ERR_UNSUPPORTED;
         }
+        if (snn::syn_any(&d.syn) || d.norm_vec) {      // per-synapse rates / bounds, per-target norms: DENSE and MCC, f32, the dense family's rules
+            if ((d.kind != SNN_CONN_DENSE && d.kind != SNN_CONN_MCC) || d.w_dtype != SNN_W_F32) return SNN_ERR_UNSUPPORTED;
+            if (snn::syn_any(&d.syn) && (d.rule == SNN_RULE_NONE || d.rule == SNN_RULE_RMAX)) return SNN_ERR_UNSUPPORTED;
+            if (!snn::syn_valid(&d.syn, L[d.dst].n)) return SNN_ERR_INVALID;
+            if (d.rule == SNN_RULE_POSTPRE && ((d.syn.nu0 && d.syn.nu0_rs) || (d.syn.nu1 && d.syn.nu1_rs))) return SNN_ERR_INVALID;
+            if (d.norm_vec && (!d.has_norm || !d.norm_ws)) return SNN_ERR_INVALID;
+        }
         if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) {        // PermuteConnection / ConstantPad2dConnection: a gather, propagation only
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
             if (d.has_norm || d.mask || d.raster_w || d.bias || d.w) return SNN_ERR_INVALID;
@@ -437,6 +445,20 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if (d.rule == SNN_RULE_POSTPRE && d.w_dtype != SNN_W_F32)
                     TRY(snn_stdp_postpre_h16(d.w, d.w_dtype, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                              d.has_min, d.wmin, d.has_max, d.wmax, st));
+                else if (snn::syn_any(&d.syn) && d.rule == SNN_RULE_POSTPRE)     // per-synapse constants: the *_pv instances (snnhip.h f13)
+                    TRY(snn_stdp_postpre_pv(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
+                                            d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, &d.syn, st));
+                else if (snn::syn_any(&d.syn) && (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE))
+                    TRY(snn_stdp_hebbian_pv(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
+                                            d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, st));
+                else if (snn::syn_any(&d.syn) && d.rule == SNN_RULE_MSTDPET)
+                    TRY(snn_mstdpet_step_pv(d.w, d.e_trace, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, S.n, D.n, d.reward,
+                                            d.nu0, R->dt, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.decay_e, d.tc_e, d.wdecay,
+                                            d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, st));
+                else if (snn::syn_any(&d.syn) && d.rule == SNN_RULE_MSTDP)
+                    TRY(snn_mstdp_step_pv(d.w, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, B, S.n, D.n,
+                                          d.reward, d.reward_vec, d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus,
+                                          d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, st));
                 else if (d.rule == SNN_RULE_POSTPRE)
                     TRY(snn_stdp_postpre(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                          d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, st));
@@ -533,6 +555,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_LOCAL || C[c].kind == SNN_CONN_CONVND || C[c].kind >= SNN_CONN_SPARSE) local = true;   // (and SparseConnection, MaxPoolNdConnection, MeanFieldConnection, PermuteConnection, ConstantPad2dConnection) plan only; no fused plan is offered the graph
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     for (int c = 0; c < nC; ++c) if (C[c].w_dtype != SNN_W_F32) local = true;   // ... and float16 / bfloat16 weights (the fused plans keep f32 tiles)
+    for (int c = 0; c < nC; ++c) if (snn::syn_any(&C[c].syn) || C[c].norm_vec) local = true;   // ... and per-synapse rates / bounds, per-target norms
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));
@@ -551,6 +574,8 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
             TRY(snn_normalize_conv2d(C[c].w, C[c].cin * C[c].local_F * C[c].local_conv_prod, C[c].local_kernel_prod, C[c].norm, st));
         else if (C[c].has_norm && C[c].w_dtype != SNN_W_F32)
             TRY(snn_normalize_h16(C[c].w, C[c].w_dtype, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_ws, st));
+        else if (C[c].has_norm && C[c].norm_vec)
+            TRY(snn_normalize_pv(C[c].w, L[C[c].src].n, L[C[c].dst].n, C[c].norm_vec, C[c].norm_abs, C[c].norm_ws, st));
         else if (C[c].has_norm && !((normalized >> c) & 1u))
             TRY(snn_normalize(C[c].w, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_abs, C[c].norm_ws, st));
     return SNN_OK;

@@ -48,12 +48,24 @@ class MCC_LearningRule(_lib.Touching):
             raise NotImplementedError(f"bindsnet_amd: MCC {type(self).__name__} on a {dtype} Weight is not supported "
                                       "(NoOp and PostPre are)")
 
-    def _bounds(self):
+    @property
+    def _takes_syn(self) -> bool:
+        """Whether the rule's updates take per-synapse clamp ranges (the *_pv entry points): a float32 Weight."""
+        return getattr(self.feature_value, "dtype", torch.float32) == torch.float32
+
+    def _nu(self, i: int) -> float:
+        return float(self.nu[i])           # (MCC_learning.py:64-66 keeps a 2-vector: tensor rates fail in the constructor)
+
+    def _bounds(self, tensors: bool = False):
+        """(lower, upper) clamp bound: None, a float or -- `tensors`, for the callers that hand them on to the *_pv entry points
+        -- a tensor of more than one element (range=[tensor, tensor], MCC_learning.py:52, :110)."""
         def one(v):
             if v is None:
                 return None
             if isinstance(v, torch.Tensor):
                 if v.numel() != 1:
+                    if tensors and self._takes_syn:
+                        return v
                     raise NotImplementedError("bindsnet_amd: per-synapse clamp ranges are not supported")
                 v = v.item()
             v = float(v)
@@ -65,13 +77,13 @@ class MCC_LearningRule(_lib.Touching):
         does not say how is refused, and so is every rule but NoOp on a manual_update connection."""
         raise NotImplementedError(f"bindsnet_amd: MCC rule {type(self).__name__} is not supported")
 
-    def _describe_batched(self, d, conn, B) -> None:
+    def _describe_batched(self, d, conn, B, dev=None, keep=None) -> None:
         """What PostPre and MSTDP share: the refusals, then bounds, decay and learning rates."""
         if conn.manual_update:
             MCC_LearningRule._describe(self, d, conn, B, None, None, None)
         if self.reduction is torch.squeeze and B != 1:
             raise RuntimeError("reduction=torch.squeeze requires batch size 1")
-        _descriptor.fill_update(d, self, self.decay)
+        _descriptor.fill_update(d, self, self.decay, dev, keep)
 
     def update(self, **kwargs) -> None:
         raise NotImplementedError
@@ -114,7 +126,7 @@ class PostPre(MCC_LearningRule):
             raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
 
     def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
-        self._describe_batched(d, conn, B)
+        self._describe_batched(d, conn, B, dev, keep)
         d.rule, d.use_dt = _lib.RULE_POSTPRE, 1
 
     def update(self, **kwargs) -> None:
@@ -124,7 +136,7 @@ class PostPre(MCC_LearningRule):
         B = self.source.batch_size
         if self.reduction is torch.squeeze and B != 1:
             raise RuntimeError("reduction=torch.squeeze requires batch size 1 (as in the reference)")
-        lo, hi = self._bounds()
+        lo, hi = self._bounds(tensors=True)
         ops.stdp_postpre(self.feature_value.data, self.source.s.reshape(B, -1).contiguous(),
                          self.source.x.reshape(B, -1), self.target.s.reshape(B, -1), self.target.x.reshape(B, -1),
                          float(self.nu[0]), float(self.nu[1]), use_dt=True, dt=float(self.connection.dt),
@@ -165,7 +177,7 @@ class MSTDP(MCC_LearningRule):
         return float(torch.exp(-dt / self.tc_plus)), float(torch.exp(-dt / self.tc_minus))   # MCC_learning.py:538,540
 
     def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
-        self._describe_batched(d, conn, B)
+        self._describe_batched(d, conn, B, dev, keep)
         _descriptor.fill_mstdp(d, self, kwargs, dev, keep)
 
     def update(self, **kwargs) -> None:
@@ -176,7 +188,7 @@ class MSTDP(MCC_LearningRule):
         self._ensure_state()
         reward, rvec = _descriptor.split_reward(kwargs["reward"], self.feature_value.device)
         dp, dm = self._decays()
-        lo, hi = self._bounds()
+        lo, hi = self._bounds(tensors=True)
         ops.mstdp_step(self.feature_value.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
                        self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
                        float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
@@ -236,7 +248,7 @@ class MSTDPET(MCC_LearningRule):
             super()._describe(d, conn, B, dev, keep, kwargs)
         if B != 1:
             raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
-        _descriptor.fill_mstdpet(d, self, self.decay, kwargs)
+        _descriptor.fill_mstdpet(d, self, self.decay, kwargs, dev, keep)
 
     def update(self, **kwargs) -> None:
         from .. import ops
@@ -244,7 +256,7 @@ class MSTDPET(MCC_LearningRule):
             raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
         self._ensure_state()
         dp, dm, de = self._decays()
-        lo, hi = self._bounds()
+        lo, hi = self._bounds(tensors=True)
         ops.mstdpet_step(self.feature_value.data, self.eligibility_trace, self.p_plus, self.p_minus, self._s_src_prev,
                          self._s_tgt_prev, self.source.s.reshape(-1).contiguous(), self.target.s.reshape(-1), float(kwargs["reward"]),
                          float(self.nu[0]), float(self.connection.dt), float(kwargs.get("a_plus", 1.0)),

@@ -11,10 +11,101 @@ def accepts(connection, rule) -> bool:
     return any(c.__name__ in getattr(connection, "_rules", ()) for c in type(rule).__mro__)
 
 
-def fill_update(d, rule, wdecay) -> None:
-    """Clamp bounds, weight-decay factor (dense rules keep it in `weight_decay`, MCC rules in `decay`) and learning rates."""
-    lo, hi = rule._bounds()
+def is_vec(v) -> bool:
+    """A constant given as a tensor of more than one element (a one-element tensor is a scalar, as for the node layers)."""
+    return isinstance(v, torch.Tensor) and v.numel() > 1
+
+
+def device_const(t, shape, dev):
+    """A tensor constant as the *_pv kernels read it: (float32 contiguous tensor on `dev`, element strides against `shape`), 0 on
+    every broadcast axis -- nothing is expanded.  A tensor that is not already there is copied once and kept on the tensor object,
+    keyed by its in-place version; while run descriptors are built the tensor is noted, so an in-place edit rebuilds them.  What does
+    not broadcast against `shape` raises torch's RuntimeError, as the reference's first update would."""
+    from ..network import nodes as _nodes
+    if _nodes._SCALARS is not None:
+        _nodes._SCALARS.append((t, t._version))
+    dev = torch.device(dev)
+    if t.device == dev and t.dtype == torch.float32 and t.is_contiguous():
+        c = t.detach()
+    else:
+        hit = getattr(t, "_snn_dev", None)
+        if hit is None or hit[0] != t._version or hit[1].device != dev:
+            hit = (t._version, t.detach().to(dev, torch.float32).contiguous())
+            t._snn_dev = hit
+        c = hit[1]
+    e = c.expand(*shape)
+    pad = len(shape) - c.dim()
+    strides = tuple(0 if (k < pad or c.shape[k - pad] == 1) else e.stride(k) for k in range(len(shape)))
+    return c, strides
+
+
+def any_nonzero(t) -> bool:
+    """`t.any()` of a rate tensor (learning.py:399), remembered on the tensor by its in-place version."""
+    hit = getattr(t, "_snn_any", None)
+    if hit is None or hit[0] != t._version:
+        hit = (t._version, bool(t.any()))
+        t._snn_any = hit
+    return hit[1]
+
+
+def all_finite(t) -> bool:
+    hit = getattr(t, "_snn_finite", None)
+    if hit is None or hit[0] != t._version:
+        hit = (t._version, bool(torch.isfinite(t).all()))
+        t._snn_finite = hit
+    return hit[1]
+
+
+def syn_params(S, N, dev, nu0, nu1, lo, hi):
+    """The constants of one rule for the C ABI.  Each of nu0, nu1 (float or tensor) and lo, hi (None, float or tensor) goes either
+    into its scalar argument or, as a tensor of more than one element, into the snn_synparams.  Returns (nu0, nu1, lo, hi, sp, keep):
+    scalars (0.0 / None where a tensor stands), the _lib.SynParams or None when there is no tensor, the device tensors it points to."""
+    vals = {"nu0": nu0, "nu1": nu1, "wmin": lo, "wmax": hi}
+    if not any(is_vec(v) for v in vals.values()):
+        return _scalar(nu0) or 0.0, _scalar(nu1) or 0.0, _bound(lo), _bound(hi), None, []
+    sp, keep = _lib.SynParams(), []
+    for name, v in vals.items():
+        if not is_vec(v):
+            continue
+        c, (rs, cs) = device_const(v, (S, N), dev)
+        keep.append(c)
+        setattr(sp, name, c.data_ptr())
+        setattr(sp, name + "_rs", rs)
+        setattr(sp, name + "_cs", cs)
+        if name in ("nu0", "nu1"):
+            setattr(sp, name + "_any", int(any_nonzero(v)))
+        vals[name] = None
+    return _scalar(vals["nu0"]) or 0.0, _scalar(vals["nu1"]) or 0.0, _bound(vals["wmin"]), _bound(vals["wmax"]), sp, keep
+
+
+def _scalar(v):
+    if v is None:
+        return None
+    return float(v.reshape(()).item()) if isinstance(v, torch.Tensor) else float(v)
+
+
+def _bound(v):
+    v = _scalar(v)
+    return None if v is None or v in (float("inf"), float("-inf")) else v
+
+
+def fill_update(d, rule, wdecay, dev=None, keep=None) -> None:
+    """Clamp bounds, weight-decay factor (dense rules keep it in `weight_decay`, MCC rules in `decay`) and learning rates.  A rule
+    that takes per-synapse constants (`_takes_syn`) hands tensors on: they go into d.syn, on `dev`."""
     d.wdecay = float(wdecay)
+    if getattr(rule, "_takes_syn", False):
+        lo, hi = rule._bounds(tensors=True)
+        nu0, nu1 = rule._nu(0), rule._nu(1)
+        if any(is_vec(v) for v in (nu0, nu1, lo, hi)):
+            nu0, nu1, lo, hi, sp, kept = syn_params(rule.source.n, rule.target.n, dev, nu0, nu1, lo, hi)
+            d.syn = sp
+            if keep is not None:
+                keep.extend(kept)
+            d.has_min, d.wmin = int(lo is not None), lo or 0.0
+            d.has_max, d.wmax = int(hi is not None), hi or 0.0
+            d.nu0, d.nu1 = nu0, nu1
+            return
+    lo, hi = rule._bounds()
     d.has_min, d.wmin = int(lo is not None), lo or 0.0
     d.has_max, d.wmax = int(hi is not None), hi or 0.0
     d.nu0, d.nu1 = float(rule.nu[0]), float(rule.nu[1])
@@ -57,11 +148,11 @@ def fill_mstdp(d, rule, kwargs, dev, keep) -> None:
     d.s_src_prev, d.s_tgt_prev = dptr(rule._s_src_prev), dptr(rule._s_tgt_prev)
 
 
-def fill_mstdpet(d, rule, wdecay, kwargs) -> None:
+def fill_mstdpet(d, rule, wdecay, kwargs, dev=None, keep=None) -> None:
     """MSTDPET's keyword arguments and device state (learning.py:2187-2248, MCC_learning.py:652-729)."""
     r = reward(kwargs)
     rule._ensure_state()
-    fill_update(d, rule, wdecay)
+    fill_update(d, rule, wdecay, dev, keep)
     dp, dm, de = rule._decays()
     d.rule, d.reward = _lib.RULE_MSTDPET, float(r)
     d.a_plus, d.a_minus = float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0))

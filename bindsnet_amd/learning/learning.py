@@ -36,8 +36,12 @@ class LearningRule(_lib.Touching):
             self.nu = torch.tensor([nu, nu], dtype=torch.float)
         elif all(isinstance(e, (float, int)) for e in nu):
             self.nu = torch.tensor(nu, dtype=torch.float)
-        else:
+        elif connection._kind != _lib.CONN_DENSE or self._rule_code in (None, _lib.RULE_RMAX):
             raise NotImplementedError("bindsnet_amd: per-synapse tensor learning rates are not supported")
+        else:                                   # learning.py:67: a pair of tensors, each broadcast against the [source.n, target.n] weights
+            self.nu = torch.stack(nu, dim=0).to(dtype=torch.float)
+            if self.nu[0].numel() > 1:
+                self.nu[0].expand(self.source.n, self.target.n)     # (what does not broadcast: torch's RuntimeError, as in the first update)
         if not self.nu.any() and not isinstance(self, NoOp):
             warnings.warn(f"nu is set to zeros for {type(self).__name__} learning rule. "
                           "It will disable the learning process.")
@@ -46,15 +50,45 @@ class LearningRule(_lib.Touching):
         self.reduction = reduction
         self.weight_decay = 1.0 - weight_decay if weight_decay else 1.0
 
-    def _bounds(self):
+    @property
+    def _takes_syn(self) -> bool:
+        """Whether the rule's updates take per-synapse constants (the *_pv entry points): the dense family's rules but Rmax."""
+        return self.connection._kind == _lib.CONN_DENSE and self._rule_code not in (None, _lib.RULE_NONE, _lib.RULE_RMAX)
+
+    def _nu(self, i: int):
+        """Learning rate i as the ops take it: a float, or the tensor of more than one element."""
+        kept = self.__dict__.get("_nu_views")          # the SAME view objects from call to call: the device copy and `.any()` are
+        if kept is None or kept[0] is not self.nu or kept[1][0]._base is not self.nu:    # remembered on them, keyed by the in-place version
+            # they share with `nu` (a copy or an unpickled rule has tensors of its own, no longer views of its `nu`: made again)
+            kept = (self.nu, (self.nu[0], self.nu[1]))
+            self.__dict__["_nu_views"] = kept
+        t = kept[1][i]
+        return t if t.numel() > 1 else float(t)
+
+    def _bounds(self, tensors: bool = False):
+        """(lower, upper) clamp bound: None where there is none, a float, or -- `tensors`, for the callers that hand them on to the
+        *_pv entry points -- a tensor of more than one element."""
         c = self.connection
         if c.wmin.numel() != 1 or c.wmax.numel() != 1:
-            raise NotImplementedError("bindsnet_amd: per-synapse wmin/wmax tensors are not supported")
+            if not (tensors and self._takes_syn):
+                raise NotImplementedError("bindsnet_amd: per-synapse wmin/wmax tensors are not supported")
+
+            def one(t, inf):
+                if t.numel() > 1:
+                    return t
+                v = _f(t)
+                return None if v == inf else v
+            return one(c.wmin, -np.inf), one(c.wmax, np.inf)
         lo, hi = _f(c.wmin), _f(c.wmax)      # (through _f: an in-place edit of the bounds invalidates the kept run descriptors)
         clamp = (lo != -np.inf or hi != np.inf) and not isinstance(self, NoOp)   # learning.py:97-104
         if not clamp:
             return None, None
         return (None if lo == -np.inf else lo), (None if hi == np.inf else hi)
+
+    def _syn_refusal(self):
+        """What a rule with per-synapse constants cannot run, as an exception (None: nothing): asked when the rule is built and
+        before a run changes any state."""
+        return None
 
     def _check_reduction(self):
         B = self.source.batch_size
@@ -75,7 +109,10 @@ class LearningRule(_lib.Touching):
         if self._rule_code is None:
             raise NotImplementedError(f"bindsnet_amd: rule {type(self).__name__} is not supported")
         self._check_reduction()
-        _descriptor.fill_update(d, self, self.weight_decay)
+        err = self._syn_refusal()
+        if err is not None:
+            raise err
+        _descriptor.fill_update(d, self, self.weight_decay, dev, keep)
         d.rule = self._rule_code
 
     def update(self, **kwargs) -> None:
@@ -102,10 +139,25 @@ class PostPre(LearningRule):
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
         assert self.source.traces and self.target.traces, "Both pre- and post-synaptic nodes must record spike traces."
         self._require_accepted()
+        err = self._syn_refusal()
+        if err is not None:
+            raise err
+
+    def _syn_refusal(self):
+        """learning.py:401-402: `target_x * nu[0]` must stay [B, 1, N] for the bmm -- rates that vary along the source axis fail there."""
+        for i in (0, 1):
+            t = self.nu[i]
+            if t.numel() > 1 and (t.dim() > 2 or (t.dim() == 2 and t.shape[0] != 1)):
+                return RuntimeError(f"PostPre: nu[{i}] of shape {list(t.shape)} does not broadcast against the [batch, 1, {self.target.n}] "
+                                    "target factor (batch2 of the bmm at learning.py:402 / :414 must stay a 3D tensor of that shape)")
+        return None
 
     def update(self, **kwargs) -> None:
         self._check_reduction()
-        self.connection._postpre(self, self.source.batch_size, *self._bounds())
+        err = self._syn_refusal()
+        if err is not None:
+            raise err
+        self.connection._postpre(self, self.source.batch_size, *self._bounds(tensors=True))
 
 
 class MSTDP(LearningRule):
@@ -186,10 +238,10 @@ class MSTDP(LearningRule):
         B = self.source.batch_size
         reward, rvec = _descriptor.split_reward(kwargs["reward"], self.connection.w.device)
         dp, dm = self._decays()
-        lo, hi = self._bounds()
+        lo, hi = self._bounds(tensors=True)
         ops.mstdp_step(self.connection.w.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
                        self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
-                       float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
+                       self._nu(0), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
                        wdecay=float(self.weight_decay), wmin=lo, wmax=hi, reward_vec=rvec)
 
     @property
@@ -214,11 +266,14 @@ class _OuterProductRule(LearningRule):
         from .. import ops
         self._check_reduction()
         B = self.source.batch_size
-        lo, hi = self._bounds()
         if self.connection._kind == _lib.CONN_CONV2D:
-            return self.connection._outer_product(self, B, lo, hi)
+            return self.connection._outer_product(self, B, *self._bounds())
+        err = self._syn_refusal()
+        if err is not None:
+            raise err
+        lo, hi = self._bounds(tensors=True)
         ops.stdp_hebbian(self.connection.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
-                         self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(self.nu[0]), float(self.nu[1]),
+                         self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), self._nu(0), self._nu(1),
                          weight_dependent=self._weight_dependent, decay=float(self.weight_decay), wmin=lo, wmax=hi)
 
 
@@ -244,6 +299,18 @@ class WeightDependentPostPre(_OuterProductRule):
         if not self.target.traces:
             raise NotImplementedError("bindsnet_amd: WeightDependentPostPre needs spike traces on the target layer too "
                                       "(the update reads target.x)")
+        err = self._syn_refusal()
+        if err is not None:
+            raise err
+
+    def _syn_refusal(self):
+        """A bound tensor with a non-finite entry passes the reference's `.any()` assertion and turns the weights into NaN."""
+        c = self.connection
+        for t in (c.wmin, c.wmax):
+            if t.numel() > 1 and not _descriptor.all_finite(t):
+                return NotImplementedError("bindsnet_amd: WeightDependentPostPre needs finite wmin and wmax for every synapse "
+                                           "(a bound tensor has a non-finite entry)")
+        return None
 
 
 class MSTDPET(LearningRule):
@@ -281,7 +348,7 @@ class MSTDPET(LearningRule):
     def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
         if B != 1:
             raise NotImplementedError("MSTDPET on a dense Connection is defined for batch size 1 (learning.py:2211-2212)")
-        _descriptor.fill_mstdpet(d, self, self.weight_decay, kwargs)
+        _descriptor.fill_mstdpet(d, self, self.weight_decay, kwargs, dev, keep)
 
     def update(self, **kwargs) -> None:
         from .. import ops
@@ -289,10 +356,10 @@ class MSTDPET(LearningRule):
             raise NotImplementedError("MSTDPET on a dense Connection is defined for batch size 1 (learning.py:2211-2212)")
         self._ensure_state()
         dp, dm, de = self._decays()
-        lo, hi = self._bounds()
+        lo, hi = self._bounds(tensors=True)
         ops.mstdpet_step(self.connection.w.data, self.eligibility_trace, self.p_plus, self.p_minus, self._s_src_prev,
                          self._s_tgt_prev, self.source.s.reshape(-1).contiguous(), self.target.s.reshape(-1), float(kwargs["reward"]),
-                         float(self.nu[0]), float(self.connection.dt), float(kwargs.get("a_plus", 1.0)),
+                         self._nu(0), float(self.connection.dt), float(kwargs.get("a_plus", 1.0)),
                          float(kwargs.get("a_minus", -1.0)), dp, dm, de, float(self.tc_e_trace),
                          wdecay=float(self.weight_decay), wmin=lo, wmax=hi)
 

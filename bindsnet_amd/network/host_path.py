@@ -436,7 +436,7 @@ def _mstdp(rule, W, src_s, tgt_s, kwargs) -> None:
         torch.bmm(rule._s_src_prev.float().unsqueeze(2), rule.p_minus.unsqueeze(1))
     if isinstance(reward, torch.Tensor) and reward.numel() > 1:
         reward = reward.view(-1, 1, 1).float()
-    W += float(rule.nu[0]) * _reduce(rule, reward * elig)
+    W += rule._nu(0) * _reduce(rule, reward * elig)
     _advance_p(rule, *rule._decays(), src_s, tgt_s, kwargs)
 
 
@@ -556,8 +556,13 @@ def _decay_clamp(rule, W, factor) -> None:
     """learning.py:87-104 / MCC_learning.py:86-110: what a rule's update ends with (dense rules keep the factor in
     `weight_decay`, MCC rules in `decay`)."""
     W *= float(factor)
-    lo, hi = rule._bounds()
-    if lo is not None or hi is not None:
+    lo, hi = rule._bounds(tensors=True)
+    if isinstance(lo, torch.Tensor) or isinstance(hi, torch.Tensor):       # per-synapse bounds: the reference's own call
+        if hasattr(rule, "feature_value"):                                 # MCC_learning.py:110 (a float beside a tensor: as a 0-dim tensor, like the device)
+            W.clamp_(*(v if v is None or isinstance(v, torch.Tensor) else torch.tensor(float(v)) for v in (rule.min, rule.max)))
+        else:
+            W.clamp_(rule.connection.wmin, rule.connection.wmax)           # learning.py:104
+    elif lo is not None or hi is not None:
         W.clamp_(lo, hi)
 
 
@@ -623,7 +628,9 @@ def _update_dense(conn, kwargs, mask) -> None:
     W = conn.w.data
     if W.dim() != 2:
         raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} on {type(conn).__name__}")
-    nu0, nu1 = float(rule.nu[0]), float(rule.nu[1])
+    nu0, nu1 = rule._nu(0), rule._nu(1)                     # floats, or per-synapse tensors (learning.py:67)
+    on0 = bool(nu0.any()) if isinstance(nu0, torch.Tensor) else bool(nu0)      # learning.py:399: `self.nu[0].any()`
+    on1 = bool(nu1.any()) if isinstance(nu1, torch.Tensor) else bool(nu1)
     if isinstance(rule, rules.MSTDPET):
         _mstdpet(rule, W, conn.dt, conn.source.s.view(-1).float(), conn.target.s.view(-1).float(), kwargs)
     elif isinstance(rule, rules.Rmax):
@@ -642,15 +649,15 @@ def _update_dense(conn, kwargs, mask) -> None:
                 W += nu1 * u2
             else:
                 update = 0
-                if nu0:
+                if on0:
                     update = update - nu0 * u1 * (W - conn.wmin)
-                if nu1:
+                if on1:
                     update = update + nu1 * u2 * (conn.wmax - W)
                 W += update
         elif isinstance(rule, rules.PostPre):               # learning.py:390-420
-            if nu0:
+            if on0:
                 W -= _reduce(rule, torch.bmm(src_s.unsqueeze(2), conn.target.x.view(B, -1).unsqueeze(1) * nu0))
-            if nu1:
+            if on1:
                 W += _reduce(rule, torch.bmm(conn.source.x.view(B, -1).unsqueeze(2), tgt_s.unsqueeze(1) * nu1))
         else:
             raise NotImplementedError(f"bindsnet_amd host path: rule {type(rule).__name__} (supported: PostPre, MSTDP, Hebbian, "

@@ -341,6 +341,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 err = rule._batch_refusal(B) if hasattr(rule, "_batch_refusal") else None
                 if err is not None:
                     raise err
+                err = rule._syn_refusal() if hasattr(rule, "_syn_refusal") else None     # ... nor with these per-synapse constants
+                if err is not None:
+                    raise err
         dev = self._device()
         if dev.type != "cuda":
             # A network whose tensors live on the host: the plain-PyTorch step loop with the reference's semantics

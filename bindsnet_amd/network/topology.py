@@ -60,6 +60,24 @@ def _matrix_weights(conn, w_dtype, kwargs):
     return Parameter(w, requires_grad=False), (Parameter(b, requires_grad=False) if b is not None else None)
 
 
+def _norm_value(norm):
+    """`norm` as ops.normalize takes it: a float, or the tensor of more than one element (one total per target neuron; a
+    one-element tensor is a scalar here)."""
+    return norm if isinstance(norm, torch.Tensor) and norm.numel() > 1 else float(norm)
+
+
+def _fill_norm(d, norm, use_abs: int, ws, n: int, dev) -> None:
+    """The column-normalisation fields of a snn_conn_desc: a scalar `norm`, or norm_vec for a tensor norm (brought to `dev` once;
+    an in-place edit of the tensor rebuilds the kept descriptors)."""
+    norm = _norm_value(norm)
+    d.has_norm, d.norm_abs, d.norm_ws = 1, use_abs, dptr(ws)
+    if isinstance(norm, torch.Tensor):
+        vec = ops.norm_vector(norm, n, dev)
+        d.norm, d.norm_vec = 0.0, dptr(vec)
+    else:
+        d.norm = norm
+
+
 class AbstractConnection(_lib.TouchingModule, Module):
     """Reference: topology.py:17-156 (wmin/wmax/norm/update_rule plumbing).
 
@@ -123,7 +141,7 @@ class AbstractConnection(_lib.TouchingModule, Module):
         if not self.w.is_cuda:
             return self._host_normalize()
         if self._norm_by == "columns":
-            ops.normalize(self.w.data.view(self.source.n, self.target.n), float(self.norm), use_abs=self._norm_abs)
+            ops.normalize(self.w.data.view(self.source.n, self.target.n), _norm_value(self.norm), use_abs=self._norm_abs)
         elif isinstance(self.norm, torch.Tensor):
             raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
         else:                     # every row of the [w.shape[0] * w.shape[1], rest] view (snn_normalize_conv2d)
@@ -158,7 +176,7 @@ class AbstractConnection(_lib.TouchingModule, Module):
         if self.norm is not None:
             if self._norm_by == "columns":
                 ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
-                d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(self.norm), int(self._norm_abs), dptr(ws)
+                _fill_norm(d, self.norm, int(self._norm_abs), ws, self.target.n, dev)
             elif isinstance(self.norm, torch.Tensor):
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
             elif self._norm_by == "rows":
@@ -208,7 +226,7 @@ class _DenseConnection(AbstractConnection):
     def _postpre(self, rule, B, lo, hi) -> None:
         """learning.py:390-420."""
         ops.stdp_postpre(self.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
-                         self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
+                         self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), rule._nu(0), rule._nu(1),
                          use_dt=False, decay=float(rule.weight_decay), wmin=lo, wmax=hi)
 
 
@@ -1385,10 +1403,8 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         # (float16 / bfloat16: `w` points at 2-byte elements and the run takes the generic plan's *_h16 kernels, csrc/snn_half.hip)
         d.kind, d.w, d.w_dtype = self._kind, dptr(val.data), ops.HALF.get(val.dtype, _lib.W_F32)
         if feat.norm is not None:
-            if isinstance(feat.norm, torch.Tensor):
-                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
             ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
-            d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, dptr(ws)
+            _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
         return [self._weights()]
 
     def _describe_pipe(self, d, B, dev, scratch):
@@ -1408,10 +1424,8 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
                 raise NotImplementedError("bindsnet_amd: the Weight of a pipeline must be a [source.n, target.n] tensor")
             d.w = dptr(feat.value.data)
             if feat.norm is not None:
-                if isinstance(feat.norm, torch.Tensor):
-                    raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
                 ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
-                d.has_norm, d.norm, d.norm_abs, d.norm_ws = 1, float(feat.norm), 0, dptr(ws)
+                _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
         return described
 
     def update(self, **kwargs) -> None:

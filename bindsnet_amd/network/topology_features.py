@@ -83,10 +83,9 @@ class AbstractFeature(_lib.Touching):
         snn_normalize_h16 (the reference's three roundings: csrc/snn_half.hpp)."""
         if self.norm is None:
             return
-        if isinstance(self.norm, torch.Tensor):
-            raise NotImplementedError("bindsnet_amd: per-target tensor norms are not supported")
         from .. import ops
-        ops.normalize(self.value.data, float(self.norm), use_abs=False)
+        norm = self.norm if isinstance(self.norm, torch.Tensor) and self.norm.numel() > 1 else float(self.norm)
+        ops.normalize(self.value.data, norm, use_abs=False)
 
     def reset_state_variables(self) -> None:
         if self.learning_rule:

@@ -43,6 +43,15 @@ def _bounds(wmin, wmax):
     return int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax
 
 
+def _syn(W, nu0, nu1, wmin, wmax):
+    """The rates and bounds of a dense update for the C ABI: (nu0, nu1, (has_min, wmin, has_max, wmax), snn_synparams or None,
+    tensors to keep alive).  A rate or bound given as a tensor of more than one element is read per synapse by the *_pv entry
+    points, broadcast against W's [Nin, N] by its strides and brought to W's device on demand."""
+    from .learning._descriptor import syn_params
+    nu0, nu1, lo, hi, sp, keep = syn_params(W.shape[0], W.shape[1], W.device, nu0, nu1, wmin, wmax)
+    return nu0, nu1, _bounds(lo, hi), sp, keep
+
+
 def prop_cascade(W, s, out, accumulate=False):
     """a5: out[b,j] (+)= sum_i W[i,j]*s[b,i] in ATen sum(dim=1) order."""
     B = s.shape[0]
@@ -518,19 +527,32 @@ def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=
                                          _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax), _stream()),
               "stdp_postpre_h16")
         return
+    nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
+    if sp is not None:                  # per-synapse rates / bounds (include/snnhip.h f13)
+        check(lib().snn_stdp_postpre_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                        B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped), C.byref(sp),
+                                        _stream()), "stdp_postpre_pv")
+        return
     check(lib().snn_stdp_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                  _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay,
-                                 *_bounds(wmin, wmax), int(assume_clamped), _stream()), "stdp_postpre")
+                                 *bounds, int(assume_clamped), _stream()), "stdp_postpre")
 
 
 def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus,
                decay_plus, decay_minus, wdecay=1.0, wmin=None, wmax=None, reward_vec=None):
     B = s_src.shape[0]
     Nin, N = W.shape
+    nu0, _, bounds, sp, _keep = _syn(W, nu0, 0.0, wmin, wmax)
+    if sp is not None:
+        check(lib().snn_mstdp_step_pv(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                      _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
+                                      reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
+                                      wdecay, *bounds, C.byref(sp), _stream()), "mstdp_step_pv")
+        return
     check(lib().snn_mstdp_step(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
                                _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
                                reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
-                               wdecay, *_bounds(wmin, wmax), _stream()), "mstdp_step")
+                               wdecay, *bounds, _stream()), "mstdp_step")
 
 
 def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, decay=1.0, wmin=None, wmax=None, ws=None):
@@ -571,17 +593,30 @@ def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False
     """f3: Hebbian (weight_dependent=False) / WeightDependentPostPre (True) on a dense weight matrix."""
     B = s_src.shape[0]
     Nin, N = W.shape
+    nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
+    if sp is not None:
+        check(lib().snn_stdp_hebbian_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                        B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, C.byref(sp), _stream()),
+              "stdp_hebbian_pv")
+        return
     check(lib().snn_stdp_hebbian(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                 B, Nin, N, nu0, nu1, int(weight_dependent), decay, *_bounds(wmin, wmax), _stream()),
+                                 B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, _stream()),
           "stdp_hebbian")
 
 
 def mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, dt, a_plus, a_minus,
                  decay_plus, decay_minus, decay_e, tc_e, wdecay=1.0, wmin=None, wmax=None):
     Nin, N = W.shape
+    nu0, _, bounds, sp, _keep = _syn(W, nu0, 0.0, wmin, wmax)
+    if sp is not None:
+        check(lib().snn_mstdpet_step_pv(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                        _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
+                                        a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *bounds, C.byref(sp),
+                                        _stream()), "mstdpet_step_pv")
+        return
     check(lib().snn_mstdpet_step(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
                                  _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
-                                 a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *_bounds(wmin, wmax), _stream()),
+                                 a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *bounds, _stream()),
           "mstdpet_step")
 
 
@@ -594,7 +629,21 @@ def normalize(W, norm, use_abs, ws=None):
             raise NotImplementedError(f"bindsnet_amd: normalisation by absolute column sums computes in float32 only (got {W.dtype})")
         check(lib().snn_normalize_h16(_ptr(W, W.dtype), HALF[W.dtype], Nin, N, norm, _ptr(ws, F32), _stream()), "normalize_h16")
         return
+    if isinstance(norm, torch.Tensor):  # one total per target neuron: norm[n] / colsum[n], a true division (snn_normalize_pv)
+        check(lib().snn_normalize_pv(_ptr(W, F32), Nin, N, _ptr(norm_vector(norm, N, W.device), F32), int(use_abs), _ptr(ws, F32),
+                                     _stream()), "normalize_pv")
+        return
     check(lib().snn_normalize(_ptr(W, F32), Nin, N, norm, int(use_abs), _ptr(ws, F32), _stream()), "normalize")
+
+
+def norm_vector(norm, N, dev):
+    """A tensor `norm` as snn_normalize_pv reads it: float32 [N] on `dev` (the tensor itself where it already is; a copy kept on
+    it otherwise).  The device takes [N] and [1, N]; the host path runs the reference's expression for every shape."""
+    from .learning._descriptor import device_const
+    if norm.numel() != N or norm.dim() > 2 or (norm.dim() == 2 and norm.shape[0] != 1):
+        raise NotImplementedError(f"bindsnet_amd: a tensor norm on the device has one entry per target neuron, [{N}] or [1, {N}], "
+                                  f"not {list(norm.shape)}")
+    return device_const(norm, (N,) if norm.dim() == 1 else (1, N), dev)[0]
 
 
 def normalize_conv2d(W, norm):

@@ -97,6 +97,22 @@ def _reject_pervec(network, mode: str, lif_thresh_ok: bool = False) -> None:
                                       "the multi-device modes do not support; run the network on one device")
 
 
+def _reject_synparams(network, mode: str) -> None:
+    """None of the multi-device modes reads per-synapse (tensor-valued) learning rates, bounds or norms: refused in the words the
+    bounds have always been refused in, before any collective."""
+    for conn in network.connections.values():
+        rule = conn._rule() if hasattr(conn, "_rule") else None
+        nu = getattr(rule, "nu", None)
+        if isinstance(nu, torch.Tensor) and nu.numel() > 2:
+            raise NotImplementedError("bindsnet_amd: per-synapse tensor learning rates are not supported")
+        if hasattr(rule, "_bounds") and getattr(rule, "connection", None) is not None:
+            rule._bounds()                   # "per-synapse wmin/wmax tensors are not supported" / "per-synapse clamp ranges are not supported"
+        for holder in [conn] + list(getattr(conn, "pipeline", [])):
+            norm = getattr(holder, "norm", None)
+            if isinstance(norm, torch.Tensor) and norm.numel() > 1:
+                raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
+
+
 def _reject_stochastic(network, mode: str) -> None:
     """None of the multi-device modes runs SRM0Nodes or Rmax: the layer draws from the ONE host generator in the global batch's
     row-major order, which no shard of the batch or of the columns reproduces, and the rule is defined for batch size 1."""
@@ -127,6 +143,7 @@ def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None,
     _reject_local(network, "sharded_run")
     _reject_stochastic(network, "sharded_run")
     _reject_pervec(network, "sharded_run", lif_thresh_ok=True)
+    _reject_synparams(network, "sharded_run")
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
     tensors = [t for t, _, _, _ in learned] + thetas
@@ -192,6 +209,7 @@ def column_shard(network, rank: int, world: int):
     _reject_local(network, "column_shard")
     _reject_stochastic(network, "column_shard")
     _reject_pervec(network, "column_shard")
+    _reject_synparams(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
         raise NotImplementedError("column sharding applies to Input -> one connection -> LIFNodes graphs (no coupling "
@@ -283,6 +301,7 @@ def _exact_check(network):
     _reject_local(network, "exact_run")
     _reject_stochastic(network, "exact_run")
     _reject_pervec(network, "exact_run")
+    _reject_synparams(network, "exact_run")
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes
     for name, layer in network.layers.items():
         if type(layer) not in (Input, LIFNodes, DiehlAndCookNodes):

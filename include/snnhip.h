@@ -549,6 +549,50 @@ int snn_stdp_postpre_h16(void *W, int w_dtype, const uint8_t *s_src, const float
                          int has_min, float wmin, int has_max, float wmax, snn_stream_t stream);
 int snn_normalize_h16(void *W, int w_dtype, int Nin, int N, float norm, float *colsum_ws, snn_stream_t stream);
 
+/* ---- f13: per-synapse learning rates and weight bounds, per-target norms --------------------------
+ * The reference takes `nu` as a pair of tensors (learning.py:44-46, :67), `wmin` / `wmax` as tensors of the weights' size
+ * (topology.py:49-52; `range` of a Weight, MCC_learning.py:52) and `norm` as one total per target neuron
+ * (topology_features.py:207-208).  snn_synparams names those constants: each pointer is a device f32 array read as
+ * p[s * rs + n * cs] for the weight element (source s, target n), with element strides rs, cs (0 on a broadcast axis, so a [N]
+ * vector stays a [N] vector in memory); a NULL pointer leaves the constant to the entry point's scalar argument.  nu0_any /
+ * nu1_any: whether ANY entry of the rate tensor is non-zero -- the reference's `self.nu[i].any()` (learning.py:399, :409, :642,
+ * :647), which decides whether the half of the update runs at all; with it set, elements whose own rate is 0 still go through the
+ * arithmetic (w - 0, like the reference).  The *_pv entry points compute what their scalar namesakes compute, every element with
+ * its own constants: the products with the rates sit where they sit there (`x_tgt * nu0`, `nu * U`, `(nu * U) * (w - wmin)`,
+ * `((nu0 * dt) * reward) * e`), the clamp is min(max(w, wmin), wmax) with an absent bound as -inf / +inf.  A NULL `sp`, or one
+ * whose four pointers are NULL, is the scalar entry point.  The pair (rs, cs) must be that of a shape that broadcasts against [Nin, N] -- (0, 0) one
+ * element, (0, 1) [N] or [1, N], (1, 0) [S, 1], (N, 1) [S, N]; a size-1 axis has stride 0 --, anything else: SNN_ERR_INVALID.
+ *   snn_stdp_postpre_pv   learning.py:390-420 / MCC_learning.py:224-302: the rates multiply the [B, N] target factors, so they
+ *                         must not vary along the source axis (nu*_rs == 0; the reference's bmm fails on anything else, :401-402).
+ *                         assume_clamped keeps its meaning: the bounds of an element do not change within a run.
+ *   snn_stdp_hebbian_pv   learning.py:1110-1135 / :626-653 (weight_dependent: every element needs finite bounds, the caller's duty).
+ *   snn_mstdp_step_pv     learning.py:1504-1574, :1561 `w += nu[0] * update`.
+ *   snn_mstdpet_step_pv   learning.py:2187-2248, :2232 `nu[0] * dt * reward * eligibility_trace`.
+ *   snn_normalize_pv      topology.py:383-392 / topology_features.py:250-266 with a tensor norm: scale[n] = norm_vec[n] / colsum[n], ONE
+ *                         IEEE division (a python-float norm is reciprocal-then-multiply in ATen: snn_normalize), then one multiply
+ *                         per weight.  norm_vec: device [N].  Column sums and the zero -> 1 guard as in snn_normalize.
+ * Added without changing SNN_ABI_VERSION: purely additive.                                                        */
+typedef struct snn_synparams {
+    const float *nu0, *nu1, *wmin, *wmax;
+    int nu0_rs, nu0_cs, nu1_rs, nu1_cs, wmin_rs, wmin_cs, wmax_rs, wmax_cs;
+    int nu0_any, nu1_any;
+} snn_synparams;
+int snn_stdp_postpre_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin,
+                        int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin, int has_max,
+                        float wmax, int assume_clamped, const snn_synparams *sp, snn_stream_t stream);
+int snn_stdp_hebbian_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin,
+                        int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin, int has_max,
+                        float wmax, const snn_synparams *sp, snn_stream_t stream);
+int snn_mstdp_step_pv(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                      const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0, float a_plus,
+                      float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin, int has_max,
+                      float wmax, const snn_synparams *sp, snn_stream_t stream);
+int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
+                        const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt, float a_plus,
+                        float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e, float wdecay, int has_min,
+                        float wmin, int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream);
+int snn_normalize_pv(float *W, int Nin, int N, const float *norm_vec, int use_abs, float *colsum_ws, snn_stream_t stream);
+
 /* ---- f2: spike encoders on the device ---------------------------------------------------------
  * bindsnet/encoding/encodings.py:51-98 (bernoulli): out [steps, n] u8 = what torch.bernoulli(max_prob *
  * datum.repeat([steps, 1])) draws from the HOST generator whose state is in *rng -- one 32-bit mt19937 output
@@ -746,6 +790,13 @@ typedef struct {
      * NONE or POSTPRE, no weight monitor, no mask: anything else is SNN_ERR_UNSUPPORTED.  A non-zero w_dtype sends the graph to the
      * generic plan, as per-neuron parameters do.  Added like the fields above: SNN_ABI_VERSION stays. */
     int w_dtype;
+    /* Per-synapse learning rates / bounds and a per-target norm (f13 above): `syn` names the tensors among nu0, nu1, wmin, wmax
+     * (the scalar fields above hold the others), norm_vec the device [target n] norms (has_norm 1; `norm` is then unused).  DENSE
+     * and MCC connections with an f32 `w` and a rule of the dense family (POSTPRE, HEBBIAN, WDPOSTPRE, MSTDP, MSTDPET; norm_vec
+     * also with NONE) only: anything else with one of these pointers is SNN_ERR_UNSUPPORTED.  Any of them sends the graph to the
+     * generic plan, as per-neuron layer parameters do.  Added like the fields above: SNN_ABI_VERSION stays. */
+    snn_synparams syn;
+    const float *norm_vec;
 } snn_conn_desc;
 
 typedef struct {
