@@ -648,6 +648,7 @@ static bool matches(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
     if (C[0].rule != SNN_RULE_NONE && C[0].rule != SNN_RULE_POSTPRE) return false;
     if (C[0].rule == SNN_RULE_POSTPRE && (C[0].wdecay != 1.0f || !L[0].x || !L[1].x)) return false;
     if (R->B > MAXB) return false;
+    if (L[1].n < 8) return false;                       // fewer than eight columns: ATen's own sum orders for those (snn_order.hpp outer_tail) are the generic plan's
     if (L[0].n > 2048 || L[0].n % 16 != 0 || L[1].n > 1024 || R->B * ((L[1].n + 31) / 32) > NT) return false;
     if ((size_t)R->B * L[0].n > (size_t)NU * NT * 16) return false;
     if ((double)(R->T + 1) * R->B * L[0].n >= 2147483648.0) return false;

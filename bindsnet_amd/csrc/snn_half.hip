@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void k_prop_h16(const uint16_t *__restrict__ W
     const int jc = valid ? j : N - 1;
     const uint8_t *srow = s + (size_t)b * Nin;
     OuterSum acc;
-    acc.init(j >= (N / 32) * 32);
+    acc.init(outer_tail(j, N));
     const uint64_t lt = (1ull << lane) - 1ull;
 
     for (int base = 0; base < Nin; base += 1024) {

@@ -131,7 +131,7 @@ __host__ __device__ inline uint16_t half_postpre_elem(uint16_t wbits, const Half
 template <int DT>
 __host__ __device__ inline float half_norm_factor(const uint16_t *W, int Nin, int N, int j, float norm) {
     OuterSum acc;
-    acc.init(j >= (N / 32) * 32);
+    acc.init(outer_tail(j, N));
     for (int base = 0; base < Nin; base += 16) {
         uint16_t v[16];
 #pragma unroll

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_prop_mcc_pipe(PipeProg P, const uint8_t
     const int jc = valid ? j : N - 1;
     const uint8_t *srow = s + (size_t)b * Nin;
     OuterSum acc;
-    acc.init(j >= (N / 32) * 32);
+    acc.init(outer_tail(j, N));
     if (P.has_add) {                       // every row is a term: the dense walk, same positions, same flush boundaries
         for (int i = 0; i < Nin; ++i) acc.add(i, pipe_term(P, (float)srow[i], i, jc, N), Nin);
     } else {

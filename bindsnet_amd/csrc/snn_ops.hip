@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k_prop(const float *__restrict__ W, const
     const int jc = valid ? j : N - 1;
     const uint8_t *srow = s + (size_t)b * Nin;
     SUM acc;
-    acc.init(j >= (N / 32) * 32);
+    acc.init(outer_tail(j, N));
     const uint64_t lt = (1ull << lane) - 1ull;
 
     for (int base = 0; base < Nin; base += 1024) {
@@ -74,10 +74,25 @@ __global__ __launch_bounds__(256) void k_prop(const float *__restrict__ W, const
     }
 }
 
+// N == 1: the reference's sum over the sources of ONE contiguous column is ATen's inner reduction (snn_order.hpp inner_sum8_terms),
+// not an outer sum.  One thread per sample; a layer of one neuron is no hot path.
+__global__ __launch_bounds__(64) void k_prop_col1(const float *__restrict__ W, const uint8_t *__restrict__ s, float *__restrict__ out,
+                                                  int B, int Nin, int accumulate) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const uint8_t *srow = s + (size_t)b * Nin;
+    const float r = inner_sum8_terms([=](int i) { return W[i] * (float)srow[i]; }, Nin);
+    out[b] = (accumulate ? out[b] : 0.0f) + r;
+}
+
 extern "C" int snn_prop_cascade_f32(const float *W, const uint8_t *s, float *out, int B, int Nin, int N,
                                     int accumulate, snn_stream_t stream) {
     if (!W || !s || !out || B <= 0 || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
     if (Nin > kMaxTerms || B > 65535) return SNN_ERR_UNSUPPORTED;
+    if (N == 1) {
+        hipLaunchKernelGGL(k_prop_col1, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, W, s, out, B, Nin, accumulate);
+        return snn_check_launch();
+    }
     hipLaunchKernelGGL(k_prop<OuterSum>, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, W,
                        (const float *)nullptr, s, out, B, Nin, N, accumulate);
     return snn_check_launch();
@@ -165,6 +180,11 @@ extern "C" int snn_prop_conv2d_f32(const float *W, const float *bias, const uint
     // a block of 256 consecutive output pixels touches at most 255 / (OH * OW) + 2 samples: their input images go to LDS when they fit 32 KB
     int nstage = 255 / (OH * OW) + 2;
     if ((size_t)nstage * Cin * H * Wd > 32 * 1024) nstage = 0; else lds += (size_t)nstage * Cin * H * Wd;
+    static bool attr_set = false;
+    if (!attr_set) {   // a 64 KiB bank and 32 KiB of staged images: up to 96 KiB of dynamic LDS
+        if (snn_check(hipFuncSetAttribute((const void *)k_conv2d, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024))) return SNN_ERR_LAUNCH;
+        attr_set = true;
+    }
     hipLaunchKernelGGL(k_conv2d, dim3((unsigned)((npix + 255) / 256), (unsigned)((Cout + 7) / 8)), dim3(256), lds, (hipStream_t)stream, W,
                        bias, s, out, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, accumulate, nstage);
     return snn_check_launch();
@@ -1186,6 +1206,29 @@ __global__ __launch_bounds__(kCsCols * kCsBlk) void k_colsum_nv(const float *__r
     colsum_body<true>(W, Nin, N, 0.f, norm_vec, use_abs, scale);
 }
 
+// Fewer than 8 columns where colsum_body's two uniform column classes do not describe ATen's order: ONE column is an inner reduction
+// (inner_sum8_terms), four to seven columns put the first four on the cascade and the rest on row_sum (outer_tail).  One thread
+// per column: a layer of fewer than eight neurons is no hot path.
+template <bool NV>
+__global__ __launch_bounds__(64) void k_colsum_few(const float *__restrict__ W, int Nin, int N, float norm, const float *__restrict__ norm_vec,
+                                                   int use_abs, float *__restrict__ scale) {
+    const int j = threadIdx.x;
+    if (j >= N) return;
+    auto term = [=](int i) { const float w = W[(size_t)i * N + j]; return use_abs ? fabsf(w) : w; };
+    float cs;
+    if (N == 1) {
+        cs = inner_sum8_terms(term, Nin);
+    } else {
+        OuterSum acc; acc.init(outer_tail(j, N));
+        for (int i = 0; i < Nin; ++i) acc.add(i, term(i), Nin);
+        cs = acc.finish(Nin);
+    }
+    if (NV) { scale[j] = syn_norm_scale(norm_vec[j], cs); return; }
+    if (cs == 0.f) cs = 1.0f;
+    scale[j] = (1.0f / cs) * norm;
+}
+static bool colsum_is_few(int N) { return N == 1 || (N >= 4 && N < 8); }
+
 __global__ __launch_bounds__(256) void k_scale_cols(float *__restrict__ W, long E, int N,
                                                     const float *__restrict__ scale) {
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (long)gridDim.x * blockDim.x)
@@ -1196,8 +1239,12 @@ extern "C" int snn_normalize(float *W, int Nin, int N, float norm, int use_abs, 
                              snn_stream_t stream) {
     if (!W || !colsum_ws || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
     if (Nin > kMaxTerms) return SNN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_colsum, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
-                       norm, use_abs, colsum_ws);
+    if (colsum_is_few(N))
+        hipLaunchKernelGGL(k_colsum_few<false>, dim3(1), dim3(64), 0, (hipStream_t)stream, W, Nin, N, norm, (const float *)nullptr, use_abs,
+                           colsum_ws);
+    else
+        hipLaunchKernelGGL(k_colsum, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
+                           norm, use_abs, colsum_ws);
     int rc = snn_check_launch();
     if (rc) return rc;
     const long E = (long)Nin * N;
@@ -1209,8 +1256,11 @@ extern "C" int snn_normalize(float *W, int Nin, int N, float norm, int use_abs, 
 extern "C" int snn_normalize_pv(float *W, int Nin, int N, const float *norm_vec, int use_abs, float *colsum_ws, snn_stream_t stream) {
     if (!W || !norm_vec || !colsum_ws || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
     if (Nin > kMaxTerms) return SNN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_colsum_nv, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
-                       norm_vec, use_abs, colsum_ws);
+    if (colsum_is_few(N))
+        hipLaunchKernelGGL(k_colsum_few<true>, dim3(1), dim3(64), 0, (hipStream_t)stream, W, Nin, N, 0.f, norm_vec, use_abs, colsum_ws);
+    else
+        hipLaunchKernelGGL(k_colsum_nv, dim3((N + kCsCols - 1) / kCsCols), dim3(kCsCols * kCsBlk), 0, (hipStream_t)stream, W, Nin, N,
+                           norm_vec, use_abs, colsum_ws);
     int rc = snn_check_launch();
     if (rc) return rc;
     const long E = (long)Nin * N;

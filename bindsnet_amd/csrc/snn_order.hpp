@@ -186,6 +186,13 @@ __host__ __device__ inline float batch_sum(TERM term, int B, long e, long E) {
     return acc.finish(B);
 }
 
+// The column class of ATen's sum over the rows of `ncols` >= 2 contiguous columns (MulticompartmentConnection.compute's sum(dim=1),
+// normalize's sum(dim=0)): true = row_sum.  Four to seven columns: the first four take the cascade; ONE column is no outer sum
+// at all but the inner reduction above (inner_sum8_terms) -- the callers send it there.
+__host__ __device__ __forceinline__ bool outer_tail(long col, long ncols) {
+    return (ncols >= 4 && ncols < 8) ? col >= 4 : col >= (ncols / 32) * 32;
+}
+
 // Plain ascending sequential sum (canonical order of the dense Connection path).
 struct SeqSum {
     float a;

@@ -256,6 +256,7 @@ bool plan(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const
     if ((C[0].rule == SNN_RULE_POSTPRE || outer2) && (!L[0].x || !L[1].x || !L[0].p.lif.traces || !L[1].p.lif.traces)) return false;
     if (C[0].kind == SNN_CONN_MCC && C[0].bias) return false;
     const int B = R->B, Nin = L[0].n, N = L[1].n;
+    if (N == 1) return false;                           // ONE target column: ATen's inner reduction (k_prop_col1, k_colsum_few), generic plan
     if (B > MAXB || R->T < 1 || Nin % 16 != 0 || Nin > 65535 || Nin > kMaxTerms) return false;
     if ((double)Nin * N >= 2147483648.0 || (double)(R->T + 1) * B * Nin >= 2147483648.0) return false;
     memset(&c, 0, sizeof(c));

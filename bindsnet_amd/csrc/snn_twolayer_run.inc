@@ -845,7 +845,7 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
     const int jj = tid & (CW - 1), bl = tid >> (31 - __clz(CW)), j = c0 + jj;
     const bool mine = tid < B * CW && j < N;
     const int kst = bl * N + j;
-    const bool tailcol = CASC && j >= (N / 32) * 32;
+    const bool tailcol = CASC && outer_tail(j, N);
     const int Etot = Nin * N, Emain = (Etot / 32) * 32;
     const int cwl = 31 - __clz(CW);                      // CW is a power of two
     constexpr bool kOuter = RULE == SNN_RULE_POSTPRE || RULE == SNN_RULE_HEBBIAN || RULE == SNN_RULE_WDPOSTPRE;   // the rules of two_stdp
@@ -1292,10 +1292,16 @@ __global__ __launch_bounds__(NT) void k_two_run(const TwoCtx c_in) {
         } else if (tid < CW * 4) {                     // row_sum columns: four interleaved lanes per column
             const int q = tid >> 2, s4 = tid & 3, n4 = Nin >> 2, nf4 = n4 >> 4;
             Cascade cc; cc.init();
-            for (int p_ = 0; p_ < n4; ++p_) { const float w = wt[(4 * p_ + s4) * CW + q]; cc.add(p_, c.norm_abs ? fabsf(w) : w, nf4); }
-            float lsum = cc.finish(nf4);
-            if (s4 == 0)
-                for (int i = n4 * 4; i < Nin; ++i) { const float w = wt[i * CW + q]; lsum += c.norm_abs ? fabsf(w) : w; }
+            float lsum;
+            if (!outer_tail(c0 + q, N)) {              // four to seven columns: the first four take the cascade all the same (lane 0 sums, the others add +0)
+                if (s4 == 0) for (int i = 0; i < Nin; ++i) { const float w = wt[i * CW + q]; cc.add(i, c.norm_abs ? fabsf(w) : w, nfull); }
+                lsum = s4 == 0 ? cc.finish(nfull) : 0.f;
+            } else {
+                for (int p_ = 0; p_ < n4; ++p_) { const float w = wt[(4 * p_ + s4) * CW + q]; cc.add(p_, c.norm_abs ? fabsf(w) : w, nf4); }
+                lsum = cc.finish(nf4);
+                if (s4 == 0)
+                    for (int i = n4 * 4; i < Nin; ++i) { const float w = wt[i * CW + q]; lsum += c.norm_abs ? fabsf(w) : w; }
+            }
             const float l1 = __shfl_down(lsum, 1, 4), l2 = __shfl_down(lsum, 2, 4), l3 = __shfl_down(lsum, 3, 4);
             float cs = ((lsum + l1) + l2) + l3;
             if (cs == 0.f) cs = 1.0f;

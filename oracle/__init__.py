@@ -164,11 +164,13 @@ def postpre(W, s_src, x_src, s_tgt, x_tgt, *, nu0, nu1, use_dt, dt=1.0, decay=1.
 
 
 def mstdp(W, elig, p_plus, p_minus, s_src, s_tgt, *, reward, nu0, a_plus=1.0, a_minus=-1.0,
-          decay_plus, decay_minus, wdecay=1.0, wmin=None, wmax=None):
+          decay_plus, decay_minus, wdecay=1.0, wmin=None, wmax=None, reward_vec=None):
+    """reward_vec: f32 [B], one reward per sample in place of the scalar."""
     B, Nin = s_src.shape
     N = s_tgt.shape[1]
+    assert reward_vec is None or reward_vec.shape == (B,)
     lib().orc_mstdp(_p(W, f32), _p(elig, f32), _p(p_plus, f32), _p(p_minus, f32), _p(s_src, u8),
-                    _p(s_tgt, u8), ci(B), ci(Nin), ci(N), cf(reward), None, cf(nu0), cf(a_plus),
+                    _p(s_tgt, u8), ci(B), ci(Nin), ci(N), cf(reward), _p(reward_vec, f32), cf(nu0), cf(a_plus),
                     cf(a_minus), cf(decay_plus), cf(decay_minus), cf(wdecay),
                     ci(wmin is not None), cf(wmin or 0.0), ci(wmax is not None), cf(wmax or 0.0))
 

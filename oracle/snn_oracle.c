@@ -104,8 +104,33 @@ static int tail_isolated(long outer, long n, long ncols)
     return c * ((ncols - 1) / c) >= ncols - tail;
 }
 
+/* Fewer than 8 contiguous columns (probed on the reference's torch, serial order): ONE column is an inner reduction --
+ * vectorized_inner_sum with 8-float vectors: lane l of 8 takes terms l, 8 + l, ... through row_sum over the n / 8 vectors, a fresh
+ * accumulator then takes the n mod 8 leftover terms in order and after them the 8 lane sums; fewer than 8 terms: row_sum.  Four to
+ * seven columns: the first four take the cascade, the rest row_sum. */
+typedef struct { orc_term_fn f; const void *ctx; long stride, off; } strided_ctx;
+static float strided_term(const void *c, long i)
+{
+    const strided_ctx *p = (const strided_ctx *)c;
+    return p->f(p->ctx, i * p->stride + p->off);
+}
+
+static float inner_sum8_terms(orc_term_fn f, const void *ctx, long n)
+{
+    if (n < 8) return row_sum4(f, ctx, n);
+    const long vs = n / 8;
+    float part[8];
+    for (int l = 0; l < 8; ++l) { strided_ctx c = { f, ctx, 8, l }; part[l] = row_sum4(strided_term, &c, vs); }
+    float fin = 0.f;
+    for (long k = vs * 8; k < n; ++k) fin += f(ctx, k);
+    for (int l = 0; l < 8; ++l) fin += part[l];
+    return fin;
+}
+
 static float outer_sum_threads(orc_term_fn f, const void *ctx, long n, long col, long ncols, long outer)
 {
+    if (ncols == 1) return inner_sum8_terms(f, ctx, n);
+    if (ncols >= 4 && ncols < 8) return col < 4 ? cascade_sum(f, ctx, 0, 1, n) : row_sum4(f, ctx, n);
     const long full = (ncols / 32) * 32;
     if (col >= full && tail_isolated(outer, n, ncols) && col - full < ((ncols - full) / 4) * 4)
         return cascade_sum(f, ctx, 0, 1, n);
