@@ -251,6 +251,14 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if (d.rule == SNN_RULE_POSTPRE && ((d.syn.nu0 && d.syn.nu0_rs) || (d.syn.nu1 && d.syn.nu1_rs))) return SNN_ERR_INVALID;
             if (d.norm_vec && (!d.has_norm || !d.norm_ws)) return SNN_ERR_INVALID;
         }
+        if (d.avg_k != 0) {                    // average_update (snnhip.h f14): MCC, f32, the three MCC rules, scalar rates and bounds
+            if (d.kind != SNN_CONN_MCC || d.w_dtype != SNN_W_F32 || snn::syn_any(&d.syn)) return SNN_ERR_UNSUPPORTED;
+            if (d.rule != SNN_RULE_POSTPRE && d.rule != SNN_RULE_MSTDP && d.rule != SNN_RULE_MSTDPET) return SNN_ERR_UNSUPPORTED;
+            if (d.avg_k < 0 || !d.avg_ring0 || d.avg_i0 < 0 || d.avg_i0 >= d.avg_k) return SNN_ERR_INVALID;
+            if (d.rule == SNN_RULE_POSTPRE && (!d.avg_ring1 || d.avg_i1 < 0 || d.avg_i1 >= d.avg_k)) return SNN_ERR_INVALID;
+            if (d.avg_squeeze && R->B != 1) return SNN_ERR_INVALID;
+            if (d.avg_k > SNN_AVG_MAX_TERMS || R->B > SNN_AVG_MAX_TERMS) return SNN_ERR_UNSUPPORTED;
+        }
         if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) {        // PermuteConnection / ConstantPad2dConnection: a gather, propagation only
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
             if (d.has_norm || d.mask || d.raster_w || d.bias || d.w) return SNN_ERR_INVALID;
@@ -442,6 +450,19 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 else if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && d.kind == SNN_CONN_CONV2D)
                     TRY(snn_conv2d_hebbian(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
                                            d.rule == SNN_RULE_WDPOSTPRE, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
+                else if (d.avg_k != 0 && d.rule == SNN_RULE_POSTPRE)           // average_update: the ring forms (snnhip.h f14); an index moves with its term
+                    TRY(snn_postpre_avg_step(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, R->dt, d.wdecay, d.has_min, d.wmin, d.has_max,
+                                             d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_ring1, d.avg_k, d.avg_continuous,
+                                             d.nu0 != 0.f ? (d.avg_i0 + t) % d.avg_k : d.avg_i0, d.nu1 != 0.f ? (d.avg_i1 + t) % d.avg_k : d.avg_i1, st));
+                else if (d.avg_k != 0 && d.rule == SNN_RULE_MSTDP)
+                    TRY(snn_mstdp_avg_step(d.w, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, B, S.n, D.n, d.reward, d.reward_vec,
+                                           d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay, d.has_min, d.wmin, d.has_max,
+                                           d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_k, d.avg_continuous, (d.avg_i0 + t) % d.avg_k, st));
+                else if (d.avg_k != 0)
+                    TRY(snn_mstdpet_avg_step(d.w, d.e_trace, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, S.n, D.n, d.reward,
+                                             d.nu0, R->dt, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.decay_e, d.tc_e, d.wdecay,
+                                             d.has_min, d.wmin, d.has_max, d.wmax, d.avg_ring0, d.avg_k, d.avg_continuous,
+                                             (d.avg_i0 + t) % d.avg_k, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.w_dtype != SNN_W_F32)
                     TRY(snn_stdp_postpre_h16(d.w, d.w_dtype, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                              d.has_min, d.wmin, d.has_max, d.wmax, st));
@@ -556,6 +577,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].pipe_n > 0) local = true;      // an MCC feature pipeline: generic plan only as well
     for (int c = 0; c < nC; ++c) if (C[c].w_dtype != SNN_W_F32) local = true;   // ... and float16 / bfloat16 weights (the fused plans keep f32 tiles)
     for (int c = 0; c < nC; ++c) if (snn::syn_any(&C[c].syn) || C[c].norm_vec) local = true;   // ... and per-synapse rates / bounds, per-target norms
+    for (int c = 0; c < nC; ++c) if (C[c].avg_k != 0) local = true;             // ... and averaged updates (the fused plans keep no ring)
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));

@@ -1,7 +1,8 @@
 """Learning rules for MulticompartmentConnection features: API mirror of
 bindsnet/learning/MCC_learning.py for `MCC_LearningRule`, `NoOp`, `PostPre`, `MSTDP`, `MSTDPET`.
 The updates themselves are snn_stdp_postpre (use_dt = 1; snn_stdp_postpre_h16 on a float16 / bfloat16 Weight) / snn_mstdp_step /
-snn_mstdpet_step."""
+snn_mstdpet_step; with average_update > 0 their ring forms snn_postpre_avg_step / snn_mstdp_avg_step / snn_mstdpet_avg_step
+(include/snnhip.h f14)."""
 import warnings
 from typing import Optional, Sequence, Union
 
@@ -40,6 +41,67 @@ class MCC_LearningRule(_lib.Touching):
             reduction = torch.squeeze if self.source.batch_size == 1 else torch.sum
         self.reduction = reduction
         self.decay = 1.0 - decay if decay else 1.0
+
+    # ---- average_update / continues_update (MCC_learning.py:182-183, :211-222, :457-466, :641-649) ----------------------------
+    _RINGS = ()                        # (ring attribute, index attribute, index of the learning rate its term runs on) per ring
+
+    def _init_average(self, kwargs) -> None:
+        """The reference's keyword arguments, rings and indices under its attribute names.  The rings are float32 zeros beside the
+        weights and are never cleared by the rule (reset_state_variables leaves them alone, :304, :550, :735-738).  What the
+        device path does not run is refused here, before anything exists."""
+        K = kwargs.get("average_update", 0)
+        if isinstance(K, bool) or not isinstance(K, int):
+            raise TypeError(f"bindsnet_amd: average_update must be an int (got {K!r})")
+        if K < 0:
+            raise NotImplementedError(f"bindsnet_amd: average_update={K} is negative: it is the number of updates to average over "
+                                      "(0: no averaging)")
+        if K > _lib.AVG_MAX_TERMS:
+            raise NotImplementedError(f"bindsnet_amd: average_update={K} is above the {_lib.AVG_MAX_TERMS} terms the ordered accumulator "
+                                      "of the ring's mean takes (SNN_AVG_MAX_TERMS)")
+        if K > 0:
+            dtype = getattr(self.feature_value, "dtype", torch.float32)
+            if dtype in (torch.float16, torch.bfloat16):
+                raise NotImplementedError(f"bindsnet_amd: average_update on a {dtype} Weight is not supported: the ring and its mean "
+                                          "are float32 and the reference's roundings of a half-precision ring are not restated")
+            if _descriptor.is_vec(self.min) or _descriptor.is_vec(self.max):
+                raise NotImplementedError("bindsnet_amd: average_update with tensor (per-synapse) clamp ranges is not supported: the "
+                                          "averaged entry points take scalar bounds")
+        self.average_update, self.continues_update = K, kwargs.get("continues_update", False)
+        if K > 0:
+            for ring, index, _ in self._RINGS:
+                setattr(self, ring, torch.zeros(K, *self.feature_value.shape, device=self.feature_value.device))
+                setattr(self, index, 0)
+
+    def _move_rings(self, device) -> None:
+        """The rings follow the Weight's value (AbstractFeature.to)."""
+        if getattr(self, "average_update", 0):
+            for ring, _, _ in self._RINGS:
+                if getattr(self, ring).device != torch.device(device):
+                    setattr(self, ring, getattr(self, ring).to(device))
+
+    def _avg_indices(self):
+        """The ring indices at the start of the next step, one per ring."""
+        return [int(getattr(self, index)) for _, index, _ in self._RINGS]
+
+    def _avg_advance(self, steps: int = 1) -> None:
+        """`steps` learning steps have run: every ring has moved on, but a PostPre term whose rate is 0 never runs (:233, :267)."""
+        for _, index, rate in self._RINGS:
+            if rate is None or float(self.nu[rate]) != 0.0:
+                setattr(self, index, (int(getattr(self, index)) + steps) % self.average_update)
+
+    def _describe_average(self, d, dev, keep, squeeze: bool) -> None:
+        """The averaging fields of snn_conn_desc; the start indices are per-call values, bound by Network.run (_bind_call)."""
+        if not getattr(self, "average_update", 0):
+            return
+        if _descriptor.is_vec(self.min) or _descriptor.is_vec(self.max):
+            raise NotImplementedError("bindsnet_amd: average_update with tensor (per-synapse) clamp ranges is not supported: the "
+                                      "averaged entry points take scalar bounds")
+        self._move_rings(dev)
+        rings = [getattr(self, ring) for ring, _, _ in self._RINGS]
+        d.avg_k, d.avg_continuous, d.avg_squeeze = self.average_update, int(bool(self.continues_update)), int(squeeze)
+        d.avg_ring0 = _lib.dptr(rings[0])
+        d.avg_ring1 = _lib.dptr(rings[1]) if len(rings) > 1 else None
+        keep.extend(rings)
 
     def _float32_only(self) -> None:
         """The reward-modulated rules keep float32 state beside the weights: a float16 / bfloat16 Weight is refused by name."""
@@ -120,14 +182,16 @@ class PostPre(MCC_LearningRule):
         from ..network.topology import MulticompartmentConnection
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
-        if kwargs.get("average_update", 0):
-            raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         if self.reduction not in (torch.sum, torch.squeeze):
             raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
+        self._init_average(kwargs)
+
+    _RINGS = (("average_buffer_pre", "average_buffer_index_pre", 0), ("average_buffer_post", "average_buffer_index_post", 1))
 
     def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
         self._describe_batched(d, conn, B, dev, keep)
         d.rule, d.use_dt = _lib.RULE_POSTPRE, 1
+        self._describe_average(d, dev, keep, self.reduction is torch.squeeze)
 
     def update(self, **kwargs) -> None:
         """One step of MCC_learning.py:224-302 through the C ABI (used when a connection is
@@ -136,6 +200,17 @@ class PostPre(MCC_LearningRule):
         B = self.source.batch_size
         if self.reduction is torch.squeeze and B != 1:
             raise RuntimeError("reduction=torch.squeeze requires batch size 1 (as in the reference)")
+        if self.average_update:                 # the ring form (snn_postpre_avg_step): scalar bounds
+            lo, hi = self._bounds()
+            self._move_rings(self.feature_value.device)
+            i_pre, i_post = self._avg_indices()
+            ops.postpre_avg_step(self.feature_value.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
+                                 self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(self.nu[0]), float(self.nu[1]),
+                                 float(self.connection.dt), self.average_buffer_pre, self.average_buffer_post, i_pre, i_post,
+                                 bool(self.continues_update), squeeze=self.reduction is torch.squeeze, decay=float(self.decay),
+                                 wmin=lo, wmax=hi)
+            self._avg_advance()
+            return
         lo, hi = self._bounds(tensors=True)
         ops.stdp_postpre(self.feature_value.data, self.source.s.reshape(B, -1).contiguous(),
                          self.source.x.reshape(B, -1), self.target.s.reshape(B, -1), self.target.x.reshape(B, -1),
@@ -157,12 +232,13 @@ class MSTDP(MCC_LearningRule):
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
         self._float32_only()
-        if kwargs.get("average_update", 0):
-            raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         if self.reduction not in (torch.sum, torch.squeeze):
             raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))
         self.tc_minus = torch.tensor(kwargs.get("tc_minus", 20.0))
+        self._init_average(kwargs)
+
+    _RINGS = (("average_buffer", "average_buffer_index", None),)
 
     def _ensure_state(self):
         B, dev = self.source.batch_size, self.feature_value.device
@@ -179,6 +255,7 @@ class MSTDP(MCC_LearningRule):
     def _describe(self, d, conn, B, dev, keep, kwargs) -> None:
         self._describe_batched(d, conn, B, dev, keep)
         _descriptor.fill_mstdp(d, self, kwargs, dev, keep)
+        self._describe_average(d, dev, keep, self.reduction is torch.squeeze)
 
     def update(self, **kwargs) -> None:
         from .. import ops
@@ -188,6 +265,16 @@ class MSTDP(MCC_LearningRule):
         self._ensure_state()
         reward, rvec = _descriptor.split_reward(kwargs["reward"], self.feature_value.device)
         dp, dm = self._decays()
+        if self.average_update:                 # the ring form (snn_mstdp_avg_step): scalar bounds
+            lo, hi = self._bounds()
+            self._move_rings(self.feature_value.device)
+            ops.mstdp_avg_step(self.feature_value.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
+                               self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward, float(self.nu[0]),
+                               float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm, self.average_buffer,
+                               self._avg_indices()[0], bool(self.continues_update), squeeze=self.reduction is torch.squeeze,
+                               wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec)
+            self._avg_advance()
+            return
         lo, hi = self._bounds(tensors=True)
         ops.mstdp_step(self.feature_value.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
                        self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
@@ -217,11 +304,12 @@ class MSTDPET(MCC_LearningRule):
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
         self._float32_only()
-        if kwargs.get("average_update", 0):
-            raise NotImplementedError("bindsnet_amd: average_update buffers are outside the accelerated path")
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))
         self.tc_minus = torch.tensor(kwargs.get("tc_minus", 20.0))
         self.tc_e_trace = torch.tensor(kwargs.get("tc_e_trace", 25.0))
+        self._init_average(kwargs)
+
+    _RINGS = (("average_buffer", "average_buffer_index", None),)
 
     def _ensure_state(self):
         dev = self.feature_value.device
@@ -249,6 +337,7 @@ class MSTDPET(MCC_LearningRule):
         if B != 1:
             raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
         _descriptor.fill_mstdpet(d, self, self.decay, kwargs, dev, keep)
+        self._describe_average(d, dev, keep, False)
 
     def update(self, **kwargs) -> None:
         from .. import ops
@@ -256,6 +345,16 @@ class MSTDPET(MCC_LearningRule):
             raise NotImplementedError("MCC MSTDPET is defined for batch size 1 (MCC_learning.py:665-666)")
         self._ensure_state()
         dp, dm, de = self._decays()
+        if self.average_update:                 # the ring form (snn_mstdpet_avg_step): scalar bounds
+            lo, hi = self._bounds()
+            self._move_rings(self.feature_value.device)
+            ops.mstdpet_avg_step(self.feature_value.data, self.eligibility_trace, self.p_plus, self.p_minus, self._s_src_prev,
+                                 self._s_tgt_prev, self.source.s.reshape(-1).contiguous(), self.target.s.reshape(-1),
+                                 float(kwargs["reward"]), float(self.nu[0]), float(self.connection.dt), float(kwargs.get("a_plus", 1.0)),
+                                 float(kwargs.get("a_minus", -1.0)), dp, dm, de, float(self.tc_e_trace), self.average_buffer,
+                                 self._avg_indices()[0], bool(self.continues_update), wdecay=float(self.decay), wmin=lo, wmax=hi)
+            self._avg_advance()
+            return
         lo, hi = self._bounds(tensors=True)
         ops.mstdpet_step(self.feature_value.data, self.eligibility_trace, self.p_plus, self.p_minus, self._s_src_prev,
                          self._s_tgt_prev, self.source.s.reshape(-1).contiguous(), self.target.s.reshape(-1), float(kwargs["reward"]),

@@ -426,6 +426,12 @@ def _reduce(rule, t):
     return _sum(t, 0) if rule.reduction is torch.sum else rule.reduction(t, dim=0)
 
 
+def _ring_mean(ring):
+    """torch.mean(ring, dim=0) of an average_update ring [K, Nin, N] (MCC_learning.py:248, :284, :527, :705): ATen's sum(dim=0) followed
+    by one true division by K -- the same bits as torch.mean --, the sum in the serial order this package pins (_sum)."""
+    return _sum(ring, 0) / ring.shape[0]
+
+
 def _mstdp(rule, W, src_s, tgt_s, kwargs) -> None:
     """learning.py:1504-1574 / MCC_learning.py:468-551 (the same arithmetic): the update uses the PREVIOUS step's eligibility
     (kept as its two factors, like on the device: elig[b] = p_plus[b] (x) s_tgt_prev[b] + s_src_prev[b] (x) p_minus[b]),
@@ -436,7 +442,13 @@ def _mstdp(rule, W, src_s, tgt_s, kwargs) -> None:
         torch.bmm(rule._s_src_prev.float().unsqueeze(2), rule.p_minus.unsqueeze(1))
     if isinstance(reward, torch.Tensor) and reward.numel() > 1:
         reward = reward.view(-1, 1, 1).float()
-    W += rule._nu(0) * _reduce(rule, reward * elig)
+    if getattr(rule, "average_update", 0) > 0:              # MCC_learning.py:518-530
+        rule.average_buffer[rule.average_buffer_index] = _reduce(rule, reward * elig)
+        rule.average_buffer_index = (rule.average_buffer_index + 1) % rule.average_update
+        if rule.continues_update or rule.average_buffer_index == 0:
+            W += rule.nu[0] * _ring_mean(rule.average_buffer)
+    else:
+        W += rule._nu(0) * _reduce(rule, reward * elig)
     _advance_p(rule, *rule._decays(), src_s, tgt_s, kwargs)
 
 
@@ -458,7 +470,13 @@ def _mstdpet(rule, W, dt, src_s, tgt_s, kwargs) -> None:
     dp, dm, de = rule._decays()
     rule.eligibility_trace *= de
     rule.eligibility_trace += rule.eligibility / rule.tc_e_trace
-    W += rule.nu[0] * dt * kwargs["reward"] * rule.eligibility_trace
+    if getattr(rule, "average_update", 0) > 0:              # MCC_learning.py:696-708
+        rule.average_buffer[rule.average_buffer_index] = rule.nu[0] * dt * kwargs["reward"] * rule.eligibility_trace
+        rule.average_buffer_index = (rule.average_buffer_index + 1) % rule.average_update
+        if rule.continues_update or rule.average_buffer_index == 0:
+            W += _ring_mean(rule.average_buffer)
+    else:
+        W += rule.nu[0] * dt * kwargs["reward"] * rule.eligibility_trace
     _advance_p(rule, dp, dm, src_s, tgt_s, kwargs)
 
 
@@ -518,12 +536,25 @@ def _conv_mstdp(conn, rule, kwargs) -> None:
 def _postpre_mcc(rule, W, s_src, x_src, s_tgt, x_tgt, dt) -> None:
     """MCC_learning.py:224-302 + :86-110 on explicit [B, n] factors (parallel.exact_run hands the GLOBAL batch's)."""
     nu0, nu1 = float(rule.nu[0]), float(rule.nu[1])
+    K = getattr(rule, "average_update", 0)
     if nu0:
         pre = torch.bmm(s_src.unsqueeze(2).float(), x_tgt.unsqueeze(1) * nu0)
-        W -= _reduce(rule, pre) * dt
+        if K > 0:                                            # MCC_learning.py:237-253: into the ring; its mean when due
+            rule.average_buffer_pre[rule.average_buffer_index_pre] = _reduce(rule, pre)
+            rule.average_buffer_index_pre = (rule.average_buffer_index_pre + 1) % K
+            if rule.continues_update or rule.average_buffer_index_pre == 0:
+                W -= _ring_mean(rule.average_buffer_pre) * dt
+        else:
+            W -= _reduce(rule, pre) * dt
     if nu1:
         post = torch.bmm(x_src.unsqueeze(2), s_tgt.unsqueeze(1).float() * nu1)
-        W += _reduce(rule, post) * dt
+        if K > 0:                                            # :273-289
+            rule.average_buffer_post[rule.average_buffer_index_post] = _reduce(rule, post)
+            rule.average_buffer_index_post = (rule.average_buffer_index_post + 1) % K
+            if rule.continues_update or rule.average_buffer_index_post == 0:
+                W += _ring_mean(rule.average_buffer_post) * dt
+        else:
+            W += _reduce(rule, post) * dt
     _decay_clamp(rule, W, rule.decay)
 
 

@@ -420,6 +420,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     conn.normalize()
         # Input.s aliases the last input slice, as in the reference (nodes.py:219)
         before = _lib.epoch()
+        if self.learning:
+            for k, rule in built["averages"]:          # every learning step moved the ring index of every term that ran
+                rule._avg_advance(T)
         for i, name, layer, _ in built["inputs"]:
             layer.s = inputs[name][T - 1]
         for mon, key, buf in rasters:
@@ -569,7 +572,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     if lname not in self.layers or isinstance(self.layers[lname], Input):
                         raise NotImplementedError(f"bindsnet_amd: {what}['{lname}'] must name a non-Input layer of the network")
             Cn = (_lib.ConnDesc * max(1, len(self.connections)))()
-            lists, dyn_conns, described, windows = [], [], [], []
+            lists, dyn_conns, described, windows, averages = [], [], [], [], []
             for k, ((src, dst), conn) in enumerate(self.connections.items()):
                 described += self._fill_conn(Cn[k], conn, self._source_index(names, index, src, conn), index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
                 if self.__dict__.get("_defer_norm", False):    # parallel.sharded_run normalises the MERGED weights itself
@@ -579,6 +582,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     dyn_conns.append((k, conn, wanted))
                 if Cn[k].window:
                     windows.append((k, conn))
+                if Cn[k].avg_k:                        # average_update: the ring indices are per-call values, the rings' addresses are watched
+                    averages.append((k, conn._rule()))
+                    described += [(conn._rule(), ring) for ring, _, _ in conn._rule()._RINGS]
                 nu = getattr(conn._rule(), "nu", None)
                 if isinstance(nu, torch.Tensor):
                     lists.append((nu, nu._version))
@@ -629,7 +635,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     self._scratch("rng_qbuf", (max(max_draws, 1),), torch.float32, dev), pool["rng_host"])
         # (assignments made while building -- a state tensor re-created by _check_state, a rule's lazily allocated
         #  memory -- belong to this build: the descriptors already point at the new objects)
-        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows,
+        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows, "averages": averages,
                 "max_draws": max_draws, "gen_bufs": gen_bufs, "T": T, "B": B, "dev": dev, "scalars": scalars,
                 "lists": lists, "epoch": _lib.epoch(), "n_objects": (len(self.layers), len(self.connections), len(self.monitors)),
                 "epoch0": epoch0, "defer_norm": bool(self.__dict__.get("_defer_norm", False)), "ptrs": ptrs}
@@ -694,8 +700,11 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         for k, conn in built["windows"]:           # a connection into a CSRM layer: its ring and where the oldest entry stands now
             win = conn._window_ring(B, dev)
             built["Cn"][k].win_ring, built["Cn"][k].win_head = _dptr(win["ring"]), win["head"]
-        for k, conn, wanted in built["conns"]:     # weights at the end of every timestep (monitors.py:94-111, 222-262)
-            mon_w = torch.empty(T, *conn.w.shape, device=dev)
+        for k, rule in built["averages"]:          # an averaged rule: where its ring indices stand now (they moved with every learning step since)
+            idx = rule._avg_indices()
+            built["Cn"][k].avg_i0, built["Cn"][k].avg_i1 = idx[0], idx[-1]
+        for k, conn, wanted in built["conns"]:    # weights at the end of every timestep (monitors.py:94-111, 222-262)
+            mon_w = torch.empty(T, *self._monitored_weights(conn).shape, device=dev)
             built["Cn"][k].raster_w = _dptr(mon_w)
             rasters += [(m, key, mon_w) for m, key in wanted]
         return rasters, keep
@@ -753,7 +762,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             elif isinstance(m, Monitor):
                 if m.obj is layer:
                     requests += [(m, v, v) for v in m.state_vars]
-                elif not isinstance(m.obj, Nodes) and not any(m.obj is c for c in self.connections.values()):
+                elif not isinstance(m.obj, Nodes) and not any(m.obj is c for c in self.connections.values()) and self._feature_owner(m.obj) is None:
                     raise NotImplementedError("bindsnet_amd: monitors on objects other than the network's layers and "
                                               "connections (features, ...) are not supported")
         for m, key, var in requests:
@@ -761,6 +770,13 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 raise NotImplementedError(f"bindsnet_amd: monitoring '{var}' of {type(layer).__name__} is "
                                           "outside the accelerated path (supported: 's', 'v')")
         return requests
+
+    def _feature_owner(self, obj):
+        """The MulticompartmentConnection whose pipeline holds the feature `obj` (a Monitor on a Weight records its `value`), or None."""
+        for conn in self.connections.values():
+            if any(obj is f for f in getattr(conn, "pipeline", ())):
+                return conn
+        return None
 
     def _conn_is_monitored(self, conn, cname) -> bool:
         """Whether any monitor records a variable of this connection."""
@@ -778,9 +794,22 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     raise NotImplementedError(f"bindsnet_amd: monitoring {list(m.state_vars)} of {type(conn).__name__} is outside "
                                               "the accelerated path (supported on connections: 'w')")
                 requests.append((m, "w"))
-        if requests and (conn.w.dtype != torch.float32 or not conn.w.is_contiguous()):
+            elif isinstance(m, Monitor) and any(m.obj is f for f in getattr(conn, "pipeline", ())):
+                # a Monitor on a feature (monitors.py:94-111 records any attribute): the `value` of the Weight the rule refers to --
+                # what the connection hands to snn_net_run as `w` -- is copied at the end of every timestep like a connection's `w`
+                if list(m.state_vars) != ["value"] or m.obj is not conn._learned():
+                    raise NotImplementedError(f"bindsnet_amd: monitoring {list(m.state_vars)} of the feature '{m.obj.name}' is outside the "
+                                              "accelerated path (supported: 'value' of the Weight the rule or the norm refers to)")
+                requests.append((m, "value"))
+        w = self._monitored_weights(conn) if requests else None
+        if requests and (w.dtype != torch.float32 or not w.is_contiguous()):
             raise NotImplementedError("bindsnet_amd: monitored connection weights must be contiguous float32")
         return requests
+
+    @staticmethod
+    def _monitored_weights(conn):
+        """The tensor a weight monitor of this connection records: `w`, or the learned Weight's value of a MulticompartmentConnection."""
+        return conn._learned().value if hasattr(conn, "pipeline") else conn.w
 
     def _fill_conn(self, d, conn, src, dst, B, dev, keep, kwargs):
         """One snn_conn_desc: the connection describes itself, then its rule does.  Returns the connection's (owner, attribute)

@@ -97,6 +97,8 @@ class AbstractFeature(_lib.Touching):
             self.value = Parameter(self.value.data.to(device), requires_grad=False)
             if hasattr(self.learning_rule, "feature_value"):
                 self.learning_rule.feature_value = self.value
+        if isinstance(self.value, torch.Tensor) and hasattr(self.learning_rule, "_move_rings") and not isinstance(self.learning_rule, type):
+            self.learning_rule._move_rings(self.value.device)        # the rings of average_update live beside the value
         return self
 
 

@@ -620,6 +620,43 @@ def mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_t
           "mstdpet_step")
 
 
+def _ring(ring, W, K):
+    """A time-averaging ring as the *_avg_step entry points take it: contiguous float32 [K, *W.shape] beside the weights."""
+    if ring.dtype != F32 or tuple(ring.shape) != (K, *W.shape) or ring.device != W.device or not ring.is_contiguous():
+        raise ValueError(f"an average_update ring must be a contiguous float32 [{K}, {W.shape[0]}, {W.shape[1]}] tensor on {W.device}")
+    return _ptr(ring, F32)
+
+
+def postpre_avg_step(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, dt, ring_pre, ring_post, idx_pre, idx_post, continuous, squeeze=False,
+                     decay=1.0, wmin=None, wmax=None):
+    """include/snnhip.h f14: one step of MCC PostPre with average_update = ring_pre.shape[0].  idx_*: the ring indices at the start of
+    the step; the caller advances the index of every term whose rate is non-zero."""
+    B, (Nin, N), K = s_src.shape[0], W.shape, ring_pre.shape[0]
+    check(lib().snn_postpre_avg_step(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Nin, N,
+                                     nu0, nu1, dt, decay, *_bounds(wmin, wmax), int(squeeze), _ring(ring_pre, W, K), _ring(ring_post, W, K),
+                                     K, int(continuous), idx_pre, idx_post, _stream()), "postpre_avg_step")
+
+
+def mstdp_avg_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus, decay_plus, decay_minus,
+                   ring, idx, continuous, squeeze=False, wdecay=1.0, wmin=None, wmax=None, reward_vec=None):
+    """include/snnhip.h f14: one step of MCC MSTDP with average_update = ring.shape[0]."""
+    B, (Nin, N), K = s_src.shape[0], W.shape, ring.shape[0]
+    check(lib().snn_mstdp_avg_step(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"), _ptr(s_tgt_prev, "spike"),
+                                   _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N, reward, _ptr(reward_vec, F32, True), nu0, a_plus,
+                                   a_minus, decay_plus, decay_minus, wdecay, *_bounds(wmin, wmax), int(squeeze), _ring(ring, W, K), K,
+                                   int(continuous), idx, _stream()), "mstdp_avg_step")
+
+
+def mstdpet_avg_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, dt, a_plus, a_minus, decay_plus,
+                     decay_minus, decay_e, tc_e, ring, idx, continuous, wdecay=1.0, wmin=None, wmax=None):
+    """include/snnhip.h f14: one step of MCC MSTDPET (batch 1) with average_update = ring.shape[0]."""
+    (Nin, N), K = W.shape, ring.shape[0]
+    check(lib().snn_mstdpet_avg_step(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                     _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt, a_plus,
+                                     a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *_bounds(wmin, wmax), _ring(ring, W, K), K,
+                                     int(continuous), idx, _stream()), "mstdpet_avg_step")
+
+
 def normalize(W, norm, use_abs, ws=None):
     Nin, N = W.shape
     if ws is None:

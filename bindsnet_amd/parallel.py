@@ -76,6 +76,10 @@ def _reject_local(network, mode: str) -> None:
         if half is not None:               # the modes merge, slice and gather float32 matrices
             raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a {half} Weight; the multi-device modes compute in "
                                       "float32 only; run the network on one device")
+        if hasattr(conn, "pipeline") and any(getattr(f.learning_rule, "average_update", 0) for f in conn.pipeline):
+            # an averaging ring is one history of the GLOBAL batch's updates: a shard's own ring, or a slice of one, is another rule
+            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a rule with average_update, whose ring of past updates "
+                                      "the multi-device modes neither merge nor slice; run the network on one device")
         if not conn._multi_device:
             if hasattr(conn, "pipeline"):
                 raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "

@@ -593,6 +593,38 @@ int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus,
                         float wmin, int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream);
 int snn_normalize_pv(float *W, int Nin, int N, const float *norm_vec, int use_abs, float *colsum_ws, snn_stream_t stream);
 
+/* ---- f14: time-averaged updates of the MulticompartmentConnection rules (average_update / continues_update) -----
+ * bindsnet/learning/MCC_learning.py:211-222, :237-289 (PostPre), :457-466, :518-535 (MSTDP), :641-649, :696-713 (MSTDPET).  With
+ * average_update = K a rule stores each step's update in slot `idx` of a ring of K weight-shaped slots (f32 [K, Nin, N], caller-owned,
+ * never cleared by the rule) and, when due, applies torch.mean(ring, dim=0): ATen's sum(dim=0) over the [K, Nin*N] ring in its own
+ * order (the batch reduction's, csrc/snn_order.hpp batch_sum, with K terms), then one division by K.  `idx` is the ring index at the
+ * START of the step (the caller advances it by one per call, mod K); due = `continuous` (continues_update), or idx + 1 == K (the step
+ * in which the index wraps).  The slot is written for every element, zeros included.  Decay and clamp run every step.
+ *   snn_postpre_avg_step   pre (nu0 != 0):  ring_pre[idx_pre] = reduce_b s_src * (x_tgt * nu0);  due: W -= mean(ring_pre) * dt;
+ *                          post (nu1 != 0): ring_post[idx_post] = reduce_b x_src * (s_tgt * nu1); due: W += mean(ring_post) * dt;
+ *                          W *= decay; clamp.  A term whose rate is 0 does not run: the caller leaves its index alone.
+ *   snn_mstdp_avg_step     ring[idx] = reduce_b reward * elig_prev[b] (no nu);  due: W += nu0 * mean(ring);  W *= wdecay; clamp;
+ *                          then p_plus / p_minus / *_prev advance as in snn_mstdp_step.
+ *   snn_mstdpet_avg_step   e_trace as in snn_mstdpet_step;  ring[idx] = ((nu0 * dt) * reward) * e_trace;  due: W += mean(ring);
+ *                          W *= wdecay; clamp;  then the factors advance.  Batch 1.
+ * reduce_b: ATen's sum(dim=0) over the batch (every shape class of batch_sum, Nin*N == 1 and 4..7 included), or with `squeeze`
+ * (batch 1, reduction = torch.squeeze) the product itself.  Limits: K <= 256 and B <= 256 (SNN_ERR_UNSUPPORTED beyond); scalar
+ * rates and bounds only.  One launch per call for the weights and the rings, one more for the factors of the reward rules.
+ * Added without changing SNN_ABI_VERSION: purely additive.                                                          */
+#define SNN_AVG_MAX_TERMS 256
+int snn_postpre_avg_step(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin,
+                         int N, float nu0, float nu1, float dt, float decay, int has_min, float wmin, int has_max, float wmax,
+                         int squeeze, float *ring_pre, float *ring_post, int K, int continuous, int idx_pre, int idx_post,
+                         snn_stream_t stream);
+int snn_mstdp_avg_step(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                       const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0, float a_plus,
+                       float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin, int has_max,
+                       float wmax, int squeeze, float *ring, int K, int continuous, int idx, snn_stream_t stream);
+int snn_mstdpet_avg_step(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
+                         const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt, float a_plus,
+                         float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e, float wdecay, int has_min,
+                         float wmin, int has_max, float wmax, float *ring, int K, int continuous, int idx, snn_stream_t stream);
+
 /* ---- f2: spike encoders on the device ---------------------------------------------------------
  * bindsnet/encoding/encodings.py:51-98 (bernoulli): out [steps, n] u8 = what torch.bernoulli(max_prob *
  * datum.repeat([steps, 1])) draws from the HOST generator whose state is in *rng -- one 32-bit mt19937 output
@@ -797,6 +829,15 @@ typedef struct {
      * generic plan, as per-neuron layer parameters do.  Added like the fields above: SNN_ABI_VERSION stays. */
     snn_synparams syn;
     const float *norm_vec;
+    /* Time-averaged updates (f14 above): avg_k = the rule's average_update (0: none), avg_ring0 the ring f32 [avg_k, Nin, N] of
+     * MSTDP / MSTDPET and PostPre's pre ring, avg_ring1 PostPre's post ring, avg_continuous its continues_update, avg_squeeze
+     * reduction = torch.squeeze.  avg_i0 / avg_i1 are the ring indices at the START of the run -- per-call values like `reward`: timestep
+     * t writes slot (avg_i + t) mod avg_k, and the caller advances its own index by T afterwards (a PostPre term whose rate is 0
+     * never moves).  MCC connections with an f32 `w`, rules POSTPRE, MSTDP and MSTDPET, scalar rates and bounds (`syn` empty):
+     * anything else with avg_k != 0 is SNN_ERR_UNSUPPORTED, avg_k > SNN_AVG_MAX_TERMS too; a missing ring or an index outside
+     * [0, avg_k) is SNN_ERR_INVALID.  avg_k != 0 sends the graph to the generic plan.  Added like the fields above. */
+    float *avg_ring0, *avg_ring1;
+    int avg_k, avg_continuous, avg_squeeze, avg_i0, avg_i1;
 } snn_conn_desc;
 
 typedef struct {
