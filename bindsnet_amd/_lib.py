@@ -139,7 +139,7 @@ class ConnDesc(C.Structure):
                 ("gat_out", C.c_int * 3), ("gat_src", C.c_int * 3), ("gat_stride", C.c_int * 3), ("gat_off", C.c_int * 3),
                 ("w_dtype", C.c_int), ("syn", SynParams), ("norm_vec", C.c_void_p),
                 ("avg_ring0", C.c_void_p), ("avg_ring1", C.c_void_p), ("avg_k", C.c_int), ("avg_continuous", C.c_int),
-                ("avg_squeeze", C.c_int), ("avg_i0", C.c_int), ("avg_i1", C.c_int)]
+                ("avg_squeeze", C.c_int), ("avg_i0", C.c_int), ("avg_i1", C.c_int), ("reduce", C.c_int)]
 
 
 class MccOp(C.Structure):
@@ -176,6 +176,7 @@ MCC_MAX_PIPE = 8          # SNN_MCC_MAX_PIPE
 MCC_OP_MUL_DRAW, MCC_OP_MUL_MASK, MCC_OP_MUL_F32, MCC_OP_ADD_F32 = 1, 2, 3, 4
 AVG_MAX_TERMS = 256       # SNN_AVG_MAX_TERMS: the largest average_update (ring slots) of an MCC rule
 W_F32, W_F16, W_BF16 = 0, 1, 2         # SNN_W_*: snn_conn_desc.w_dtype, the element type of a connection's `w`
+REDUCE = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}      # SNN_REDUCE_*: the batch reduction of a rule's update (snnhip.h f15)
 RULE_NONE, RULE_POSTPRE, RULE_MSTDP, RULE_HEBBIAN, RULE_WDPOSTPRE, RULE_MSTDPET, RULE_RMAX = 0, 1, 2, 3, 4, 5, 6
 
 _lib = None
@@ -242,6 +243,16 @@ _SIGS = {
     "snn_postpre_avg_step": ([_vp] * 5 + [_i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_mstdp_avg_step": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _i, _i, _i, _vp], _i),
     "snn_mstdpet_avg_step": ([_vp] * 8 + [_i, _i] + [_f] * 10 + [_i, _f, _i, _f, _vp, _i, _i, _i, _vp], _i),
+    "snn_stdp_postpre_red": ([_vp] * 5 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _i, C.POINTER(SynParams), _i, _vp], _i),
+    "snn_stdp_hebbian_red": ([_vp] * 5 + [_i, _i, _i, _f, _f, _i, _f, _i, _f, _i, _f, C.POINTER(SynParams), _i, _vp], _i),
+    "snn_mstdp_step_red": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, C.POINTER(SynParams), _i, _vp], _i),
+    "snn_conv2d_postpre_red": ([_vp] * 5 + [_i] * 9 + [_f, _f, _f, _i, _f, _i, _f, _vp, _i, _vp], _i),
+    "snn_conv2d_hebbian_red": ([_vp] * 5 + [_i] * 9 + [_f, _f, _i, _f, _i, _f, _i, _f, _vp, _i, _vp], _i),
+    "snn_local_postpre_red": ([_vp] * 6 + [_i] * 6 + [_f] * 3 + [_i, _f, _i, _f, _i, _vp], _i),
+    "snn_convnd_postpre_red": ([_vp] * 6 + [_i] * 5 + [_f] * 3 + [_i, _f, _i, _f, _vp, _i, _vp], _i),
+    "snn_stdp_postpre_h16_red": ([_vp, _i] + [_vp] * 4 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _i, _vp], _i),
+    "snn_postpre_avg_step_red": ([_vp] * 5 + [_i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "snn_mstdp_avg_step_red": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_normalize_conv2d": ([_vp, _i, _i, _f, _vp], _i),
     "snn_prop_cascade_h16": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_stdp_postpre_h16": ([_vp, _i] + [_vp] * 4 + [_i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _f, _vp], _i),

@@ -24,14 +24,16 @@ unsigned avg_grid(long n) {
     return (unsigned)(g < (long)kAvgMaxGrid ? (g > 0 ? g : 1) : (long)kAvgMaxGrid);
 }
 
+template <int R = kReduceSum>
 __global__ __launch_bounds__(256) void k_avg_postpre(float *W, const AvgPostPre a) {
     const long E = (long)a.Nin * a.N;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < E; e += (long)gridDim.x * 256) avg_postpre_elem(W, a, e);
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < E; e += (long)gridDim.x * 256) avg_postpre_elem<R>(W, a, e);
 }
 
+template <int R = kReduceSum>
 __global__ __launch_bounds__(256) void k_avg_mstdp(float *W, const AvgMstdp a) {
     const long E = (long)a.Nin * a.N;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < E; e += (long)gridDim.x * 256) avg_mstdp_elem(W, a, e);
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < E; e += (long)gridDim.x * 256) avg_mstdp_elem<R>(W, a, e);
 }
 
 __global__ __launch_bounds__(256) void k_avg_mstdpet(float *W, const AvgMstdpet a) {
@@ -55,10 +57,11 @@ bool ring_ok(const float *ring, int K, int continuous, int idx) {
 
 }  // namespace
 
-extern "C" int snn_postpre_avg_step(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
-                                    int Nin, int N, float nu0, float nu1, float dt, float decay, int has_min, float wmin, int has_max,
-                                    float wmax, int squeeze, float *ring_pre, float *ring_post, int K, int continuous, int idx_pre,
-                                    int idx_post, snn_stream_t stream) {
+extern "C" int snn_postpre_avg_step_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                        int Nin, int N, float nu0, float nu1, float dt, float decay, int has_min, float wmin, int has_max,
+                                        float wmax, int squeeze, float *ring_pre, float *ring_post, int K, int continuous, int idx_pre,
+                                        int idx_post, int reduce, snn_stream_t stream) {
+    if (reduce < SNN_REDUCE_SUM || reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;
     if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
     if (!ring_ok(ring_pre, K, continuous, idx_pre) || !ring_ok(ring_post, K, continuous, idx_post)) return SNN_ERR_INVALID;
     if (squeeze && B != 1) return SNN_ERR_INVALID;
@@ -70,15 +73,28 @@ extern "C" int snn_postpre_avg_step(float *W, const uint8_t *s_src, const float 
     a.fin = AvgBounds{decay, has_min, wmin, has_max, wmax};
     a.pre = avg_ring(ring_pre, K, idx_pre, continuous);
     a.post = avg_ring(ring_post, K, idx_post, continuous);
-    hipLaunchKernelGGL(k_avg_postpre, dim3(avg_grid((long)Nin * N)), dim3(256), 0, (hipStream_t)stream, W, a);
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(avg_grid((long)Nin * N)), dim3(256), 0, (hipStream_t)stream, W, a); };
+    if (reduce == SNN_REDUCE_MEAN) launch(k_avg_postpre<kReduceMean>);
+    else if (reduce == SNN_REDUCE_AMAX) launch(k_avg_postpre<kReduceAmax>);
+    else if (reduce == SNN_REDUCE_AMIN) launch(k_avg_postpre<kReduceAmin>);
+    else launch(k_avg_postpre<>);
     return snn_check_launch();
 }
 
-extern "C" int snn_mstdp_avg_step(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
-                                  const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
-                                  float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
-                                  int has_max, float wmax, int squeeze, float *ring, int K, int continuous, int idx,
-                                  snn_stream_t stream) {
+extern "C" int snn_postpre_avg_step(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                    int Nin, int N, float nu0, float nu1, float dt, float decay, int has_min, float wmin, int has_max,
+                                    float wmax, int squeeze, float *ring_pre, float *ring_post, int K, int continuous, int idx_pre,
+                                    int idx_post, snn_stream_t stream) {
+    return snn_postpre_avg_step_red(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, dt, decay, has_min, wmin, has_max, wmax, squeeze,
+                                    ring_pre, ring_post, K, continuous, idx_pre, idx_post, SNN_REDUCE_SUM, stream);
+}
+
+extern "C" int snn_mstdp_avg_step_red(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                                      const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                                      float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                                      int has_max, float wmax, int squeeze, float *ring, int K, int continuous, int idx, int reduce,
+                                      snn_stream_t stream) {
+    if (reduce < SNN_REDUCE_SUM || reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;
     if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
     if (!ring_ok(ring, K, continuous, idx) || (squeeze && B != 1)) return SNN_ERR_INVALID;
     if (K > kAvgMaxTerms || B > kAvgMaxTerms) return SNN_ERR_UNSUPPORTED;
@@ -88,13 +104,27 @@ extern "C" int snn_mstdp_avg_step(float *W, float *p_plus, float *p_minus, uint8
     a.reward = reward; a.reward_vec = reward_vec; a.nu0 = nu0; a.squeeze = squeeze ? 1 : 0;
     a.fin = AvgBounds{wdecay, has_min, wmin, has_max, wmax};
     a.ring = avg_ring(ring, K, idx, continuous);
-    hipLaunchKernelGGL(k_avg_mstdp, dim3(avg_grid((long)Nin * N)), dim3(256), 0, (hipStream_t)stream, W, a);
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(avg_grid((long)Nin * N)), dim3(256), 0, (hipStream_t)stream, W, a); };
+    if (reduce == SNN_REDUCE_MEAN) launch(k_avg_mstdp<kReduceMean>);
+    else if (reduce == SNN_REDUCE_AMAX) launch(k_avg_mstdp<kReduceAmax>);
+    else if (reduce == SNN_REDUCE_AMIN) launch(k_avg_mstdp<kReduceAmin>);
+    else launch(k_avg_mstdp<>);
     int rc = snn_check_launch();
     if (rc) return rc;
     const long n = (long)B * ((long)Nin + N);
     hipLaunchKernelGGL(k_avg_traces, dim3(avg_grid(n)), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src,
                        s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus, decay_minus);
     return snn_check_launch();
+}
+
+extern "C" int snn_mstdp_avg_step(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                                  const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                                  float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                                  int has_max, float wmax, int squeeze, float *ring, int K, int continuous, int idx,
+                                  snn_stream_t stream) {
+    return snn_mstdp_avg_step_red(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                                  decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, squeeze, ring, K, continuous, idx,
+                                  SNN_REDUCE_SUM, stream);
 }
 
 extern "C" int snn_mstdpet_avg_step(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,

@@ -62,18 +62,20 @@ struct AvgPostPre {
     AvgRing pre, post;           // a term whose rate is 0 does not run at all: its ring and index stand still
 };
 
+// R: the batch reduction whose result goes into the ring slot (snn_order.hpp batch_sum<R>; SUM is the function as it was); the ring's own mean stays.
+template <int R = kReduceSum>
 __host__ __device__ inline void avg_postpre_elem(float *W, const AvgPostPre &a, long e) {
     const long E = (long)a.Nin * a.N;
     const int i = (int)(e / a.N), j = (int)(e - (long)i * a.N);
     float w = W[e], m;
     if (a.nu0 != 0.f) {          // reduction(bmm(s_src, x_tgt * nu0), dim=0)
         auto term = [&a, i, j](int b) { return (float)a.s_src[(long)b * a.Nin + i] * (a.x_tgt[(long)b * a.N + j] * a.nu0); };
-        const float v = a.squeeze ? term(0) : batch_sum(term, a.B, e, E);
+        const float v = a.squeeze ? term(0) : batch_sum<R>(term, a.B, e, E);
         if (avg_push(a.pre, v, e, E, &m)) w = w - m * a.dt;
     }
     if (a.nu1 != 0.f) {          // reduction(bmm(x_src, s_tgt * nu1), dim=0)
         auto term = [&a, i, j](int b) { return a.x_src[(long)b * a.Nin + i] * ((float)a.s_tgt[(long)b * a.N + j] * a.nu1); };
-        const float v = a.squeeze ? term(0) : batch_sum(term, a.B, e, E);
+        const float v = a.squeeze ? term(0) : batch_sum<R>(term, a.B, e, E);
         if (avg_push(a.post, v, e, E, &m)) w = w + m * a.dt;
     }
     W[e] = avg_finish(w, a.fin);
@@ -92,6 +94,7 @@ struct AvgMstdp {
     AvgRing ring;
 };
 
+template <int R = kReduceSum>
 __host__ __device__ inline void avg_mstdp_elem(float *W, const AvgMstdp &a, long e) {
     const long E = (long)a.Nin * a.N;
     const int i = (int)(e / a.N), j = (int)(e - (long)i * a.N);
@@ -101,7 +104,7 @@ __host__ __device__ inline void avg_mstdp_elem(float *W, const AvgMstdp &a, long
         const float el = e1 + e2;
         return (a.reward_vec ? a.reward_vec[b] : a.reward) * el;       // reward * eligibility
     };
-    const float v = a.squeeze ? term(0) : batch_sum(term, a.B, e, E);
+    const float v = a.squeeze ? term(0) : batch_sum<R>(term, a.B, e, E);
     float w = W[e], m;
     if (avg_push(a.ring, v, e, E, &m)) w = w + a.nu0 * m;              // :527-530
     W[e] = avg_finish(w, a.fin);

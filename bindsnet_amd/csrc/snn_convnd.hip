@@ -71,7 +71,8 @@ __global__ __launch_bounds__(kThreads) void k_convnd_pack_tgt(const uint8_t *__r
 // pre / post terms of snn_convnd.hpp, then the batch reduction in ATen's sum(dim=0) order (batch_sum; one term at B = 1,
 // where the reference squeezes), then w - nu0*pre (nu0 != 0), w + nu1*post (nu1 != 0), w * decay, clamp
 // (learning.py:87-104).  STAGED: the workgroup packs the target masks into LDS itself; else they come from k_convnd_pack_tgt.
-template <bool STAGED>
+// R: the batch reduction (snn_order.hpp batch_sum<R>; SUM is the function as it was).
+template <bool STAGED, int R = kReduceSum>
 __global__ __launch_bounds__(kThreads) void k_convnd_postpre(float *__restrict__ W, const int *__restrict__ tab,
                                                              const uint8_t *__restrict__ s_src, const float *__restrict__ x_src,
                                                              const uint8_t *__restrict__ s_tgt, const float *__restrict__ x_tgt,
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(kThreads) void k_convnd_postpre(float *__restrict__
         const int co = (int)(e / J), j = (int)(e - (long)co * J);
         float w = W[e];
         if (nu0 != 0.f) {
-            const float pre = batch_sum([&](int b) {
+            const float pre = batch_sum<R>([&](int b) {
                 const uint8_t *ss = s_src + (size_t)b * n_src;
                 return convnd_pp_pre(tab, L, J, j, x_tgt + ((size_t)b * Cout + co) * L, [&](int i) { return (float)ss[i]; });
             }, B, e, E);
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void k_convnd_postpre(float *__restrict__
             w = w - u;
         }
         if (nu1 != 0.f) {
-            const float post = batch_sum([&](int b) {
+            const float post = batch_sum<R>([&](int b) {
                 const uint32_t *mk = masks + ((size_t)b * Cout + co) * nw;
                 const float *xs = x_src + (size_t)b * n_src;
                 return convnd_pp_post(tab, L, J, j, [&](int k) { return mk[k]; }, [&](int i) { return xs[i]; });
@@ -146,9 +147,25 @@ extern "C" int snn_prop_convnd_f32(const float *W, const float *bias, const uint
     return snn_check_launch();
 }
 
-extern "C" int snn_convnd_postpre(float *W, const int *pp_src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
-                                  const float *x_tgt, int B, int Cout, int L, int J, int n_src, float nu0, float nu1, float decay,
-                                  int has_min, float wmin, int has_max, float wmax, uint32_t *ws, snn_stream_t stream) {
+// One launch of k_convnd_postpre<STAGED, R> for each of the four reductions.
+template <bool STAGED>
+static void launch_convnd_postpre(int reduce, dim3 grid, hipStream_t st, float *W, const int *pp_src, const uint8_t *s_src, const float *x_src,
+                                  const uint8_t *s_tgt, const float *x_tgt, const uint32_t *masks, int B, int Cout, int L, int J, int n_src,
+                                  float nu0, float nu1, float decay, int has_min, float wmin, int has_max, float wmax) {
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, st, W, pp_src, s_src, x_src, s_tgt, x_tgt, masks, B, Cout, L, J, n_src, nu0, nu1,
+                           decay, has_min, wmin, has_max, wmax);
+    };
+    if (reduce == SNN_REDUCE_MEAN) launch(k_convnd_postpre<STAGED, kReduceMean>);
+    else if (reduce == SNN_REDUCE_AMAX) launch(k_convnd_postpre<STAGED, kReduceAmax>);
+    else if (reduce == SNN_REDUCE_AMIN) launch(k_convnd_postpre<STAGED, kReduceAmin>);
+    else launch(k_convnd_postpre<STAGED>);
+}
+
+extern "C" int snn_convnd_postpre_red(float *W, const int *pp_src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                                      const float *x_tgt, int B, int Cout, int L, int J, int n_src, float nu0, float nu1, float decay,
+                                      int has_min, float wmin, int has_max, float wmax, uint32_t *ws, int reduce, snn_stream_t stream) {
+    if (reduce < SNN_REDUCE_SUM || reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;
     if (!W || !pp_src || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Cout <= 0 || L <= 0 || J <= 0 || n_src <= 0)
         return SNN_ERR_INVALID;
     const long E = (long)Cout * J, nw = (L + 31) / 32, words = (long)B * Cout * nw;
@@ -158,16 +175,23 @@ extern "C" int snn_convnd_postpre(float *W, const int *pp_src, const uint8_t *s_
     const long g = (E + kThreads - 1) / kThreads;
     const dim3 grid((unsigned)(g < 4096 ? g : 4096));
     if (staged) {
-        hipLaunchKernelGGL(k_convnd_postpre<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, W, pp_src, s_src, x_src, s_tgt, x_tgt,
-                           (const uint32_t *)nullptr, B, Cout, L, J, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
+        launch_convnd_postpre<true>(reduce, grid, (hipStream_t)stream, W, pp_src, s_src, x_src, s_tgt, x_tgt, (const uint32_t *)nullptr, B, Cout,
+                                    L, J, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
     } else {
         if (nu1 != 0.f) {
             const long pg = (words + kThreads - 1) / kThreads;
             hipLaunchKernelGGL(k_convnd_pack_tgt, dim3((unsigned)(pg < 4096 ? pg : 4096)), dim3(kThreads), 0, (hipStream_t)stream, s_tgt, ws,
                                (long)B * Cout, L);
         }
-        hipLaunchKernelGGL(k_convnd_postpre<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, W, pp_src, s_src, x_src, s_tgt, x_tgt,
-                           (const uint32_t *)ws, B, Cout, L, J, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
+        launch_convnd_postpre<false>(reduce, grid, (hipStream_t)stream, W, pp_src, s_src, x_src, s_tgt, x_tgt, (const uint32_t *)ws, B, Cout, L,
+                                     J, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
     }
     return snn_check_launch();
+}
+
+extern "C" int snn_convnd_postpre(float *W, const int *pp_src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                                  const float *x_tgt, int B, int Cout, int L, int J, int n_src, float nu0, float nu1, float decay,
+                                  int has_min, float wmin, int has_max, float wmax, uint32_t *ws, snn_stream_t stream) {
+    return snn_convnd_postpre_red(W, pp_src, s_src, x_src, s_tgt, x_tgt, B, Cout, L, J, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax, ws,
+                                  SNN_REDUCE_SUM, stream);
 }

@@ -81,7 +81,7 @@ extern "C" int snn_prop_cascade_h16(const void *W, int w_dtype, const uint8_t *s
 // =============================================================================================
 constexpr int kPpRows = 16;
 
-template <int DT>
+template <int DT, int R = kReduceSum>
 __global__ __launch_bounds__(256) void k_postpre_h16(uint16_t *__restrict__ W, const HalfPostPre a) {
     __shared__ uint32_t mS[kPpRows][kHalfMaskWords];
     __shared__ uint32_t mT[kHalfMaskWords][256];
@@ -108,20 +108,37 @@ __global__ __launch_bounds__(256) void k_postpre_h16(uint16_t *__restrict__ W, c
         const int i = i0 + r;
         if (i >= a.Nin) break;
         const size_t e = (size_t)i * a.N + j;
-        W[e] = half_postpre_elem<DT>(W[e], a, i, j, &mS[r][0], 1, &mT[0][tid], 256);
+        W[e] = half_postpre_elem<DT, R>(W[e], a, i, j, &mS[r][0], 1, &mT[0][tid], 256);
     }
+}
+
+template <int DT>
+static void launch_postpre_h16(int reduce, dim3 grid, hipStream_t st, uint16_t *W, const HalfPostPre &a) {
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, W, a); };
+    if (reduce == SNN_REDUCE_MEAN) launch(k_postpre_h16<DT, kReduceMean>);
+    else if (reduce == SNN_REDUCE_AMAX) launch(k_postpre_h16<DT, kReduceAmax>);
+    else if (reduce == SNN_REDUCE_AMIN) launch(k_postpre_h16<DT, kReduceAmin>);
+    else launch(k_postpre_h16<DT>);
+}
+
+extern "C" int snn_stdp_postpre_h16_red(void *W, int w_dtype, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                                        const float *x_tgt, int B, int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay,
+                                        int has_min, float wmin, int has_max, float wmax, int reduce, snn_stream_t stream) {
+    if (reduce < SNN_REDUCE_SUM || reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || (w_dtype != kWF16 && w_dtype != kWBF16)) return SNN_ERR_INVALID;
+    if (B > kHalfMaxB || (Nin + kPpRows - 1) / kPpRows > 65535) return SNN_ERR_UNSUPPORTED;
+    const HalfPostPre a{s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax};
+    const dim3 grid((N + 255) / 256, (Nin + kPpRows - 1) / kPpRows);
+    if (w_dtype == kWF16) launch_postpre_h16<kWF16>(reduce, grid, (hipStream_t)stream, (uint16_t *)W, a);
+    else launch_postpre_h16<kWBF16>(reduce, grid, (hipStream_t)stream, (uint16_t *)W, a);
+    return snn_check_launch();
 }
 
 extern "C" int snn_stdp_postpre_h16(void *W, int w_dtype, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
                                     const float *x_tgt, int B, int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay,
                                     int has_min, float wmin, int has_max, float wmax, snn_stream_t stream) {
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || (w_dtype != kWF16 && w_dtype != kWBF16)) return SNN_ERR_INVALID;
-    if (B > kHalfMaxB || (Nin + kPpRows - 1) / kPpRows > 65535) return SNN_ERR_UNSUPPORTED;
-    const HalfPostPre a{s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax};
-    const dim3 grid((N + 255) / 256, (Nin + kPpRows - 1) / kPpRows);
-    if (w_dtype == kWF16) hipLaunchKernelGGL(k_postpre_h16<kWF16>, grid, dim3(256), 0, (hipStream_t)stream, (uint16_t *)W, a);
-    else hipLaunchKernelGGL(k_postpre_h16<kWBF16>, grid, dim3(256), 0, (hipStream_t)stream, (uint16_t *)W, a);
-    return snn_check_launch();
+    return snn_stdp_postpre_h16_red(W, w_dtype, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax,
+                                    SNN_REDUCE_SUM, stream);
 }
 
 // =============================================================================================

@@ -92,7 +92,8 @@ __host__ __device__ __forceinline__ bool half_mask_any(const uint32_t *m, int st
     return any != 0;
 }
 
-template <int DT>
+// R: the batch reduction (snn_order.hpp batch_sum<R>; SUM is the function as it was).  An element without an event keeps u = 0 under each of them.
+template <int DT, int R = kReduceSum>
 __host__ __device__ inline uint16_t half_postpre_elem(uint16_t wbits, const HalfPostPre &a, int i, int j, const uint32_t *mS, int strideS,
                                                       const uint32_t *mT, int strideT) {
     const long E = (long)a.Nin * a.N, e = (long)i * a.N + j;
@@ -104,7 +105,7 @@ __host__ __device__ inline uint16_t half_postpre_elem(uint16_t wbits, const Half
         };
         float u = 0.f;
         if (a.B == 1) u = term(0);                       // reduction = torch.squeeze
-        else if (half_mask_any(mS, strideS, a.B)) u = batch_sum(term, a.B, e, E);
+        else if (half_mask_any(mS, strideS, a.B)) u = batch_sum<R>(term, a.B, e, E);
         if (a.use_dt) u = u * a.dt;
         w = half_round<DT>(w - u);
     }
@@ -115,7 +116,7 @@ __host__ __device__ inline uint16_t half_postpre_elem(uint16_t wbits, const Half
         };
         float u = 0.f;
         if (a.B == 1) u = term(0);
-        else if (half_mask_any(mT, strideT, a.B)) u = batch_sum(term, a.B, e, E);
+        else if (half_mask_any(mT, strideT, a.B)) u = batch_sum<R>(term, a.B, e, E);
         if (a.use_dt) u = u * a.dt;
         w = half_round<DT>(w + u);
     }

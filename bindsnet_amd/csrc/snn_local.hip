@@ -62,6 +62,8 @@ __global__ __launch_bounds__(kLocalThreads) void k_prop_local(const float *__res
 // post[b, r, j] = s_tgt[b, r] * x_src[b, src(r, j)] exactly; the batch reduction is ATen's sum(dim=0) order over the
 // W.numel() columns (batch_sum; one term at B = 1 == torch.squeeze).  Then w - nu0*pre, w + nu1*post (each half only when its
 // rate is non-zero), w * decay, clamp.  One thread per weight element (grid-stride); every weight is read and written once.
+// RED: the batch reduction (snn_order.hpp batch_sum<R>; SUM is the function as it was).
+template <int RED = kReduceSum>
 __global__ __launch_bounds__(kLocalThreads) void k_local_postpre(float *__restrict__ W, const int *__restrict__ src,
                                                                  const uint8_t *__restrict__ s_src, const float *__restrict__ x_src,
                                                                  const uint8_t *__restrict__ s_tgt, const float *__restrict__ x_tgt,
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(kLocalThreads) void k_local_postpre(float *__restri
         const int sc = in ? si : 0;
         float w = W[e];
         if (nu0 != 0.f) {
-            const float pre = batch_sum([&](int b) {
+            const float pre = batch_sum<RED>([&](int b) {
                 const float sv = in ? (float)s_src[(size_t)b * n_src + sc] : 0.0f;
                 return x_tgt[(size_t)b * R + r] * sv;
             }, B, e, E);
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(kLocalThreads) void k_local_postpre(float *__restri
             w = w - u;
         }
         if (nu1 != 0.f) {
-            const float post = batch_sum([&](int b) {
+            const float post = batch_sum<RED>([&](int b) {
                 const float xv = in ? x_src[(size_t)b * n_src + sc] : 0.0f;
                 return (float)s_tgt[(size_t)b * R + r] * xv;
             }, B, e, E);
@@ -122,9 +124,11 @@ extern "C" int snn_prop_local_f32(const float *W, const int *src, const uint8_t 
     return snn_check_launch();
 }
 
-extern "C" int snn_local_postpre(float *W, const int *src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
-                                 const float *x_tgt, int B, int Cin, int F, int conv_prod, int kernel_prod, int n_src, float nu0,
-                                 float nu1, float decay, int has_min, float wmin, int has_max, float wmax, snn_stream_t stream) {
+extern "C" int snn_local_postpre_red(float *W, const int *src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                                     const float *x_tgt, int B, int Cin, int F, int conv_prod, int kernel_prod, int n_src, float nu0,
+                                     float nu1, float decay, int has_min, float wmin, int has_max, float wmax, int reduce,
+                                     snn_stream_t stream) {
+    if (reduce < SNN_REDUCE_SUM || reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;
     if (!W || !src || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Cin <= 0 || F <= 0 || conv_prod <= 0 || kernel_prod <= 0 ||
         n_src <= 0)
         return SNN_ERR_INVALID;
@@ -132,7 +136,20 @@ extern "C" int snn_local_postpre(float *W, const int *src, const uint8_t *s_src,
     if (R > (1L << 30) || E > (1L << 40) || B > kMaxTerms) return SNN_ERR_UNSUPPORTED;
     const long g = (E + kLocalThreads - 1) / kLocalThreads;
     const unsigned grid = (unsigned)(g < 4096 ? g : 4096);
-    hipLaunchKernelGGL(k_local_postpre, dim3(grid), dim3(kLocalThreads), 0, (hipStream_t)stream, W, src, s_src, x_src, s_tgt, x_tgt, B,
-                       Cin, (int)R, conv_prod, kernel_prod, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kLocalThreads), 0, (hipStream_t)stream, W, src, s_src, x_src, s_tgt, x_tgt, B,
+                           Cin, (int)R, conv_prod, kernel_prod, n_src, nu0, nu1, decay, has_min, wmin, has_max, wmax);
+    };
+    if (reduce == SNN_REDUCE_MEAN) launch(k_local_postpre<kReduceMean>);
+    else if (reduce == SNN_REDUCE_AMAX) launch(k_local_postpre<kReduceAmax>);
+    else if (reduce == SNN_REDUCE_AMIN) launch(k_local_postpre<kReduceAmin>);
+    else launch(k_local_postpre<>);
     return snn_check_launch();
+}
+
+extern "C" int snn_local_postpre(float *W, const int *src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                                 const float *x_tgt, int B, int Cin, int F, int conv_prod, int kernel_prod, int n_src, float nu0,
+                                 float nu1, float decay, int has_min, float wmin, int has_max, float wmax, snn_stream_t stream) {
+    return snn_local_postpre_red(W, src, s_src, x_src, s_tgt, x_tgt, B, Cin, F, conv_prod, kernel_prod, n_src, nu0, nu1, decay, has_min, wmin,
+                                 has_max, wmax, SNN_REDUCE_SUM, stream);
 }

@@ -10,6 +10,7 @@
 #include "../../include/snnhip.h"
 #include "snn_conv_events.hpp"
 #include "snn_order.hpp"
+#include "snn_conv_apply.hpp"
 #include "snn_common.hpp"
 #include "snn_rng.hpp"
 #include "snn_synparams.hpp"
@@ -577,8 +578,25 @@ constexpr int kTI = 16;
 #define SNN_PLASTICITY_PV 1
 #include "snn_plasticity.inc"
 #undef SNN_PLASTICITY_PV
+// ... and a third time as k_plasticity_red<TJ, ACC>: the batch reductions beside sum (snnhip.h f15)
+#define SNN_PLASTICITY_PV 2
+#include "snn_plasticity.inc"
+#undef SNN_PLASTICITY_PV
 
-static int launch_plasticity(const StdpArgs &a, hipStream_t st) {
+// One launcher for the three inclusions of the kernel text: the LDS formula, the tile thresholds and the > 64 KiB attribute of the
+// narrow-tile instance are in one place.  FAMILY names the four tile instances; `extra` is what the kernel takes behind StdpArgs.
+struct PlasticityScalar {                              // k_plasticity<TJ>(StdpArgs)
+    template <int TJ> static auto kernel() { return k_plasticity<TJ>; }
+};
+struct PlasticityPv {                                  // k_plasticity_pv<TJ>(StdpArgs, snn_synparams)
+    template <int TJ> static auto kernel() { return k_plasticity_pv<TJ>; }
+};
+template <int R> struct PlasticityRed {                // k_plasticity_red<TJ, BatchReduce<R>>(StdpArgs, snn_synparams)
+    template <int TJ> static auto kernel() { return k_plasticity_red<TJ, BatchReduce<R>>; }
+};
+
+template <class FAMILY, class... EXTRA>
+static int launch_plasticity_tiles(const StdpArgs &a, hipStream_t st, const EXTRA &...extra) {
     const int B = a.B, MW = (B + 31) / 32;
     auto lds = [&](int TJ) {
         return (size_t)B * TJ * 4 + (size_t)B * kTI * 4 + (size_t)(TJ + kTI) * MW * 4 + (size_t)B * TJ + (size_t)B * kTI;
@@ -586,60 +604,68 @@ static int launch_plasticity(const StdpArgs &a, hipStream_t st) {
     const dim3 blk(256);
     const unsigned gy = (a.Nin + kTI - 1) / kTI;
     constexpr size_t kSmall = 64 * 1024, kBig = 144 * 1024;   // 160 KiB LDS per CU on gfx950
-    static bool attr_set = false;
+    static bool attr_set = false;                      // (one per FAMILY)
     if (!attr_set) {   // allow > 64 KiB dynamic LDS for the narrow-tile instantiation
-        if (snn_check(hipFuncSetAttribute((const void *)k_plasticity<32>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (snn_check(hipFuncSetAttribute((const void *)FAMILY::template kernel<32>(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)kBig)))
             return SNN_ERR_LAUNCH;
         attr_set = true;
     }
     if (lds(256) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity<256>, dim3((a.N + 255) / 256, gy), blk, lds(256), st, a);
+        hipLaunchKernelGGL(FAMILY::template kernel<256>(), dim3((a.N + 255) / 256, gy), blk, lds(256), st, a, extra...);
     } else if (lds(128) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity<128>, dim3((a.N + 127) / 128, gy), blk, lds(128), st, a);
+        hipLaunchKernelGGL(FAMILY::template kernel<128>(), dim3((a.N + 127) / 128, gy), blk, lds(128), st, a, extra...);
     } else if (lds(64) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity<64>, dim3((a.N + 63) / 64, gy), blk, lds(64), st, a);
+        hipLaunchKernelGGL(FAMILY::template kernel<64>(), dim3((a.N + 63) / 64, gy), blk, lds(64), st, a, extra...);
     } else if (lds(32) <= kBig) {
-        hipLaunchKernelGGL(k_plasticity<32>, dim3((a.N + 31) / 32, gy), blk, lds(32), st, a);
+        hipLaunchKernelGGL(FAMILY::template kernel<32>(), dim3((a.N + 31) / 32, gy), blk, lds(32), st, a, extra...);
     } else {
         return SNN_ERR_UNSUPPORTED;
     }
     return snn_check_launch();
 }
 
-// The same tiles and LDS layout for the per-synapse instance (k_plasticity_pv).
+static int launch_plasticity(const StdpArgs &a, hipStream_t st) { return launch_plasticity_tiles<PlasticityScalar>(a, st); }
+
+// The same tiles and LDS layout for the per-synapse instance (k_plasticity_pv) ...
 static int launch_plasticity_pv(const StdpArgs &a, const snn_synparams &q, hipStream_t st) {
-    const int B = a.B, MW = (B + 31) / 32;
-    auto lds = [&](int TJ) {
-        return (size_t)B * TJ * 4 + (size_t)B * kTI * 4 + (size_t)(TJ + kTI) * MW * 4 + (size_t)B * TJ + (size_t)B * kTI;
-    };
-    const dim3 blk(256);
-    const unsigned gy = (a.Nin + kTI - 1) / kTI;
-    constexpr size_t kSmall = 64 * 1024, kBig = 144 * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (snn_check(hipFuncSetAttribute((const void *)k_plasticity_pv<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBig)))
-            return SNN_ERR_LAUNCH;
-        attr_set = true;
+    return launch_plasticity_tiles<PlasticityPv>(a, st, q);
+}
+
+static bool reduce_valid(int reduce) { return reduce >= SNN_REDUCE_SUM && reduce <= SNN_REDUCE_AMIN; }
+
+// ... and for the instances of another batch reduction (k_plasticity_red<TJ, BatchReduce<R>>).
+// `reduce` is MEAN, AMAX or AMIN here (the *_red entry points forward SUM to their *_pv namesakes); a NULL `sp` is the empty snn_synparams.
+static int launch_plasticity_red(const StdpArgs &a, const snn_synparams &q, int reduce, hipStream_t st) {
+    switch (reduce) {
+        case SNN_REDUCE_MEAN: return launch_plasticity_tiles<PlasticityRed<SNN_REDUCE_MEAN>>(a, st, q);
+        case SNN_REDUCE_AMAX: return launch_plasticity_tiles<PlasticityRed<SNN_REDUCE_AMAX>>(a, st, q);
+        case SNN_REDUCE_AMIN: return launch_plasticity_tiles<PlasticityRed<SNN_REDUCE_AMIN>>(a, st, q);
+        default: return SNN_ERR_INVALID;
     }
-    if (lds(256) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity_pv<256>, dim3((a.N + 255) / 256, gy), blk, lds(256), st, a, q);
-    } else if (lds(128) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity_pv<128>, dim3((a.N + 127) / 128, gy), blk, lds(128), st, a, q);
-    } else if (lds(64) <= kSmall) {
-        hipLaunchKernelGGL(k_plasticity_pv<64>, dim3((a.N + 63) / 64, gy), blk, lds(64), st, a, q);
-    } else if (lds(32) <= kBig) {
-        hipLaunchKernelGGL(k_plasticity_pv<32>, dim3((a.N + 31) / 32, gy), blk, lds(32), st, a, q);
-    } else {
-        return SNN_ERR_UNSUPPORTED;
-    }
-    return snn_check_launch();
 }
 
 // The scalar fields of StdpArgs for the per-synapse instance: a rate given as a tensor leaves "any entry non-zero" in its place.
 static void syn_rates(StdpArgs &a, const snn_synparams &q) {
     if (q.nu0) a.nu0 = q.nu0_any ? 1.f : 0.f;
     if (q.nu1) a.nu1 = q.nu1_any ? 1.f : 0.f;
+}
+
+extern "C" int snn_stdp_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                    int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
+                                    int has_max, float wmax, int assume_clamped, const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
+    if (reduce == SNN_REDUCE_SUM)
+        return snn_stdp_postpre_pv(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax,
+                                   assume_clamped, sp, stream);
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
+    if (sp && ((sp->nu0 && sp->nu0_rs != 0) || (sp->nu1 && sp->nu1_rs != 0))) return SNN_ERR_INVALID;     // learning.py:401-402
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max,
+               wmax, (assume_clamped && decay == 1.0f) ? 1 : 0, 0, 0.f, nullptr};
+    const snn_synparams q = sp ? *sp : snn_synparams{};
+    syn_rates(a, q);
+    return launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
 }
 
 extern "C" int snn_stdp_postpre_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
@@ -777,28 +803,16 @@ __global__ __launch_bounds__(256) void k_conv_pp_partial_ev(const uint8_t *__res
     part[(size_t)B * E + id] = p;
 }
 
-// element e's partial sums of the B samples in ATen's sum(dim=0) order (the loads of sixteen samples are issued together, then added in that
-// order: one round trip per sixteen terms)
-__device__ __forceinline__ float conv_pp_batch_sum(const float *__restrict__ base, int B, long E, long e, bool tail) {
-    OuterSum acc; acc.init(tail);
-    for (int b0 = 0; b0 < B; b0 += 16) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = base[(size_t)min(b0 + u, B - 1) * E + e];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) if (b0 + u < B) acc.add(b0 + u, v[u], B);
-    }
-    return acc.finish(B);
-}
-
+// phase 2: one thread per weight element reduces the samples' partial sums (conv_pp_batch_sum, snn_conv_apply.hpp) and applies rates, decay and clamp
+template <class ACC = OuterSum>
 __global__ __launch_bounds__(256) void k_conv_pp_apply(float *__restrict__ W, const float *__restrict__ part, int B, long E, float nu0,
                                                        float nu1, float decay, int has_min, float wmin, int has_max, float wmax) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     const bool tail = e >= (E / 32) * 32;
     float w = W[e];
-    if (nu0 != 0.f) w = w - nu0 * conv_pp_batch_sum(part, B, E, e, tail);
-    if (nu1 != 0.f) w = w + nu1 * conv_pp_batch_sum(part + (size_t)B * E, B, E, e, tail);
+    if (nu0 != 0.f) w = w - nu0 * conv_pp_batch_sum<ACC>(part, B, E, e, tail);
+    if (nu1 != 0.f) w = w + nu1 * conv_pp_batch_sum<ACC>(part + (size_t)B * E, B, E, e, tail);
     w = w * decay;
     if (has_min && w < wmin) w = wmin;
     if (has_max && w > wmax) w = wmax;
@@ -822,9 +836,11 @@ static int conv_pp_partials(const uint8_t *s_src, const float *x_src, const uint
     return SNN_OK;
 }
 
-extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
-                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
-                                  float decay, int has_min, float wmin, int has_max, float wmax, float *ws, snn_stream_t stream) {
+extern "C" int snn_conv2d_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                      int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                      float decay, int has_min, float wmin, int has_max, float wmax, float *ws, int reduce,
+                                      snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
     if (!W || !s_src || !x_src || !s_tgt || !x_tgt || !ws || B <= 0 || Cin <= 0 || H <= 0 || Wd <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 ||
         stride <= 0 || pad < 0) return SNN_ERR_INVALID;
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1;
@@ -832,14 +848,28 @@ extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x
     const long E = (long)Cout * Cin * KH * KW;
     const int rc = conv_pp_partials(s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, ws, (hipStream_t)stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_conv_pp_apply, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ws, B, E, nu0, nu1, decay,
-                       has_min, wmin, has_max, wmax);
+    const dim3 grid((unsigned)((E + 255) / 256));
+    auto apply = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, W, (const float *)ws, B, E, nu0, nu1, decay, has_min, wmin, has_max, wmax);
+    };
+    if (reduce == SNN_REDUCE_MEAN) apply(k_conv_pp_apply<BatchReduce<SNN_REDUCE_MEAN>>);
+    else if (reduce == SNN_REDUCE_AMAX) apply(k_conv_pp_apply<BatchReduce<SNN_REDUCE_AMAX>>);
+    else if (reduce == SNN_REDUCE_AMIN) apply(k_conv_pp_apply<BatchReduce<SNN_REDUCE_AMIN>>);
+    else apply(k_conv_pp_apply<>);
     return snn_check_launch();
+}
+
+extern "C" int snn_conv2d_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                  float decay, int has_min, float wmin, int has_max, float wmax, float *ws, snn_stream_t stream) {
+    return snn_conv2d_postpre_red(W, s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, decay, has_min, wmin,
+                                  has_max, wmax, ws, SNN_REDUCE_SUM, stream);
 }
 
 // Hebbian (learning.py:1348-1380) / WeightDependentPostPre (:920-976) on a Conv2dConnection: the two sums PostPre reduces (the same partial
 // kernels, k_conv_pp_apply's ordered batch reduction), then the statements k_plasticity runs for the dense family (modes 2 / 3) -- except
 // that the reference's `w += update` also runs when both rates are zero (update is then the integer 0: a -0.0 weight becomes +0.0).
+template <class ACC = OuterSum>
 __global__ __launch_bounds__(256) void k_conv_hebb_apply(float *__restrict__ W, const float *__restrict__ part, int B, long E, float nu0,
                                                          float nu1, int weight_dependent, float decay, int has_min, float wmin, int has_max,
                                                          float wmax) {
@@ -848,8 +878,8 @@ __global__ __launch_bounds__(256) void k_conv_hebb_apply(float *__restrict__ W, 
     const bool tail = e >= (E / 32) * 32;
     float w = W[e];
     // (Hebbian's two statements always run; WeightDependentPostPre skips a side whose rate is zero, and its loads with it)
-    const float pre = (!weight_dependent || nu0 != 0.f) ? conv_pp_batch_sum(part, B, E, e, tail) : 0.f;
-    const float post = (!weight_dependent || nu1 != 0.f) ? conv_pp_batch_sum(part + (size_t)B * E, B, E, e, tail) : 0.f;
+    const float pre = (!weight_dependent || nu0 != 0.f) ? conv_pp_batch_sum<ACC>(part, B, E, e, tail) : 0.f;
+    const float post = (!weight_dependent || nu1 != 0.f) ? conv_pp_batch_sum<ACC>(part + (size_t)B * E, B, E, e, tail) : 0.f;
     if (!weight_dependent) {                            // w += nu0 * pre; w += nu1 * post
         w = w + nu0 * pre;
         w = w + nu1 * post;
@@ -865,10 +895,11 @@ __global__ __launch_bounds__(256) void k_conv_hebb_apply(float *__restrict__ W, 
     W[e] = w;
 }
 
-extern "C" int snn_conv2d_hebbian(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
-                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
-                                  int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax, float *ws,
-                                  snn_stream_t stream) {
+extern "C" int snn_conv2d_hebbian_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                      int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                      int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax, float *ws,
+                                      int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
     if (!W || !s_src || !x_src || !s_tgt || !x_tgt || !ws || B <= 0 || Cin <= 0 || H <= 0 || Wd <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 ||
         stride <= 0 || pad < 0) return SNN_ERR_INVALID;
     if (weight_dependent && !(has_min && has_max)) return SNN_ERR_INVALID;      // learning.py:600-602: finite wmin and wmax
@@ -877,9 +908,24 @@ extern "C" int snn_conv2d_hebbian(float *W, const uint8_t *s_src, const float *x
     const long E = (long)Cout * Cin * KH * KW;
     const int rc = conv_pp_partials(s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW, ws, (hipStream_t)stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_conv_hebb_apply, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ws, B, E, nu0, nu1,
-                       weight_dependent, decay, has_min, wmin, has_max, wmax);
+    const dim3 grid((unsigned)((E + 255) / 256));
+    auto apply = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, W, (const float *)ws, B, E, nu0, nu1, weight_dependent, decay, has_min, wmin,
+                           has_max, wmax);
+    };
+    if (reduce == SNN_REDUCE_MEAN) apply(k_conv_hebb_apply<BatchReduce<SNN_REDUCE_MEAN>>);
+    else if (reduce == SNN_REDUCE_AMAX) apply(k_conv_hebb_apply<BatchReduce<SNN_REDUCE_AMAX>>);
+    else if (reduce == SNN_REDUCE_AMIN) apply(k_conv_hebb_apply<BatchReduce<SNN_REDUCE_AMIN>>);
+    else apply(k_conv_hebb_apply<>);
     return snn_check_launch();
+}
+
+extern "C" int snn_conv2d_hebbian(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                                  int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1,
+                                  int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax, float *ws,
+                                  snn_stream_t stream) {
+    return snn_conv2d_hebbian_red(W, s_src, x_src, s_tgt, x_tgt, B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, weight_dependent, decay,
+                                  has_min, wmin, has_max, wmax, ws, SNN_REDUCE_SUM, stream);
 }
 
 // MSTDP on a Conv2dConnection (learning.py:1942-2015, batch 1).  State: E = eligibility [Cout, K], P = P^+ in input space
@@ -977,6 +1023,23 @@ extern "C" int snn_stdp_hebbian_pv(float *W, const uint8_t *s_src, const float *
                weight_dependent ? 3 : 2, 0.f, nullptr};
     syn_rates(a, *sp);
     return launch_plasticity_pv(a, *sp, (hipStream_t)stream);
+}
+
+extern "C" int snn_stdp_hebbian_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                    int Nin, int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin,
+                                    int has_max, float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
+    if (reduce == SNN_REDUCE_SUM)
+        return snn_stdp_hebbian_pv(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax,
+                                   sp, stream);
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
+    if (weight_dependent && !((has_min || (sp && sp->wmin)) && (has_max || (sp && sp->wmax)))) return SNN_ERR_INVALID;   // learning.py:600-602
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, 0, 1.f, decay, has_min, wmin, has_max, wmax, 0,
+               weight_dependent ? 3 : 2, 0.f, nullptr};
+    const snn_synparams q = sp ? *sp : snn_synparams{};
+    syn_rates(a, q);
+    return launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
 }
 
 // The per-synapse instance of k_mstdpet: the element's own nu0 inside ((nu0 * dt) * reward), its own bounds in the clamp.
@@ -1092,6 +1155,31 @@ extern "C" int snn_mstdp_step(float *W, float *p_plus, float *p_minus, uint8_t *
     int rc = launch_plasticity(a, (hipStream_t)stream);
     if (rc) return rc;
     // (2) trace updates + remember this step's spikes as the factors of the next eligibility.
+    const long n = (long)B * (Nin + N);
+    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
+                       s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
+                       decay_minus);
+    return snn_check_launch();
+}
+
+extern "C" int snn_mstdp_step_red(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                                  const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                                  float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                                  int has_max, float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
+    if (reduce == SNN_REDUCE_SUM)
+        return snn_mstdp_step_pv(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                                 decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, sp, stream);
+    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
+        return SNN_ERR_INVALID;
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    // (1) W += nu0 * reduce_b reward * elig_prev[b]; decay; clamp -- the samples without a previous-step spike on the element are zero terms
+    StdpArgs a{W, s_src_prev, p_plus, s_tgt_prev, p_minus, B, Nin, N, nu0, 0.f, 0, 1.f, wdecay, has_min, wmin,
+               has_max, wmax, 0, 1, reward, reward_vec};
+    const snn_synparams q = sp ? *sp : snn_synparams{};
+    int rc = launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
+    if (rc) return rc;
     const long n = (long)B * (Nin + N);
     const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,

@@ -173,17 +173,63 @@ __host__ __device__ inline float inner_sum8(const float *x, int n) {
     return inner_sum8_terms([x](int k) { return x[k]; }, n);
 }
 
+// ---- the batch reductions beside sum (snnhip.h f15: reduction = torch.mean / torch.amax / torch.amin) ------------------------------
+// BatchReduce<R> has OuterSum's interface, so the update kernels take it as their accumulator type; BatchReduce<SUM> IS OuterSum.
+// batch_sum<R> (below) is the same for the kernels that visit every sample.
+//   MEAN        ATen's sum(dim=0) in OuterSum's order, then ONE correctly rounded division by the batch size -- the same bits as
+//               torch.mean (checked on the host: tests/test_reduction_hostcheck.py); never a multiplication by a reciprocal.
+//   AMAX / AMIN the maximum / minimum of the terms.  The event-driven kernels add only the samples that have a spike on the element's
+//               source or target; every sample they skip contributes a zero term, so a reduction that saw fewer than `n` terms folds
+//               0.0f in (and one that saw none is 0).  The sign of a zero result is not defined (torch's own differs between its
+//               scalar and vector paths): callers compare -0 and +0 as equal.  A NaN term makes the result NaN, as in torch.
+constexpr int kReduceSum = 0, kReduceMean = 1, kReduceAmax = 2, kReduceAmin = 3;      // SNN_REDUCE_*
+
+template <int R> struct BatchReduce;
+template <> struct BatchReduce<kReduceSum> : OuterSum {};
+template <> struct BatchReduce<kReduceMean> {
+    OuterSum s;
+    __host__ __device__ __forceinline__ void init(bool is_tail) { s.init(is_tail); }
+    __host__ __device__ __forceinline__ void add(int pos, float term, int n) { s.add(pos, term, n); }
+    __host__ __device__ __forceinline__ float finish(int n) { return s.finish(n) / (float)n; }
+};
+template <int R> struct BatchExtreme {
+    float m;
+    int seen;
+    // (a NaN term is kept, as torch.amax / torch.amin propagate it: `b != b` takes a NaN b, and no comparison replaces a NaN a)
+    __host__ __device__ __forceinline__ static float pick(float a, float b) {
+        return R == kReduceAmax ? ((b > a || b != b) ? b : a) : ((b < a || b != b) ? b : a);
+    }
+    __host__ __device__ __forceinline__ void init(bool) { m = 0.f; seen = 0; }
+    __host__ __device__ __forceinline__ void add(int, float term, int) { m = seen ? pick(m, term) : term; ++seen; }
+    __host__ __device__ __forceinline__ float finish(int n) { return seen < n ? pick(m, 0.f) : m; }
+};
+template <> struct BatchReduce<kReduceAmax> : BatchExtreme<kReduceAmax> {};
+template <> struct BatchReduce<kReduceAmin> : BatchExtreme<kReduceAmin> {};
+
 // ATen's sum(dim=0) of a contiguous [B, E] tensor, column e, with term(b) = element (b, e) (probed on the reference's torch):
 // E == 1 is an inner reduction (inner_sum8_terms); 4 <= E < 8 takes the first 4 columns through the cascade and the rest
 // through row_sum; otherwise the columns below 32*floor(E/32) take the cascade, the rest row_sum (OuterSum).  Used by the
-// PostPre batch reductions of snn_local.hip and snn_convnd.hip.
-template <class TERM>
+// PostPre batch reductions of snn_local.hip and snn_convnd.hip, snn_half.hpp and snn_average.hpp, which visit every sample.
+// R: the batch reduction (above).  SUM, the default, is the function as it was -- `if constexpr` leaves nothing else in its
+// instantiation --; MEAN divides that sum by B once; AMAX / AMIN take the extreme of the B terms.
+template <int R = kReduceSum, class TERM>
 __host__ __device__ inline float batch_sum(TERM term, int B, long e, long E) {
-    if (E == 1) return inner_sum8_terms(term, B);
-    const bool tail = (E >= 4 && E < 8) ? e >= 4 : e >= (E / 32) * 32;
-    OuterSum acc; acc.init(tail);
-    for (int b = 0; b < B; ++b) acc.add(b, term(b), B);
-    return acc.finish(B);
+    if constexpr (R == kReduceAmax || R == kReduceAmin) {
+        BatchExtreme<R> acc;
+        acc.init(false);
+        for (int b = 0; b < B; ++b) acc.add(b, term(b), B);
+        return acc.finish(B);
+    } else {
+        if (E == 1) {
+            const float s = inner_sum8_terms(term, B);
+            if constexpr (R == kReduceMean) return s / (float)B; else return s;
+        }
+        const bool tail = (E >= 4 && E < 8) ? e >= 4 : e >= (E / 32) * 32;
+        OuterSum acc; acc.init(tail);
+        for (int b = 0; b < B; ++b) acc.add(b, term(b), B);
+        const float s = acc.finish(B);
+        if constexpr (R == kReduceMean) return s / (float)B; else return s;
+    }
 }
 
 // The column class of ATen's sum over the rows of `ncols` >= 2 contiguous columns (MulticompartmentConnection.compute's sum(dim=1),

@@ -1,4 +1,4 @@
-// snn_plasticity.inc -- the outer-product plasticity kernel of snn_ops.hip, included twice:
+// snn_plasticity.inc -- the outer-product plasticity kernel of snn_ops.hip, included three times:
 //   SNN_PLASTICITY_PV 0: k_plasticity<TJ>(StdpArgs) -- scalar learning rates and bounds; its text is what it was before the per-synapse
 //                        instance existed, line for line, so that its code does not change;
 //   SNN_PLASTICITY_PV 1: k_plasticity_pv<TJ>(StdpArgs, snn_synparams) -- every element reads its own rates and bounds through syn_at()
@@ -7,10 +7,22 @@
 //                        rows from L1 / L2 and never becomes a full-matrix stream.  a.nu0 / a.nu1 hold, for a rate given as a tensor,
 //                        1 or 0: whether any of its entries is non-zero (the reference's `nu[i].any()`); PostPre's rates multiply the
 //                        staged [B, TJ] target factors and so vary by column only.
+//   SNN_PLASTICITY_PV 2: k_plasticity_red<TJ, ACC>(StdpArgs, snn_synparams) -- the per-synapse text with the batch accumulator ACC in
+//                        OuterSum's place (BatchReduce<R> of snn_order.hpp: reduction = torch.mean / amax / amin, snnhip.h f15).  Scalar
+//                        rates and bounds reach it through syn_at()'s scalar side, so these reductions need no instance of their own of
+//                        the scalar text.  SNN_PLASTICITY_ACC is OuterSum in the two sum instances: after preprocessing their token
+//                        streams are what they were.  The assume_clamped skips stay valid: a reduction of zeros only is zero.
+#if SNN_PLASTICITY_PV == 2
+#define SNN_PLASTICITY_ACC ACC
+template <int TJ, class ACC>
+__global__ __launch_bounds__(256) void k_plasticity_red(StdpArgs a, snn_synparams q) {
+#elif SNN_PLASTICITY_PV
+#define SNN_PLASTICITY_ACC OuterSum
 template <int TJ>
-#if SNN_PLASTICITY_PV
 __global__ __launch_bounds__(256) void k_plasticity_pv(StdpArgs a, snn_synparams q) {
 #else
+#define SNN_PLASTICITY_ACC OuterSum
+template <int TJ>
 __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -83,7 +95,7 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
 #endif
         if (a.mode == 0) {
             if (a.nu0 != 0.f) {                         // pre: sum_b s_src[b,i] * (x_tgt[b,j]*nu0)
-                OuterSum acc; acc.init(tail);
+                SNN_PLASTICITY_ACC acc; acc.init(tail);
                 for (int w = 0; w < MW; ++w) {
                     uint32_t m = mS[ii * MW + w];
                     while (m) {
@@ -100,7 +112,7 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
 #endif
             }
             if (a.nu1 != 0.f) {                         // post: sum_b x_src[b,i] * (s_tgt[b,j]*nu1)
-                OuterSum acc; acc.init(tail);
+                SNN_PLASTICITY_ACC acc; acc.init(tail);
                 for (int w = 0; w < MW; ++w) {
                     uint32_t m = mT[jj * MW + w];
                     while (m) {
@@ -124,7 +136,7 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
         } else if (a.mode == 2 || a.mode == 3) {
             float u1 = 0.f, u2 = 0.f;
             {   // U1 = sum_b s_src[b,i] * x_tgt[b,j]
-                OuterSum acc; acc.init(tail);
+                SNN_PLASTICITY_ACC acc; acc.init(tail);
                 for (int w = 0; w < MW; ++w) {
                     uint32_t m = mS[ii * MW + w];
                     while (m) { const int b = w * 32 + __ffs(m) - 1; m &= m - 1; acc.add(b, (float)vS[(size_t)b * kTI + ii] * xt[(size_t)b * TJ + jj], B); }
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
                 u1 = acc.finish(B);
             }
             {   // U2 = sum_b x_src[b,i] * s_tgt[b,j]
-                OuterSum acc; acc.init(tail);
+                SNN_PLASTICITY_ACC acc; acc.init(tail);
                 for (int w = 0; w < MW; ++w) {
                     uint32_t m = mT[jj * MW + w];
                     while (m) { const int b = w * 32 + __ffs(m) - 1; m &= m - 1; acc.add(b, xs[(size_t)b * kTI + ii] * (float)vT[(size_t)b * TJ + jj], B); }
@@ -154,7 +166,7 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
             }
 #endif
         } else {                                        // MSTDP: sum_b reward * elig[b][i,j]
-            OuterSum acc; acc.init(tail);
+            SNN_PLASTICITY_ACC acc; acc.init(tail);
             for (int w = 0; w < MW; ++w) {
                 uint32_t m = mS[ii * MW + w] | mT[jj * MW + w];
                 while (m) {
@@ -183,3 +195,4 @@ __global__ __launch_bounds__(256) void k_plasticity(StdpArgs a) {
 #endif
     }
 }
+#undef SNN_PLASTICITY_ACC

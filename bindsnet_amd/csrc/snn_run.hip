@@ -232,6 +232,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
         if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && (!L[d.src].x || !L[d.dst].x)) return SNN_ERR_INVALID;
         if (d.rule == SNN_RULE_MSTDPET && (!d.e_trace || R->B != 1)) return SNN_ERR_INVALID;
         if (d.rule < SNN_RULE_NONE || d.rule > SNN_RULE_RMAX) return SNN_ERR_INVALID;
+        if (d.reduce < SNN_REDUCE_SUM || d.reduce > SNN_REDUCE_AMIN) return SNN_ERR_INVALID;      // the rule's batch reduction (snnhip.h f15)
         if (d.rule == SNN_RULE_RMAX) {         // learning.py:2858-2960: a dense matrix into an SRM0 layer, additive source traces, batch 1
             if (d.kind != SNN_CONN_DENSE) return SNN_ERR_UNSUPPORTED;
             if (L[d.dst].kind != SNN_LAYER_SRM0 || !L[d.src].x || !L[d.src].p.lif.traces_additive || !d.e_trace) return SNN_ERR_INVALID;
@@ -439,33 +440,44 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                               d.pad, d.reward, d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay,
                                               d.has_min, d.wmin, d.has_max, d.wmax, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_LOCAL)
-                    TRY(snn_local_postpre(d.w, d.local_src, ss, S.x, D.s, D.x, B, d.cin, d.local_F, d.local_conv_prod, d.local_kernel_prod,
-                                          d.local_n_src, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, st));
+                    TRY(snn_local_postpre_red(d.w, d.local_src, ss, S.x, D.s, D.x, B, d.cin, d.local_F, d.local_conv_prod, d.local_kernel_prod,
+                                              d.local_n_src, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.reduce, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONVND)
-                    TRY(snn_convnd_postpre(d.w, d.conv_pp_src, ss, S.x, D.s, D.x, B, d.cout, d.conv_pp_rows, d.cin * d.conv_kd * d.kh * d.kw,
-                                           S.n, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, (uint32_t *)d.rule_ws, st));
+                    TRY(snn_convnd_postpre_red(d.w, d.conv_pp_src, ss, S.x, D.s, D.x, B, d.cout, d.conv_pp_rows, d.cin * d.conv_kd * d.kh * d.kw,
+                                               S.n, d.nu0, d.nu1, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, (uint32_t *)d.rule_ws, d.reduce, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.kind == SNN_CONN_CONV2D)
-                    TRY(snn_conv2d_postpre(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
-                                           d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
+                    TRY(snn_conv2d_postpre_red(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
+                                               d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, d.reduce, st));
                 else if ((d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE) && d.kind == SNN_CONN_CONV2D)
-                    TRY(snn_conv2d_hebbian(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
-                                           d.rule == SNN_RULE_WDPOSTPRE, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, st));
+                    TRY(snn_conv2d_hebbian_red(d.w, ss, S.x, D.s, D.x, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, d.nu0, d.nu1,
+                                               d.rule == SNN_RULE_WDPOSTPRE, d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, d.rule_ws, d.reduce, st));
                 else if (d.avg_k != 0 && d.rule == SNN_RULE_POSTPRE)           // average_update: the ring forms (snnhip.h f14); an index moves with its term
-                    TRY(snn_postpre_avg_step(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, R->dt, d.wdecay, d.has_min, d.wmin, d.has_max,
-                                             d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_ring1, d.avg_k, d.avg_continuous,
-                                             d.nu0 != 0.f ? (d.avg_i0 + t) % d.avg_k : d.avg_i0, d.nu1 != 0.f ? (d.avg_i1 + t) % d.avg_k : d.avg_i1, st));
+                    TRY(snn_postpre_avg_step_red(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, R->dt, d.wdecay, d.has_min, d.wmin, d.has_max,
+                                                 d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_ring1, d.avg_k, d.avg_continuous,
+                                                 d.nu0 != 0.f ? (d.avg_i0 + t) % d.avg_k : d.avg_i0, d.nu1 != 0.f ? (d.avg_i1 + t) % d.avg_k : d.avg_i1,
+                                                 d.reduce, st));
                 else if (d.avg_k != 0 && d.rule == SNN_RULE_MSTDP)
-                    TRY(snn_mstdp_avg_step(d.w, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, B, S.n, D.n, d.reward, d.reward_vec,
-                                           d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay, d.has_min, d.wmin, d.has_max,
-                                           d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_k, d.avg_continuous, (d.avg_i0 + t) % d.avg_k, st));
+                    TRY(snn_mstdp_avg_step_red(d.w, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, B, S.n, D.n, d.reward, d.reward_vec,
+                                               d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay, d.has_min, d.wmin, d.has_max,
+                                               d.wmax, d.avg_squeeze, d.avg_ring0, d.avg_k, d.avg_continuous, (d.avg_i0 + t) % d.avg_k, d.reduce, st));
                 else if (d.avg_k != 0)
                     TRY(snn_mstdpet_avg_step(d.w, d.e_trace, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, S.n, D.n, d.reward,
                                              d.nu0, R->dt, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.decay_e, d.tc_e, d.wdecay,
                                              d.has_min, d.wmin, d.has_max, d.wmax, d.avg_ring0, d.avg_k, d.avg_continuous,
                                              (d.avg_i0 + t) % d.avg_k, st));
                 else if (d.rule == SNN_RULE_POSTPRE && d.w_dtype != SNN_W_F32)
-                    TRY(snn_stdp_postpre_h16(d.w, d.w_dtype, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
-                                             d.has_min, d.wmin, d.has_max, d.wmax, st));
+                    TRY(snn_stdp_postpre_h16_red(d.w, d.w_dtype, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
+                                                 d.has_min, d.wmin, d.has_max, d.wmax, d.reduce, st));
+                else if (d.reduce != SNN_REDUCE_SUM && d.rule == SNN_RULE_POSTPRE)      // another batch reduction: the *_red instances (snnhip.h f15), per-synapse or not
+                    TRY(snn_stdp_postpre_red(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
+                                             d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, &d.syn, d.reduce, st));
+                else if (d.reduce != SNN_REDUCE_SUM && (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE))
+                    TRY(snn_stdp_hebbian_red(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
+                                             d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, d.reduce, st));
+                else if (d.reduce != SNN_REDUCE_SUM && d.rule == SNN_RULE_MSTDP)
+                    TRY(snn_mstdp_step_red(d.w, d.p_plus, d.p_minus, d.s_src_prev, d.s_tgt_prev, ss, D.s, B, S.n, D.n,
+                                           d.reward, d.reward_vec, d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus,
+                                           d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, d.reduce, st));
                 else if (snn::syn_any(&d.syn) && d.rule == SNN_RULE_POSTPRE)     // per-synapse constants: the *_pv instances (snnhip.h f13)
                     TRY(snn_stdp_postpre_pv(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
                                             d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, &d.syn, st));
@@ -578,6 +590,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].w_dtype != SNN_W_F32) local = true;   // ... and float16 / bfloat16 weights (the fused plans keep f32 tiles)
     for (int c = 0; c < nC; ++c) if (snn::syn_any(&C[c].syn) || C[c].norm_vec) local = true;   // ... and per-synapse rates / bounds, per-target norms
     for (int c = 0; c < nC; ++c) if (C[c].avg_k != 0) local = true;             // ... and averaged updates (the fused plans keep no ring)
+    for (int c = 0; c < nC; ++c) if (C[c].reduce != SNN_REDUCE_SUM) local = true;   // ... and a batch reduction other than sum (the fused plans sum)
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));

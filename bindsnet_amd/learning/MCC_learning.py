@@ -146,6 +146,7 @@ class MCC_LearningRule(_lib.Touching):
         if self.reduction is torch.squeeze and B != 1:
             raise RuntimeError("reduction=torch.squeeze requires batch size 1")
         _descriptor.fill_update(d, self, self.decay, dev, keep)
+        d.reduce = _lib.REDUCE[_descriptor.reduce_of(self, B)]       # (checked here too: `reduction` may have been assigned since the constructor)
 
     def update(self, **kwargs) -> None:
         raise NotImplementedError
@@ -182,8 +183,7 @@ class PostPre(MCC_LearningRule):
         from ..network.topology import MulticompartmentConnection
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
-        if self.reduction not in (torch.sum, torch.squeeze):
-            raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
+        _descriptor.check_reduction(self)
         self._init_average(kwargs)
 
     _RINGS = (("average_buffer_pre", "average_buffer_index_pre", 0), ("average_buffer_post", "average_buffer_index_post", 1))
@@ -208,14 +208,14 @@ class PostPre(MCC_LearningRule):
                                  self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), float(self.nu[0]), float(self.nu[1]),
                                  float(self.connection.dt), self.average_buffer_pre, self.average_buffer_post, i_pre, i_post,
                                  bool(self.continues_update), squeeze=self.reduction is torch.squeeze, decay=float(self.decay),
-                                 wmin=lo, wmax=hi)
+                                 wmin=lo, wmax=hi, reduce=_descriptor.reduce_of(self, B))
             self._avg_advance()
             return
         lo, hi = self._bounds(tensors=True)
         ops.stdp_postpre(self.feature_value.data, self.source.s.reshape(B, -1).contiguous(),
                          self.source.x.reshape(B, -1), self.target.s.reshape(B, -1), self.target.x.reshape(B, -1),
                          float(self.nu[0]), float(self.nu[1]), use_dt=True, dt=float(self.connection.dt),
-                         decay=float(self.decay), wmin=lo, wmax=hi)
+                         decay=float(self.decay), wmin=lo, wmax=hi, reduce=_descriptor.reduce_of(self, B))
 
 
 class MSTDP(MCC_LearningRule):
@@ -232,8 +232,7 @@ class MSTDP(MCC_LearningRule):
         if not isinstance(connection, MulticompartmentConnection):
             raise NotImplementedError("This learning rule is not supported for this Connection type.")
         self._float32_only()
-        if self.reduction not in (torch.sum, torch.squeeze):
-            raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
+        _descriptor.check_reduction(self)
         self.tc_plus = torch.tensor(kwargs.get("tc_plus", 20.0))
         self.tc_minus = torch.tensor(kwargs.get("tc_minus", 20.0))
         self._init_average(kwargs)
@@ -272,14 +271,14 @@ class MSTDP(MCC_LearningRule):
                                self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward, float(self.nu[0]),
                                float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm, self.average_buffer,
                                self._avg_indices()[0], bool(self.continues_update), squeeze=self.reduction is torch.squeeze,
-                               wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec)
+                               wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec, reduce=_descriptor.reduce_of(self, B))
             self._avg_advance()
             return
         lo, hi = self._bounds(tensors=True)
         ops.mstdp_step(self.feature_value.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
                        self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
                        float(self.nu[0]), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
-                       wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec)
+                       wdecay=float(self.decay), wmin=lo, wmax=hi, reward_vec=rvec, reduce=_descriptor.reduce_of(self, B))
 
     @property
     def eligibility(self) -> torch.Tensor:

@@ -89,6 +89,30 @@ def _bound(v):
     return None if v is None or v in (float("inf"), float("-inf")) else v
 
 
+# The batch reductions a rule takes (learning.py:76-82, MCC_learning.py:75-81), with the name each goes by on the device (SNN_REDUCE_*,
+# _lib.REDUCE); torch.squeeze is the sum path at batch size 1.
+REDUCTIONS = ((torch.sum, "sum"), (torch.squeeze, "sum"), (torch.mean, "mean"), (torch.amax, "amax"), (torch.amin, "amin"))
+
+
+def reduction_name(f) -> str:
+    name = getattr(f, "__name__", None)
+    return repr(f) if name is None else (f"torch.{name}" if getattr(torch, name, None) is f else name)
+
+
+def check_reduction(rule) -> None:
+    """Any callable but the five is refused by name."""
+    if not any(rule.reduction is f for f, _ in REDUCTIONS):
+        raise NotImplementedError(f"bindsnet_amd: reduction={reduction_name(rule.reduction)} is not supported: torch.sum, torch.squeeze "
+                                  "(batch size 1), torch.mean, torch.amax and torch.amin are")
+
+
+def reduce_of(rule, B: int) -> str:
+    """The rule's batch reduction as the ops take it: "sum", "mean", "amax" or "amin".  At batch size 1 all five are the identity
+    (x / 1.0f == x) and share the sum path, as torch.squeeze does."""
+    check_reduction(rule)
+    return "sum" if B == 1 else next(name for f, name in REDUCTIONS if rule.reduction is f)
+
+
 def fill_update(d, rule, wdecay, dev=None, keep=None) -> None:
     """Clamp bounds, weight-decay factor (dense rules keep it in `weight_decay`, MCC rules in `decay`) and learning rates.  A rule
     that takes per-synapse constants (`_takes_syn`) hands tensors on: they go into d.syn, on `dev`."""

@@ -96,8 +96,12 @@ class LearningRule(_lib.Touching):
             if B != 1:
                 raise RuntimeError("reduction=torch.squeeze with batch size > 1: pass reduction=torch.sum "
                                    "(the reference fails with a broadcast error here)")
-        elif self.reduction is not torch.sum:
-            raise NotImplementedError("bindsnet_amd: only reduction=torch.sum (or squeeze at batch 1) is supported")
+        else:
+            _descriptor.check_reduction(self)
+
+    def _reduce(self) -> str:
+        """The batch reduction as the ops take it ("sum", "mean", "amax", "amin")."""
+        return _descriptor.reduce_of(self, self.source.batch_size)
 
     def _require_accepted(self) -> None:
         if not _descriptor.accepts(self.connection, self):
@@ -114,6 +118,8 @@ class LearningRule(_lib.Touching):
             raise err
         _descriptor.fill_update(d, self, self.weight_decay, dev, keep)
         d.rule = self._rule_code
+        # (anything but sum: the generic plan, the *_red entry points; a rule that reduces nothing keeps every plan)
+        d.reduce = _lib.REDUCE["sum" if self._rule_code == _lib.RULE_NONE else _descriptor.reduce_of(self, B)]
 
     def update(self, **kwargs) -> None:
         raise NotImplementedError
@@ -213,6 +219,7 @@ class MSTDP(LearningRule):
         if not self._conv:
             return _descriptor.fill_mstdp(d, self, kwargs, dev, keep)
         d.reward = self._conv_reward(B, kwargs)                                    # learning.py:1942-2015, batch 1
+        d.reduce = _lib.REDUCE["sum"]                                              # (:2013 hard-codes torch.sum: `reduction` is ignored)
         d.a_plus, d.a_minus = _descriptor.a_plus_minus(kwargs)
         self._ensure_state()
         d.decay_plus, d.decay_minus = self._decays()
@@ -242,7 +249,7 @@ class MSTDP(LearningRule):
         ops.mstdp_step(self.connection.w.data, self.p_plus, self.p_minus, self._s_src_prev, self._s_tgt_prev,
                        self.source.s.reshape(B, -1).contiguous(), self.target.s.reshape(B, -1), reward,
                        self._nu(0), float(kwargs.get("a_plus", 1.0)), float(kwargs.get("a_minus", -1.0)), dp, dm,
-                       wdecay=float(self.weight_decay), wmin=lo, wmax=hi, reward_vec=rvec)
+                       wdecay=float(self.weight_decay), wmin=lo, wmax=hi, reward_vec=rvec, reduce=self._reduce())
 
     @property
     def eligibility(self) -> torch.Tensor:
@@ -274,7 +281,7 @@ class _OuterProductRule(LearningRule):
         lo, hi = self._bounds(tensors=True)
         ops.stdp_hebbian(self.connection.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
                          self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), self._nu(0), self._nu(1),
-                         weight_dependent=self._weight_dependent, decay=float(self.weight_decay), wmin=lo, wmax=hi)
+                         weight_dependent=self._weight_dependent, decay=float(self.weight_decay), wmin=lo, wmax=hi, reduce=self._reduce())
 
 
 class Hebbian(_OuterProductRule):

@@ -421,9 +421,16 @@ def _update_convnd(conn, rule) -> None:
 
 
 def _reduce(rule, t):
+    """`rule.reduction(t, dim=0)` of the per-sample terms [B, ...].  The sums in the serial order this package pins (_sum); mean is that
+    sum followed by one true division by B -- the bits of torch.mean on one thread, whose own order follows the caller's thread count;
+    amax / amin are exact in any order (the sign of a zero result aside, which torch itself leaves to the path it takes)."""
     if rule.reduction is torch.squeeze:
         return t.squeeze(0)
-    return _sum(t, 0) if rule.reduction is torch.sum else rule.reduction(t, dim=0)
+    if rule.reduction is torch.sum:
+        return _sum(t, 0)
+    if rule.reduction is torch.mean:
+        return _sum(t, 0) / t.shape[0]
+    return rule.reduction(t, dim=0)
 
 
 def _ring_mean(ring):
@@ -568,6 +575,9 @@ def _update_mcc(conn, dt, kwargs) -> None:
         return
     B = conn.source.batch_size
     W = feat.value.data
+    if not isinstance(rule, rules.MSTDPET):          # (MSTDPET never calls its reduction: MCC_learning.py:652-729)
+        from ..learning import _descriptor
+        _descriptor.check_reduction(rule)            # (`reduction` may have been assigned since the constructor checked it)
     if rule.reduction is torch.squeeze and B != 1 and not isinstance(rule, rules.MSTDPET):
         raise RuntimeError("reduction=torch.squeeze requires batch size 1")      # (the reference fails with a broadcast error here)
     if isinstance(rule, rules.PostPre):

@@ -227,7 +227,7 @@ class _DenseConnection(AbstractConnection):
         """learning.py:390-420."""
         ops.stdp_postpre(self.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
                          self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), rule._nu(0), rule._nu(1),
-                         use_dt=False, decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+                         use_dt=False, decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
 
 class Connection(_DenseConnection):
@@ -869,7 +869,7 @@ class Conv2dConnection(AbstractConnection):
         src, tgt = self.source, self.target
         ops.conv2d_postpre(self.w.data, src.s.reshape(B, *src.shape).contiguous(), src.x.reshape(B, *src.shape),
                            tgt.s.reshape(B, *tgt.shape), tgt.x.reshape(B, *tgt.shape), float(rule.nu[0]), float(rule.nu[1]),
-                           stride=self.stride[0], pad=self.padding[0], decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+                           stride=self.stride[0], pad=self.padding[0], decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
     def _outer_product(self, rule, B, lo, hi) -> None:
         """learning.py:1348-1380 (Hebbian) / :920-976 (WeightDependentPostPre)."""
@@ -877,7 +877,7 @@ class Conv2dConnection(AbstractConnection):
         ops.conv2d_hebbian(self.w.data, src.s.reshape(B, *src.shape).contiguous(), src.x.reshape(B, *src.shape),
                            tgt.s.reshape(B, *tgt.shape), tgt.x.reshape(B, *tgt.shape), float(rule.nu[0]), float(rule.nu[1]),
                            weight_dependent=rule._weight_dependent, stride=self.stride[0], pad=self.padding[0],
-                           decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+                           decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
 
 class _ConvNdConnection(AbstractConnection):
@@ -963,7 +963,7 @@ class _ConvNdConnection(AbstractConnection):
         src, tgt = self.source, self.target
         ops.convnd_postpre(self.w.data, self.pp_src, src.s.reshape(B, -1).contiguous(), src.x.reshape(B, -1),
                            tgt.s.reshape(B, -1).contiguous(), tgt.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
-                           decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+                           decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
 
 class Conv1dConnection(_ConvNdConnection):
@@ -1115,7 +1115,7 @@ class _LocalConnectionND(AbstractConnection):
         src, tgt = self.source, self.target
         ops.local_postpre(self.w.data, self.src, src.s.reshape(B, -1).contiguous(), src.x.reshape(B, -1),
                           tgt.s.reshape(B, -1).contiguous(), tgt.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
-                          self.n_filters, decay=float(rule.weight_decay), wmin=lo, wmax=hi)
+                          self.n_filters, decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
     def reset_state_variables(self) -> None:
         super().reset_state_variables()

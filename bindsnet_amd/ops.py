@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import DcParams, LifParams, check, lib
+from ._lib import REDUCE, DcParams, LifParams, check, lib
 
 
 def _stream():
@@ -41,6 +41,13 @@ HALF = {torch.float16: _lib.W_F16, torch.bfloat16: _lib.W_BF16}
 def _bounds(wmin, wmax):
     """The clamp arguments of the C ABI (has_min, wmin, has_max, wmax) from optional bounds."""
     return int(wmin is not None), 0.0 if wmin is None else wmin, int(wmax is not None), 0.0 if wmax is None else wmax
+
+
+def _reduce(reduce) -> int:
+    """SNN_REDUCE_* of an update's `reduce` argument: "sum", "mean", "amax" or "amin" (include/snnhip.h f15)."""
+    if reduce not in REDUCE:
+        raise ValueError(f"reduce={reduce!r}: one of {', '.join(REDUCE)}")
+    return REDUCE[reduce]
 
 
 def _syn(W, nu0, nu1, wmin, wmax):
@@ -157,7 +164,7 @@ def prop_local(W, src, s, out, n_filters, accumulate=False):
     return out
 
 
-def local_postpre(W, src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, n_filters, decay=1.0, wmin=None, wmax=None):
+def local_postpre(W, src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, n_filters, decay=1.0, wmin=None, wmax=None, reduce="sum"):
     """f5: PostPre on LocalConnection1D/2D/3D weights (learning.py:208-389); s_src / x_src [B, n_src], s_tgt / x_tgt
     [B, F*conv_prod]."""
     B = s_src.shape[0]
@@ -166,6 +173,11 @@ def local_postpre(W, src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, n_filters, decay
     if tuple(W.shape) != (Cin, n_filters * conv_prod, kernel_prod) or x_src.numel() != B * n_src \
             or s_tgt.numel() != B * n_filters * conv_prod or x_tgt.numel() != s_tgt.numel():
         raise ValueError("local_postpre: operand shapes do not match the gather table")
+    if _reduce(reduce):
+        check(lib().snn_local_postpre_red(_ptr(W, F32), _ptr(src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
+                                          _ptr(x_tgt, F32), B, Cin, n_filters, conv_prod, kernel_prod, n_src, float(nu0), float(nu1),
+                                          float(decay), *_bounds(wmin, wmax), _reduce(reduce), _stream()), "local_postpre_red")
+        return
     check(lib().snn_local_postpre(_ptr(W, F32), _ptr(src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                   _ptr(x_tgt, F32), B, Cin, n_filters, conv_prod, kernel_prod, n_src, float(nu0), float(nu1),
                                   float(decay), *_bounds(wmin, wmax), _stream()), "local_postpre")
@@ -195,7 +207,7 @@ def prop_convnd(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
     return out
 
 
-def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, wmin=None, wmax=None, ws=None):
+def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, wmin=None, wmax=None, ws=None, reduce="sum"):
     """f6: PostPre on Conv1dConnection / Conv3dConnection weights [Cout, Cin, *kernel] (learning.py:422-455 / :499-559);
     pp_src int32 [L, Cin*K] (the connection's gather table), s_src / x_src [B, n_src], s_tgt / x_tgt [B, Cout*L]."""
     B = s_src.shape[0]
@@ -206,6 +218,11 @@ def convnd_postpre(W, pp_src, s_src, x_src, s_tgt, x_tgt, nu0, nu1, decay=1.0, w
         raise ValueError("convnd_postpre: operand shapes do not match the gather table")
     if ws is None:
         ws = torch.empty(B * Cout * ((L + 31) // 32), dtype=torch.int32, device=W.device)
+    if _reduce(reduce):
+        check(lib().snn_convnd_postpre_red(_ptr(W, F32), _ptr(pp_src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32),
+                                           _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Cout, L, J, n_src, float(nu0), float(nu1), float(decay),
+                                           *_bounds(wmin, wmax), _ptr(ws, torch.int32), _reduce(reduce), _stream()), "convnd_postpre_red")
+        return
     check(lib().snn_convnd_postpre(_ptr(W, F32), _ptr(pp_src, torch.int32), _ptr(s_src, "spike"), _ptr(x_src, F32),
                                    _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Cout, L, J, n_src, float(nu0), float(nu1), float(decay),
                                    *_bounds(wmin, wmax), _ptr(ws, torch.int32), _stream()), "convnd_postpre")
@@ -519,15 +536,27 @@ def dc_arbitrate(s, x, p: DcParams, noise_q, cursor, status, raster_s=None):
 
 
 def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=1.0, wmin=None, wmax=None,
-                 assume_clamped=False):
+                 assume_clamped=False, reduce="sum"):
+    """a8 / a9: PostPre on a dense or MCC weight matrix.  reduce: the batch reduction, "sum" (the entry points as they were), "mean",
+    "amax" or "amin" (the *_red entry points, include/snnhip.h f15)."""
     B = s_src.shape[0]
     Nin, N = W.shape
+    if W.dtype in HALF and _reduce(reduce):
+        check(lib().snn_stdp_postpre_h16_red(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
+                                             _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax),
+                                             _reduce(reduce), _stream()), "stdp_postpre_h16_red")
+        return
     if W.dtype in HALF:                 # (every element is visited: assume_clamped has nothing to skip)
         check(lib().snn_stdp_postpre_h16(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                          _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax), _stream()),
               "stdp_postpre_h16")
         return
     nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
+    if _reduce(reduce):                 # another batch reduction, per-synapse constants or not
+        check(lib().snn_stdp_postpre_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                         B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped),
+                                         None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "stdp_postpre_red")
+        return
     if sp is not None:                  # per-synapse rates / bounds (include/snnhip.h f13)
         check(lib().snn_stdp_postpre_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
                                         B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped), C.byref(sp),
@@ -539,10 +568,16 @@ def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=
 
 
 def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus,
-               decay_plus, decay_minus, wdecay=1.0, wmin=None, wmax=None, reward_vec=None):
+               decay_plus, decay_minus, wdecay=1.0, wmin=None, wmax=None, reward_vec=None, reduce="sum"):
     B = s_src.shape[0]
     Nin, N = W.shape
     nu0, _, bounds, sp, _keep = _syn(W, nu0, 0.0, wmin, wmax)
+    if _reduce(reduce):
+        check(lib().snn_mstdp_step_red(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                       _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
+                                       reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
+                                       wdecay, *bounds, None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "mstdp_step_red")
+        return
     if sp is not None:
         check(lib().snn_mstdp_step_pv(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
                                       _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
@@ -555,24 +590,34 @@ def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward,
                                wdecay, *bounds, _stream()), "mstdp_step")
 
 
-def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, decay=1.0, wmin=None, wmax=None, ws=None):
+def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, decay=1.0, wmin=None, wmax=None, ws=None, reduce="sum"):
     """f4: PostPre on Conv2dConnection weights [Cout,Cin,KH,KW]; s_src / x_src [B,Cin,H,W], s_tgt / x_tgt [B,Cout,OH,OW]."""
     B, Cin, H, Wd = s_src.shape
     Cout, _, KH, KW = W.shape
     if ws is None:
         ws = torch.empty(2 * B * W.numel(), dtype=F32, device=W.device)
+    if _reduce(reduce):
+        check(lib().snn_conv2d_postpre_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                           B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, decay, *_bounds(wmin, wmax),
+                                           _ptr(ws, F32), _reduce(reduce), _stream()), "conv2d_postpre_red")
+        return
     check(lib().snn_conv2d_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
                                    B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, decay, *_bounds(wmin, wmax),
                                    _ptr(ws, F32), _stream()), "conv2d_postpre")
 
 
 def conv2d_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False, stride=1, pad=0, decay=1.0, wmin=None, wmax=None,
-                   ws=None):
+                   ws=None, reduce="sum"):
     """f4: Hebbian (weight_dependent=False) / WeightDependentPostPre (True) on Conv2dConnection weights; shapes as conv2d_postpre."""
     B, Cin, H, Wd = s_src.shape
     Cout, _, KH, KW = W.shape
     if ws is None:
         ws = torch.empty(2 * B * W.numel(), dtype=F32, device=W.device)
+    if _reduce(reduce):
+        check(lib().snn_conv2d_hebbian_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                           B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, int(weight_dependent), decay,
+                                           *_bounds(wmin, wmax), _ptr(ws, F32), _reduce(reduce), _stream()), "conv2d_hebbian_red")
+        return
     check(lib().snn_conv2d_hebbian(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
                                    B, Cin, H, Wd, Cout, KH, KW, stride, pad, nu0, nu1, int(weight_dependent), decay,
                                    *_bounds(wmin, wmax), _ptr(ws, F32), _stream()), "conv2d_hebbian")
@@ -589,11 +634,16 @@ def conv2d_mstdp_step(W, elig, p_plus, p_minus, s_src, s_tgt, reward, nu0, a_plu
                                       decay_plus, decay_minus, wdecay, *_bounds(wmin, wmax), _stream()), "conv2d_mstdp_step")
 
 
-def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False, decay=1.0, wmin=None, wmax=None):
+def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False, decay=1.0, wmin=None, wmax=None, reduce="sum"):
     """f3: Hebbian (weight_dependent=False) / WeightDependentPostPre (True) on a dense weight matrix."""
     B = s_src.shape[0]
     Nin, N = W.shape
     nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
+    if _reduce(reduce):
+        check(lib().snn_stdp_hebbian_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                         B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, None if sp is None else C.byref(sp),
+                                         _reduce(reduce), _stream()), "stdp_hebbian_red")
+        return
     if sp is not None:
         check(lib().snn_stdp_hebbian_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
                                         B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, C.byref(sp), _stream()),
@@ -628,19 +678,32 @@ def _ring(ring, W, K):
 
 
 def postpre_avg_step(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, dt, ring_pre, ring_post, idx_pre, idx_post, continuous, squeeze=False,
-                     decay=1.0, wmin=None, wmax=None):
+                     decay=1.0, wmin=None, wmax=None, reduce="sum"):
     """include/snnhip.h f14: one step of MCC PostPre with average_update = ring_pre.shape[0].  idx_*: the ring indices at the start of
     the step; the caller advances the index of every term whose rate is non-zero."""
     B, (Nin, N), K = s_src.shape[0], W.shape, ring_pre.shape[0]
+    if _reduce(reduce):             # the reduced update goes into the ring slot; the ring's own mean is unchanged
+        check(lib().snn_postpre_avg_step_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Nin,
+                                             N, nu0, nu1, dt, decay, *_bounds(wmin, wmax), int(squeeze), _ring(ring_pre, W, K),
+                                             _ring(ring_post, W, K), K, int(continuous), idx_pre, idx_post, _reduce(reduce), _stream()),
+              "postpre_avg_step_red")
+        return
     check(lib().snn_postpre_avg_step(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32), B, Nin, N,
                                      nu0, nu1, dt, decay, *_bounds(wmin, wmax), int(squeeze), _ring(ring_pre, W, K), _ring(ring_post, W, K),
                                      K, int(continuous), idx_pre, idx_post, _stream()), "postpre_avg_step")
 
 
 def mstdp_avg_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus, decay_plus, decay_minus,
-                   ring, idx, continuous, squeeze=False, wdecay=1.0, wmin=None, wmax=None, reward_vec=None):
+                   ring, idx, continuous, squeeze=False, wdecay=1.0, wmin=None, wmax=None, reward_vec=None, reduce="sum"):
     """include/snnhip.h f14: one step of MCC MSTDP with average_update = ring.shape[0]."""
     B, (Nin, N), K = s_src.shape[0], W.shape, ring.shape[0]
+    if _reduce(reduce):
+        check(lib().snn_mstdp_avg_step_red(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                           _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N, reward,
+                                           _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus, wdecay,
+                                           *_bounds(wmin, wmax), int(squeeze), _ring(ring, W, K), K, int(continuous), idx, _reduce(reduce),
+                                           _stream()), "mstdp_avg_step_red")
+        return
     check(lib().snn_mstdp_avg_step(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"), _ptr(s_tgt_prev, "spike"),
                                    _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N, reward, _ptr(reward_vec, F32, True), nu0, a_plus,
                                    a_minus, decay_plus, decay_minus, wdecay, *_bounds(wmin, wmax), int(squeeze), _ring(ring, W, K), K,

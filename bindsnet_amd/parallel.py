@@ -80,6 +80,14 @@ def _reject_local(network, mode: str) -> None:
             # an averaging ring is one history of the GLOBAL batch's updates: a shard's own ring, or a slice of one, is another rule
             raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a rule with average_update, whose ring of past updates "
                                       "the multi-device modes neither merge nor slice; run the network on one device")
+        rule = conn._rule() if hasattr(conn, "_rule") else None
+        reduction = None if rule is None or type(rule).__name__ == "NoOp" else getattr(rule, "reduction", None)
+        if reduction is not None and reduction is not torch.sum and reduction is not torch.squeeze:
+            # the modes merge per-shard SUMS of updates (or slice the global batch's): a mean, maximum or minimum over a shard's samples
+            # is not a part of the global batch's
+            from .learning._descriptor import reduction_name
+            raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} has a rule with reduction={reduction_name(reduction)}; the "
+                                      "multi-device modes reduce with torch.sum (or torch.squeeze) only; run the network on one device")
         if not conn._multi_device:
             if hasattr(conn, "pipeline"):
                 raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "

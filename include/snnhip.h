@@ -625,6 +625,61 @@ int snn_mstdpet_avg_step(float *W, float *e_trace, float *p_plus, float *p_minus
                          float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e, float wdecay, int has_min,
                          float wmin, int has_max, float wmax, float *ring, int K, int continuous, int idx, snn_stream_t stream);
 
+/* ---- f15: batch reductions beside sum (reduction = torch.mean / torch.amax / torch.amin) -----------------------------
+ * Every learning rule of the reference folds the per-sample terms T[b, e] of a batch with `self.reduction(T, dim=0)`
+ * (learning.py:76-82, MCC_learning.py:75-81).  The *_red entry points compute what their namesakes compute with that fold chosen by
+ * `reduce`; the reduction sits where the reference has it, BEFORE nu / dt / the weight-dependent factors wherever the namesake applies
+ * those to the sum, and with the rate inside the terms where the namesake has it there (PostPre on dense and MCC connections).
+ *   SNN_REDUCE_SUM   the namesake itself (the call is forwarded).
+ *   SNN_REDUCE_MEAN  ATen's sum(dim=0) in the namesake's order, then ONE correctly rounded f32 division by B -- the bits of torch.mean
+ *                    on one thread; never a multiplication by 1/B.
+ *   SNN_REDUCE_AMAX  the maximum over all B terms.  The event-driven kernels visit only the samples with a spike on the element's
+ *   SNN_REDUCE_AMIN  source or target; every other sample is a zero term, so 0.0f is folded in whenever fewer than B were visited.
+ *                    The SIGN of a zero result is not defined (torch.amax of a column holding +0 and -0 differs between its scalar
+ *                    and vector paths); it never reaches a value: w + (+-0), clamp and normalize give the same weights.
+ *                    A NaN term makes the result NaN, as torch.amax / torch.amin propagate it.
+ * A `reduce` outside the enum is SNN_ERR_INVALID.  `sp` as in the *_pv entry points (NULL: scalar rates and bounds); the dense
+ * family runs these reductions through the per-synapse kernel's tiles with the accumulator exchanged, scalars included.  `squeeze`
+ * (batch 1) keeps its meaning where it exists; at B == 1 every reduction is the identity.  MSTDPET and MSTDP on a Conv2dConnection
+ * hard-code torch.sum in the reference (batch 1) and have no *_red form; Rmax has no reduction.
+ * Added without changing SNN_ABI_VERSION: purely additive.                                                          */
+enum { SNN_REDUCE_SUM = 0, SNN_REDUCE_MEAN = 1, SNN_REDUCE_AMAX = 2, SNN_REDUCE_AMIN = 3 };
+int snn_stdp_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin,
+                         int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin, int has_max,
+                         float wmax, int assume_clamped, const snn_synparams *sp, int reduce, snn_stream_t stream);
+int snn_stdp_hebbian_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin,
+                         int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin, int has_max,
+                         float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream);
+int snn_mstdp_step_red(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                       const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0, float a_plus,
+                       float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin, int has_max,
+                       float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream);
+int snn_conv2d_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Cin,
+                           int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1, float decay,
+                           int has_min, float wmin, int has_max, float wmax, float *ws, int reduce, snn_stream_t stream);
+int snn_conv2d_hebbian_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Cin,
+                           int H, int Wd, int Cout, int KH, int KW, int stride, int pad, float nu0, float nu1, int weight_dependent,
+                           float decay, int has_min, float wmin, int has_max, float wmax, float *ws, int reduce, snn_stream_t stream);
+int snn_local_postpre_red(float *W, const int *src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                          int B, int Cin, int F, int conv_prod, int kernel_prod, int n_src, float nu0, float nu1, float decay,
+                          int has_min, float wmin, int has_max, float wmax, int reduce, snn_stream_t stream);
+int snn_convnd_postpre_red(float *W, const int *pp_src, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
+                           const float *x_tgt, int B, int Cout, int L, int J, int n_src, float nu0, float nu1, float decay,
+                           int has_min, float wmin, int has_max, float wmax, uint32_t *ws, int reduce, snn_stream_t stream);
+int snn_stdp_postpre_h16_red(void *W, int w_dtype, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
+                             int B, int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
+                             int has_max, float wmax, int reduce, snn_stream_t stream);
+/* The reduced update is what goes into the ring slot (MCC_learning.py:238, :275, :519); the ring's own mean is unchanged. */
+int snn_postpre_avg_step_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                             int Nin, int N, float nu0, float nu1, float dt, float decay, int has_min, float wmin, int has_max,
+                             float wmax, int squeeze, float *ring_pre, float *ring_post, int K, int continuous, int idx_pre,
+                             int idx_post, int reduce, snn_stream_t stream);
+int snn_mstdp_avg_step_red(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                           const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                           float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                           int has_max, float wmax, int squeeze, float *ring, int K, int continuous, int idx, int reduce,
+                           snn_stream_t stream);
+
 /* ---- f2: spike encoders on the device ---------------------------------------------------------
  * bindsnet/encoding/encodings.py:51-98 (bernoulli): out [steps, n] u8 = what torch.bernoulli(max_prob *
  * datum.repeat([steps, 1])) draws from the HOST generator whose state is in *rng -- one 32-bit mt19937 output
@@ -838,6 +893,11 @@ typedef struct {
      * [0, avg_k) is SNN_ERR_INVALID.  avg_k != 0 sends the graph to the generic plan.  Added like the fields above. */
     float *avg_ring0, *avg_ring1;
     int avg_k, avg_continuous, avg_squeeze, avg_i0, avg_i1;
+    /* The rule's batch reduction (f15 above), SNN_REDUCE_*; 0 = SUM keeps every plan and kernel the connection had.  Another value
+     * sends the graph to the generic plan, whose update calls take it through the *_red entry points (rules POSTPRE, HEBBIAN,
+     * WDPOSTPRE and MSTDP; MSTDPET, RMAX, MSTDP on a CONV2D connection and NONE ignore it).  Outside the enum: SNN_ERR_INVALID.
+     * Added like the fields above: SNN_ABI_VERSION stays. */
+    int reduce;
 } snn_conn_desc;
 
 typedef struct {
