@@ -139,11 +139,17 @@ class ConnDesc(C.Structure):
                 ("gat_out", C.c_int * 3), ("gat_src", C.c_int * 3), ("gat_stride", C.c_int * 3), ("gat_off", C.c_int * 3),
                 ("w_dtype", C.c_int), ("syn", SynParams), ("norm_vec", C.c_void_p),
                 ("avg_ring0", C.c_void_p), ("avg_ring1", C.c_void_p), ("avg_k", C.c_int), ("avg_continuous", C.c_int),
-                ("avg_squeeze", C.c_int), ("avg_i0", C.c_int), ("avg_i1", C.c_int), ("reduce", C.c_int)]
+                ("avg_squeeze", C.c_int), ("avg_i0", C.c_int), ("avg_i1", C.c_int), ("reduce", C.c_int),
+                ("activity", C.c_void_p)]
 
 
 class MccOp(C.Structure):
     _fields_ = [("kind", C.c_int), ("scalar", C.c_int), ("val", C.c_void_p), ("bits", C.c_void_p)]
+
+
+class RecordSegment(C.Structure):
+    """snn_record_segment: timestep t copies `bytes` bytes from `src` to `dst + t * bytes` (snn_record_segments)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bytes", C.c_ulonglong)]
 
 
 class RunDesc(C.Structure):
@@ -151,7 +157,8 @@ class RunDesc(C.Structure):
                 ("noise_q", C.c_void_p), ("q_len", C.c_longlong), ("rng", C.c_void_p), ("qbuf", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_ulonglong),
                 ("cursor", C.c_void_p), ("status", C.c_void_p), ("one_step", C.c_int), ("plan", C.c_int),
-                ("status2", C.c_void_p), ("host_state", C.c_void_p)]
+                ("status2", C.c_void_p), ("host_state", C.c_void_p),
+                ("records", C.POINTER(RecordSegment)), ("n_records", C.c_int)]
 
 
 class FillSegment(C.Structure):
@@ -159,6 +166,7 @@ class FillSegment(C.Structure):
 
 
 MAX_FILL_SEGMENTS = 32
+MAX_RECORD_SEGMENTS = 32  # SNN_MAX_RECORD_SEGMENTS: segments per launch of snn_record_segments (more take further launches)
 LAYER_INPUT, LAYER_LIF, LAYER_DC = 0, 1, 2
 LAYER_MCP, LAYER_IF, LAYER_BOOSTED, LAYER_CURRENT, LAYER_IZH, LAYER_SRM0 = 3, 4, 5, 6, 7, 8
 LAYER_CSRM = 9
@@ -261,6 +269,7 @@ _SIGS = {
     "snn_encode_bernoulli": ([_vp, _vp, _i, _i, _f, _vp, _vp], _i),
     "snn_encode_poisson": ([_vp, _i, _i, _f, C.c_ulonglong, _vp, _vp], _i),
     "snn_fill_segments": ([C.POINTER(FillSegment), _i, _vp], _i),
+    "snn_record_segments": ([C.POINTER(RecordSegment), _i, _ll, _vp], _i),
     "snn_dist_unique_id": ([_vp], _i),
     "snn_dist_init": ([_i, _i, _vp, C.POINTER(_vp)], _i),
     "snn_dist_world": ([_vp, C.POINTER(_i), C.POINTER(_i)], _i),

@@ -97,6 +97,9 @@ class PassThroughNodes(Nodes):
     run changes state (Network.run asks `_run_refusal`)."""
     _STATE = ()
 
+    def _recordable(self) -> tuple:
+        return ()                                         # (no step writes `x`: see _describe)
+
     def __init__(self, n: Optional[int] = None, shape: Optional[Iterable[int]] = None, traces: bool = False,
                  traces_additive: bool = False, tc_trace: Scalar = 20.0, trace_scale: Scalar = 1.0, sum_input: bool = False) -> None:
         super().__init__(n=n, shape=shape, traces=traces, traces_additive=traces_additive, tc_trace=tc_trace,

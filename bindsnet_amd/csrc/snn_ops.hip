@@ -1423,3 +1423,66 @@ extern "C" int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stre
     hipLaunchKernelGGL(k_fill_segments, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return snn_check_launch();
 }
+
+// =============================================================================================
+// Monitor.record() for float state (monitors.py:94-111): timestep t's copy of every monitored tensor into its [T, ...] recording,
+// ONE launch for up to SNN_MAX_RECORD_SEGMENTS tensors.  Like k_fill_segments: the table by value in the kernel arguments, a
+// block-to-segment map, 4 KiB per block.  Memory-bound and tiny (a few KiB per step for the layer sizes monitors are used at):
+// what counts is that it is one launch, and 16 bytes per lane where both ends allow it.
+// =============================================================================================
+namespace {
+struct RecordSeg { const unsigned char *src; unsigned char *dst; unsigned long long bytes; };      // dst: already the slice of timestep t
+struct RecordArgs { RecordSeg seg[SNN_MAX_RECORD_SEGMENTS]; unsigned first_block[SNN_MAX_RECORD_SEGMENTS + 1]; unsigned wide; int n; };
+
+__global__ __launch_bounds__(256) void k_record_segments(const RecordArgs a) {
+    int k = 0;
+    while (k + 1 < a.n && blockIdx.x >= a.first_block[k + 1]) ++k;          // (n <= 32: a short uniform scan)
+    const RecordSeg sg = a.seg[k];
+    const size_t base = (size_t)(blockIdx.x - a.first_block[k]) * 4096;      // this block's 4 KiB of the segment
+    if ((a.wide >> k) & 1u) {                                                // both ends 16-byte aligned: 16 bytes per lane, words at the tail
+        const size_t off = base + (size_t)threadIdx.x * 16;
+        if (off + 16 <= sg.bytes) *(uint4 *)(sg.dst + off) = *(const uint4 *)(sg.src + off);
+        else for (size_t b = off; b < sg.bytes; b += 4) *(uint32_t *)(sg.dst + b) = *(const uint32_t *)(sg.src + b);
+    } else {                                                                 // 4-byte aligned only: consecutive lanes, consecutive words
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const size_t off = base + ((size_t)q * 256 + threadIdx.x) * 4;
+            if (off < sg.bytes) *(uint32_t *)(sg.dst + off) = *(const uint32_t *)(sg.src + off);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int snn_record_segments(const snn_record_segment *h_segs, int n, long long t, snn_stream_t stream) {
+    if (n < 0 || t < 0 || (n > 0 && !h_segs)) return SNN_ERR_INVALID;
+    for (int k = 0; k < n; ++k) {              // every segment is checked before the first group is launched
+        if (!h_segs[k].bytes) continue;
+        if (!h_segs[k].src || !h_segs[k].dst || (h_segs[k].bytes & 3)) return SNN_ERR_INVALID;
+        if ((((uintptr_t)h_segs[k].src) | ((uintptr_t)h_segs[k].dst)) & 3) return SNN_ERR_INVALID;
+        if (h_segs[k].bytes > (1ull << 36)) return SNN_ERR_UNSUPPORTED;      // (32 such segments still fit the grid's 2^31 blocks)
+    }
+    for (int k0 = 0; k0 < n; ) {
+        RecordArgs a;
+        a.n = 0;
+        a.wide = 0;
+        unsigned blocks = 0;
+        for (; k0 < n && a.n < SNN_MAX_RECORD_SEGMENTS; ++k0) {
+            const snn_record_segment &h = h_segs[k0];
+            if (!h.bytes) continue;
+            RecordSeg &sg = a.seg[a.n];
+            sg.src = (const unsigned char *)h.src;
+            sg.dst = (unsigned char *)h.dst + (size_t)t * h.bytes;
+            sg.bytes = h.bytes;
+            if (((((uintptr_t)sg.src) | ((uintptr_t)sg.dst)) & 15) == 0) a.wide |= 1u << a.n;
+            a.first_block[a.n] = blocks;
+            blocks += (unsigned)((h.bytes + 4095) / 4096);
+            ++a.n;
+        }
+        if (!a.n) continue;
+        a.first_block[a.n] = blocks;
+        hipLaunchKernelGGL(k_record_segments, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+        const int rc = snn_check_launch();
+        if (rc) return rc;
+    }
+    return SNN_OK;
+}

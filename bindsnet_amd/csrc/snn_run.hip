@@ -94,6 +94,11 @@ __global__ __launch_bounds__(256) void k_add_current(float *__restrict__ cur, co
 __global__ __launch_bounds__(256) void k_mask_fill(float *__restrict__ W, const uint8_t *__restrict__ mask, long total) {
     for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < total; k += (long)gridDim.x * 256) if (mask[k]) W[k] = 0.f;     // topology.py:129-133
 }
+// MulticompartmentConnection(traces=True): the connection's activity [B, N] feeds the target's current -- the first contribution
+// is stored, a later one added as the accumulate path of the propagation kernels adds its own sum (`*dst + acc`)
+__global__ __launch_bounds__(256) void k_feed_activity(float *__restrict__ cur, const float *__restrict__ act, long total, int accumulate) {
+    for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < total; k += (long)gridDim.x * 256) cur[k] = accumulate ? cur[k] + act[k] : act[k];
+}
 static unsigned grid_for(long n) { const long g = (n + 255) / 256; return (unsigned)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
 
 // The per-neuron vectors of a layer as its step reads them: d.pv, with thresh_vec (the older field) standing in for the threshold
@@ -111,6 +116,11 @@ static bool has_pervec(const snn_layer_desc &d) {
 
 static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R) {
     if (!L || nL <= 0 || (nC > 0 && !C) || !R || R->B <= 0 || R->T < 0) return SNN_ERR_INVALID;
+    if (R->n_records < 0 || (R->n_records > 0 && !R->records)) return SNN_ERR_INVALID;      // state monitors: what snn_record_segments would refuse at t = 0, refused before anything runs
+    for (int k = 0; k < R->n_records; ++k) {
+        const snn_record_segment &g = R->records[k];
+        if (g.bytes && (!g.src || !g.dst || (g.bytes & 3) || ((((uintptr_t)g.src) | ((uintptr_t)g.dst)) & 3))) return SNN_ERR_INVALID;
+    }
     for (int l = 0; l < nL; ++l) {
         const snn_layer_desc &d = L[l];
         if (d.n <= 0) return SNN_ERR_INVALID;
@@ -205,6 +215,7 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
     for (int c = 0; c < nC; ++c) {
         const snn_conn_desc &d = C[c];
         if (d.src < 0 || d.src >= nL || d.dst < 0 || d.dst >= nL) return SNN_ERR_INVALID;
+        if (d.activity && d.kind != SNN_CONN_MCC) return SNN_ERR_INVALID;      // traces=True: MulticompartmentConnection only (topology.py:415-435)
         if (d.pipe_n != 0) {                   // MCC with a feature pipeline: `w` only where a Weight carries the rule / the norm
             if (d.kind != SNN_CONN_MCC || d.pipe_n < 0 || d.pipe_n > SNN_MCC_MAX_PIPE || d.mask || d.bias) return SNN_ERR_INVALID;
             for (int k = 0; k < d.pipe_n; ++k) {
@@ -338,7 +349,9 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 if (only_dst >= 0 && d.dst != only_dst) continue;
                 const snn_layer_desc &S = L[d.src], &D = L[d.dst];
                 const uint8_t *sp = layer_spikes(S, B, t, only_dst >= 0 && d.src < only_dst);
-                const int acc = fed[d.dst] ? 1 : 0;
+                // traces=True: the connection's own sum goes to its activity buffer, k_feed_activity hands it on to the target below
+                const int acc = d.activity ? 0 : fed[d.dst] ? 1 : 0;
+                float *const out = d.activity ? d.activity : D.current;
                 if (d.kind == SNN_CONN_MCC && d.pipe_n > 0) {
                     // one compute() of the reference: every Probability draws its [S, N] mask, in pipeline order, then the terms are summed
                     snn_mcc_op ops[SNN_MCC_MAX_PIPE];
@@ -347,10 +360,10 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                         if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW)
                             TRY(snn_mcc_bernoulli(R->rng, (const float *)d.pipe_val[k], d.pipe_scalar[k], S.n, D.n, d.pipe_bits[k], st));
                     }
-                    TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, D.current, B, S.n, D.n, acc, st));
+                    TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, out, B, S.n, D.n, acc, st));
                 }
-                else if (d.kind == SNN_CONN_MCC && d.w_dtype != SNN_W_F32) TRY(snn_prop_cascade_h16(d.w, d.w_dtype, sp, D.current, B, S.n, D.n, acc, st));
-                else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, D.current, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_MCC && d.w_dtype != SNN_W_F32) TRY(snn_prop_cascade_h16(d.w, d.w_dtype, sp, out, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, out, B, S.n, D.n, acc, st));
                 else if (d.window) TRY(snn_prop_window_f32(d.w, d.bias, d.win_ring, (d.win_head + t) % d.win_size, sp, D.csrm_xwin, B, d.win_size,
                                                            S.n, D.n, acc, st));
                 else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
@@ -367,6 +380,8 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                                                           d.local_conv_prod, d.local_kernel_prod, d.local_n_src, acc, st));
                 else TRY(snn_prop_conv2d_f32(d.w, d.bias, sp, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw,
                                              d.stride, d.pad, acc, st));
+                if (d.activity)
+                    hipLaunchKernelGGL(k_feed_activity, dim3(grid_for((long)B * D.n)), dim3(256), 0, st, D.current, d.activity, (long)B * D.n, fed[d.dst] ? 1 : 0);
                 fed[d.dst] = true;
             }
             return SNN_OK;
@@ -523,6 +538,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 if (hipMemcpyAsync(C[c].raster_w + (size_t)t * ne, C[c].w, ne * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                     return SNN_ERR_LAUNCH;
             }
+        if (R->n_records > 0) TRY(snn_record_segments(R->records, R->n_records, t, st));      // ... and the state monitors, one launch (monitors.py:94-111)
         if (prof) snn_prof_end(st);
     }
     return snn_check_launch();
@@ -579,7 +595,8 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     // (a Conv2dConnection with a rule: the generic plan, except PostPre / Hebbian / WeightDependentPostPre on the Input -> Conv2d -> LIF graph -- snn_try_fused_convpp, whole-run form only)
     bool conv_rule = false;
     for (int c = 0; c < nC; ++c) if (C[c].kind == SNN_CONN_CONV2D && C[c].rule != SNN_RULE_NONE) conv_rule = true;
-    for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w) mode = 1;
+    for (int c = 0; c < nC; ++c) if (C[c].mask || C[c].raster_w || C[c].activity) mode = 1;
+    if (R->n_records > 0) mode = 1;                                   // state monitors: the generic plan's kernels keep x / theta / refrac_count / i in memory every step
     if (R->one_step) mode = 1;
     for (int l = 0; l < nL; ++l) if (has_pervec(L[l])) mode = 1;     // per-neuron parameters: generic plan
     bool other_nodes = false;                                          // McCullochPitts .. IzhikevichNodes, SRM0Nodes, CSRMNodes, SubtractiveResetIFNodes, PassThroughNodes: generic plan only

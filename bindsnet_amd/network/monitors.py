@@ -3,7 +3,11 @@
 The reference allocates and copies every monitored tensor once per timestep
 (monitors.py:94-111).  Here Network.run hands the node kernels a [T, B, *shape] buffer and they
 write the raster directly, so `get()` returns a tensor with the reference's shape and contents
-without any per-step host work.  Supported variables: `s` of any layer, `v` of LIF / D&C layers.  `Monitor(sparse=True)` hands the recording back as a
+without any per-step host work.  Supported variables: `s` of any layer, `v` of the layers that keep one, and the float state
+the step kernels update in place -- `x` (traces=True, Input included), `theta`, `refrac_count`, `i` on the classes that keep
+them (Nodes._RECORD) and `activity` of a MulticompartmentConnection(traces=True): these are copied out at the end of every
+timestep by one launch for all of them (snn_record_segments) and, like `w`, send the run to the generic plan.
+`Monitor(sparse=True)` hands the recording back as a
 sparse COO tensor like the reference; `NetworkMonitor` keeps float recordings of `s` / `v` of the chosen layers -- and
 of `w` of the chosen connections -- in a rolling window.  A monitor on a connection's `w` makes the run take the generic
 plan (the fused plans keep the weights on chip for the whole run): the weights are copied out at the end of every step.

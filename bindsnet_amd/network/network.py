@@ -508,6 +508,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         index = {n: i for i, n in enumerate(names)}
         L = (_lib.LayerDesc * len(names))()
         dyn_inputs, dyn_layers = [], []
+        records = []                              # (owner, attribute, [(monitor, key)]) per float32 tensor recorded through snn_run_desc.records
         max_draws = 0
         scalars = _nodes._SCALARS = []
         try:
@@ -520,20 +521,33 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     layer._trace_fields(d.p.lif, pv)
                     layer._fill_pv(d, pv, keep)
                     d.x = _dptr(layer.x) if layer.traces else None
-                    wanted = []                        # (monitor, key) pairs recording this layer's spikes
+                    wanted, traced = [], []            # (monitor, key) pairs recording this layer's spikes / its trace
                     for m in self.monitors.values():
                         if isinstance(m, Monitor) and m.obj is layer:
-                            if list(m.state_vars) != ["s"]:
-                                raise NotImplementedError("bindsnet_amd: Input layers can only be monitored for 's'")
-                            wanted.append((m, "s"))
-                        elif isinstance(m, NetworkMonitor) and (name, "s") in m._wanted():
-                            wanted.append((m, (name, "s")))
+                            for var in m.state_vars:
+                                if var != "s" and var not in layer._recordable():
+                                    raise NotImplementedError("bindsnet_amd: Input layers can only be monitored for 's'"
+                                                              + (" and 'x'" if layer.traces else " (and 'x' with traces=True)"))
+                                (wanted if var == "s" else traced).append((m, var))
+                        elif isinstance(m, NetworkMonitor):
+                            got = m._wanted()
+                            if (name, "s") in got:
+                                wanted.append((m, (name, "s")))
+                            if (name, "x") in got and layer.traces:
+                                traced.append((m, (name, "x")))
+                    if traced:
+                        self._check_recorded(layer, "x", B * layer.n, dev)
+                        records.append((layer, "x", traced))
                     dyn_inputs.append((i, name, layer, wanted))
                     continue
                 if type(layer)._describe is Nodes._describe:
                     layer._describe(d, keep, scalars)             # (raises: a layer type outside the accelerated path)
                 self._check_state(layer, B, dev)
                 requests = self._monitor_requests(layer, name)
+                for var in dict.fromkeys(v for _, _, v in requests if v not in ("s", "v")):      # x, theta, refrac_count, i: one buffer per tensor
+                    self._check_recorded(layer, var, layer.n if var == "theta" else B * layer.n, dev)
+                    records.append((layer, var, [(m, key) for m, key, v in requests if v == var]))
+                requests = [r for r in requests if r[2] in ("s", "v")]
                 cur = self._scratch("cur_" + name, (B, layer.n), torch.float32, dev)
                 d.v, d.s, d.current = _dptr(layer.v), _dptr(layer.s), _dptr(cur)
                 d.refrac = _dptr(layer.refrac_count) if "refrac_count" in layer._STATE else None
@@ -580,6 +594,9 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 wanted = self._conn_monitor_requests(conn, (src, dst))
                 if wanted:
                     dyn_conns.append((k, conn, wanted))
+                traced = self._activity_requests(conn)
+                if traced:                             # (the buffer itself: MulticompartmentConnection._describe, traces=True)
+                    records.append((conn, "activity", traced))
                 if Cn[k].window:
                     windows.append((k, conn))
                 if Cn[k].avg_k:                        # average_update: the ring indices are per-call values, the rings' addresses are watched
@@ -620,6 +637,10 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         R = _lib.RunDesc()
         R.B, R.T, R.dt, R.learning = B, T, float(self.dt), int(self.learning)
         R.one_step = int(bool(one_step))                  # network.py:388-393 (generic plan)
+        rec_arr = (_lib.RecordSegment * len(records))() if records else None
+        for k, (owner, attr, _) in enumerate(records):    # the sources stay where they are (`ptrs` watches them); _bind_call gives every call fresh recordings
+            t = getattr(owner, attr)
+            rec_arr[k].src, rec_arr[k].bytes = t.data_ptr(), 4 * t.numel()
         need = int(_lib.lib().snn_net_workspace_bytes(L, len(names), Cn, len(self.connections), C.byref(R)))
         if need:
             ws = self.__dict__.get("_workspace")
@@ -635,7 +656,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     self._scratch("rng_qbuf", (max(max_draws, 1),), torch.float32, dev), pool["rng_host"])
         # (assignments made while building -- a state tensor re-created by _check_state, a rule's lazily allocated
         #  memory -- belong to this build: the descriptors already point at the new objects)
-        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows, "averages": averages,
+        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows, "averages": averages, "records": records, "rec_arr": rec_arr,
                 "max_draws": max_draws, "gen_bufs": gen_bufs, "T": T, "B": B, "dev": dev, "scalars": scalars,
                 "lists": lists, "epoch": _lib.epoch(), "n_objects": (len(self.layers), len(self.connections), len(self.monitors)),
                 "epoch0": epoch0, "defer_norm": bool(self.__dict__.get("_defer_norm", False)), "ptrs": ptrs}
@@ -707,6 +728,14 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             mon_w = torch.empty(T, *self._monitored_weights(conn).shape, device=dev)
             built["Cn"][k].raster_w = _dptr(mon_w)
             rasters += [(m, key, mon_w) for m, key in wanted]
+        # float state at the end of every timestep (monitors.py:94-111): one [T, *shape] buffer per tensor, shared by its monitors
+        # and new for every call -- what an earlier get() handed out is never written again
+        R, rec_arr = built["R"], built["rec_arr"]
+        for k, (owner, attr, wanted) in enumerate(built["records"]):
+            buf = torch.empty(T, *getattr(owner, attr).shape, dtype=torch.float32, device=dev)
+            rec_arr[k].dst = buf.data_ptr()
+            rasters += [(m, key, buf) for m, key in wanted]
+        R.records, R.n_records = (rec_arr, len(built["records"])) if rec_arr is not None else (None, 0)
         return rasters, keep
 
     # ------------------------------------------------------------------ helpers
@@ -766,10 +795,28 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     raise NotImplementedError("bindsnet_amd: monitors on objects other than the network's layers and "
                                               "connections (features, ...) are not supported")
         for m, key, var in requests:
-            if var != "s" and not (var == "v" and "v" in layer._STATE):
-                raise NotImplementedError(f"bindsnet_amd: monitoring '{var}' of {type(layer).__name__} is "
-                                          "outside the accelerated path (supported: 's', 'v')")
+            if var != "s" and not (var == "v" and "v" in layer._STATE) and var not in layer._recordable():
+                supported = ["s"] + (["v"] if "v" in layer._STATE else []) + list(layer._recordable())
+                raise NotImplementedError(f"bindsnet_amd: monitoring '{var}' of {type(layer).__name__} is outside the accelerated "
+                                          "path (supported on this layer: " + ", ".join(f"'{v}'" for v in supported)
+                                          + "; 'x' with traces=True; 'theta', 'refrac_count' and 'i' where the class keeps them)")
         return requests
+
+    @staticmethod
+    def _check_recorded(owner, attr, numel, dev):
+        """A tensor a state monitor records: what snn_record_segments copies, float32 words in place."""
+        t = getattr(owner, attr, None)
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"monitored state '{attr}' of {type(owner).__name__} must be a contiguous float32 tensor of {numel} elements on {dev}")
+
+    @staticmethod
+    def _records_activity(m, conn) -> bool:
+        """Whether `m` is a Monitor of nothing but the `activity` of `conn`, a MulticompartmentConnection(traces=True)."""
+        return isinstance(m, Monitor) and m.obj is conn and getattr(conn, "traces", False) and list(m.state_vars) == ["activity"]
+
+    def _activity_requests(self, conn):
+        """(monitor, key handed back to its _append) for every Monitor recording the `activity` of a traces=True connection."""
+        return [(m, "activity") for m in self.monitors.values() if self._records_activity(m, conn)]
 
     def _feature_owner(self, obj):
         """The MulticompartmentConnection whose pipeline holds the feature `obj` (a Monitor on a Weight records its `value`), or None."""
@@ -779,8 +826,8 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         return None
 
     def _conn_is_monitored(self, conn, cname) -> bool:
-        """Whether any monitor records a variable of this connection."""
-        return any((isinstance(m, Monitor) and m.obj is conn) or
+        """Whether any monitor records a variable of this connection (its `activity` aside: that is a buffer of its own, not `w`)."""
+        return any((isinstance(m, Monitor) and m.obj is conn and not self._records_activity(m, conn)) or
                    (isinstance(m, NetworkMonitor) and any(c == cname for c, _ in m._wanted_conns())) for m in self.monitors.values())
 
     def _conn_monitor_requests(self, conn, cname):
@@ -789,10 +836,13 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         for m in self.monitors.values():
             if isinstance(m, NetworkMonitor):
                 requests += [(m, (c, v)) for c, v in m._wanted_conns() if c == cname]
+            elif self._records_activity(m, conn):
+                continue                               # (_activity_requests: recorded through snn_run_desc.records)
             elif isinstance(m, Monitor) and m.obj is conn:
                 if list(m.state_vars) != ["w"] or not hasattr(conn, "w"):
                     raise NotImplementedError(f"bindsnet_amd: monitoring {list(m.state_vars)} of {type(conn).__name__} is outside "
-                                              "the accelerated path (supported on connections: 'w')")
+                                              "the accelerated path (supported on connections: 'w'; 'activity' alone on a "
+                                              "MulticompartmentConnection with traces=True)")
                 requests.append((m, "w"))
             elif isinstance(m, Monitor) and any(m.obj is f for f in getattr(conn, "pipeline", ())):
                 # a Monitor on a feature (monitors.py:94-111 records any attribute): the `value` of the Weight the rule refers to --

@@ -170,6 +170,12 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
 
     # float32 [B, n] state tensors (beside `s` and `x`) whose addresses the layer's snn_layer_desc holds
     _STATE = ("v", "refrac_count")
+    # float32 tensors the generic plan's step kernels update in place and that a Monitor may record beside `s` and `v`: Network.run
+    # copies them out at the end of every timestep (snn_run_desc.records).  `x` joins them on a layer with traces=True.
+    _RECORD = ("refrac_count",)
+
+    def _recordable(self) -> tuple:
+        return self._RECORD + (("x",) if self.traces else ())
 
     def _node_params(self, pv: Optional[dict] = None, **fields) -> _lib.LifParams:
         """snn_lif_params of a layer that has `thresh`: thresh, dt, lbound and the trace fields, plus the named ones.  Per-neuron
@@ -212,6 +218,7 @@ class AbstractInput:
 
 class Input(Nodes, AbstractInput):
     """User-driven spikes (reference: nodes.py:172-228): `s` aliases the input, trace optional."""
+    _RECORD = ()
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, **kwargs) -> None:
@@ -310,6 +317,7 @@ class _AdaptiveThresholdNodes(Nodes):
     membrane / threshold arithmetic (SNN_LAYER_DC).  They differ only in DiehlAndCookNodes' one-spike arbitration.  Private, so
     that neither class is an instance of the other, as in the reference."""
     _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
+    _RECORD = ("refrac_count", "theta")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -422,6 +430,7 @@ class McCullochPitts(Nodes):
     input tensor; on the device this layer holds its own [B, n] copy of it (the step kernel writes it), on the host it
     aliases like the reference."""
     _STATE = ("v",)
+    _RECORD = ()
     _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
@@ -563,6 +572,7 @@ class CurrentLIFNodes(Nodes):
     """Current-based LIF layer (reference: nodes.py:681-826): the input feeds a decaying synaptic current `i`, which feeds
     the membrane."""
     _STATE = ("v", "refrac_count", "i")
+    _RECORD = ("refrac_count", "i")
     _PERVEC = Nodes._PERVEC + ("thresh", "decay", "i_decay")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
@@ -635,6 +645,7 @@ class IzhikevichNodes(Nodes):
     user-visible `S` and refreshed when `S` is replaced, changed in place or moved.  Layers of more than `_lib.IZH_MAX_N`
     neurons raise NotImplementedError there: the lateral sum's order is pinned against torch up to that size only."""
     _STATE = ("v", "u")
+    _RECORD = ()
     _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
@@ -839,6 +850,7 @@ class CSRMNodes(Nodes):
     order of torch's einsum -- `v` agrees with the reference to rounding, everything that depends on `v` only through the spikes
     bit for bit whenever the spikes do."""
     _STATE = ("v",)
+    _RECORD = ("theta",)
     _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
     # refused as tensors on the device, by name
     _SCALAR_ONLY = ("rest", "tau", "reset_const")

@@ -1204,9 +1204,11 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
     def __init__(self, source: Nodes, target: Nodes, device, pipeline: list = [], manual_update: bool = False,
                  traces: bool = False, **kwargs) -> None:
         super().__init__(source, target, device, pipeline, **kwargs)
-        if traces:
-            raise NotImplementedError("bindsnet_amd: connection activity traces are outside the accelerated path")
         self.traces, self.manual_update = traces, manual_update
+        if traces:
+            # topology.py:434-435, :473-474: the connection's own [B, target.n] contribution of the last step, "for monitors".  On
+            # the device a float32 buffer that Network.run's propagation writes (snn_conn_desc.activity), on the host the sum itself
+            self.activity = None
 
     def _names(self) -> list:
         return [type(f).__name__ for f in self.pipeline]
@@ -1295,12 +1297,29 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         out = torch.empty(B, self.target.n, device=dev)
         self._prop_into(s.reshape(B, -1).contiguous(), out)
         half = self._half_dtype() if self._single() else None
+        if self.traces:
+            self.activity = out
         if half is not None:                    # the reference returns the sum in the Weight's dtype; the values already are
             out = out.to(half)
         return out.view(B, *self.target.shape)
 
     def _host_compute(self, s):
-        return host_path._propagate_mcc(self, s) if self._single() else host_path._propagate_mcc_pipe(self, s)
+        out = host_path._propagate_mcc(self, s) if self._single() else host_path._propagate_mcc_pipe(self, s)
+        if self.traces:
+            self.activity = out.reshape(s.shape[0], self.target.n)
+        return out
+
+    def _activity_buffer(self, d, B, dev) -> list:
+        """traces=True on the device: `activity` as the float32 [B, target.n] buffer the run's propagation writes and a Monitor's
+        record segment reads.  Returns the (owner, attribute) pair whose address `d` now holds."""
+        if not self.traces:
+            return []
+        act = self.__dict__.get("activity")
+        if not isinstance(act, torch.Tensor) or tuple(act.shape) != (B, self.target.n) or act.dtype != torch.float32 \
+                or act.device != dev or not act.is_contiguous():
+            self.activity = torch.zeros(B, self.target.n, device=dev)
+        d.activity = dptr(self.activity)
+        return [(self, "activity")]
 
     def _program(self, dev, scratch, key):
         """The feature program of a multi-feature pipeline on `dev`: [(kind, value tensor, scalar flag, bit workspace)] in
@@ -1405,7 +1424,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         if feat.norm is not None:
             ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
             _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
-        return [self._weights()]
+        return [self._weights()] + self._activity_buffer(d, B, dev)
 
     def _describe_pipe(self, d, B, dev, scratch):
         """The feature program at the end of snn_conn_desc; d.w is the Weight the rule and the norm refer to (NULL without one)."""
@@ -1426,7 +1445,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             if feat.norm is not None:
                 ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
                 _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
-        return described
+        return described + self._activity_buffer(d, B, dev)
 
     def update(self, **kwargs) -> None:
         """Reference: topology.py:509-518 (note the default learning=False)."""

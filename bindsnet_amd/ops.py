@@ -322,6 +322,21 @@ def prop_meanfield(w, s, out, accumulate=False, store=False):
     return out
 
 
+def record_segments(pairs, t: int):
+    """Monitor.record() for float state, one launch (snn_record_segments): for every (src, dst) of `pairs` -- contiguous float32
+    device tensors, dst holding a whole number of src-sized slices, [T, *src.shape] -- slice `t` of dst becomes a bit copy of src.
+    A src must not overlap the slice it is copied to."""
+    pairs = list(pairs)
+    arr = (_lib.RecordSegment * max(1, len(pairs)))()
+    for k, (src, dst) in enumerate(pairs):
+        n = src.numel()
+        if n == 0 or dst.numel() % n or not 0 <= t < dst.numel() // n:
+            raise ValueError(f"record_segments: pair {k}: dst must hold whole slices of src's size and 0 <= t < their number "
+                             f"(src {tuple(src.shape)}, dst {tuple(dst.shape)}, t = {t})")
+        arr[k].src, arr[k].dst, arr[k].bytes = _ptr(src, F32).value, _ptr(dst, F32).value, 4 * n
+    check(lib().snn_record_segments(arr, len(pairs), t, _stream()), "record_segments")
+
+
 def input_step(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None, pv=None):
     """pv (here and in every step below): optional {quantity name (_lib.PERVEC): f32 [N] device tensor} of per-neuron
     parameters that take the place of the scalars (include/snnhip.h f10)."""

@@ -88,6 +88,10 @@ def _reject_local(network, mode: str) -> None:
             from .learning._descriptor import reduction_name
             raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} has a rule with reduction={reduction_name(reduction)}; the "
                                       "multi-device modes reduce with torch.sum (or torch.squeeze) only; run the network on one device")
+        if getattr(conn, "traces", False):
+            # `activity` is the step's sum over the GLOBAL source layer and batch: a column or batch shard's own is another tensor
+            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has traces=True, whose `activity` the multi-device modes "
+                                      "neither merge nor slice; run the network on one device")
         if not conn._multi_device:
             if hasattr(conn, "pipeline"):
                 raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "
@@ -318,6 +322,10 @@ def _exact_check(network):
     for name, layer in network.layers.items():
         if type(layer) not in (Input, LIFNodes, DiehlAndCookNodes):
             raise NotImplementedError(f"exact_run: layer type {type(layer).__name__} ('{name}')")
+    for m in network.monitors.values():        # x, theta, refrac_count, i, a connection's activity: recorded by Network.run on one device only, like `w`
+        extra = [v for v in getattr(m, "state_vars", ()) if v in ("x", "theta", "refrac_count", "i", "activity")]
+        if extra:
+            raise NotImplementedError(f"exact_run: monitoring {extra} (Monitor objects on layers, 's' and 'v', are supported)")
     learned = []
     for key, conn in network.connections.items():
         if conn._exact_learns():

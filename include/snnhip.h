@@ -712,6 +712,20 @@ int snn_mcc_bernoulli(snn_rng_state *rng, const float *p, int p_scalar, int S, i
 typedef struct { void *ptr; unsigned long long bytes; uint32_t pattern; } snn_fill_segment;
 int snn_fill_segments(const snn_fill_segment *h_segs, int n, snn_stream_t stream);
 
+/* ---- Monitor.record for float state (x, theta, refrac_count, i, a connection's activity) -----
+ * bindsnet/network/monitors.py:94-111, called at the end of every timestep (network.py:459-461): record() clones whatever
+ * attribute it is given.  Here the [T, ...] recording is one device buffer per monitored tensor, and timestep t copies
+ * segment k's `bytes` bytes from `src` to `dst + t * bytes` -- all n segments in one launch per group of at most
+ * SNN_MAX_RECORD_SEGMENTS (the table travels by value in the kernel arguments: no host synchronisation, no staging copy).
+ * A plain copy of 32-bit words: the sign of zero and NaN payloads survive.  A segment whose source and destination slice are
+ * both 16-byte aligned moves 16 bytes per lane, any other (a theta of odd length beyond t = 0, a view that starts one float
+ * into a buffer) 4 bytes per lane.  SNN_ERR_INVALID, before anything is launched: n < 0, t < 0, a NULL table with n > 0, a
+ * NULL or not 4-byte aligned pointer in a non-empty segment, `bytes` not a multiple of 4.  Empty segments are skipped.
+ * Source and destination slice of a segment must not overlap.  Added without changing SNN_ABI_VERSION: purely additive. */
+#define SNN_MAX_RECORD_SEGMENTS 32
+typedef struct { const void *src; void *dst; unsigned long long bytes; } snn_record_segment;
+int snn_record_segments(const snn_record_segment *h_segs, int n, long long t, snn_stream_t stream);
+
 /* ---- a1: Network.run ------------------------------------------------------------------------
  * bindsnet/network/network.py:380-465 (the per-timestep loop and the post-loop normalisation),
  * for graphs built from {Input, LIFNodes, DiehlAndCookNodes / AdaptiveLIFNodes, McCullochPitts, IFNodes, BoostedLIFNodes,
@@ -898,6 +912,13 @@ typedef struct {
      * WDPOSTPRE and MSTDP; MSTDPET, RMAX, MSTDP on a CONV2D connection and NONE ignore it).  Outside the enum: SNN_ERR_INVALID.
      * Added like the fields above: SNN_ABI_VERSION stays. */
     int reduce;
+    /* MulticompartmentConnection(traces=True) (topology.py:415-435, :473-474): nullable f32 [B, target n], the connection's own
+     * summed signal of the step.  With it the connection propagates into `activity` (accumulate = 0) and one elementwise launch
+     * feeds the target: current = activity for the target's first connection, current = current + activity behind it -- the
+     * arithmetic of the accumulate path's `*dst + acc`, so the currents keep their bits.  MCC only (any pipeline, any w_dtype):
+     * another kind with it is SNN_ERR_INVALID.  It sends the graph to the generic plan.  To record it, name it in
+     * snn_run_desc.records.  Added like the fields above: SNN_ABI_VERSION stays. */
+    float *activity;
 } snn_conn_desc;
 
 typedef struct {
@@ -930,6 +951,15 @@ typedef struct {
                                    workspace is (re)allocated or written by anybody else, otherwise left alone.  The library notes there
                                    what it knows about the workspace's content, so that consecutive pipelined runs need not clear their
                                    exchange area with a memset each (the gated second attempt does it for the next run).  (ABI 8) */
+    /* State monitors (snn_record_segments above): n_records segments, each a float32 tensor the generic plan's kernels update in
+     * place (a layer's x, theta, refrac_count, i; a connection's activity) and its [T, ...] recording.  The run calls
+     * snn_record_segments(records, n_records, t) at the END of timestep t -- behind the layers' steps, the clamps, the learning
+     * updates, the masks and the weight-monitor copies, where the reference records (network.py:459-461); with one_step at the
+     * same point.  n_records > 0 sends the graph to the generic plan, as a weight monitor does.  n_records < 0, a NULL table with
+     * n_records > 0 or a segment snn_record_segments refuses: SNN_ERR_INVALID before anything runs.  Added at the end without
+     * changing SNN_ABI_VERSION, like every additive field so far. */
+    const snn_record_segment *records;
+    int n_records;
 } snn_run_desc;
 
 /* Runs T timesteps.  Asynchronous; the caller synchronises the stream before reading *status /
