@@ -122,7 +122,7 @@ class ConnDesc(C.Structure):
                 ("s_tgt_prev", C.c_void_p), ("reward", C.c_float), ("reward_vec", C.c_void_p),
                 ("a_plus", C.c_float), ("a_minus", C.c_float), ("decay_plus", C.c_float),
                 ("decay_minus", C.c_float),
-                ("has_norm", C.c_int), ("norm", C.c_float), ("norm_abs", C.c_int), ("norm_ws", C.c_void_p),
+                ("has_norm", C.c_int), ("norm", C.c_float), ("norm_abs", C.c_int), ("norm_step", C.c_int), ("norm_ws", C.c_void_p),
                 ("e_trace", C.c_void_p), ("decay_e", C.c_float), ("tc_e", C.c_float), ("rule_ws", C.c_void_p),
                 ("mask", C.c_void_p), ("raster_w", C.c_void_p),
                 ("local_src", C.c_void_p), ("local_F", C.c_int), ("local_conv_prod", C.c_int),
@@ -248,6 +248,8 @@ _SIGS = {
     "snn_mstdpet_step_pv": ([_vp] * 8 + [_i, _i] + [_f] * 10 + [_i, _f, _i, _f, C.POINTER(SynParams), _vp], _i),
     "snn_mstdp_step_pv": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, C.POINTER(SynParams), _vp], _i),
     "snn_normalize_pv": ([_vp, _i, _i, _vp, _i, _vp, _vp], _i),
+    "snn_prop_cascade_norm_f32": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp], _i),
+    "snn_prop_cascade_norm_pv_f32": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "snn_postpre_avg_step": ([_vp] * 5 + [_i, _i, _i, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_mstdp_avg_step": ([_vp] * 7 + [_i, _i, _i, _f, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _i, _f, _i, _vp, _i, _i, _i, _vp], _i),
     "snn_mstdpet_avg_step": ([_vp] * 8 + [_i, _i] + [_f] * 10 + [_i, _f, _i, _f, _vp, _i, _i, _i, _vp], _i),

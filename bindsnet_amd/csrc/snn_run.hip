@@ -271,6 +271,9 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
             if (d.avg_squeeze && R->B != 1) return SNN_ERR_INVALID;
             if (d.avg_k > SNN_AVG_MAX_TERMS || R->B > SNN_AVG_MAX_TERMS) return SNN_ERR_UNSUPPORTED;
         }
+        if (d.norm_step != 0) {                // Weight(norm_frequency="time step") (snnhip.h f16): MCC, f32, the Weight's signed column sums; 1 = the two calls, 2 = the fused launch
+            if ((d.norm_step != 1 && d.norm_step != 2) || (d.norm_step == 2 && d.pipe_n != 0) || d.kind != SNN_CONN_MCC || d.w_dtype != SNN_W_F32 || !d.w || !d.has_norm || d.norm_abs || !d.norm_ws) return SNN_ERR_INVALID;
+        }
         if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) {        // PermuteConnection / ConstantPad2dConnection: a gather, propagation only
             if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
             if (d.has_norm || d.mask || d.raster_w || d.bias || d.w) return SNN_ERR_INVALID;
@@ -361,8 +364,18 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                             TRY(snn_mcc_bernoulli(R->rng, (const float *)d.pipe_val[k], d.pipe_scalar[k], S.n, D.n, d.pipe_bits[k], st));
                     }
                     TRY(snn_prop_mcc_pipe_f32(ops, d.pipe_n, sp, out, B, S.n, D.n, acc, st));
+                    // norm_frequency="time step": the pipeline's Weight is normalised behind its compute() (topology_features.py:641-643)
+                    if (d.norm_step && d.norm_vec) TRY(snn_normalize_pv(d.w, S.n, D.n, d.norm_vec, 0, d.norm_ws, st));
+                    else if (d.norm_step) TRY(snn_normalize(d.w, S.n, D.n, d.norm, 0, d.norm_ws, st));
                 }
                 else if (d.kind == SNN_CONN_MCC && d.w_dtype != SNN_W_F32) TRY(snn_prop_cascade_h16(d.w, d.w_dtype, sp, out, B, S.n, D.n, acc, st));
+                else if (d.kind == SNN_CONN_MCC && d.norm_step == 2 && d.norm_vec) TRY(snn_prop_cascade_norm_pv_f32(d.w, sp, out, B, S.n, D.n, acc, d.norm_vec, d.norm_ws, st));
+                else if (d.kind == SNN_CONN_MCC && d.norm_step == 2) TRY(snn_prop_cascade_norm_f32(d.w, sp, out, B, S.n, D.n, acc, d.norm, d.norm_ws, st));
+                else if (d.kind == SNN_CONN_MCC && d.norm_step) {      // ... or as the two calls: the currents from the old values, then the normalisation
+                    TRY(snn_prop_cascade_f32(d.w, sp, out, B, S.n, D.n, acc, st));
+                    if (d.norm_vec) TRY(snn_normalize_pv(d.w, S.n, D.n, d.norm_vec, 0, d.norm_ws, st));
+                    else TRY(snn_normalize(d.w, S.n, D.n, d.norm, 0, d.norm_ws, st));
+                }
                 else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, out, B, S.n, D.n, acc, st));
                 else if (d.window) TRY(snn_prop_window_f32(d.w, d.bias, d.win_ring, (d.win_head + t) % d.win_size, sp, D.csrm_xwin, B, d.win_size,
                                                            S.n, D.n, acc, st));
@@ -485,7 +498,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                                  d.has_min, d.wmin, d.has_max, d.wmax, d.reduce, st));
                 else if (d.reduce != SNN_REDUCE_SUM && d.rule == SNN_RULE_POSTPRE)      // another batch reduction: the *_red instances (snnhip.h f15), per-synapse or not
                     TRY(snn_stdp_postpre_red(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
-                                             d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, &d.syn, d.reduce, st));
+                                             d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0 && !d.norm_step, &d.syn, d.reduce, st));
                 else if (d.reduce != SNN_REDUCE_SUM && (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE))
                     TRY(snn_stdp_hebbian_red(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
                                              d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, d.reduce, st));
@@ -495,7 +508,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                            d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, d.reduce, st));
                 else if (snn::syn_any(&d.syn) && d.rule == SNN_RULE_POSTPRE)     // per-synapse constants: the *_pv instances (snnhip.h f13)
                     TRY(snn_stdp_postpre_pv(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
-                                            d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, &d.syn, st));
+                                            d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0 && !d.norm_step, &d.syn, st));
                 else if (snn::syn_any(&d.syn) && (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE))
                     TRY(snn_stdp_hebbian_pv(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
                                             d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, st));
@@ -509,7 +522,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                                           d.wdecay, d.has_min, d.wmin, d.has_max, d.wmax, &d.syn, st));
                 else if (d.rule == SNN_RULE_POSTPRE)
                     TRY(snn_stdp_postpre(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.use_dt, R->dt, d.wdecay,
-                                         d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0, st));
+                                         d.has_min, d.wmin, d.has_max, d.wmax, /*assume_clamped=*/t > 0 && !d.norm_step, st));
                 else if (d.rule == SNN_RULE_HEBBIAN || d.rule == SNN_RULE_WDPOSTPRE)
                     TRY(snn_stdp_hebbian(d.w, ss, S.x, D.s, D.x, B, S.n, D.n, d.nu0, d.nu1, d.rule == SNN_RULE_WDPOSTPRE, d.wdecay,
                                          d.has_min, d.wmin, d.has_max, d.wmax, st));
@@ -607,6 +620,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].w_dtype != SNN_W_F32) local = true;   // ... and float16 / bfloat16 weights (the fused plans keep f32 tiles)
     for (int c = 0; c < nC; ++c) if (snn::syn_any(&C[c].syn) || C[c].norm_vec) local = true;   // ... and per-synapse rates / bounds, per-target norms
     for (int c = 0; c < nC; ++c) if (C[c].avg_k != 0) local = true;             // ... and averaged updates (the fused plans keep no ring)
+    for (int c = 0; c < nC; ++c) if (C[c].norm_step != 0) local = true;         // ... and a Weight normalised every timestep (no fused plan normalises inside its loop)
     for (int c = 0; c < nC; ++c) if (C[c].reduce != SNN_REDUCE_SUM) local = true;   // ... and a batch reduction other than sum (the fused plans sum)
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
@@ -622,7 +636,8 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     }
     // network.py:464-465: normalise every connection after the loop (learning or not)
     for (int c = 0; c < nC; ++c)
-        if (C[c].has_norm && C[c].kind == SNN_CONN_LOCAL)     // topology.py:1601 / :1748-1759 / :1898: every [kernel_prod] row to sum `norm`
+        if (C[c].norm_step) continue;                         // norm_frequency="time step": connection.normalize() does nothing at the end of the run (topology_features.py:663-671)
+        else if (C[c].has_norm && C[c].kind == SNN_CONN_LOCAL)     // topology.py:1601 / :1748-1759 / :1898: every [kernel_prod] row to sum `norm`
             TRY(snn_normalize_conv2d(C[c].w, C[c].cin * C[c].local_F * C[c].local_conv_prod, C[c].local_kernel_prod, C[c].norm, st));
         else if (C[c].has_norm && C[c].w_dtype != SNN_W_F32)
             TRY(snn_normalize_h16(C[c].w, C[c].w_dtype, L[C[c].src].n, L[C[c].dst].n, C[c].norm, C[c].norm_ws, st));

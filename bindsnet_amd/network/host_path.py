@@ -274,7 +274,17 @@ def _propagate_mcc(conn, s):
     """MulticompartmentConnection.compute with one Weight (topology.py:437-479, topology_features.py:633-645)."""
     B = s.shape[0]
     spikes = s.reshape(B, conn.source.n, 1).repeat(1, 1, conn.target.n)
-    return _sum(conn._weight().value * spikes, 1).view(B, *conn.target.shape)
+    feat = conn._weight()
+    signal = feat.value * spikes
+    _normalize_step(feat)
+    return _sum(signal, 1).view(B, *conn.target.shape)
+
+
+def _normalize_step(feat) -> None:
+    """Weight.compute's closing statement (topology_features.py:641-643): with norm_frequency="time step" the value is normalised in
+    place behind the product that read it, at every compute(), learning or not."""
+    if feat._norm_step():
+        _normalize_columns(feat.value.data, feat.norm, False)
 
 
 def _propagate_mcc_pipe(conn, s):
@@ -290,6 +300,7 @@ def _propagate_mcc_pipe(conn, s):
             x = x * torch.bernoulli(f.value)
         elif isinstance(f, Weight):
             x = f.value * x
+            _normalize_step(f)
         elif isinstance(f, Bias):
             x = x + f.value
         else:                                       # Mask, Intensity

@@ -1200,6 +1200,11 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
     _norm_by = "columns"               # the Weight's SIGNED column sums (topology_features.py:250-266), by snn_net_run
     _takes_mask = _host_refuses_mask = False           # (no `w`: the device path refuses a mask, the host path ignores it)
     _MAX_PIPE = 8                      # SNN_MCC_MAX_PIPE
+    # How a single Weight with norm_frequency="time step" is propagated and normalised (snn_conn_desc.norm_step): 1 -- snn_prop_cascade_f32
+    # and snn_normalize(_pv), 2 -- snn_prop_cascade_norm(_pv)_f32, one launch.  The two forms leave the same bits; the three launches are
+    # the faster ones at the flagship shape (profiles/NOTES_norm_step.md: the fused kernel keeps 25 workgroups busy, k_prop 64), so they
+    # are what runs.  tools/bench_norm_step.py and tests/test_gpu_norm_step.py select the other form through this attribute.
+    _NORM_STEP_FORM = 1
 
     def __init__(self, source: Nodes, target: Nodes, device, pipeline: list = [], manual_update: bool = False,
                  traces: bool = False, **kwargs) -> None:
@@ -1278,6 +1283,8 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
                                            "(NoOp and PostPre are)")
             if isinstance(feat.norm, torch.Tensor):
                 return NotImplementedError(f"bindsnet_amd: tensor norms are not supported on a {half} Weight")
+        if any(getattr(f, "norm_frequency", "sample") == "time step" for f in self.pipeline):
+            return NotImplementedError(f"bindsnet_amd: norm_frequency='time step' on a {half} Weight is not supported (float32 is)")
         return None
 
     def _on_host(self) -> bool:
@@ -1347,7 +1354,13 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
 
     def _prop_into(self, s, out, accumulate=False) -> None:
         if self._single():
-            return ops.prop_cascade(self.pipeline[0].value.data, s, out, accumulate=accumulate)
+            feat = self.pipeline[0]
+            if feat._norm_step() and self._NORM_STEP_FORM == 2:
+                return ops.prop_cascade_norm(feat.value.data, s, out, _norm_value(feat.norm), accumulate=accumulate)
+            ops.prop_cascade(feat.value.data, s, out, accumulate=accumulate)
+            if feat._norm_step():                  # Weight.compute normalises behind its product (topology_features.py:641-643)
+                ops.normalize(feat.value.data, _norm_value(feat.norm), use_abs=False)
+            return out
         pool = self.__dict__.setdefault("_bits_pool", {})
 
         def scratch(key, shape, dtype, dev):
@@ -1361,13 +1374,16 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             ops.mcc_bernoulli_from_host([p for p, _ in draws], [b for _, b in draws], self.source.n, self.target.n)
         ops.prop_mcc_pipe([(kind, f.value.data, flag, bits) for kind, f, flag, bits in prog], s, out, self.source.n, self.target.n,
                           accumulate=accumulate)
+        for f in self.pipeline:                     # a Weight with norm_frequency="time step": normalised behind the step's signal
+            if getattr(f, "_norm_step", bool)():
+                ops.normalize(f.value.data, _norm_value(f.norm), use_abs=False)
 
     def _host_update(self, kwargs, mask) -> None:
         host_path._update_mcc(self, float(self.dt), kwargs)
 
     def _host_normalize(self) -> None:
-        for feat in self.pipeline:                    # topology.py:520-527: every feature that has a norm
-            if feat.norm is not None:
+        for feat in self.pipeline:                    # topology.py:520-527: every feature that has a norm (a "time step" Weight: a no-op, topology_features.py:663-671)
+            if feat.norm is not None and getattr(feat, "norm_frequency", "sample") == "sample":
                 host_path._normalize_columns(feat.value.data, feat.norm, False)
 
     def _rule(self):
@@ -1424,6 +1440,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
         if feat.norm is not None:
             ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
             _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
+            d.norm_step = self._NORM_STEP_FORM if feat._norm_step() else 0
         return [self._weights()] + self._activity_buffer(d, B, dev)
 
     def _describe_pipe(self, d, B, dev, scratch):
@@ -1445,6 +1462,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             if feat.norm is not None:
                 ws = scratch(f"norm_{d.src}_{d.dst}", (self.target.n,), torch.float32, dev)
                 _fill_norm(d, feat.norm, 0, ws, self.target.n, dev)
+                d.norm_step = int(feat._norm_step())      # (snn_prop_mcc_pipe_f32, then the normalisation: the two-call form)
         return described + self._activity_buffer(d, B, dev)
 
     def update(self, **kwargs) -> None:

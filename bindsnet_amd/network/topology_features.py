@@ -103,15 +103,19 @@ class AbstractFeature(_lib.Touching):
 
 
 class Weight(AbstractFeature):
-    """Per-synapse scalar gain (reference: topology_features.py:575-671)."""
+    """Per-synapse scalar gain (reference: topology_features.py:575-671).  norm_frequency="sample": normalised at the end of run();
+    "time step": behind every compute() of its connection instead (float32; the generic plan, snn_conn_desc.norm_step)."""
 
     def __init__(self, name: str, value=None, value_dtype: torch.dtype = torch.float32,
                  range: Optional[Sequence[float]] = None, norm=None, norm_frequency: Optional[str] = "sample",
                  learning_rule=None, nu: Optional[Union[list, tuple]] = None, reduction=None,
                  enforce_polarity: Optional[bool] = False, decay: float = 0.0, sparse: Optional[bool] = False,
                  batch_size: int = 1) -> None:
-        if norm_frequency != "sample":
-            raise NotImplementedError("bindsnet_amd: norm_frequency='time step' is outside the accelerated path")
+        if norm_frequency not in ("sample", "time step"):
+            raise NotImplementedError(f"bindsnet_amd: norm_frequency={norm_frequency!r} is outside the accelerated path "
+                                      "('sample' and 'time step' are supported)")
+        if norm_frequency == "time step" and value_dtype in (torch.float16, torch.bfloat16):      # (a given value is cast to value_dtype)
+            raise NotImplementedError(f"bindsnet_amd: norm_frequency='time step' on a {value_dtype} Weight is not supported (float32 is)")
         self.norm_frequency, self.enforce_polarity = norm_frequency, enforce_polarity
         if value_dtype in (torch.float16, torch.bfloat16) and isinstance(norm, torch.Tensor):
             raise NotImplementedError(f"bindsnet_amd: tensor norms are not supported on a {value_dtype} Weight")
@@ -127,6 +131,17 @@ class Weight(AbstractFeature):
 
     def reset_state_variables(self) -> None:
         pass
+
+    def _norm_step(self) -> bool:
+        """norm_frequency="time step" with a norm: the value is normalised behind every compute() of its connection, learning or
+        not, and by nothing else (reference: topology_features.py:641-643, :663-671)."""
+        return self.norm_frequency == "time step" and self.norm is not None
+
+    def normalize(self) -> None:
+        """Reference: topology_features.py:663-671 -- called from outside compute() (Network.run's end, connection.normalize()) this
+        normalises a "sample" Weight only."""
+        if self.norm_frequency == "sample":
+            super().normalize()
 
     def compute(self, conn_spikes):
         raise NotImplementedError("Weight.compute is fused into MulticompartmentConnection.compute on the device")

@@ -73,6 +73,26 @@ def prop_cascade(W, s, out, accumulate=False):
     return out
 
 
+def prop_cascade_norm(W, s, out, norm, accumulate=False, ws=None):
+    """f16: prop_cascade(W, s, out, accumulate) from W as it was, then normalize(W, norm, use_abs=False), in one launch -- one step
+    of a Weight with norm_frequency="time step".  Bit-identical to the two calls in `out` and in W; float32 only.  `norm`: a
+    float, or a tensor with one total per target neuron."""
+    B = s.shape[0]
+    Nin, N = W.shape
+    assert s.numel() == B * Nin and out.numel() == B * N
+    if W.dtype != F32:
+        raise NotImplementedError(f"bindsnet_amd: norm_frequency='time step' computes in float32 only (got {W.dtype})")
+    if ws is None:
+        ws = torch.empty(N, dtype=F32, device=W.device)
+    if isinstance(norm, torch.Tensor):
+        check(lib().snn_prop_cascade_norm_pv_f32(_ptr(W, F32), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate),
+                                                 _ptr(norm_vector(norm, N, W.device), F32), _ptr(ws, F32), _stream()), "prop_cascade_norm_pv")
+        return out
+    check(lib().snn_prop_cascade_norm_f32(_ptr(W, F32), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N, int(accumulate), float(norm),
+                                          _ptr(ws, F32), _stream()), "prop_cascade_norm")
+    return out
+
+
 def prop_mcc_pipe(program, s, out, Nin, N, accumulate=False):
     """f8: out[b,j] (+)= sum_i term(b,i,j) of a MulticompartmentConnection feature pipeline, in ATen sum(dim=1) order.
     program: [(kind, value tensor, scalar flag, bit workspace or None)] in pipeline order (_lib.MCC_OP_*); the bit workspaces

@@ -80,6 +80,10 @@ def _reject_local(network, mode: str) -> None:
             # an averaging ring is one history of the GLOBAL batch's updates: a shard's own ring, or a slice of one, is another rule
             raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a rule with average_update, whose ring of past updates "
                                       "the multi-device modes neither merge nor slice; run the network on one device")
+        if hasattr(conn, "pipeline") and any(getattr(f, "norm_frequency", "sample") == "time step" for f in conn.pipeline):
+            # every step normalises the GLOBAL matrix's columns before that step's update: a merge of shard deltas after the run cannot
+            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a Weight with norm_frequency='time step', which the "
+                                      "multi-device modes do not reproduce; run the network on one device")
         rule = conn._rule() if hasattr(conn, "_rule") else None
         reduction = None if rule is None or type(rule).__name__ == "NoOp" else getattr(rule, "reduction", None)
         if reduction is not None and reduction is not torch.sum and reduction is not torch.squeeze:

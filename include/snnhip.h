@@ -593,6 +593,19 @@ int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus,
                         float wmin, int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream);
 int snn_normalize_pv(float *W, int Nin, int N, const float *norm_vec, int use_abs, float *colsum_ws, snn_stream_t stream);
 
+/* ---- f16: Weight(norm_frequency="time step") -- propagation and normalisation of one Weight in one launch --------
+ * bindsnet/network/topology_features.py:633-645: Weight.compute forms value * conn_spikes and then, in "time step" mode, normalises
+ * the value in place (:250-266, signed column sums).  out[b, j] (+)= sum_i W[i, j] * s[b, i] from the weights AS THEY WERE, in
+ * snn_prop_cascade_f32's order (accumulate as there); then every column of W is scaled and written back once.
+ * Contract: bit-identical, in `out` and in `W`, to snn_prop_cascade_f32 followed by snn_normalize(use_abs 0) -- the _pv form:
+ * snn_normalize_pv(use_abs 0), norm_vec device [N] -- with the same argument checks.  A workgroup keeps 16 columns with all their
+ * rows in LDS (csrc/snn_normstep.hip); where that tile does not fit (Nin above about 1100) the entry point makes the two calls
+ * itself, through colsum_ws ([N] floats, always required).  Added without changing SNN_ABI_VERSION: purely additive. */
+int snn_prop_cascade_norm_f32(float *W, const uint8_t *s, float *out, int B, int Nin, int N, int accumulate, float norm,
+                              float *colsum_ws, snn_stream_t stream);
+int snn_prop_cascade_norm_pv_f32(float *W, const uint8_t *s, float *out, int B, int Nin, int N, int accumulate,
+                                 const float *norm_vec, float *colsum_ws, snn_stream_t stream);
+
 /* ---- f14: time-averaged updates of the MulticompartmentConnection rules (average_update / continues_update) -----
  * bindsnet/learning/MCC_learning.py:211-222, :237-289 (PostPre), :457-466, :518-535 (MSTDP), :641-649, :696-713 (MSTDPET).  With
  * average_update = K a rule stores each step's update in slot `idx` of a ring of K weight-shaped slots (f32 [K, Nin, N], caller-owned,
@@ -827,6 +840,14 @@ typedef struct {
     uint8_t *s_src_prev, *s_tgt_prev;
     float reward; const float *reward_vec; float a_plus, a_minus, decay_plus, decay_minus;
     int has_norm; float norm; int norm_abs;   /* post-run normalisation (norm_abs: Connection) */
+    /* Weight(norm_frequency="time step") (f16): non-zero -- the connection's Weight is normalised in EVERY timestep, right behind the
+     * propagation that read its old values and before the step's learning update, learning or not, and the run's closing
+     * normalisation skips the connection.  1: through snn_prop_cascade_f32 (a feature pipeline: snn_prop_mcc_pipe_f32) and
+     * snn_normalize(_pv); 2: through snn_prop_cascade_norm_f32 / snn_prop_cascade_norm_pv_f32, one launch (pipe_n 0 only) -- the same bits.  Needs has_norm
+     * (norm / norm_vec, norm_ws) with norm_abs 0 on an MCC connection with an f32 `w`: anything else with it is SNN_ERR_INVALID.  It
+     * sends the graph to the generic plan.  The field takes what was padding in front of norm_ws: no offset and no size changes,
+     * SNN_ABI_VERSION stays. */
+    int norm_step;
     float *norm_ws;             /* [N] scratch when has_norm */
     float *e_trace;             /* MSTDPET: dense eligibility trace [Nin,N]; CONV2D + MSTDP: the eligibility [Cout,Cin*KH*KW]
                                    (p_plus is then [Cin,H,W], p_minus [Cout,OH*OW]; batch 1, s_*_prev unused) */
