@@ -635,7 +635,7 @@ static int launch_plasticity_pv(const StdpArgs &a, const snn_synparams &q, hipSt
 static bool reduce_valid(int reduce) { return reduce >= SNN_REDUCE_SUM && reduce <= SNN_REDUCE_AMIN; }
 
 // ... and for the instances of another batch reduction (k_plasticity_red<TJ, BatchReduce<R>>).
-// `reduce` is MEAN, AMAX or AMIN here (the *_red entry points forward SUM to their *_pv namesakes); a NULL `sp` is the empty snn_synparams.
+// `reduce` is MEAN, AMAX or AMIN here (SUM is the two instances above: launch_plasticity_for); a NULL `sp` is the empty snn_synparams.
 static int launch_plasticity_red(const StdpArgs &a, const snn_synparams &q, int reduce, hipStream_t st) {
     switch (reduce) {
         case SNN_REDUCE_MEAN: return launch_plasticity_tiles<PlasticityRed<SNN_REDUCE_MEAN>>(a, st, q);
@@ -651,47 +651,48 @@ static void syn_rates(StdpArgs &a, const snn_synparams &q) {
     if (q.nu1) a.nu1 = q.nu1_any ? 1.f : 0.f;
 }
 
-extern "C" int snn_stdp_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
-                                    int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
-                                    int has_max, float wmax, int assume_clamped, const snn_synparams *sp, int reduce, snn_stream_t stream) {
+// The instance of an update, chosen once per rule body: another batch reduction -> k_plasticity_red; per-synapse constants ->
+// k_plasticity_pv; else the scalar kernel, which never looks at `sp`.
+static int launch_plasticity_for(const StdpArgs &a, const snn_synparams *sp, int reduce, hipStream_t st) {
+    if (reduce != SNN_REDUCE_SUM) return launch_plasticity_red(a, sp ? *sp : snn_synparams{}, reduce, st);
+    return syn_any(sp) ? launch_plasticity_pv(a, *sp, st) : launch_plasticity(a, st);
+}
+
+// a8 / a9: PostPre.  The scalar name passes sp = NULL and SUM, the *_pv name SUM.
+static int postpre_dense(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin, int N,
+                         float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin, int has_max, float wmax,
+                         int assume_clamped, const snn_synparams *sp, int reduce, snn_stream_t stream) {
     if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
-    if (reduce == SNN_REDUCE_SUM)
-        return snn_stdp_postpre_pv(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax,
-                                   assume_clamped, sp, stream);
     if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
     if (sp && ((sp->nu0 && sp->nu0_rs != 0) || (sp->nu1 && sp->nu1_rs != 0))) return SNN_ERR_INVALID;     // learning.py:401-402
     if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max,
-               wmax, (assume_clamped && decay == 1.0f) ? 1 : 0, 0, 0.f, nullptr};
-    const snn_synparams q = sp ? *sp : snn_synparams{};
-    syn_rates(a, q);
-    return launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
+    StdpArgs a{.W = W, .s_src = s_src, .x_src = x_src, .s_tgt = s_tgt, .x_tgt = x_tgt, .B = B, .Nin = Nin, .N = N, .nu0 = nu0, .nu1 = nu1,
+               .use_dt = use_dt, .dt = dt, .decay = decay, .has_min = has_min, .wmin = wmin, .has_max = has_max, .wmax = wmax,
+               .assume_clamped = (assume_clamped && decay == 1.0f) ? 1 : 0, .mode = 0, .reward = 0.f, .reward_vec = nullptr};
+    if (sp) syn_rates(a, *sp);                           // (a tensor rate makes the instance per-synapse: nothing changes on the scalar path)
+    return launch_plasticity_for(a, sp, reduce, (hipStream_t)stream);
+}
+
+extern "C" int snn_stdp_postpre_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
+                                    int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
+                                    int has_max, float wmax, int assume_clamped, const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    return postpre_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax, assume_clamped,
+                         sp, reduce, stream);
 }
 
 extern "C" int snn_stdp_postpre_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
                                    int Nin, int N, float nu0, float nu1, int use_dt, float dt, float decay, int has_min, float wmin,
                                    int has_max, float wmax, int assume_clamped, const snn_synparams *sp, snn_stream_t stream) {
-    if (!syn_any(sp))
-        return snn_stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax,
-                                assume_clamped, stream);
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
-    if ((sp->nu0 && sp->nu0_rs != 0) || (sp->nu1 && sp->nu1_rs != 0)) return SNN_ERR_INVALID;     // learning.py:401-402
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max,
-               wmax, (assume_clamped && decay == 1.0f) ? 1 : 0, 0, 0.f, nullptr};
-    syn_rates(a, *sp);
-    return launch_plasticity_pv(a, *sp, (hipStream_t)stream);
+    return postpre_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax, assume_clamped,
+                         sp, SNN_REDUCE_SUM, stream);
 }
 
 extern "C" int snn_stdp_postpre(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt,
                                 const float *x_tgt, int B, int Nin, int N, float nu0, float nu1, int use_dt,
                                 float dt, float decay, int has_min, float wmin, int has_max, float wmax,
                                 int assume_clamped, snn_stream_t stream) {
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max,
-               wmax, (assume_clamped && decay == 1.0f) ? 1 : 0, 0, 0.f, nullptr};
-    return launch_plasticity(a, (hipStream_t)stream);
+    return postpre_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, use_dt, dt, decay, has_min, wmin, has_max, wmax, assume_clamped,
+                         nullptr, SNN_REDUCE_SUM, stream);
 }
 
 __global__ __launch_bounds__(256) void k_mstdp_traces(float *__restrict__ p_plus, float *__restrict__ p_minus,
@@ -715,6 +716,18 @@ __global__ __launch_bounds__(256) void k_mstdp_traces(float *__restrict__ p_plus
             s_tgt_prev[q] = sv;
         }
     }
+}
+
+// The traces behind an MSTDP / MSTDPET update: p_plus / p_minus decay and take this step's spikes, which are remembered as the factors of
+// the next eligibility.  `max_blocks` > 0 caps the grid (MSTDP's B * (Nin + N) elements); 0: one thread per element (MSTDPET, batch 1).
+static int launch_mstdp_traces(float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                               const uint8_t *s_tgt, long n_src, long n_tgt, float a_plus, float a_minus, float decay_plus, float decay_minus,
+                               long max_blocks, hipStream_t st) {
+    long blocks = (n_src + n_tgt + 255) / 256;
+    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+    hipLaunchKernelGGL(k_mstdp_traces, dim3((unsigned)blocks), dim3(256), 0, st, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, n_src,
+                       n_tgt, a_plus, a_minus, decay_plus, decay_minus);
+    return snn_check_launch();
 }
 
 // f4: PostPre on a Conv2dConnection (learning.py:457-497).  Phase 1: one thread per (sample, weight element) sums its
@@ -999,47 +1012,40 @@ extern "C" int snn_conv2d_mstdp_step(float *W, float *elig, float *p_plus, float
     return snn_check_launch();
 }
 
+// f3: Hebbian (weight_dependent = 0) / WeightDependentPostPre (1).  A bound of the weight-dependent form may come from `sp`.
+static int hebbian_dense(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Nin, int N,
+                         float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin, int has_max, float wmax,
+                         const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
+    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
+    if (weight_dependent && !((has_min || (sp && sp->wmin)) && (has_max || (sp && sp->wmax)))) return SNN_ERR_INVALID;   // learning.py:600-602: finite wmin and wmax
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    StdpArgs a{.W = W, .s_src = s_src, .x_src = x_src, .s_tgt = s_tgt, .x_tgt = x_tgt, .B = B, .Nin = Nin, .N = N, .nu0 = nu0, .nu1 = nu1,
+               .use_dt = 0, .dt = 1.f, .decay = decay, .has_min = has_min, .wmin = wmin, .has_max = has_max, .wmax = wmax,
+               .assume_clamped = 0, .mode = weight_dependent ? 3 : 2, .reward = 0.f, .reward_vec = nullptr};
+    if (sp) syn_rates(a, *sp);
+    return launch_plasticity_for(a, sp, reduce, (hipStream_t)stream);
+}
+
 extern "C" int snn_stdp_hebbian(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt,
                                 int B, int Nin, int N, float nu0, float nu1, int weight_dependent, float decay, int has_min,
                                 float wmin, int has_max, float wmax, snn_stream_t stream) {
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
-    if (weight_dependent && !(has_min && has_max)) return SNN_ERR_INVALID;      // learning.py:600-602: finite wmin and wmax
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, 0, 1.f, decay, has_min, wmin, has_max, wmax, 0,
-               weight_dependent ? 3 : 2, 0.f, nullptr};
-    return launch_plasticity(a, (hipStream_t)stream);
+    return hebbian_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax, nullptr,
+                         SNN_REDUCE_SUM, stream);
 }
 
 extern "C" int snn_stdp_hebbian_pv(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
                                    int Nin, int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin,
                                    int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
-    if (!syn_any(sp))
-        return snn_stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax,
-                                stream);
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
-    if (weight_dependent && !((has_min || sp->wmin) && (has_max || sp->wmax))) return SNN_ERR_INVALID;   // learning.py:600-602
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, 0, 1.f, decay, has_min, wmin, has_max, wmax, 0,
-               weight_dependent ? 3 : 2, 0.f, nullptr};
-    syn_rates(a, *sp);
-    return launch_plasticity_pv(a, *sp, (hipStream_t)stream);
+    return hebbian_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax, sp,
+                         SNN_REDUCE_SUM, stream);
 }
 
 extern "C" int snn_stdp_hebbian_red(float *W, const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B,
                                     int Nin, int N, float nu0, float nu1, int weight_dependent, float decay, int has_min, float wmin,
                                     int has_max, float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream) {
-    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
-    if (reduce == SNN_REDUCE_SUM)
-        return snn_stdp_hebbian_pv(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax,
-                                   sp, stream);
-    if (!W || !s_src || !x_src || !s_tgt || !x_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N)) return SNN_ERR_INVALID;
-    if (weight_dependent && !((has_min || (sp && sp->wmin)) && (has_max || (sp && sp->wmax)))) return SNN_ERR_INVALID;   // learning.py:600-602
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, 0, 1.f, decay, has_min, wmin, has_max, wmax, 0,
-               weight_dependent ? 3 : 2, 0.f, nullptr};
-    const snn_synparams q = sp ? *sp : snn_synparams{};
-    syn_rates(a, q);
-    return launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
+    return hebbian_dense(W, s_src, x_src, s_tgt, x_tgt, B, Nin, N, nu0, nu1, weight_dependent, decay, has_min, wmin, has_max, wmax, sp,
+                         reduce, stream);
 }
 
 // The per-synapse instance of k_mstdpet: the element's own nu0 inside ((nu0 * dt) * reward), its own bounds in the clamp.
@@ -1056,50 +1062,6 @@ __global__ __launch_bounds__(256) void k_mstdpet_pv(float *__restrict__ W, float
         const float w = syn_mstdpet(W[e], &e_trace[e], el, decay_e, tc_e, c.nu0, dt, reward);
         W[e] = syn_finish(w, wdecay, c.lo, c.hi);
     }
-}
-
-extern "C" int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
-                                   const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt,
-                                   float a_plus, float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e,
-                                   float wdecay, int has_min, float wmin, int has_max, float wmax, const snn_synparams *sp,
-                                   snn_stream_t stream) {
-    if (!syn_any(sp))
-        return snn_mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, Nin, N, reward, nu0, dt, a_plus, a_minus,
-                                decay_plus, decay_minus, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, stream);
-    if (!W || !e_trace || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
-        return SNN_ERR_INVALID;
-    const long E = (long)Nin * N;
-    const unsigned grid = (unsigned)((E + 255) / 256 < 4096 ? (E + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_mstdpet_pv, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev,
-                       Nin, N, nu0, dt, reward, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, *sp);
-    int rc = snn_check_launch();
-    if (rc) return rc;
-    const long n = (long)Nin + N;
-    hipLaunchKernelGGL(k_mstdp_traces, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
-                       s_tgt_prev, s_src, s_tgt, (long)Nin, (long)N, a_plus, a_minus, decay_plus, decay_minus);
-    return snn_check_launch();
-}
-
-extern "C" int snn_mstdp_step_pv(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
-                                 const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
-                                 float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
-                                 int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
-    if (!syn_any(sp))
-        return snn_mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
-                              decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, stream);
-    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
-        return SNN_ERR_INVALID;
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    StdpArgs a{W, s_src_prev, p_plus, s_tgt_prev, p_minus, B, Nin, N, nu0, 0.f, 0, 1.f, wdecay, has_min, wmin,
-               has_max, wmax, 0, 1, reward, reward_vec};
-    int rc = launch_plasticity_pv(a, *sp, (hipStream_t)stream);
-    if (rc) return rc;
-    const long n = (long)B * (Nin + N);
-    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
-                       s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
-                       decay_minus);
-    return snn_check_launch();
 }
 
 // MSTDPET (learning.py:2187-2248, batch 1): the eligibility TRACE is genuinely dense state; the point eligibility is the
@@ -1123,22 +1085,63 @@ __global__ __launch_bounds__(256) void k_mstdpet(float *__restrict__ W, float *_
     }
 }
 
+// (1) the weights from the OLD p_plus / p_minus and previous-step spikes, (2) the traces.  Per-synapse nu0 / bounds: k_mstdpet_pv.
+static int mstdpet_dense(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
+                         const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt, float a_plus,
+                         float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e, float wdecay, int has_min, float wmin,
+                         int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
+    if (!W || !e_trace || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
+        return SNN_ERR_INVALID;
+    const long E = (long)Nin * N;
+    const unsigned grid = (unsigned)((E + 255) / 256 < 4096 ? (E + 255) / 256 : 4096);
+    if (syn_any(sp)) {
+        hipLaunchKernelGGL(k_mstdpet_pv, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev,
+                           Nin, N, nu0, dt, reward, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, *sp);
+    } else {
+        const float scale = (nu0 * dt) * reward;        // ((nu[0] * dt) * reward) * eligibility_trace
+        hipLaunchKernelGGL(k_mstdpet, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev,
+                           Nin, N, scale, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax);
+    }
+    int rc = snn_check_launch();
+    if (rc) return rc;
+    return launch_mstdp_traces(p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, Nin, N, a_plus, a_minus, decay_plus, decay_minus, 0,
+                               (hipStream_t)stream);
+}
+
 extern "C" int snn_mstdpet_step(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
                                 const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt,
                                 float a_plus, float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e,
                                 float wdecay, int has_min, float wmin, int has_max, float wmax, snn_stream_t stream) {
-    if (!W || !e_trace || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || Nin <= 0 || N <= 0) return SNN_ERR_INVALID;
-    const long E = (long)Nin * N;
-    const unsigned grid = (unsigned)((E + 255) / 256 < 4096 ? (E + 255) / 256 : 4096);
-    const float scale = (nu0 * dt) * reward;            // ((nu[0] * dt) * reward) * eligibility_trace
-    hipLaunchKernelGGL(k_mstdpet, dim3(grid), dim3(256), 0, (hipStream_t)stream, W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev,
-                       Nin, N, scale, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax);
-    int rc = snn_check_launch();
+    return mstdpet_dense(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, Nin, N, reward, nu0, dt, a_plus, a_minus,
+                         decay_plus, decay_minus, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, nullptr, stream);
+}
+
+extern "C" int snn_mstdpet_step_pv(float *W, float *e_trace, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
+                                   const uint8_t *s_src, const uint8_t *s_tgt, int Nin, int N, float reward, float nu0, float dt,
+                                   float a_plus, float a_minus, float decay_plus, float decay_minus, float decay_e, float tc_e,
+                                   float wdecay, int has_min, float wmin, int has_max, float wmax, const snn_synparams *sp,
+                                   snn_stream_t stream) {
+    return mstdpet_dense(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, Nin, N, reward, nu0, dt, a_plus, a_minus,
+                         decay_plus, decay_minus, decay_e, tc_e, wdecay, has_min, wmin, has_max, wmax, sp, stream);
+}
+
+// MSTDP (StdpArgs mode 1).  (1) W += nu0 * reduce_b reward * elig_prev[b]; decay; clamp -- uses the OLD p_plus / p_minus; with another
+// reduction the samples without a previous-step spike on the element are zero terms.  (2) the traces.
+static int mstdp_dense(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                       const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0, float a_plus,
+                       float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin, int has_max, float wmax,
+                       const snn_synparams *sp, int reduce, snn_stream_t stream) {
+    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
+    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
+        return SNN_ERR_INVALID;
+    if (B > 256) return SNN_ERR_UNSUPPORTED;
+    const StdpArgs a{.W = W, .s_src = s_src_prev, .x_src = p_plus, .s_tgt = s_tgt_prev, .x_tgt = p_minus, .B = B, .Nin = Nin, .N = N,
+                     .nu0 = nu0, .nu1 = 0.f, .use_dt = 0, .dt = 1.f, .decay = wdecay, .has_min = has_min, .wmin = wmin, .has_max = has_max,
+                     .wmax = wmax, .assume_clamped = 0, .mode = 1, .reward = reward, .reward_vec = reward_vec};
+    int rc = launch_plasticity_for(a, sp, reduce, (hipStream_t)stream);      // (nu0 is read per element through syn_elem: no syn_rates)
     if (rc) return rc;
-    const long n = (long)Nin + N;
-    hipLaunchKernelGGL(k_mstdp_traces, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
-                       s_tgt_prev, s_src, s_tgt, (long)Nin, (long)N, a_plus, a_minus, decay_plus, decay_minus);
-    return snn_check_launch();
+    return launch_mstdp_traces(p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
+                               decay_minus, 2048, (hipStream_t)stream);
 }
 
 extern "C" int snn_mstdp_step(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev,
@@ -1146,46 +1149,24 @@ extern "C" int snn_mstdp_step(float *W, float *p_plus, float *p_minus, uint8_t *
                               const float *reward_vec, float nu0, float a_plus, float a_minus, float decay_plus,
                               float decay_minus, float wdecay, int has_min, float wmin, int has_max, float wmax,
                               snn_stream_t stream) {
-    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0)
-        return SNN_ERR_INVALID;
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    // (1) W += nu0 * sum_b reward * elig_prev[b]; decay; clamp -- uses the OLD p_plus/p_minus.
-    StdpArgs a{W, s_src_prev, p_plus, s_tgt_prev, p_minus, B, Nin, N, nu0, 0.f, 0, 1.f, wdecay, has_min, wmin,
-               has_max, wmax, 0, 1, reward, reward_vec};
-    int rc = launch_plasticity(a, (hipStream_t)stream);
-    if (rc) return rc;
-    // (2) trace updates + remember this step's spikes as the factors of the next eligibility.
-    const long n = (long)B * (Nin + N);
-    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
-                       s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
-                       decay_minus);
-    return snn_check_launch();
+    return mstdp_dense(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                       decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, nullptr, SNN_REDUCE_SUM, stream);
+}
+
+extern "C" int snn_mstdp_step_pv(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
+                                 const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
+                                 float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
+                                 int has_max, float wmax, const snn_synparams *sp, snn_stream_t stream) {
+    return mstdp_dense(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                       decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, sp, SNN_REDUCE_SUM, stream);
 }
 
 extern "C" int snn_mstdp_step_red(float *W, float *p_plus, float *p_minus, uint8_t *s_src_prev, uint8_t *s_tgt_prev, const uint8_t *s_src,
                                   const uint8_t *s_tgt, int B, int Nin, int N, float reward, const float *reward_vec, float nu0,
                                   float a_plus, float a_minus, float decay_plus, float decay_minus, float wdecay, int has_min, float wmin,
                                   int has_max, float wmax, const snn_synparams *sp, int reduce, snn_stream_t stream) {
-    if (!reduce_valid(reduce)) return SNN_ERR_INVALID;
-    if (reduce == SNN_REDUCE_SUM)
-        return snn_mstdp_step_pv(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
-                                 decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, sp, stream);
-    if (!W || !p_plus || !p_minus || !s_src_prev || !s_tgt_prev || !s_src || !s_tgt || B <= 0 || Nin <= 0 || N <= 0 || !syn_valid(sp, N))
-        return SNN_ERR_INVALID;
-    if (B > 256) return SNN_ERR_UNSUPPORTED;
-    // (1) W += nu0 * reduce_b reward * elig_prev[b]; decay; clamp -- the samples without a previous-step spike on the element are zero terms
-    StdpArgs a{W, s_src_prev, p_plus, s_tgt_prev, p_minus, B, Nin, N, nu0, 0.f, 0, 1.f, wdecay, has_min, wmin,
-               has_max, wmax, 0, 1, reward, reward_vec};
-    const snn_synparams q = sp ? *sp : snn_synparams{};
-    int rc = launch_plasticity_red(a, q, reduce, (hipStream_t)stream);
-    if (rc) return rc;
-    const long n = (long)B * (Nin + N);
-    const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_mstdp_traces, dim3(grid), dim3(256), 0, (hipStream_t)stream, p_plus, p_minus, s_src_prev,
-                       s_tgt_prev, s_src, s_tgt, (long)B * Nin, (long)B * N, a_plus, a_minus, decay_plus,
-                       decay_minus);
-    return snn_check_launch();
+    return mstdp_dense(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, B, Nin, N, reward, reward_vec, nu0, a_plus, a_minus,
+                       decay_plus, decay_minus, wdecay, has_min, wmin, has_max, wmax, sp, reduce, stream);
 }
 
 // =============================================================================================

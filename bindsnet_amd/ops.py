@@ -576,30 +576,16 @@ def stdp_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, use_dt, dt=1.0, decay=
     "amax" or "amin" (the *_red entry points, include/snnhip.h f15)."""
     B = s_src.shape[0]
     Nin, N = W.shape
-    if W.dtype in HALF and _reduce(reduce):
+    if W.dtype in HALF:                 # (every element is visited: assume_clamped has nothing to skip)
         check(lib().snn_stdp_postpre_h16_red(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
                                              _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax),
-                                             _reduce(reduce), _stream()), "stdp_postpre_h16_red")
+                                             _reduce(reduce), _stream()), "stdp_postpre_h16")
         return
-    if W.dtype in HALF:                 # (every element is visited: assume_clamped has nothing to skip)
-        check(lib().snn_stdp_postpre_h16(_ptr(W, W.dtype), HALF[W.dtype], _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
-                                         _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *_bounds(wmin, wmax), _stream()),
-              "stdp_postpre_h16")
-        return
+    # the entry point chooses the instance: another batch reduction, per-synapse rates / bounds (include/snnhip.h f13), or the scalar kernel
     nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
-    if _reduce(reduce):                 # another batch reduction, per-synapse constants or not
-        check(lib().snn_stdp_postpre_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                         B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped),
-                                         None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "stdp_postpre_red")
-        return
-    if sp is not None:                  # per-synapse rates / bounds (include/snnhip.h f13)
-        check(lib().snn_stdp_postpre_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                        B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped), C.byref(sp),
-                                        _stream()), "stdp_postpre_pv")
-        return
-    check(lib().snn_stdp_postpre(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"),
-                                 _ptr(x_tgt, F32), B, Nin, N, nu0, nu1, int(use_dt), dt, decay,
-                                 *bounds, int(assume_clamped), _stream()), "stdp_postpre")
+    check(lib().snn_stdp_postpre_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                     B, Nin, N, nu0, nu1, int(use_dt), dt, decay, *bounds, int(assume_clamped),
+                                     None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "stdp_postpre")
 
 
 def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, a_plus, a_minus,
@@ -607,22 +593,10 @@ def mstdp_step(W, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward,
     B = s_src.shape[0]
     Nin, N = W.shape
     nu0, _, bounds, sp, _keep = _syn(W, nu0, 0.0, wmin, wmax)
-    if _reduce(reduce):
-        check(lib().snn_mstdp_step_red(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
-                                       _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
-                                       reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
-                                       wdecay, *bounds, None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "mstdp_step_red")
-        return
-    if sp is not None:
-        check(lib().snn_mstdp_step_pv(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
-                                      _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
-                                      reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
-                                      wdecay, *bounds, C.byref(sp), _stream()), "mstdp_step_pv")
-        return
-    check(lib().snn_mstdp_step(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
-                               _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
-                               reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
-                               wdecay, *bounds, _stream()), "mstdp_step")
+    check(lib().snn_mstdp_step_red(_ptr(W, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                   _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), B, Nin, N,
+                                   reward, _ptr(reward_vec, F32, True), nu0, a_plus, a_minus, decay_plus, decay_minus,
+                                   wdecay, *bounds, None if sp is None else C.byref(sp), _reduce(reduce), _stream()), "mstdp_step")
 
 
 def conv2d_postpre(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, stride=1, pad=0, decay=1.0, wmin=None, wmax=None, ws=None, reduce="sum"):
@@ -674,35 +648,19 @@ def stdp_hebbian(W, s_src, x_src, s_tgt, x_tgt, nu0, nu1, weight_dependent=False
     B = s_src.shape[0]
     Nin, N = W.shape
     nu0, nu1, bounds, sp, _keep = _syn(W, nu0, nu1, wmin, wmax)
-    if _reduce(reduce):
-        check(lib().snn_stdp_hebbian_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                         B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, None if sp is None else C.byref(sp),
-                                         _reduce(reduce), _stream()), "stdp_hebbian_red")
-        return
-    if sp is not None:
-        check(lib().snn_stdp_hebbian_pv(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                        B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, C.byref(sp), _stream()),
-              "stdp_hebbian_pv")
-        return
-    check(lib().snn_stdp_hebbian(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
-                                 B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, _stream()),
-          "stdp_hebbian")
+    check(lib().snn_stdp_hebbian_red(_ptr(W, F32), _ptr(s_src, "spike"), _ptr(x_src, F32), _ptr(s_tgt, "spike"), _ptr(x_tgt, F32),
+                                     B, Nin, N, nu0, nu1, int(weight_dependent), decay, *bounds, None if sp is None else C.byref(sp),
+                                     _reduce(reduce), _stream()), "stdp_hebbian")
 
 
 def mstdpet_step(W, e_trace, p_plus, p_minus, s_src_prev, s_tgt_prev, s_src, s_tgt, reward, nu0, dt, a_plus, a_minus,
                  decay_plus, decay_minus, decay_e, tc_e, wdecay=1.0, wmin=None, wmax=None):
     Nin, N = W.shape
     nu0, _, bounds, sp, _keep = _syn(W, nu0, 0.0, wmin, wmax)
-    if sp is not None:
-        check(lib().snn_mstdpet_step_pv(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
-                                        _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
-                                        a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *bounds, C.byref(sp),
-                                        _stream()), "mstdpet_step_pv")
-        return
-    check(lib().snn_mstdpet_step(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
-                                 _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
-                                 a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *bounds, _stream()),
-          "mstdpet_step")
+    check(lib().snn_mstdpet_step_pv(_ptr(W, F32), _ptr(e_trace, F32), _ptr(p_plus, F32), _ptr(p_minus, F32), _ptr(s_src_prev, "spike"),
+                                    _ptr(s_tgt_prev, "spike"), _ptr(s_src, "spike"), _ptr(s_tgt, "spike"), Nin, N, reward, nu0, dt,
+                                    a_plus, a_minus, decay_plus, decay_minus, decay_e, tc_e, wdecay, *bounds,
+                                    None if sp is None else C.byref(sp), _stream()), "mstdpet_step")
 
 
 def _ring(ring, W, K):

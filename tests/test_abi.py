@@ -31,6 +31,82 @@ def test_entry_points_validate_arguments_without_a_gpu():
     assert L.snn_stdp_postpre(1, 1, 1, 1, 1, 300, 4, 4, 0.1, 0.1, 1, 1.0, 1.0, 0, 0.0, 0, 0.0, 0, None) == -2
     assert L.snn_normalize(None, 1, 1, 1.0, 0, None, None) == -1
     assert L.snn_net_run(None, 0, None, 0, None, None) == -1
+    for name, kw, want in _DENSE_RULE_ROWS:
+        assert _call_dense_rule(L, name, **kw) == want, (name, kw)
+    assert {name for name, _, _ in _DENSE_RULE_ROWS} == set(_DENSE_RULE_NAMES)
+
+
+# The eleven entry points of the dense learning rules (scalar, *_pv: per-synapse constants, *_red: another batch reduction) and the
+# return code of argument combinations that are refused before any launch.  Pointers are dummies: nothing here may reach the device.
+_DENSE_RULE_NAMES = ("snn_stdp_postpre", "snn_stdp_postpre_pv", "snn_stdp_postpre_red", "snn_stdp_hebbian", "snn_stdp_hebbian_pv",
+                     "snn_stdp_hebbian_red", "snn_mstdp_step", "snn_mstdp_step_pv", "snn_mstdp_step_red", "snn_mstdpet_step",
+                     "snn_mstdpet_step_pv")
+
+
+def _call_dense_rule(L, name, W=1, B=2, Nin=4, N=4, wd=0, bounds=(0, 0.0, 0, 0.0), sp=None, reduce=0):
+    """One call of a dense-rule entry point with dummy pointers; `sp`: SynParams fields, `reduce`: SNN_REDUCE_* (the *_red names)."""
+    import ctypes as C
+    from bindsnet_amd import _lib
+    tail = []
+    if name.endswith(("_pv", "_red")):
+        tail.append(None if sp is None else C.byref(_lib.SynParams(**sp)))
+    if name.endswith("_red"):
+        tail.append(reduce)
+    tail.append(None)                                   # stream
+    if "postpre" in name:
+        args = [W, 1, 1, 1, 1, B, Nin, N, 0.1, 0.1, 1, 1.0, 1.0, *bounds, 0]
+    elif "hebbian" in name:
+        args = [W, 1, 1, 1, 1, B, Nin, N, 0.1, 0.1, wd, 1.0, *bounds]
+    elif "mstdpet" in name:
+        args = [W, 1, 1, 1, 1, 1, 1, 1, Nin, N] + [1.0] * 10 + [*bounds]
+    else:
+        args = [W, 1, 1, 1, 1, 1, 1, B, Nin, N, 1.0, None, 0.1, 1.0, 1.0, 0.9, 0.9, 1.0, *bounds]
+    return getattr(L, name)(*args, *tail)
+
+
+def _dense_rule_rows():
+    INVALID, UNSUPPORTED = -1, -2
+    batched = [n for n in _DENSE_RULE_NAMES if "mstdpet" not in n]
+    red = [n for n in _DENSE_RULE_NAMES if n.endswith("_red")]
+    syn = [n for n in _DENSE_RULE_NAMES if n.endswith(("_pv", "_red"))]
+    hebb = [n for n in _DENSE_RULE_NAMES if "hebbian" in n]
+    rows = []
+    rows += [(n, dict(W=None), INVALID) for n in _DENSE_RULE_NAMES]                   # a null W
+    rows += [(n, dict(N=0), INVALID) for n in _DENSE_RULE_NAMES]                      # N = 0
+    rows += [(n, dict(B=257), UNSUPPORTED) for n in batched]                          # more samples than the tile's masks hold
+    rows += [(n, dict(B=257, N=0), INVALID) for n in batched]                         # ... decided behind the arguments' validity
+    rows += [(n, dict(B=257, reduce=r), UNSUPPORTED) for n in red for r in (1, 2, 3)]
+    rows += [(n, dict(reduce=r), INVALID) for n in red for r in (-1, 4, 99)]          # an invalid reduce
+    rows += [(n, dict(B=257, reduce=99), INVALID) for n in red]                       # ... is refused first
+    rows += [(n, dict(W=None, reduce=1), INVALID) for n in red]
+    # weight-dependent without bounds, with one bound, with both
+    rows += [(n, dict(wd=1), INVALID) for n in hebb]
+    rows += [(n, dict(wd=1, B=257), INVALID) for n in hebb]
+    rows += [(n, dict(wd=1, B=257, bounds=(1, 0.0, 0, 0.0)), INVALID) for n in hebb]
+    rows += [(n, dict(wd=1, B=257, bounds=(1, 0.0, 1, 1.0)), UNSUPPORTED) for n in hebb]
+    rows += [("snn_stdp_hebbian_red", dict(wd=1, reduce=1), INVALID), ("snn_stdp_hebbian_red", dict(wd=1, B=257, reduce=2), INVALID)]
+    # ... with the bounds only in sp: the scalar name has no sp and refuses (above); *_pv and *_red get past the check
+    both = dict(wmin=1, wmax=1)
+    rows += [(n, dict(wd=1, B=257, sp=both), UNSUPPORTED) for n in hebb[1:]]
+    rows += [(n, dict(wd=1, B=257, sp=dict(wmin=1)), INVALID) for n in hebb[1:]]
+    rows += [(n, dict(wd=1, B=257, sp=dict(wmax=1), bounds=(1, 0.0, 0, 0.0)), UNSUPPORTED) for n in hebb[1:]]
+    rows += [("snn_stdp_hebbian_red", dict(wd=1, B=257, sp=both, reduce=3), UNSUPPORTED),
+             ("snn_stdp_hebbian_red", dict(wd=1, B=257, sp=dict(wmin=1), reduce=3), INVALID)]
+    # a rate tensor with a row stride: PostPre refuses it (its rates sit inside the batch sums), the other rules take it
+    row = dict(nu0=1, nu0_rs=1)
+    rows += [(n, dict(B=257, sp=row), INVALID if "postpre" in n else UNSUPPORTED) for n in syn if "mstdpet" not in n]
+    rows += [(n, dict(B=257, sp=dict(nu1=1, nu1_rs=4, nu1_cs=1)), INVALID if "postpre" in n else UNSUPPORTED) for n in syn if "mstdpet" not in n]
+    rows += [(n, dict(B=257, sp=dict(nu0=1, nu0_cs=1)), UNSUPPORTED) for n in syn if "mstdpet" not in n]
+    rows += [("snn_stdp_postpre_red", dict(B=257, sp=row, reduce=1), INVALID), ("snn_stdp_postpre_red", dict(sp=row, reduce=2), INVALID),
+             ("snn_stdp_postpre_red", dict(B=257, sp=dict(nu0=1, nu0_cs=1), reduce=1), UNSUPPORTED)]
+    # strides that broadcast against no [Nin, N] matrix; on a field without a tensor they are not read
+    rows += [(n, dict(sp=dict(wmax=1, wmax_rs=3, wmax_cs=2)), INVALID) for n in syn]
+    rows += [(n, dict(B=257, sp=dict(wmax_rs=3, wmax_cs=2)), UNSUPPORTED) for n in syn if "mstdpet" not in n]
+    rows += [(n, dict(sp=dict(nu0=1, nu0_rs=5, nu0_cs=1), reduce=1), INVALID) for n in red]
+    return rows
+
+
+_DENSE_RULE_ROWS = _dense_rule_rows()
 
 
 def test_struct_layouts_match_header():

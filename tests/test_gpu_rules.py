@@ -215,3 +215,68 @@ def _mcc_mstdpet(name):
     with pytest.raises(NotImplementedError):
         X_.batch_size = 2
         rule.update(reward=0.3)
+
+
+def test_dense_rule_entry_points_agree():
+    """The scalar, *_pv and *_red names of a dense rule are one body (csrc/snn_ops.hip): from identical inputs, every name Python no longer
+    calls leaves the bits ops.* leaves -- the scalar name, *_pv with sp = NULL and *_red with sp = NULL and SUM; *_pv and *_red + SUM with an
+    [S, N] wmax in the same snn_synparams; for MSTDPET the scalar name and *_pv.  B = 3, Nin = 17, N = 33: one row past the 16-row tile, one
+    column past the 32-column class boundary of the ATen-ordered sums.  Weights, traces and the remembered spikes are compared as integers."""
+    import ctypes as C
+    from bindsnet_amd import ops
+    from bindsnet_amd._lib import lib
+    L, P, B, Nin, N = lib(), ops._ptr, 3, 17, 33
+    nu, lo, hi = (1e-2, 3e-2), 0.0, 1.0
+    hi_t = torch.from_numpy(synth.uniform_f32(704, (Nin, N), 0.5, 1.0))
+    W0 = synth.uniform_f32(700, (Nin, N), 0.0, 1.0)
+    s_src, s_tgt = dev(synth.dense_spikes(701, (B, Nin), 0.3)), dev(synth.dense_spikes(702, (B, N), 0.3))
+    x_src, x_tgt = dev(synth.uniform_f32(703, (B, Nin), 0.0, 1.0)), dev(synth.uniform_f32(705, (B, N), 0.0, 1.0))
+    # MSTDP's state behind W: p_plus, p_minus, s_src_prev, s_tgt_prev
+    traces = [synth.uniform_f32(706, (B, Nin), 0.0, 1.0), synth.uniform_f32(707, (B, N), -1.0, 0.0),
+              synth.dense_spikes(708, (B, Nin), 0.3), synth.dense_spikes(709, (B, N), 0.3)]
+
+    def as_int(t):
+        a = host(t)
+        return bits(a) if a.dtype == np.float32 else a.view(np.uint8)
+
+    def agree(base, state0, via_ops, args, red=True):
+        def run(call):
+            st = [dev(a.copy()) for a in state0]
+            keep = call(st)
+            torch.cuda.synchronize()
+            del keep
+            return [as_int(t) for t in st]
+
+        def native(suffix, wmax):
+            def call(st):
+                nu0, nu1, bounds, sp, keep = ops._syn(st[0], nu[0], nu[1], lo, wmax)
+                ref = None if sp is None else C.byref(sp)
+                tail = {"": [], "_pv": [ref], "_red": [ref, 0]}[suffix]
+                rc = getattr(L, base + suffix)(*args(st, nu0, nu1, bounds), *tail, ops._stream())
+                assert rc == 0, (base + suffix, rc)
+                return keep
+            return call
+
+        for wmax in (hi, hi_t):
+            want = run(lambda st: via_ops(st, wmax))
+            assert not np.array_equal(want[0], bits(W0)), base
+            for suffix in ["_pv"] + ["_red"] * red + [""] * (wmax is hi):
+                for k, (g, w) in enumerate(zip(run(native(suffix, wmax)), want)):
+                    np.testing.assert_array_equal(g, w, err_msg=f"{base}{suffix}, wmax {'scalar' if wmax is hi else '[S,N]'}, state {k}")
+
+    agree("snn_stdp_postpre", [W0],
+          lambda st, wmax: ops.stdp_postpre(st[0], s_src, x_src, s_tgt, x_tgt, nu[0], nu[1], True, 0.5, 0.99, lo, wmax),
+          lambda st, nu0, nu1, bounds: [P(st[0]), P(s_src), P(x_src), P(s_tgt), P(x_tgt), B, Nin, N, nu0, nu1, 1, 0.5, 0.99, *bounds, 0])
+    for wd in (0, 1):
+        agree("snn_stdp_hebbian", [W0],
+              lambda st, wmax: ops.stdp_hebbian(st[0], s_src, x_src, s_tgt, x_tgt, nu[0], nu[1], bool(wd), 0.99, lo, wmax),
+              lambda st, nu0, nu1, bounds: [P(st[0]), P(s_src), P(x_src), P(s_tgt), P(x_tgt), B, Nin, N, nu0, nu1, wd, 0.99, *bounds])
+    agree("snn_mstdp_step", [W0] + traces,
+          lambda st, wmax: ops.mstdp_step(*st, s_src, s_tgt, 0.7, nu[0], 1.0, -1.0, 0.9, 0.8, 0.99, lo, wmax),
+          lambda st, nu0, nu1, bounds: [*map(P, st), P(s_src), P(s_tgt), B, Nin, N, 0.7, None, nu0, 1.0, -1.0, 0.9, 0.8, 0.99, *bounds])
+    # MSTDPET, batch 1: the eligibility trace in front of MSTDP's state
+    et_state = [W0, synth.uniform_f32(710, (Nin, N), -0.5, 0.5)] + [a[0].copy() for a in traces]
+    agree("snn_mstdpet_step", et_state,
+          lambda st, wmax: ops.mstdpet_step(*st, s_src[0], s_tgt[0], 0.7, nu[0], 0.5, 1.0, -1.0, 0.9, 0.8, 0.95, 25.0, 0.99, lo, wmax),
+          lambda st, nu0, nu1, bounds: [*map(P, st), P(s_src[0]), P(s_tgt[0]), Nin, N, 0.7, nu0, 0.5, 1.0, -1.0, 0.9, 0.8, 0.95, 25.0, 0.99,
+                                        *bounds], red=False)
