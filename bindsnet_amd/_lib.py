@@ -100,7 +100,8 @@ class LayerDesc(C.Structure):
                 ("srm_eps0", C.c_float), ("srm_rho0", C.c_float), ("srm_dthresh", C.c_float),
                 ("srm_sprob", C.c_void_p), ("srm_rho", C.c_void_p),
                 ("csrm_xwin", C.c_void_p), ("csrm_last", C.c_void_p), ("csrm_resk", C.c_void_p), ("csrm_refk", C.c_void_p),
-                ("csrm_wres", C.c_int), ("csrm_wref", C.c_int), ("summed", C.c_void_p)]
+                ("csrm_wres", C.c_int), ("csrm_wref", C.c_int), ("summed", C.c_void_p),
+                ("ext_real", C.c_void_p), ("s_real", C.c_void_p), ("raster_real", C.c_void_p)]
 
 
 class SynParams(C.Structure):
@@ -204,6 +205,9 @@ _SIGS = {
     "snn_prop_meanfield_f32": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_dense_mfma_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
+    "snn_prop_dense_real_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_prop_conv2d_real_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
+    "snn_input_step_real_pv": ([_vp, _vp, _i, _i, _f, _f, _i, C.POINTER(PerVec), _vp, _vp], _i),
     "snn_prop_local_f32": ([_vp] * 4 + [_i] * 7 + [_vp], _i),
     "snn_local_postpre": ([_vp] * 6 + [_i] * 6 + [_f] * 3 + [_i, _f, _i, _f, _vp], _i),
     "snn_prop_convnd_f32": ([_vp] * 4 + [_i] * 12 + [_vp], _i),

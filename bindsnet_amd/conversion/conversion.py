@@ -18,7 +18,14 @@ with the batch-inclusive dims; a Conv2d without bias gets zeros(layer.shape[1]),
 grows by padding[0] + padding[1], the left and right pads.  Where the resulting graph cannot run, the run raises before it
 changes any state.  `torch.load` of a path is called as the reference calls it.
 
-On the device the limits of the parts apply: Conv2d with dilation 1, symmetric stride and padding; uint8 / bool input spikes; no
+How to drive it: `data_based_normalization` scales every layer by percentiles of the ANN's real-valued activations, so the network
+is meant to be fed the real-valued sample itself at every step (encoding.repeat / `image.repeat(time, ...)`), not a Poisson train.
+That analog input -- a float32 [T, B, *shape] entry of `inputs` -- runs on the device where the first child is a Linear or a Conv2d
+(csrc/snn_real.hip: the ordered dense product and convolution over real values, include/snnhip.h f17); uint8 / bool spike trains
+run as before, and float32 zeros and ones give the bits their bytes give.
+
+On the device the limits of the parts apply: Conv2d with dilation 1, symmetric stride and padding; an analog input into a
+PermuteConnection or ConstantPad2dConnection (a first child Permute / ConstantPad2d) raises; no
 fused plan (`network.last_plan == "generic"`); no monitor on `summed`.  A Conv2d with more than 16 input channels runs in the stated
 order of snn_prop_conv2d_f32 (include/snnhip.h): equal to the reference bit for bit where every partial sum is exact, else up to
 summation rounding."""

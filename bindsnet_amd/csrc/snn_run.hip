@@ -138,6 +138,7 @@ static int validate_layer(const snn_layer_desc &d, const snn_run_desc *R) {
         if (R->B > 65535 && d.kind != SNN_LAYER_SRM0 && d.kind != SNN_LAYER_CSRM && !(d.kind == SNN_LAYER_LIF && !snn::pervec_any(&d.pv))) return SNN_ERR_UNSUPPORTED;
     }
     if (d.summed && d.kind != SNN_LAYER_SIF) return SNN_ERR_INVALID;       // sum_input: SubtractiveResetIFNodes only
+    if (d.kind != SNN_LAYER_INPUT && (d.ext_real || d.s_real || d.raster_real)) return SNN_ERR_INVALID;
     switch (d.kind) {
         case SNN_LAYER_PASS:              // conversion/nodes.py:122: s = x, nothing else; x must be 0 or 1 (checked per connection below)
             if (!d.s || !d.current) return SNN_ERR_INVALID;
@@ -148,7 +149,10 @@ static int validate_layer(const snn_layer_desc &d, const snn_run_desc *R) {
             if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
             break;
         case SNN_LAYER_INPUT:
-            if (!d.ext_spikes || !d.s) return SNN_ERR_INVALID;
+            if (d.ext_real) {                  // a real-valued Input (snnhip.h f17): the float twins stand for ext_spikes / s / raster_s
+                if (!d.s_real || d.ext_spikes || d.s || d.raster_s) return SNN_ERR_INVALID;
+                if (R->B > 65535) return SNN_ERR_UNSUPPORTED;
+            } else if (!d.ext_spikes || !d.s || d.s_real || d.raster_real) return SNN_ERR_INVALID;
             if (d.p.lif.traces && !d.x) return SNN_ERR_INVALID;
             break;
         case SNN_LAYER_DC:
@@ -208,6 +212,10 @@ static int validate_conn(const snn_layer_desc *L, int nL, const snn_conn_desc &d
         if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
     } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL && d.kind != SNN_CONN_PERMUTE && d.kind != SNN_CONN_PAD) return SNN_ERR_INVALID;
     if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
+    if (L[d.src].kind == SNN_LAYER_INPUT && L[d.src].ext_real) {      // out of a real-valued Input: the two ordered products, propagation only
+        if ((d.kind != SNN_CONN_DENSE && d.kind != SNN_CONN_CONV2D) || d.window || L[d.dst].kind == SNN_LAYER_CSRM || d.rule != SNN_RULE_NONE)
+            return SNN_ERR_UNSUPPORTED;
+    }
     if ((L[d.dst].kind == SNN_LAYER_CSRM) != (d.window != 0)) return SNN_ERR_INVALID;      // topology.py:348: compute_window, and only there
     if (d.window) {                        // network.py:232-246: only Connection has a compute_window that runs
         if (d.kind != SNN_CONN_DENSE || !d.win_ring || d.win_size != L[d.dst].csrm_wres || d.win_head < 0 || d.win_head >= d.win_size) return SNN_ERR_INVALID;
@@ -332,9 +340,13 @@ static int validate(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int
 }
 
 // spikes of layer l as seen by connections BEFORE (after=false) / AFTER (after=true) its forward() at step t
-static const uint8_t *layer_spikes(const snn_layer_desc &d, int B, int t, bool after) {
+static const void *layer_spikes(const snn_layer_desc &d, int B, int t, bool after) {
     if (d.kind != SNN_LAYER_INPUT) return d.s;
     const size_t stride = (size_t)B * d.n;
+    if (d.ext_real) {                          // a real-valued Input: f32 slices
+        if (after) return d.ext_real + (size_t)t * stride;
+        return t == 0 ? d.s_real : d.ext_real + (size_t)(t - 1) * stride;
+    }
     if (after) return d.ext_spikes + (size_t)t * stride;
     return t == 0 ? d.s : d.ext_spikes + (size_t)(t - 1) * stride;
 }
@@ -354,9 +366,15 @@ static size_t conn_numel(const snn_conn_desc &d, const snn_layer_desc *L) {
 }
 
 // (1) one connection hands its source's spikes `sp` on to its target; `fed`: an earlier connection has written the target's currents
-static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_run_desc *R, int t, const uint8_t *sp, bool fed, hipStream_t st) {
+static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_run_desc *R, int t, const void *spv, bool fed, hipStream_t st) {
     const int B = R->B;
     const snn_layer_desc &S = L[d.src], &D = L[d.dst];
+    if (S.kind == SNN_LAYER_INPUT && S.ext_real) {      // (validate_conn: DENSE or CONV2D, no window, no rule)
+        const float *xr = (const float *)spv;
+        if (d.kind == SNN_CONN_DENSE) return snn_prop_dense_real_f32(d.w, d.bias, xr, D.current, B, S.n, D.n, fed ? 1 : 0, st);
+        return snn_prop_conv2d_real_f32(d.w, d.bias, xr, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, fed ? 1 : 0, st);
+    }
+    const uint8_t *sp = (const uint8_t *)spv;
     // traces=True: the connection's own sum goes to its activity buffer, k_feed_activity hands it on to the target below
     const int acc = d.activity ? 0 : fed ? 1 : 0;
     float *const out = d.activity ? d.activity : D.current;
@@ -409,6 +427,11 @@ static int step_layer(const snn_layer_desc &d, const snn_run_desc *R, int t, boo
     float *rv = d.raster_v ? d.raster_v + off : nullptr;
     const snn_pervec pvl = layer_pervec(d);
     const snn_pervec *pv = has_pervec(d) ? &pvl : nullptr;     // (NULL: every *_pv entry point is its scalar namesake)
+    if (d.kind == SNN_LAYER_INPUT && d.ext_real) {          // (the monitor's copy: snn_net_run, one copy behind the plan)
+        TRY(snn_input_step_real_pv(d.ext_real + off, d.p.lif.traces ? d.x : nullptr, B, d.n,
+                                   d.p.lif.trace_decay, d.p.lif.trace_scale, d.p.lif.traces_additive, pv, nullptr, st));
+        return SNN_OK;
+    }
     if (d.kind == SNN_LAYER_INPUT) {
         TRY(snn_input_step_pv(d.ext_spikes + off, d.p.lif.traces ? d.x : nullptr, B, d.n,
                               d.p.lif.trace_decay, d.p.lif.trace_scale, d.p.lif.traces_additive, pv, rs, st));
@@ -463,7 +486,7 @@ static int learn_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn
     const int B = R->B;
     if (d.rule == SNN_RULE_NONE) return SNN_OK;
     const snn_layer_desc &S = L[d.src], &D = L[d.dst];
-    const uint8_t *ss = layer_spikes(S, B, t, true);
+    const uint8_t *ss = (const uint8_t *)layer_spikes(S, B, t, true);      // (no rule reads a real-valued Input: validate_conn)
     if (d.rule == SNN_RULE_MSTDP && d.kind == SNN_CONN_CONV2D)
         TRY(snn_conv2d_mstdp_step(d.w, d.e_trace, d.p_plus, d.p_minus, ss, D.s, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride,
                                   d.pad, d.reward, d.nu0, d.a_plus, d.a_minus, d.decay_plus, d.decay_minus, d.wdecay,
@@ -533,7 +556,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
             for (int c = 0; c < nC; ++c) {
                 const snn_conn_desc &d = C[c];
                 if (only_dst >= 0 && d.dst != only_dst) continue;
-                const uint8_t *sp = layer_spikes(L[d.src], B, t, only_dst >= 0 && d.src < only_dst);
+                const void *sp = layer_spikes(L[d.src], B, t, only_dst >= 0 && d.src < only_dst);
                 TRY(feed_conn(L, d, R, t, sp, fed[d.dst], st));
                 fed[d.dst] = true;
             }
@@ -583,6 +606,16 @@ extern "C" int snn_net_run(const snn_layer_desc *L, int nL, const snn_conn_desc 
     hipStream_t st = (hipStream_t)stream;
     bool any = false;
     for (int l = 0; l < nL; ++l) any = any || (L[l].kind == SNN_LAYER_INPUT && L[l].raster_s);
+    for (int l = 0; l < nL; ++l)           // a real-valued Input's monitor: a copy of its f32 input, behind the run like the byte copy below
+        if (L[l].kind == SNN_LAYER_INPUT && L[l].ext_real && L[l].raster_real) {
+            std::vector<snn_layer_desc> Lr(L, L + nL);
+            for (int k = 0; k < nL; ++k) Lr[k].raster_real = nullptr;
+            TRY(snn_net_run(Lr.data(), nL, C, nC, R, stream));
+            for (int k = l; k < nL; ++k)
+                if (L[k].kind == SNN_LAYER_INPUT && L[k].ext_real && L[k].raster_real)
+                    TRY(snn_check(hipMemcpyAsync(L[k].raster_real, L[k].ext_real, sizeof(float) * (size_t)R->T * R->B * L[k].n, hipMemcpyDeviceToDevice, (hipStream_t)stream)));
+            return SNN_OK;
+        }
     if (!any) return net_run_plans(L, nL, C, nC, R, st);
     std::vector<snn_layer_desc> L2(L, L + nL);
     g_in_raster_done = 0;
@@ -629,6 +662,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     for (int c = 0; c < nC; ++c) if (C[c].avg_k != 0) local = true;             // ... and averaged updates (the fused plans keep no ring)
     for (int c = 0; c < nC; ++c) if (C[c].norm_step != 0) local = true;         // ... and a Weight normalised every timestep (no fused plan normalises inside its loop)
     for (int c = 0; c < nC; ++c) if (C[c].reduce != SNN_REDUCE_SUM) local = true;   // ... and a batch reduction other than sum (the fused plans sum)
+    for (int l = 0; l < nL; ++l) if (L[l].kind == SNN_LAYER_INPUT && L[l].ext_real) local = true;   // ... and a real-valued Input (the fused plans read spike bytes)
     if (local || other_nodes) { mode = 1; conv_rule = false; }
     if (conv_rule) {
         if (mode == 0 || mode == 3) TRY(snn_try_fused_convpp(L, nL, C, nC, R, st, &handled));

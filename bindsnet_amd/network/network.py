@@ -321,6 +321,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 inputs[key] = inputs[key].unsqueeze(1)
         self._csrm_refusals(inputs)                        # what a CSRMNodes layer cannot run: before the run changes any state
         self._layer_refusals(inputs, injects_v)            # ... and what a layer knows it cannot run on the device
+        self._analog_refusals(inputs)                      # ... and what a real-valued (float32) input cannot drive there
         for key in inputs:
             if inputs[key].size(1) != self.batch_size:
                 self.batch_size = inputs[key].size(1)
@@ -445,6 +446,51 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                 err = layer._run_refusal(name, feeders, name in inputs, injects_v.get(name) is not None)
                 if err is not None:
                     raise err
+
+    def _is_analog(self, layer, x) -> bool:
+        """Whether this run drives the Input `layer` with real values: a float32 entry of `inputs`, or a byte train behind a float32
+        `s` that an analog run left and nobody reset -- connections read that `s` at t = 0, so the run is promoted to float32
+        (exact: float32 zeros and ones give the bits their bytes give, include/snnhip.h f17)."""
+        if x.dtype == torch.float32:
+            return True
+        left = getattr(layer, "s", None)
+        return x.dtype in (torch.uint8, torch.bool) and isinstance(left, torch.Tensor) and left.dtype == torch.float32 \
+            and left.numel() == x[0].numel() and bool(left.ne(0).any())
+
+    def _analog_refusals(self, inputs) -> None:
+        """A real-valued input on the device (snnhip.h f17): float32, into Connection / Conv2dConnection without a rule, no CSRMNodes
+        target.  Raised before anything changes."""
+        if self._device().type != "cuda":
+            return
+        from .topology import Connection, Conv2dConnection
+        for name, layer in self.layers.items():
+            x = inputs.get(name)
+            if not isinstance(layer, Input) or x is None:
+                continue
+            if x.is_floating_point() and x.dtype != torch.float32:
+                raise NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}: a real-valued (analog) input must be float32 on "
+                                          "the device; call .float() on it")
+            if not self._is_analog(layer, x):
+                continue
+            if not any(getattr(conn, "source", None) is layer for conn in self.connections.values()):
+                # (real values are defined by what reads them: without a Connection or Conv2dConnection the device has no use for them)
+                raise NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}, but no Connection or Conv2dConnection reads the "
+                                          f"Input layer '{name}': a real-valued (analog) input is accepted for those two classes; "
+                                          "spike trains are uint8 or bool")
+            for (src, dst), conn in self.connections.items():
+                if getattr(conn, "source", None) is not layer:
+                    continue
+                if type(conn) not in (Connection, Conv2dConnection):
+                    raise NotImplementedError(f"bindsnet_amd: {type(conn).__name__} out of the Input layer '{name}' takes no real-valued "
+                                              "(analog) values on the device: its input spike trains must be uint8 or bool "
+                                              f"(got {x.dtype}); a float32 input drives Connection and Conv2dConnection only")
+                rule = conn._rule()
+                if type(rule).__name__ != "NoOp":
+                    raise NotImplementedError(f"bindsnet_amd: {type(rule).__name__} on a connection out of the Input layer '{name}' "
+                                              "cannot learn from a real-valued (analog) input on the device; use no rule (NoOp)")
+                if isinstance(self.layers[dst], CSRMNodes):
+                    raise NotImplementedError(f"bindsnet_amd: a real-valued (analog) input into the CSRMNodes layer '{dst}' is not "
+                                              "supported on the device (its window holds spike bytes)")
 
     def _csrm_refusals(self, inputs) -> None:
         """CSRMNodes layers (nodes.py:1319): what the reference's first step would raise half-way through it -- kernels that do not
@@ -673,12 +719,31 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             x = inputs[name]
             if x.shape[0] < T:
                 raise ValueError(f"inputs['{name}'] has {x.shape[0]} timesteps, run() needs {T}")
-            if x.dtype not in (torch.uint8, torch.bool):
-                raise NotImplementedError("bindsnet_amd: input spike trains must be uint8 or bool "
-                                          f"(got {x.dtype}); encoders produce uint8")
+            if x.dtype not in (torch.uint8, torch.bool, torch.float32):
+                raise NotImplementedError("bindsnet_amd: input spike trains must be uint8 or bool, or float32 for a real-valued "
+                                          f"(analog) input (got {x.dtype}); encoders produce uint8")
+            analog = self._is_analog(layer, x)             # (what it may drive: _analog_refusals, before the run began)
             x = x.to(dev).contiguous()
             if x.numel() != x.shape[0] * B * layer.n:
                 raise ValueError(f"inputs['{name}'] has shape {tuple(x.shape)}, expected [T, {B}, {layer.n}]")
+            if analog:                                 # a real-valued Input (snnhip.h f17): the float twins of ext_spikes / s / raster_s
+                x = x.float()                          # (a byte train behind a float `s` left by an analog run: promoted, exact)
+                entry = layer.s
+                if entry.numel() != B * layer.n or entry.device != dev:
+                    entry = torch.zeros(B, layer.n, dtype=torch.float32, device=dev)
+                entry = entry.float().contiguous()     # (a byte `s` left by a spike run: by value, as compute()'s s.float())
+                keep += [x, entry]
+                L[i].ext_spikes, L[i].s, L[i].raster_s = None, None, None
+                L[i].ext_real, L[i].s_real = _dptr(x), _dptr(entry)
+                if wanted:
+                    xcopy = torch.empty_like(x[:T])
+                    L[i].raster_real = _dptr(xcopy)
+                    rasters += [(m, key, xcopy.view(T, B, *layer.shape)) for m, key in wanted]
+                else:
+                    L[i].raster_real = None
+                inputs[name] = x
+                continue
+            L[i].ext_real, L[i].s_real, L[i].raster_real = None, None, None
             entry = layer.s
             if entry.dtype not in (torch.uint8, torch.bool) or entry.numel() != B * layer.n or entry.device != dev:
                 entry = torch.zeros(B, layer.n, dtype=torch.uint8, device=dev)

@@ -235,6 +235,10 @@ class Input(Nodes, AbstractInput):
         self.s = x
         if self.traces:
             pv = {}
+            if x.dtype == torch.float32:                  # a real-valued (analog) input: the trace reads the values themselves
+                ops.input_step_real(x.contiguous(), self.x, self._sv("trace_decay", pv), self._sv("trace_scale", pv),
+                                    self.traces_additive, pv=pv)
+                return
             ops.input_step(x.contiguous(), self.x, self._sv("trace_decay", pv), self._sv("trace_scale", pv), self.traces_additive,
                            pv=pv)
 

@@ -219,7 +219,12 @@ class _DenseConnection(AbstractConnection):
     _host_compute, _host_update = host_path._propagate_dense, host_path._update_dense
 
     def _prop_into(self, s, out, accumulate=False) -> None:
-        """s.view(B,-1) @ w (+ b) in canonical ascending-source order (topology.py:332-346)."""
+        """s.view(B,-1) @ w (+ b) in canonical ascending-source order (topology.py:332-346).  A float32 `s` on a Connection: the
+        same order over real values (ops.prop_dense_real)."""
+        if s.dtype == torch.float32 and type(self) is Connection:
+            ops.prop_dense_real(self.w.data, s.reshape(s.size(0), -1).contiguous(), out, bias=None if self.b is None else self.b.data,
+                                accumulate=accumulate)
+            return
         ops.prop_dense(self.w.data, s.reshape(s.size(0), -1).contiguous(), out, bias=None if self.b is None else self.b.data,
                        accumulate=accumulate)
 
@@ -850,6 +855,10 @@ class Conv2dConnection(AbstractConnection):
         return None
 
     def _prop_into(self, s, out, accumulate=False) -> None:
+        if s.dtype == torch.float32:                   # real-valued sources: the same tap order (ops.prop_conv2d_real)
+            ops.prop_conv2d_real(self.w.data, s.reshape(s.size(0), *self.source.shape).contiguous(), out, bias=self.b.data,
+                                 stride=self.stride[0], pad=self.padding[0], accumulate=accumulate)
+            return
         ops.prop_conv2d(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0],
                         accumulate=accumulate)
 

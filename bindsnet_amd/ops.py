@@ -171,6 +171,35 @@ def prop_conv2d(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
     return out
 
 
+def prop_dense_real(W, x, out, bias=None, accumulate=False):
+    """f17: out (+)= x @ W (+ b) over real-valued float32 sources x [B, Nin]: ascending-i sequential f32, one rounded multiply and
+    one rounded add per term, bias last (include/snnhip.h)."""
+    B = x.shape[0]
+    Nin, N = W.shape
+    assert x.numel() == B * Nin and out.numel() == B * N
+    check(lib().snn_prop_dense_real_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(x, F32), _ptr(out, F32), B, Nin, N,
+                                        int(accumulate), _stream()), "prop_dense_real")
+    return out
+
+
+def prop_conv2d_real(W, x, out, bias=None, stride=1, pad=0, accumulate=False):
+    """f17: F.conv2d on real-valued float32 sources in the order of prop_conv2d; x [B,Cin,H,W], W [Cout,Cin,KH,KW], out [B,Cout,OH,OW]."""
+    B, Cin, H, Wd = x.shape
+    Cout, Cin2, KH, KW = W.shape
+    assert Cin == Cin2
+    check(lib().snn_prop_conv2d_real_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(x, F32), _ptr(out, F32), B, Cin, H,
+                                         Wd, Cout, KH, KW, stride, pad, int(accumulate), _stream()), "prop_conv2d_real")
+    return out
+
+
+def input_step_real(s, x=None, trace_decay=0.0, trace_scale=1.0, additive=False, raster=None, pv=None):
+    """f17: the step of a real-valued Input layer, s float32 [B, ...]: the trace x (nullable) and the float32 raster (nullable)."""
+    B = s.shape[0]
+    arg, _keep = _pv(pv, s.numel() // B) if pv else (None, None)
+    check(lib().snn_input_step_real_pv(_ptr(s, F32), _ptr(x, F32, True), B, s.numel() // B, trace_decay, trace_scale,
+                                       int(additive), arg, _ptr(raster, F32, True), _stream()), "input_step_real")
+
+
 def prop_local(W, src, s, out, n_filters, accumulate=False):
     """f5: LocalConnection1D/2D/3D.compute; W [Cin, F*conv_prod, kernel_prod] f32, src int32 [Cin, conv_prod, kernel_prod],
     s [B, n_src] spikes, out [B, F*conv_prod]."""

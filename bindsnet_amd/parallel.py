@@ -155,6 +155,17 @@ def _reject_stochastic(network, mode: str) -> None:
                                       "the multi-device modes do not reproduce; run the network on one device")
 
 
+def _reject_analog(network, inputs, mode: str) -> None:
+    """A real-valued (float) input of an Input layer runs on one device only (Network.run, generic plan): the multi-device modes
+    exchange and merge spike bytes."""
+    from .network.nodes import Input
+    for name, layer in network.layers.items():
+        x = inputs.get(name) if isinstance(inputs, dict) else None
+        if isinstance(layer, Input) and isinstance(x, torch.Tensor) and x.dtype not in (torch.uint8, torch.bool):
+            raise NotImplementedError(f"bindsnet_amd: {mode} takes no real-valued (analog) input for the Input layer '{name}': its input "
+                                      f"spike trains must be uint8 or bool (got {x.dtype}); Network.run on one device takes float32")
+
+
 def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, **kwargs) -> None:
     """network.run on this rank's batch shard, then merge learning across ranks (see module doc): the weights and
     thresholds become  before + sum_over_ranks(after - before), are clamped, and only then normalised.  The post-run
@@ -164,6 +175,7 @@ def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None,
     _reject_stochastic(network, "sharded_run")
     _reject_pervec(network, "sharded_run", lif_thresh_ok=True)
     _reject_synparams(network, "sharded_run")
+    _reject_analog(network, inputs, "sharded_run")
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
     tensors = [t for t, _, _, _ in learned] + thetas
@@ -574,6 +586,7 @@ def exact_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, c
     from .network.nodes import DiehlAndCookNodes, Input
     assert type(inputs) == dict, "'inputs' must be a dict of names of layers (str) and relevant input tensors."
     _reject_local(network, "exact_run")                       # (before the batch size below is taken from the inputs)
+    _reject_analog(network, inputs, "exact_run")
     if comm is not None:
         world, rank = comm.world, comm.rank
     else:

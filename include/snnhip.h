@@ -161,6 +161,36 @@ int snn_prop_conv2d_f32(const float *W, const float *bias, const uint8_t *s, flo
                         int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
                         int stride, int pad, int accumulate, snn_stream_t stream);
 
+/* ---- f17: a real-valued (analog) Input layer -------------------------------------------------------
+ * The reference's Input.forward is `self.s = x` for any dtype (nodes.py:219) and every compute() starts with `s.float()`: a
+ * network may be driven by the real-valued sample itself at every step (encoding.repeat), which is how a network made by
+ * bindsnet.conversion is meant to be driven.  An INPUT layer may therefore be fed a FLOAT32 [T,B,n] tensor.  The arithmetic is
+ * the stated orders of a6 / a7 / the input step with the spike byte replaced by the real value x, every multiply and every add
+ * rounded on its own (-ffp-contract=off); csrc/snn_real.hpp holds the bodies.
+ *   Dense   out[b,j] (+)= (...((0 + x[b,0]*W[0,j]) + x[b,1]*W[1,j]) + ...) (+ bias[j]): source index ascending, one rounded
+ *           multiply and one rounded add per term, bias (nullable) last, accumulate as in snn_prop_dense_f32.  A kernel may skip a
+ *           source whose value is zero for all the samples it handles: the skipped term is +-0, a chain that starts at +0 never
+ *           becomes -0, so the result is the same for finite weights (a NaN or an infinite weight at such a source is not seen).
+ *   Conv2d  the order of snn_prop_conv2d_f32: one bias-free sequential sum over (kh, kw, cin), input channel innermost,
+ *           out-of-image taps skipped, one rounding per multiply and per add, bias last; zero values skipped as above.  Any Cin,
+ *           stride >= 1, pad >= 0; the SNN_ERR_UNSUPPORTED limits of snn_prop_conv2d_f32.
+ *   Input   s is the caller's slice; x = x * trace_decay, then x = trace_scale where s != 0 (set mode) or x = x + trace_scale * s
+ *           (additive: the product rounded, then the add); per-neuron trace_decay / trace_scale through pv as snn_input_step_pv.
+ * 0/1 invariance: values that are all 0.0 or 1.0 give, bit for bit, what the same values give as spike bytes through
+ * snn_prop_dense_f32 / snn_prop_conv2d_f32 / snn_input_step_pv (x * w is then w or +-0 exactly).
+ * snn_prop_dense_real_f32: thread <-> target column, each wave carries the chains of 2 samples (one load of W[i,j] serves the
+ * 8 samples of its workgroup), W and the samples' values are staged in LDS chunk by chunk, the skip is per wave.  No split-K, no
+ * matrix cores: snn_prop_dense_mfma_f32's equivalence holds for 0/1 operands only.  Limits: Nin < 2^24, B <= 65535.
+ * snn_prop_conv2d_real_f32: direct; 8 output channels per thread, their filters in LDS where Cin*KH*KW <= 1024, the block's
+ * images in LDS where they fit 48 KiB, else both through L2.  snn_input_step_real_pv: raster_out f32 (nullable), pv nullable,
+ * B <= 65535.  (ABI 8, additive)                                                                                            */
+int snn_prop_dense_real_f32(const float *W, const float *bias, const float *x, float *out,
+                            int B, int Nin, int N, int accumulate, snn_stream_t stream);
+int snn_prop_conv2d_real_f32(const float *W, const float *bias, const float *x, float *out,
+                             int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
+                             int stride, int pad, int accumulate, snn_stream_t stream);
+/* (snn_input_step_real_pv is declared behind snn_pervec, next to snn_input_step_pv) */
+
 /* ---- f5: LocalConnection1D / 2D / 3D.compute --------------------------------------------------
  * bindsnet/network/topology.py:1573-1597 (1D), :1731-1746 (2D), :1880-1896 (3D).  s [B, n_src] u8, W [Cin, F*conv_prod,
  * kernel_prod], out [B, F*conv_prod]; src int32 [Cin, conv_prod, kernel_prod] = flat source index of tap k of receptive
@@ -362,6 +392,9 @@ typedef struct { const float *v[SNN_PV_COUNT]; } snn_pervec;
 
 int snn_input_step_pv(const uint8_t *s, float *x, int B, int N, float trace_decay, float trace_scale, int additive,
                       const snn_pervec *pv, uint8_t *raster_out, snn_stream_t stream);
+/* f17: the step of a real-valued Input layer (s, raster_out f32).  (ABI 8, additive) */
+int snn_input_step_real_pv(const float *s, float *x, int B, int N, float trace_decay, float trace_scale, int additive,
+                           const snn_pervec *pv, float *raster_out, snn_stream_t stream);
 int snn_lif_step_pv(float *v, float *refrac, uint8_t *s, float *x, float *I, int B, int N, const snn_lif_params *h_p,
                     const snn_pervec *pv, uint8_t *raster_s, float *raster_v, snn_stream_t stream);
 int snn_mcp_step_pv(float *v, uint8_t *s, float *x, const float *I, int B, int N, const snn_lif_params *h_p,
@@ -823,6 +856,14 @@ typedef struct {
     /* SIF (snn_sif_step): the layer's `summed` f32 [B,n] -- Nodes(sum_input=True): every step adds the layer's raw input --, NULL
      * without sum_input.  Any other kind with it is SNN_ERR_INVALID.  Added like the fields above: SNN_ABI_VERSION stays. */
     float *summed;
+    /* INPUT, real-valued (f17): ext_real != NULL makes the layer one.  ext_real is the f32 [T,B,n] input tensor (aliased per step),
+     * s_real the f32 [B,n] values at entry (what connections read at t = 0), raster_real the nullable f32 [T,B,n] monitor copy; they
+     * stand for ext_spikes / s / raster_s, which must then be NULL.  snn_net_run takes the generic plan; a connection out of such a
+     * layer must be DENSE or CONV2D with rule NONE and a target that is no CSRM layer, else SNN_ERR_UNSUPPORTED.  On any other
+     * kind the three are SNN_ERR_INVALID.  Added like the fields above: SNN_ABI_VERSION stays. */
+    const float *ext_real;
+    const float *s_real;
+    float *raster_real;
 } snn_layer_desc;
 
 typedef struct {
