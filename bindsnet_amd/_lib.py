@@ -144,6 +144,11 @@ class ConnDesc(C.Structure):
                 ("activity", C.c_void_p)]
 
 
+class ConnProp(C.Structure):
+    """snn_conn_prop: one per connection, beside the ConnDesc array (snn_net_run_props) -- what snn_prop_dense_auto_f32 needs."""
+    _fields_ = [("prop_auto", C.c_int), ("prop_flags", C.c_void_p), ("prop_counters", C.c_void_p)]
+
+
 class MccOp(C.Structure):
     _fields_ = [("kind", C.c_int), ("scalar", C.c_int), ("val", C.c_void_p), ("bits", C.c_void_p)]
 
@@ -204,6 +209,8 @@ _SIGS = {
     "snn_prop_pool_f32": ([_vp, _vp, _vp, _i, _i] + [C.POINTER(_i)] * 5 + [_f, _i, _vp], _i),
     "snn_prop_meanfield_f32": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_dense_mfma_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "snn_prop_dense_auto_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "snn_set_dense_prop_mode": ([_i], None),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
     "snn_prop_dense_real_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_real_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
@@ -283,6 +290,7 @@ _SIGS = {
     "snn_dist_allgather_step": ([_vp, _vp, _vp, _ll, _vp], _i),
     "snn_dist_destroy": ([_vp], _i),
     "snn_net_run": ([C.POINTER(LayerDesc), _i, C.POINTER(ConnDesc), _i, C.POINTER(RunDesc), _vp], _i),
+    "snn_net_run_props": ([C.POINTER(LayerDesc), _i, C.POINTER(ConnDesc), _i, C.POINTER(ConnProp), C.POINTER(RunDesc), _vp], _i),
     "snn_net_workspace_bytes": ([C.POINTER(LayerDesc), _i, C.POINTER(ConnDesc), _i, C.POINTER(RunDesc)], C.c_ulonglong),
     "snn_plan_name": ([], C.c_char_p),
     "snn_dc2015_last_form": ([], C.c_int),

@@ -139,7 +139,8 @@ def _ann_to_snn_helper(prev, current, node_type, last=False, **kwargs):
         bias = current.bias if current.bias is not None else torch.zeros(layer.n)
         # (a transposed view, as in the reference -- on the host MKL is then handed the same operand; Connection stores it contiguously
         #  once it moves to the device, where the kernels read [in, out] row-major)
-        return layer, topology.Connection(source=prev, target=layer, w=current.weight.t(), b=bias)
+        # (prop_auto: the IF layers of a converted network fire at their normalised rates, densely -- the product's body is chosen on the device)
+        return layer, topology.Connection(source=prev, target=layer, w=current.weight.t(), b=bias, prop_auto=True)
     if isinstance(current, nn.Conv2d):
         layer = node_type(shape=(current.out_channels, *_conv_output(prev, current)), **spiking)
         bias = current.bias if current.bias is not None else torch.zeros(layer.shape[1])

@@ -8,6 +8,9 @@
 
 int snn_check_launch();            // snn_api.hip: hipGetLastError() -> SNN_* code
 int snn_check(hipError_t e);
+// snn_ops.hip: the event-driven dense propagation whose workgroups of a flagged tile return at once (the second launch of snn_prop_dense_auto_f32)
+int snn_launch_prop_dense_flagged(const float *W, const float *bias, const uint8_t *s, float *out, int B, int Nin, int N, int accumulate,
+                                  const int *flags, hipStream_t stream);
 
 namespace snn {
 

@@ -25,9 +25,9 @@ using namespace snn;
 // W[i,j] (coalesced 1 KiB row segments) through the ordered-sum state machine.
 // =============================================================================================
 template <class SUM>
-__global__ __launch_bounds__(256) void k_prop(const float *__restrict__ W, const float *__restrict__ bias,
-                                              const uint8_t *__restrict__ s, float *__restrict__ out,
-                                              int B, int Nin, int N, int accumulate) {
+__device__ __forceinline__ void prop_body(const float *__restrict__ W, const float *__restrict__ bias,
+                                          const uint8_t *__restrict__ s, float *__restrict__ out,
+                                          int B, int Nin, int N, int accumulate) {
     __shared__ uint32_t list[4][256];
     __shared__ int cnt[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -75,6 +75,22 @@ __global__ __launch_bounds__(256) void k_prop(const float *__restrict__ W, const
     }
 }
 
+template <class SUM>
+__global__ __launch_bounds__(256) void k_prop(const float *__restrict__ W, const float *__restrict__ bias,
+                                              const uint8_t *__restrict__ s, float *__restrict__ out,
+                                              int B, int Nin, int N, int accumulate) {
+    prop_body<SUM>(W, bias, s, out, B, Nin, N, accumulate);
+}
+
+// The second launch of snn_prop_dense_auto_f32 (csrc/snn_mfma.hip): the same body, but the workgroups of a sample whose tile of 16
+// the matrix kernel has stored (flags[b / 16] != 0, written by the launch before this one) return at once.
+__global__ __launch_bounds__(256) void k_prop_flagged(const float *__restrict__ W, const float *__restrict__ bias,
+                                                      const uint8_t *__restrict__ s, float *__restrict__ out,
+                                                      int B, int Nin, int N, int accumulate, const int *__restrict__ flags) {
+    if (flags[blockIdx.y >> 4]) return;                 // (uniform)
+    prop_body<SeqSum>(W, bias, s, out, B, Nin, N, accumulate);
+}
+
 // N == 1: the reference's sum over the sources of ONE contiguous column is ATen's inner reduction (snn_order.hpp inner_sum8_terms),
 // not an outer sum.  One thread per sample; a layer of one neuron is no hot path.
 __global__ __launch_bounds__(64) void k_prop_col1(const float *__restrict__ W, const uint8_t *__restrict__ s, float *__restrict__ out,
@@ -105,6 +121,12 @@ extern "C" int snn_prop_dense_f32(const float *W, const float *bias, const uint8
     if (Nin >= (1 << 24) || B > 65535) return SNN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_prop<SeqSum>, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, W, bias, s,
                        out, B, Nin, N, accumulate);
+    return snn_check_launch();
+}
+
+int snn_launch_prop_dense_flagged(const float *W, const float *bias, const uint8_t *s, float *out, int B, int Nin, int N, int accumulate,
+                                  const int *flags, hipStream_t stream) {
+    hipLaunchKernelGGL(k_prop_flagged, dim3((N + 255) / 256, B), dim3(256), 0, stream, W, bias, s, out, B, Nin, N, accumulate, flags);
     return snn_check_launch();
 }
 

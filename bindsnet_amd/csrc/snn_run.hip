@@ -71,6 +71,8 @@ int snn_launch_dc_arbitrate(uint8_t *s, float *x, int B, int N, const snn_dc_par
 int snn_launch_rng_fill(snn_rng_state *rng, const uint8_t *s, int B, int N, float *qbuf, long long *cursor,
                         hipStream_t st);
 
+bool snn_dense_prop_takes(int Nin, int asked);            // snn_mfma.hip
+
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // ---- run(..., clamp / unclamp / injects_v / masks): small elementwise helpers of the generic plan (network.py:395-449)
@@ -366,7 +368,8 @@ static size_t conn_numel(const snn_conn_desc &d, const snn_layer_desc *L) {
 }
 
 // (1) one connection hands its source's spikes `sp` on to its target; `fed`: an earlier connection has written the target's currents
-static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_run_desc *R, int t, const void *spv, bool fed, hipStream_t st) {
+static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_conn_prop *p, const snn_run_desc *R, int t, const void *spv, bool fed,
+                     hipStream_t st) {
     const int B = R->B;
     const snn_layer_desc &S = L[d.src], &D = L[d.dst];
     if (S.kind == SNN_LAYER_INPUT && S.ext_real) {      // (validate_conn: DENSE or CONV2D, no window, no rule)
@@ -400,6 +403,11 @@ static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_
     else if (d.kind == SNN_CONN_MCC) TRY(snn_prop_cascade_f32(d.w, sp, out, B, S.n, D.n, acc, st));
     else if (d.window) TRY(snn_prop_window_f32(d.w, d.bias, d.win_ring, (d.win_head + t) % d.win_size, sp, D.csrm_xwin, B, d.win_size,
                                                S.n, D.n, acc, st));
+    // (the body -- matrix cores or event-driven -- is chosen on the device, per tile of 16 samples: the same launches whatever the spikes are)
+    else if (d.kind == SNN_CONN_DENSE && p && p->prop_auto && !p->prop_flags) return SNN_ERR_INVALID;
+    else if (d.kind == SNN_CONN_DENSE && p && p->prop_flags && snn_dense_prop_takes(S.n, p->prop_auto)) {
+        TRY(snn_prop_dense_auto_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, p->prop_flags, p->prop_counters, st));
+    }
     else if (d.kind == SNN_CONN_DENSE) TRY(snn_prop_dense_f32(d.w, d.bias, sp, D.current, B, S.n, D.n, acc, st));
     else if (d.kind == SNN_CONN_SPARSE) TRY(snn_prop_sparse_f32(d.sparse_ptr, d.sparse_col, d.sparse_val, d.sparse_nnz, d.bias, sp,
                                                                 D.current, B, S.n, D.n, acc, st));
@@ -541,7 +549,8 @@ static int learn_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn
     return SNN_OK;
 }
 
-static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R,
+// P: the caller's snn_conn_prop table [nC] (snn_net_run_props), entry c for connection c; NULL: none
+static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_conn_prop *P, const snn_run_desc *R,
                        hipStream_t st) {
     const int B = R->B;
     bool fed[64];
@@ -557,7 +566,7 @@ static int run_generic(const snn_layer_desc *L, int nL, const snn_conn_desc *C, 
                 const snn_conn_desc &d = C[c];
                 if (only_dst >= 0 && d.dst != only_dst) continue;
                 const void *sp = layer_spikes(L[d.src], B, t, only_dst >= 0 && d.src < only_dst);
-                TRY(feed_conn(L, d, R, t, sp, fed[d.dst], st));
+                TRY(feed_conn(L, d, P ? P + c : nullptr, R, t, sp, fed[d.dst], st));
                 fed[d.dst] = true;
             }
             return SNN_OK;
@@ -597,11 +606,17 @@ static thread_local unsigned g_in_raster_done;
 uint8_t *snn_input_raster_request(int layer) { return layer >= 0 && layer < 8 ? g_in_raster_req[layer] : nullptr; }
 void snn_input_raster_done(int layer) { if (layer >= 0 && layer < 8) g_in_raster_done |= 1u << layer; }
 
-static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R, hipStream_t st);
+static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_conn_prop *P, const snn_run_desc *R, hipStream_t st);
 void snn_dc2015_ws_key_in(unsigned long long key);   // snn_dc2015.hip: the caller's host_state[0] as this run found it
 
 extern "C" int snn_net_run(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R,
                            snn_stream_t stream) {
+    return snn_net_run_props(L, nL, C, nC, nullptr, R, stream);
+}
+
+// (every plan passes `C` on index for index, so entry c of P stays connection c's)
+extern "C" int snn_net_run_props(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_conn_prop *P,
+                                 const snn_run_desc *R, snn_stream_t stream) {
     TRY(validate(L, nL, C, nC, R));
     hipStream_t st = (hipStream_t)stream;
     bool any = false;
@@ -610,13 +625,13 @@ extern "C" int snn_net_run(const snn_layer_desc *L, int nL, const snn_conn_desc 
         if (L[l].kind == SNN_LAYER_INPUT && L[l].ext_real && L[l].raster_real) {
             std::vector<snn_layer_desc> Lr(L, L + nL);
             for (int k = 0; k < nL; ++k) Lr[k].raster_real = nullptr;
-            TRY(snn_net_run(Lr.data(), nL, C, nC, R, stream));
+            TRY(snn_net_run_props(Lr.data(), nL, C, nC, P, R, stream));
             for (int k = l; k < nL; ++k)
                 if (L[k].kind == SNN_LAYER_INPUT && L[k].ext_real && L[k].raster_real)
                     TRY(snn_check(hipMemcpyAsync(L[k].raster_real, L[k].ext_real, sizeof(float) * (size_t)R->T * R->B * L[k].n, hipMemcpyDeviceToDevice, (hipStream_t)stream)));
             return SNN_OK;
         }
-    if (!any) return net_run_plans(L, nL, C, nC, R, st);
+    if (!any) return net_run_plans(L, nL, C, nC, P, R, st);
     std::vector<snn_layer_desc> L2(L, L + nL);
     g_in_raster_done = 0;
     for (int l = 0; l < nL; ++l) {
@@ -625,7 +640,7 @@ extern "C" int snn_net_run(const snn_layer_desc *L, int nL, const snn_conn_desc 
         L2[l].raster_s = nullptr;
         if (l < 8) g_in_raster_req[l] = L[l].raster_s;
     }
-    const int rc = net_run_plans(L2.data(), nL, C, nC, R, st);
+    const int rc = net_run_plans(L2.data(), nL, C, nC, P, R, st);
     for (int l = 0; l < nL && l < 8; ++l) g_in_raster_req[l] = nullptr;
     if (rc) return rc;
     for (int l = 0; l < nL; ++l)
@@ -634,7 +649,7 @@ extern "C" int snn_net_run(const snn_layer_desc *L, int nL, const snn_conn_desc 
     return SNN_OK;
 }
 
-static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_run_desc *R, hipStream_t st) {
+static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C, int nC, const snn_conn_prop *P, const snn_run_desc *R, hipStream_t st) {
     // What a pipelined caller's earlier runs knew about the workspace's content (snn_run_desc.host_state[0]: "the exchange areas are clean
     // for this layout") holds only from one chained lean D&C run to the next: EVERY run takes the word away first, and only that path puts
     // it back (snn_dc2015.hip) -- a plan that scribbles over the workspace can never leave a stale "clean" behind.
@@ -673,7 +688,7 @@ static int net_run_plans(const snn_layer_desc *L, int nL, const snn_conn_desc *C
     if (mode != 1 && !handled) TRY(snn_try_fused_convlif(L, nL, C, nC, R, st, &handled));
     if (!handled) {
         g_plan = "generic";
-        TRY(run_generic(L, nL, C, nC, R, st));
+        TRY(run_generic(L, nL, C, nC, P, R, st));
     }
     // network.py:464-465: normalise every connection after the loop (learning or not)
     for (int c = 0; c < nC; ++c)

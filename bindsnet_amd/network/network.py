@@ -83,6 +83,16 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         f.seek(0)
         return torch.load(f, weights_only=False)
 
+    def prop_stats(self) -> dict:
+        """Connection.prop_stats() of every connection that keeps them, by connection key: which body -- matrix cores or
+        event-driven -- the generic plan's dense propagation took, in (tile of 16 samples, timestep) pairs."""
+        return {key: c.prop_stats() for key, c in self.connections.items() if hasattr(c, "prop_stats")}
+
+    def reset_prop_stats(self) -> None:
+        for c in self.connections.values():
+            if hasattr(c, "reset_prop_stats"):
+                c.reset_prop_stats()
+
     _TRANSIENT = ("_workspace", "_scratch_pool", "_keep", "last_plan", "resident_retries", "lean_retries", "_lean_cooldown",
                   "_run_cache", "_reset_cache", "_shard_state", "_defer_norm", "_pipe", "_ws_state")
 
@@ -283,7 +293,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         if cool > 0:
             self.__dict__["_lean_cooldown"] = cool - 1
         try:
-            _lib.check(lib.snn_net_run(L, len(names), Cn, len(self.connections), C.byref(R), stream), "snn_net_run")
+            _lib.check(lib.snn_net_run_props(L, len(names), Cn, len(self.connections), built["Pn"], C.byref(R), stream), "snn_net_run")
         finally:
             R.status2 = None
         self.__dict__["last_plan"] = lib.snn_plan_name().decode()
@@ -391,7 +401,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             with DeviceGenerator(dev, max_draws, gen_bufs) as ns:  # host generator <-> device, exact (rng.py)
                 R.rng, R.qbuf = _dptr(ns.state), _dptr(ns.qbuf)
                 R.cursor, R.status = _dptr(ns.cursor), _dptr(ns.status)
-                _lib.check(lib.snn_net_run(L, len(names), Cn, len(self.connections), C.byref(R), stream), "snn_net_run")
+                _lib.check(lib.snn_net_run_props(L, len(names), Cn, len(self.connections), built["Pn"], C.byref(R), stream), "snn_net_run")
                 self.__dict__["last_plan"] = lib.snn_plan_name().decode()
                 # plans that hand spikes between workgroups report a failed hand-off (or a step the lean form does not
                 # handle) through the status word: it is read back after EVERY such run, with or without one_spike
@@ -632,9 +642,12 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     if lname not in self.layers or isinstance(self.layers[lname], Input):
                         raise NotImplementedError(f"bindsnet_amd: {what}['{lname}'] must name a non-Input layer of the network")
             Cn = (_lib.ConnDesc * max(1, len(self.connections)))()
+            Pn = (_lib.ConnProp * max(1, len(self.connections)))()      # snn_conn_prop, index for index
             lists, dyn_conns, described, windows, averages = [], [], [], [], []
             for k, ((src, dst), conn) in enumerate(self.connections.items()):
                 described += self._fill_conn(Cn[k], conn, self._source_index(names, index, src, conn), index[dst], B, dev, keep, kwargs)   # (the collector stays on: clamp bounds are read through _f() as well)
+                if hasattr(conn, "_describe_prop"):
+                    described += conn._describe_prop(Pn[k], Cn[k], B, dev, self._scratch)
                 if self.__dict__.get("_defer_norm", False):    # parallel.sharded_run normalises the MERGED weights itself
                     Cn[k].has_norm = 0
                 wanted = self._conn_monitor_requests(conn, (src, dst))
@@ -702,7 +715,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     self._scratch("rng_qbuf", (max(max_draws, 1),), torch.float32, dev), pool["rng_host"])
         # (assignments made while building -- a state tensor re-created by _check_state, a rule's lazily allocated
         #  memory -- belong to this build: the descriptors already point at the new objects)
-        return {"L": L, "Cn": Cn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows, "averages": averages, "records": records, "rec_arr": rec_arr,
+        return {"L": L, "Cn": Cn, "Pn": Pn, "R": R, "names": names, "keep": keep, "inputs": dyn_inputs, "layers": dyn_layers, "conns": dyn_conns, "windows": windows, "averages": averages, "records": records, "rec_arr": rec_arr,
                 "max_draws": max_draws, "gen_bufs": gen_bufs, "T": T, "B": B, "dev": dev, "scalars": scalars,
                 "lists": lists, "epoch": _lib.epoch(), "n_objects": (len(self.layers), len(self.connections), len(self.monitors)),
                 "epoch0": epoch0, "defer_norm": bool(self.__dict__.get("_defer_norm", False)), "ptrs": ptrs}

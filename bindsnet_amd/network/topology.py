@@ -242,6 +242,10 @@ class Connection(_DenseConnection):
                  w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
         super().__init__(source, target, nu, reduction, weight_decay, **kwargs)
         self.w, self.b = _matrix_weights(self, w_dtype, kwargs)
+        # Not in the reference.  True: on the generic plan the product's body -- matrix cores or event-driven -- is chosen on the device,
+        # per tile of 16 samples and timestep, which pays where the source fires densely and costs a second
+        # launch per step where it does not; False (the default): the single event-driven launch, as ever.
+        self.prop_auto = bool(kwargs.get("prop_auto", False))
 
     # -- the window of a connection into a CSRMNodes layer (topology.py:329-330, :348-374) ---------------------------------
     # `s_w` reads as the reference's attribute: None until first use, then float32 [B, res_window_size, *source.shape], oldest
@@ -274,7 +278,31 @@ class Connection(_DenseConnection):
             for key in ("host", "ring"):
                 if win[key] is not None:
                     win[key] = fn(win[key])
+        if self.__dict__.get("_prop_counters") is not None:      # (int32: a cast of the module leaves it, a move takes it along)
+            self.__dict__["_prop_counters"] = fn(self.__dict__["_prop_counters"])
         return out
+
+    # -- which body the generic plan's propagation took (snn_prop_dense_auto_f32): two int32 words on the device, {matrix, event}
+    # tile-steps, added to by the kernels and read only here.  They live in self.__dict__["_prop_counters"], which .to(), clone()
+    # and save() carry along.
+    def _prop_counter_words(self, dev):
+        cnt = self.__dict__.get("_prop_counters")
+        if cnt is None:
+            cnt = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.__dict__["_prop_counters"] = cnt = cnt.to(dev)
+        return cnt
+
+    def prop_stats(self) -> dict:
+        """{"matrix_tiles", "event_tiles"}: how many (tile of 16 samples, timestep) pairs of Network.run took the matrix-core body and
+        how many the event-driven one, since construction or the last reset_prop_stats().  One device read; zeros on the host.  The two
+        counters are int32 words: they wrap after 2^31 - 1 tile-steps."""
+        cnt = self.__dict__.get("_prop_counters")
+        m, e = (0, 0) if cnt is None else cnt.tolist()
+        return {"matrix_tiles": int(m), "event_tiles": int(e)}
+
+    def reset_prop_stats(self) -> None:
+        if self.__dict__.get("_prop_counters") is not None:
+            self.__dict__["_prop_counters"].zero_()
 
     def _window_ring(self, B: int, dev):
         """The window as snn_prop_window_f32 keeps it, made from `s_w` where that was last written on the host: the "_win" entry
@@ -330,6 +358,16 @@ class Connection(_DenseConnection):
             win = self._window_ring(B, dev)
             d.window, d.win_ring, d.win_head, d.win_size = 1, dptr(win["ring"]), win["head"], win["ring"].shape[1]
         return described
+
+    def _describe_prop(self, p, d, B: int, dev, scratch) -> list:
+        """This connection's snn_conn_prop `p` beside its filled snn_conn_desc `d`: spike bytes go through snn_prop_dense_auto_f32 where
+        snn_net_run finds the shape worth its second launch (a real-valued Input never reaches it:
+        snn_net_run routes that first).  Returns (owner, attribute) pairs like `_describe`."""
+        if d.window:
+            return []
+        flags = scratch(f"prop_flags_{d.src}_{d.dst}", ((B + 15) // 16,), torch.int32, dev)
+        p.prop_auto, p.prop_flags, p.prop_counters = int(bool(getattr(self, "prop_auto", False))), dptr(flags), dptr(self._prop_counter_words(dev))
+        return [(self, "_prop_counters")]
 
     def _column_slice(self, source, target, lo, hi):
         def scalar(t) -> float:

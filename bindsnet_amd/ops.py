@@ -161,6 +161,31 @@ def prop_dense_mfma(W, s, out, bias=None, accumulate=False):
     return out
 
 
+def prop_dense_auto(W, s, out, bias=None, accumulate=False, counters=None, flags=None):
+    """a6 with its body chosen on the device, per tile of 16 samples: the matrix-core chain where the tile's spikes are dense and
+    all 0/1, the event-driven walk elsewhere (snn_prop_dense_auto_f32).  Bit-identical to prop_dense.  `counters`: an int32 [2]
+    device tensor that the call adds its {matrix, event} tile counts to; `flags`: int32 [ceil(B / 16)] scratch (made here if
+    missing; afterwards 1 where the matrix body ran)."""
+    B = s.shape[0]
+    Nin, N = W.shape
+    assert s.numel() == B * Nin and out.numel() == B * N
+    tiles = (B + 15) // 16
+    if flags is None:
+        flags = torch.empty(tiles, dtype=torch.int32, device=W.device)
+    if flags.numel() < tiles or (counters is not None and counters.numel() < 2):
+        raise ValueError(f"prop_dense_auto: flags needs {tiles} int32 words, counters 2")
+    check(lib().snn_prop_dense_auto_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(s, "spike"), _ptr(out, F32), B, Nin, N,
+                                        int(accumulate), _ptr(flags, torch.int32), _ptr(counters, torch.int32, True), _stream()),
+          "prop_dense_auto")
+    return out
+
+
+def set_dense_prop_mode(mode: int) -> None:
+    """Which body prop_dense_auto and the generic plan's dense connections take (tests, measurements): 0 the cost rule, 1 always
+    event-driven, 2 the matrix body wherever it is exact."""
+    lib().snn_set_dense_prop_mode(int(mode))
+
+
 def prop_conv2d(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
     """a7: F.conv2d on spikes; s [B,Cin,H,W], W [Cout,Cin,KH,KW], out [B,Cout,OH,OW]."""
     B, Cin, H, Wd = s.shape

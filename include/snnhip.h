@@ -141,6 +141,26 @@ int snn_prop_meanfield_f32(const float *w, int w_numel, const uint8_t *s, float 
 int snn_prop_dense_mfma_f32(const float *W, const float *bias, const uint8_t *s, float *out,
                             int B, int Nin, int N, int accumulate, snn_stream_t stream);
 
+/* snn_prop_dense_f32 with its body chosen ON THE DEVICE, per tile of 16 samples and per call: the matrix-core chain above for
+ * a tile whose spikes are dense, the event-driven walk for the others.  `out` has snn_prop_dense_f32's bits whichever body
+ * runs.  Two launches, always the same two, no host read-back: the matrix kernel first -- every workgroup of a tile counts the
+ * non-zero spike bytes of the tile's valid rows and notes any byte above 1 (csrc/snn_dense_auto.hpp: the census), all of them
+ * reach the same decision, a tile that decides "event" returns there, the first column group of a tile writes flags[tile]
+ * (1 = the matrix body has stored this tile) and adds 1 to counters[0] (matrix) or counters[1] (event) --, then the
+ * event-driven kernel, whose workgroups of a flagged tile return at once.
+ * A tile takes the matrix body only if (a) every spike byte of its valid rows is 0 or 1 -- another byte makes k_prop's
+ * multiply-then-add two roundings where the MFMA has one -- and (b) the cost rule of csrc/snn_dense_auto.hpp says the walk of
+ * the tile's longest event list costs more than Nin / 16 rounds of the chain.  (b) costs time when it is wrong, never bits.
+ * flags: int32 [ceil(B / 16)], written on every call (no memset needed); counters: nullable int32 [2], only ever added to.
+ * Limit: a non-finite weight in a row that did not spike gives NaN in the matrix body (0 * inf, as a matmul does) and is
+ * not seen by the event-driven body.  Limits of snn_prop_dense_f32: Nin < 2^24, B <= 65535.  (ABI 8, additive)              */
+int snn_prop_dense_auto_f32(const float *W, const float *bias, const uint8_t *s, float *out, int B, int Nin, int N,
+                            int accumulate, int *flags, int *counters, snn_stream_t stream);
+/* Which body snn_prop_dense_auto_f32 takes, for tests and measurements (process-wide, like snn_set_plan_mode): 0 = the
+ * rule above, 1 = always the event-driven body, 2 = the matrix body wherever it is exact (a tile with a byte above 1 still
+ * takes the event-driven body).  Another value is taken as 0.                                                              */
+void snn_set_dense_prop_mode(int mode);
+
 /* ---- a7: Conv2dConnection.compute ---------------------------------------------------------
  * bindsnet/network/topology.py:799-815 (F.conv2d).  s [B,Cin,H,W] u8, W [Cout,Cin,KH,KW],
  * out [B,Cout,OH,OW].  Stated order, any Cin: every output element is ONE bias-free sequential f32 sum over (kh,kw,cin) --
@@ -983,6 +1003,22 @@ typedef struct {
     float *activity;
 } snn_conn_desc;
 
+/* What a connection needs to have its product's body chosen on the device (snn_prop_dense_auto_f32 above): one entry per
+ * connection, in a table of its own beside the snn_conn_desc array (snn_net_run_props below) -- the descriptors keep their layout.
+ * prop_flags: the connection's int32 [ceil(B / 16)] device scratch -- with it a DENSE connection fed by spike bytes (no window, not a
+ * real-valued Input) CAN propagate through snn_prop_dense_auto_f32 on the generic plan; prop_counters: two device int32 words
+ * {matrix tile-steps, event tile-steps} that the caller keeps across runs (nullable; they wrap after 2^31 - 1 tile-steps).
+ * prop_auto != 0: the connection's owner ASKS for the device's choice.  Under the rule (snn_set_dense_prop_mode 0) a connection
+ * takes snn_prop_dense_auto_f32 only if it is asked for and has at least 256 source neurons -- the choice costs a second launch
+ * every step, 3 to 6 us however sparse the spikes are, so nobody pays it unasked; every other connection keeps the single launch
+ * of snn_prop_dense_f32, as without the table.  Modes 1 and 2 (tests, measurements) take every connection that has prop_flags.
+ * prop_auto without prop_flags is SNN_ERR_INVALID.  Ignored by every other kind and by the fused plans, which keep the event-driven form; an
+ * MCC connection sums in ATen's cascade order, which a single chain cannot reproduce, and stays event-driven too. */
+typedef struct {
+    int prop_auto;
+    int *prop_flags, *prop_counters;
+} snn_conn_prop;
+
 typedef struct {
     int B, T;
     float dt;
@@ -1028,6 +1064,10 @@ typedef struct {
  * cursor[0].  Picks a fused plan when the graph matches one (snn_plan_name reports which).  */
 int snn_net_run(const snn_layer_desc *h_layers, int n_layers, const snn_conn_desc *h_conns, int n_conns,
                 const snn_run_desc *h_run, snn_stream_t stream);
+/* snn_net_run with a snn_conn_prop per connection (h_props [n_conns], host memory; NULL: exactly snn_net_run).  The table is read
+ * by the generic plan only; every other argument, result and plan is snn_net_run's.  (ABI 8, additive) */
+int snn_net_run_props(const snn_layer_desc *h_layers, int n_layers, const snn_conn_desc *h_conns, int n_conns,
+                      const snn_conn_prop *h_props, const snn_run_desc *h_run, snn_stream_t stream);
 /* Device scratch (bytes) a fused plan would need for this network; 0 if none applies.  A run
  * whose descriptor carries less falls back to the generic plan.                               */
 unsigned long long snn_net_workspace_bytes(const snn_layer_desc *h_layers, int n_layers, const snn_conn_desc *h_conns,
