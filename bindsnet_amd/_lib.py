@@ -56,6 +56,11 @@ class SnnError(RuntimeError):
     pass
 
 
+def raise_if(err) -> None:           # what a `_..._refusal` piece returned: an exception, or None for "nothing against it"
+    if err is not None:
+        raise err
+
+
 class LifParams(C.Structure):
     _fields_ = [("decay", C.c_float), ("rest", C.c_float), ("reset", C.c_float), ("thresh", C.c_float),
                 ("refrac", C.c_float), ("dt", C.c_float), ("has_lbound", C.c_int), ("lbound", C.c_float),

@@ -21,6 +21,12 @@ class SubtractiveResetIFNodes(Nodes):
     every class."""
     _SUMS_INPUT = True
     _SCALAR_ONLY = ("thresh", "reset", "refrac", "lbound")      # refused as tensors on the device, by name
+    _WATCHED = ("summed",)
+
+    def _multi_device_refusal(self, mode, name):
+        """bindsnet.conversion's layers run on the generic plan of one device only."""
+        return NotImplementedError(f"{mode}: layer '{name}' ({type(self).__name__}) is not supported by the multi-device modes; "
+                                   "run the network on one device")
 
     def __init__(self, n: Optional[int] = None, shape: Optional[Iterable[int]] = None, traces: bool = False,
                  traces_additive: bool = False, tc_trace: Scalar = 20.0, trace_scale: Scalar = 1.0, sum_input: bool = False,
@@ -47,10 +53,7 @@ class SubtractiveResetIFNodes(Nodes):
         self.refrac_count.zero_()
 
     def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
-        for name in self._SCALAR_ONLY:
-            t = getattr(self, name)
-            if isinstance(t, torch.Tensor) and t.numel() != 1:
-                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on SubtractiveResetIFNodes is not supported on the device")
+        self._scalars_only()
         return self._node_params(pv, reset=self.reset, refrac=self.refrac)
 
     def _summed(self) -> Optional[torch.Tensor]:
@@ -94,8 +97,10 @@ class PassThroughNodes(Nodes):
     same values (a deviation in dtype only), and is accepted only where exactly one connection feeds it and that connection is
     a MaxPool1d/2d/3dConnection, PermuteConnection or ConstantPad2dConnection, whose outputs are 0 or 1: anything else -- another
     connection class, a second incoming connection, an external current, `injects_v` -- raises NotImplementedError before the
-    run changes state (Network.run asks `_run_refusal`)."""
+    run changes state (`_refusals`)."""
     _STATE = ()
+    _WATCHED = ("v",)
+    _multi_device_refusal = SubtractiveResetIFNodes._multi_device_refusal
 
     def _recordable(self) -> tuple:
         return ()                                         # (no step writes `x`: see _describe)
@@ -108,6 +113,10 @@ class PassThroughNodes(Nodes):
 
     def reset_state_variables(self) -> None:
         self.s.zero_()
+
+    def _refusals(self, name, req):
+        if req.on_device:
+            yield self._run_refusal(name, req.feeders(name), name in req.inputs, req.injects_v.get(name) is not None)
 
     def _run_refusal(self, name: str, feeders: list, has_current: bool, injected: bool):
         """Why a device run must not start with this layer in it, or None.  `feeders`: the connections into the layer."""

@@ -9,16 +9,13 @@ import torch
 from .. import _lib, ops
 from ..network import host_path
 from ..network.nodes import Nodes
-from ..network.topology import AbstractConnection
+from ..network.topology import _FixedConnection
 
 
-class _GatherConnection(AbstractConnection):
+class _GatherConnection(_FixedConnection):
     """What the two classes share.  No `w`: nothing learns (a rule other than NoOp raises in the rule's constructor), nothing is
     normalised, a mask or a monitor on the connection raises before the run, as for the MaxPoolNdConnection classes; like those
     the connection runs in training mode, and parallel.py's multi-device modes refuse it by name."""
-
-    _rules = frozenset(("NoOp",))
-    _host_update = host_path._update_nothing
 
     def _geometry(self):
         """(arrays of snn_prop_gather_f32, the shape of one output sample); raises what the class cannot run on the device."""
@@ -36,12 +33,12 @@ class _GatherConnection(AbstractConnection):
             return NotImplementedError(f"bindsnet_amd: a mask on a {type(self).__name__} is not supported (it has no weights)")
         if monitored:
             return NotImplementedError(f"bindsnet_amd: a monitor on a {type(self).__name__} is not supported (it has no state)")
-        if self.source.s.is_cuda or self.target.s.is_cuda:
-            try:
-                self._checked_geometry()
-            except (NotImplementedError, RuntimeError) as e:
-                return e
         return None
+
+    def _refusals(self, key, req):
+        yield from super()._refusals(key, req)
+        if req.on_device:
+            self._checked_geometry()                      # (raises what the device cannot gather; the host path runs torch's own calls)
 
     def compute(self, s: torch.Tensor) -> torch.Tensor:
         if not s.is_cuda:
@@ -68,16 +65,6 @@ class _GatherConnection(AbstractConnection):
             for a in range(3):
                 getattr(d, name)[a] = arr[a]
         return []
-
-    def update(self, **kwargs) -> None:
-        """Nothing learns; a mask has nothing to fill."""
-        if kwargs.get("mask", None) is not None:
-            raise self._run_refusal(kwargs["mask"], False)
-
-    def normalize(self) -> None:
-        """No weights -> no normalization."""
-
-    _host_normalize = normalize
 
 
 class PermuteConnection(_GatherConnection):

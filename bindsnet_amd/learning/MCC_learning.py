@@ -12,7 +12,7 @@ from .. import _lib
 from . import _descriptor
 
 
-class MCC_LearningRule(_lib.Touching):
+class MCC_LearningRule(_descriptor.Rule):
     """Reference: MCC_learning.py:16-118 (nu parsing, reduction default, decay, clamp range)."""
 
     _rule_code = None                  # snn_conn_desc.rule (include/snnhip.h)
@@ -156,7 +156,7 @@ class MCC_LearningRule(_lib.Touching):
 
 
 class NoOp(MCC_LearningRule):
-    _rule_code = _lib.RULE_NONE
+    _rule_code, _learns = _lib.RULE_NONE, False
 
     def __init__(self, **args) -> None:
         pass

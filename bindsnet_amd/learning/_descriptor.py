@@ -6,6 +6,26 @@ from .. import _lib
 from .._lib import dptr
 
 
+class Rule(_lib.Touching):
+    """What both rule trees say about a run before it starts (network/_preflight.py), each answer an exception or None."""
+
+    _learns = True                     # whether the rule changes the weights: all but NoOp
+
+    def _batch_refusal(self, B: int):
+        """Why the rule cannot learn at batch size B."""
+
+    def _syn_refusal(self):
+        """What a rule with per-synapse constants cannot run: asked when the rule is built and before a run changes any state."""
+
+    def _multi_device_refusal(self, mode: str, key):
+        """The rule's reason against parallel.py's mode `mode`."""
+
+    def _refusals(self, key, req):
+        """Why the learning run `req` must not start with this rule on connection `key`: asked behind the connection's own."""
+        yield self._batch_refusal(req.B)
+        yield self._syn_refusal()
+
+
 def accepts(connection, rule) -> bool:
     """True when the connection's family lists the rule's class (or one of its bases) by name in `_rules`."""
     return any(c.__name__ in getattr(connection, "_rules", ()) for c in type(rule).__mro__)

@@ -14,7 +14,7 @@ from .. import _lib
 from . import _descriptor
 
 
-class LearningRule(_lib.Touching):
+class LearningRule(_descriptor.Rule):
     """Reference: learning.py:25-104.  Which rules a connection family takes is the family's `_rules` (network/topology.py)."""
 
     _rule_code = None                       # snn_conn_desc.rule (include/snnhip.h)
@@ -24,9 +24,7 @@ class LearningRule(_lib.Touching):
         if getattr(connection, "_rules_only", None) and not _descriptor.accepts(connection, self):
             raise NotImplementedError(f"bindsnet_amd: {type(self).__name__} on {type(connection).__name__} is not supported "
                                       f"({connection._rules_only})")
-        refusal = getattr(connection, "_rule_refusal", None)        # a family's own reason against this rule (Conv2dConnection: wide inputs)
-        if refusal is not None and refusal(self) is not None:
-            raise NotImplementedError(refusal(self))
+        _lib.raise_if(connection._rule_refusal(self))   # a family's own reason against this rule (Conv2dConnection: wide inputs)
         self.connection = connection
         self.source, self.target = connection.source, connection.target
         self.wmin, self.wmax = connection.wmin, connection.wmax
@@ -85,11 +83,6 @@ class LearningRule(_lib.Touching):
             return None, None
         return (None if lo == -np.inf else lo), (None if hi == np.inf else hi)
 
-    def _syn_refusal(self):
-        """What a rule with per-synapse constants cannot run, as an exception (None: nothing): asked when the rule is built and
-        before a run changes any state."""
-        return None
-
     def _check_reduction(self):
         B = self.source.batch_size
         if self.reduction is torch.squeeze:
@@ -113,9 +106,7 @@ class LearningRule(_lib.Touching):
         if self._rule_code is None:
             raise NotImplementedError(f"bindsnet_amd: rule {type(self).__name__} is not supported")
         self._check_reduction()
-        err = self._syn_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._syn_refusal())
         _descriptor.fill_update(d, self, self.weight_decay, dev, keep)
         d.rule = self._rule_code
         # (anything but sum: the generic plan, the *_red entry points; a rule that reduces nothing keeps every plan)
@@ -129,7 +120,7 @@ class LearningRule(_lib.Touching):
 
 
 class NoOp(LearningRule):
-    _rule_code = _lib.RULE_NONE
+    _rule_code, _learns = _lib.RULE_NONE, False
 
     def update(self, **kwargs) -> None:
         if self.weight_decay != 1.0:
@@ -145,9 +136,7 @@ class PostPre(LearningRule):
         super().__init__(connection=connection, nu=nu, reduction=reduction, weight_decay=weight_decay, **kwargs)
         assert self.source.traces and self.target.traces, "Both pre- and post-synaptic nodes must record spike traces."
         self._require_accepted()
-        err = self._syn_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._syn_refusal())
 
     def _syn_refusal(self):
         """learning.py:401-402: `target_x * nu[0]` must stay [B, 1, N] for the bmm -- rates that vary along the source axis fail there."""
@@ -160,9 +149,7 @@ class PostPre(LearningRule):
 
     def update(self, **kwargs) -> None:
         self._check_reduction()
-        err = self._syn_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._syn_refusal())
         self.connection._postpre(self, self.source.batch_size, *self._bounds(tensors=True))
 
 
@@ -275,9 +262,7 @@ class _OuterProductRule(LearningRule):
         B = self.source.batch_size
         if self.connection._kind == _lib.CONN_CONV2D:
             return self.connection._outer_product(self, B, *self._bounds())
-        err = self._syn_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._syn_refusal())
         lo, hi = self._bounds(tensors=True)
         ops.stdp_hebbian(self.connection.w.data, self.source.s.reshape(B, -1).contiguous(), self.source.x.reshape(B, -1),
                          self.target.s.reshape(B, -1), self.target.x.reshape(B, -1), self._nu(0), self._nu(1),
@@ -306,9 +291,7 @@ class WeightDependentPostPre(_OuterProductRule):
         if not self.target.traces:
             raise NotImplementedError("bindsnet_amd: WeightDependentPostPre needs spike traces on the target layer too "
                                       "(the update reads target.x)")
-        err = self._syn_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._syn_refusal())
 
     def _syn_refusal(self):
         """A bound tensor with a non-finite entry passes the reference's `.any()` assertion and turns the weights into NaN."""
@@ -394,8 +377,11 @@ class Rmax(LearningRule):
         self.tc_e_trace = torch.tensor(kwargs.get("tc_e_trace", 25.0))
 
     def _batch_refusal(self, B: int):
-        """What Network.run asks before the run changes any state."""
         return NotImplementedError(self._B1) if B != 1 else None
+
+    def _multi_device_refusal(self, mode, key):
+        return NotImplementedError(f"{mode}: Rmax on connection {key} is not supported by the multi-device modes (the rule is defined for "
+                                   "batch size 1 and reads a layer that draws from the host generator); run the network on one device")
 
     def _ensure_state(self) -> None:
         w = self.connection.w

@@ -423,9 +423,7 @@ def _postpre_unfolded(conn, rule, target_x, target_s, unfolded) -> None:
 def _update_convnd(conn, rule) -> None:
     """PostPre on Conv1dConnection / Conv3dConnection, the reference's expressions (learning.py:422-455 / :499-559 + :87-104).
     The source operands go through the connection's `_pp_unfold`, the reference's own pad + unfold + reshape chain."""
-    err = conn._postpre_error(rule)
-    if err is not None:
-        raise RuntimeError(err)
+    _lib.raise_if(conn._postpre_error(rule))
     B, Cout = conn.source.batch_size, conn.out_channels
     _postpre_unfolded(conn, rule, conn.target.x.view(B, Cout, -1), conn.target.s.view(B, Cout, -1).float(),
                       lambda t: conn._pp_unfold(t.reshape(B, *conn.source.shape)))
@@ -720,7 +718,7 @@ def _update_dense(conn, kwargs, mask) -> None:
 
 
 def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs) -> None:
-    from .nodes import CSRMNodes, Input, Nodes
+    from .nodes import Input, Nodes
     clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
     injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
     if isinstance(kwargs.get("a_plus"), dict) or isinstance(kwargs.get("a_minus"), dict):
@@ -743,7 +741,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
             if only is not None and dst != only:
                 continue
             tgt = network.layers[dst]
-            window = isinstance(tgt, CSRMNodes)          # network.py:232-246: a CSRM layer gathers windows
+            window = tgt._gathers_window                 # network.py:232-246: a CSRM layer gathers windows
             if dst not in cur:
                 cur[dst] = torch.zeros(network.batch_size, tgt.res_window_size, *tgt.shape) if window else torch.zeros(network.batch_size, *tgt.shape)
             cur[dst] += conn.compute_window(conn.source.s) if window else conn._host_compute(conn.source.s)     # (the connection's own source, as network.py:227)
@@ -766,7 +764,7 @@ def run(network, inputs: Dict[str, torch.Tensor], T: int, one_step: bool, kwargs
                 # layer with an incoming connection: the current survives only where no connection feeds the layer
                 if name in inputs and not fed_now:
                     ext = inputs[name][t].float()
-                    if not (isinstance(layer, CSRMNodes) and x is not None):     # (a window: `+=` broadcasts the current over its slots, as there)
+                    if not (layer._gathers_window and x is not None):     # (a window: `+=` broadcasts the current over its slots, as there)
                         ext = ext.view(network.batch_size, *layer.shape)
                     x = ext.clone() if x is None else x + ext
                 if x is None:

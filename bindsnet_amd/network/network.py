@@ -17,8 +17,9 @@ from .. import _lib
 from .._lib import dptr as _dptr
 from ..rng import DeviceGenerator
 from . import host_path
+from ._preflight import RunRequest, is_analog
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
-from .nodes import AdaptiveLIFNodes, CSRMNodes, DiehlAndCookNodes, Input, LIFNodes, Nodes, _AdaptiveThresholdNodes, _f
+from .nodes import Input, Nodes
 
 
 def load(file_name: str, map_location: str = "cpu", learning: bool = None) -> "Network":
@@ -109,25 +110,21 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         self.last_plan = None
 
     def reset_state_variables(self) -> None:
-        """Reference: network.py:467-481.  The state tensors of the stock layer classes (s, x, refrac_count <- 0,
-        v <- rest; theta is NOT reset, nodes.py:1113-1120) are filled by ONE launch (snn_fill_segments) instead of
-        four small fills per layer.  The segment table is kept while nothing has been assigned to a network object
+        """Reference: network.py:467-481.  The state tensors of the layers that name them (Nodes._reset_fill: the stock classes'
+        s, x, refrac_count <- 0, v <- rest; theta is NOT reset, nodes.py:1113-1120) are filled by ONE launch (snn_fill_segments)
+        instead of four small fills per layer.  The segment table is kept while nothing has been assigned to a network object
         (_lib.epoch()); only Input.s, which aliases the last input slice of the previous run, is looked up again."""
-        import struct
         plan = self.__dict__.get("_reset_cache")
         if plan is None or plan["epoch"] != _lib.epoch() or not _DESC_CACHE:
             segs, others, rebind = [], [], []
             for l in self.layers.values():
-                if type(l) in (Input, LIFNodes, DiehlAndCookNodes, AdaptiveLIFNodes) and l.s.is_cuda and l.s.is_contiguous():
-                    if type(l) is Input:
-                        rebind.append((len(segs), l))
-                    segs.append((l.s, 0))
-                    if l.traces:
-                        segs.append((l.x, 0))
-                    if type(l) is not Input:
-                        segs += [(l.refrac_count, 0), (l.v, struct.unpack("<I", struct.pack("<f", _f(l.rest)))[0])]
-                else:
+                fill = l._reset_fill() if l.s.is_cuda and l.s.is_contiguous() else None
+                if fill is None:
                     others.append(l)
+                else:
+                    if isinstance(l, Input):
+                        rebind.append((len(segs), l))
+                    segs += fill
             arr = None
             if segs and all(t.is_contiguous() for t, _ in segs) and len(segs) <= _lib.MAX_FILL_SEGMENTS:
                 arr = (_lib.FillSegment * len(segs))()
@@ -135,7 +132,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
                     arr[k].ptr, arr[k].bytes, arr[k].pattern = t.data_ptr(), t.numel() * t.element_size(), pat
             plan = {"epoch": _lib.epoch(), "segs": segs, "arr": arr, "others": others, "rebind": rebind,
                     "rests": [(l.rest, l.rest._version) for l in self.layers.values()
-                              if type(l) is not Input and isinstance(getattr(l, "rest", None), torch.Tensor)]}
+                              if isinstance(getattr(l, "rest", None), torch.Tensor)]}
             self.__dict__["_reset_cache"] = plan if all(t._version == v for t, v in plan["rests"]) else None
         elif any(t._version != v for t, v in plan["rests"]):     # layer.rest changed in place: rebuild next time, and now
             self.__dict__["_reset_cache"] = None
@@ -306,57 +303,16 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             f"Got {type(inputs).__name__} instead.")
         clamps, unclamps = kwargs.get("clamp", {}) or {}, kwargs.get("unclamp", {}) or {}
         injects_v, masks = kwargs.get("injects_v", {}) or {}, kwargs.get("masks", {}) or {}
-        for key, conn in self.connections.items():         # what a family knows it cannot run at all: before the run changes any state
-            if hasattr(conn, "_run_refusal"):
-                err = conn._run_refusal(masks.get(key), self._conn_is_monitored(conn, key))
-                if err is not None:
-                    raise err
-        for m in self.monitors.values():                   # a Monitor on a float16 / bfloat16 feature value: recordings are float32
-            val = getattr(getattr(m, "obj", None), "value", None)
-            if isinstance(val, torch.Tensor) and val.dtype in (torch.float16, torch.bfloat16):
-                raise NotImplementedError(f"bindsnet_amd: a Monitor on a {val.dtype} Weight.value is not supported")
-        if self.learning and int(time / self.dt) > 0:
-            for conn in self.connections.values():         # what a family knows it cannot learn: before the run changes any state
-                err = conn._refusal() if hasattr(conn, "_refusal") else None
-                if err is not None:
-                    raise RuntimeError(err)
+        self._normalise(inputs)
+        dev = self._device()
+        req = RunRequest.of(self, inputs, time, masks, injects_v, on_device=dev.type == "cuda")
+        for err in self._preflight(req):                   # what any object of the network cannot run: before the run changes any state
+            raise err
         if self.reward_fn is not None:
             kwargs["reward"] = self.reward_fn.compute(**kwargs)
-
-        # shape normalisation + dynamic batch size (network.py:329-353)
-        for key in inputs:
-            if inputs[key].dim() == 1:
-                inputs[key] = inputs[key].unsqueeze(0).unsqueeze(0)
-            elif inputs[key].dim() == 2:
-                inputs[key] = inputs[key].unsqueeze(1)
-        self._csrm_refusals(inputs)                        # what a CSRMNodes layer cannot run: before the run changes any state
-        self._layer_refusals(inputs, injects_v)            # ... and what a layer knows it cannot run on the device
-        self._analog_refusals(inputs)                      # ... and what a real-valued (float32) input cannot drive there
-        for key in inputs:
-            if inputs[key].size(1) != self.batch_size:
-                self.batch_size = inputs[key].size(1)
-                for l in self.layers.values():
-                    l.set_batch_size(self.batch_size)
-                for m in self.monitors.values():
-                    m.reset_state_variables()
-            break
-
-        T, B = int(time / self.dt), self.batch_size
-        for conn in self.connections.values():             # ... and what it cannot run at this batch size
-            err = conn._batch_refusal(B) if hasattr(conn, "_batch_refusal") else None
-            if err is not None:
-                raise err
-        if self.learning and T > 0:
-            for conn in self.connections.values():         # ... nor its rule (Rmax is defined for batch size 1)
-                rule = conn._rule() if hasattr(conn, "_rule") else None
-                err = rule._batch_refusal(B) if hasattr(rule, "_batch_refusal") else None
-                if err is not None:
-                    raise err
-                err = rule._syn_refusal() if hasattr(rule, "_syn_refusal") else None     # ... nor with these per-synapse constants
-                if err is not None:
-                    raise err
-        dev = self._device()
-        if dev.type != "cuda":
+        self._set_batch_size(req.B)
+        T, B = req.T, self.batch_size
+        if not req.on_device:
             # A network whose tensors live on the host: the plain-PyTorch step loop with the reference's semantics
             # (network/host_path.py).  Function, not speed -- the product is the MI355X path below; nothing is ever
             # silently moved between the two (a network on the GPU never falls back to this).
@@ -446,94 +402,48 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if kept is not None and kept["epoch"] == before:
                 kept["epoch"] = _lib.epoch()
 
-    def _layer_refusals(self, inputs, injects_v) -> None:
-        """Layers with a `_run_refusal` (PassThroughNodes: which connections may feed it on the device), asked before anything changes."""
-        if self._device().type != "cuda":
-            return
-        for name, layer in self.layers.items():
-            if hasattr(layer, "_run_refusal") and not isinstance(layer, CSRMNodes):
-                feeders = [conn for (_, dst), conn in self.connections.items() if dst == name]
-                err = layer._run_refusal(name, feeders, name in inputs, injects_v.get(name) is not None)
-                if err is not None:
-                    raise err
-
-    def _is_analog(self, layer, x) -> bool:
-        """Whether this run drives the Input `layer` with real values: a float32 entry of `inputs`, or a byte train behind a float32
-        `s` that an analog run left and nobody reset -- connections read that `s` at t = 0, so the run is promoted to float32
-        (exact: float32 zeros and ones give the bits their bytes give, include/snnhip.h f17)."""
-        if x.dtype == torch.float32:
-            return True
-        left = getattr(layer, "s", None)
-        return x.dtype in (torch.uint8, torch.bool) and isinstance(left, torch.Tensor) and left.dtype == torch.float32 \
-            and left.numel() == x[0].numel() and bool(left.ne(0).any())
-
-    def _analog_refusals(self, inputs) -> None:
-        """A real-valued input on the device (snnhip.h f17): float32, into Connection / Conv2dConnection without a rule, no CSRMNodes
-        target.  Raised before anything changes."""
-        if self._device().type != "cuda":
-            return
-        from .topology import Connection, Conv2dConnection
-        for name, layer in self.layers.items():
-            x = inputs.get(name)
-            if not isinstance(layer, Input) or x is None:
-                continue
-            if x.is_floating_point() and x.dtype != torch.float32:
-                raise NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}: a real-valued (analog) input must be float32 on "
-                                          "the device; call .float() on it")
-            if not self._is_analog(layer, x):
-                continue
-            if not any(getattr(conn, "source", None) is layer for conn in self.connections.values()):
-                # (real values are defined by what reads them: without a Connection or Conv2dConnection the device has no use for them)
-                raise NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}, but no Connection or Conv2dConnection reads the "
-                                          f"Input layer '{name}': a real-valued (analog) input is accepted for those two classes; "
-                                          "spike trains are uint8 or bool")
-            for (src, dst), conn in self.connections.items():
-                if getattr(conn, "source", None) is not layer:
-                    continue
-                if type(conn) not in (Connection, Conv2dConnection):
-                    raise NotImplementedError(f"bindsnet_amd: {type(conn).__name__} out of the Input layer '{name}' takes no real-valued "
-                                              "(analog) values on the device: its input spike trains must be uint8 or bool "
-                                              f"(got {x.dtype}); a float32 input drives Connection and Conv2dConnection only")
-                rule = conn._rule()
-                if type(rule).__name__ != "NoOp":
-                    raise NotImplementedError(f"bindsnet_amd: {type(rule).__name__} on a connection out of the Input layer '{name}' "
-                                              "cannot learn from a real-valued (analog) input on the device; use no rule (NoOp)")
-                if isinstance(self.layers[dst], CSRMNodes):
-                    raise NotImplementedError(f"bindsnet_amd: a real-valued (analog) input into the CSRMNodes layer '{dst}' is not "
-                                              "supported on the device (its window holds spike bytes)")
-
-    def _csrm_refusals(self, inputs) -> None:
-        """CSRMNodes layers (nodes.py:1319): what the reference's first step would raise half-way through it -- kernels that do not
-        fit the windows, a window made at another batch size --, a connection class without a working compute_window, and what
-        the device path leaves out (external currents, tensor-valued parameters), all raised before anything changes."""
-        if not any(isinstance(l, CSRMNodes) for l in self.layers.values()):
-            return
-        B = self.batch_size
+    @staticmethod
+    def _normalise(inputs) -> None:
+        """network.py:329-339: inputs of shape [n] and [T, n] get their time and batch dimensions."""
         for key in inputs:
-            B = inputs[key].size(1)
-            break
-        on_device = self._device().type == "cuda"
-        from .topology import Connection
-        for name, layer in self.layers.items():
-            if not isinstance(layer, CSRMNodes):
-                continue
-            err = layer._run_refusal(B)
-            if err is not None:
-                raise err
-            if on_device:
-                if name in inputs:
-                    raise NotImplementedError(f"bindsnet_amd: `inputs['{name}']`, an external current into a CSRMNodes layer, is not "
-                                              "supported on the device")
-                layer._csrm_params({})
-        for (src, dst), conn in self.connections.items():
-            if not isinstance(self.layers[dst], CSRMNodes):
-                continue
-            if type(conn) is not Connection:
-                raise NotImplementedError(f"bindsnet_amd: {type(conn).__name__} into a CSRMNodes layer is not supported: only Connection "
-                                          "has a compute_window (topology.py:348) that runs in the reference")
-            err = conn._window_refusal(B)
-            if err is not None:
-                raise err
+            if inputs[key].dim() == 1:
+                inputs[key] = inputs[key].unsqueeze(0).unsqueeze(0)
+            elif inputs[key].dim() == 2:
+                inputs[key] = inputs[key].unsqueeze(1)
+
+    def _set_batch_size(self, B: int) -> None:
+        """network.py:340-353: the batch size follows the first input."""
+        if B != self.batch_size:
+            self.batch_size = B
+            for l in self.layers.values():
+                l.set_batch_size(B)
+            for m in self.monitors.values():
+                m.reset_state_variables()
+
+    def _preflight(self, req: RunRequest):
+        """Every reason against `req` in the order asked (some raised by the question itself): each connection, then its rule; each layer; the network's own."""
+        def asked():
+            for key, conn in self.connections.items():
+                yield from conn._refusals(key, req)
+                if req.learning:
+                    yield from conn._rule()._refusals(key, req)
+            for name, layer in self.layers.items():
+                yield from layer._refusals(name, req)
+            for m in self.monitors.values():               # a Monitor on a float16 / bfloat16 feature value: recordings are float32
+                val = getattr(getattr(m, "obj", None), "value", None)
+                if isinstance(val, torch.Tensor) and val.dtype in (torch.float16, torch.bfloat16):
+                    yield NotImplementedError(f"bindsnet_amd: a Monitor on a {val.dtype} Weight.value is not supported")
+            for name, layer in self.layers.items() if req.on_device else ():      # a real-valued input on the device (snnhip.h f17)
+                x = req.inputs.get(name) if isinstance(layer, Input) else None
+                if x is not None and x.is_floating_point() and x.dtype != torch.float32:
+                    yield NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}: a real-valued (analog) input must be float32 on "
+                                              "the device; call .float() on it")
+                elif name in req.analog and not req.readers(layer):
+                    # (real values are defined by what reads them: without a Connection or Conv2dConnection the device has no use for them)
+                    yield NotImplementedError(f"bindsnet_amd: inputs['{name}'] is {x.dtype}, but no Connection or Conv2dConnection reads the "
+                                              f"Input layer '{name}': a real-valued (analog) input is accepted for those two classes; "
+                                              "spike trains are uint8 or bool")
+        return (err for err in asked() if err is not None)
 
     # ------------------------------------------------------------------ descriptors
     def _cache_valid(self, built, T, B, dev) -> bool:
@@ -686,10 +596,8 @@ class Network(_lib.TouchingModule, torch.nn.Module):
         # without any attribute assignment, so the kept arrays are only valid while these still are where they were
         ptrs = []
         for layer in self.layers.values():
-            for attr in ("v", "refrac_count", "x", "theta", "i", "u", "a", "b", "c", "d", "s_prob", "rho", "last_spikes", "resKernel", "refKernel", "summed") + tuple(k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1):
-                t = getattr(layer, attr, None)
-                if isinstance(t, torch.Tensor):
-                    ptrs.append((layer, attr, t.data_ptr()))
+            for attr in layer._watched() + [k for k in _lib.PERVEC if isinstance(getattr(layer, k, None), torch.Tensor) and getattr(layer, k).numel() > 1]:
+                ptrs.append((layer, attr, getattr(layer, attr).data_ptr()))
             if not isinstance(layer, Input) and isinstance(getattr(layer, "s", None), torch.Tensor):
                 ptrs.append((layer, "s", layer.s.data_ptr()))
         ptrs += [(obj, attr, getattr(obj, attr).data_ptr()) for obj, attr in described]     # what the connections' _describe wrote
@@ -735,7 +643,7 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if x.dtype not in (torch.uint8, torch.bool, torch.float32):
                 raise NotImplementedError("bindsnet_amd: input spike trains must be uint8 or bool, or float32 for a real-valued "
                                           f"(analog) input (got {x.dtype}); encoders produce uint8")
-            analog = self._is_analog(layer, x)             # (what it may drive: _analog_refusals, before the run began)
+            analog = is_analog(layer, x)                   # (what it may drive: the readers' _refusals, before the run began)
             x = x.to(dev).contiguous()
             if x.numel() != x.shape[0] * B * layer.n:
                 raise ValueError(f"inputs['{name}'] has shape {tuple(x.shape)}, expected [T, {B}, {layer.n}]")
@@ -902,11 +810,6 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             if any(obj is f for f in getattr(conn, "pipeline", ())):
                 return conn
         return None
-
-    def _conn_is_monitored(self, conn, cname) -> bool:
-        """Whether any monitor records a variable of this connection (its `activity` aside: that is a buffer of its own, not `w`)."""
-        return any((isinstance(m, Monitor) and m.obj is conn and not self._records_activity(m, conn)) or
-                   (isinstance(m, NetworkMonitor) and any(c == cname for c, _ in m._wanted_conns())) for m in self.monitors.values())
 
     def _conn_monitor_requests(self, conn, cname):
         """(monitor, key handed back to its _append) for every monitor recording this connection's weights."""

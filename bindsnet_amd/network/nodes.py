@@ -113,6 +113,14 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
     # whether the class takes sum_input=True (nodes.py:105-107: `summed += x` behind every step); every class without it raises
     _SUMS_INPUT = False
 
+    _SCALAR_ONLY = ()                  # parameters the class refuses as tensors on the device, by name
+
+    def _scalars_only(self) -> None:
+        for name in self._SCALAR_ONLY:
+            t = getattr(self, name)
+            if isinstance(t, torch.Tensor) and t.numel() != 1:
+                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on {type(self).__name__} is not supported on the device")
+
     def _state_device(self) -> torch.device:
         v = getattr(self, "v", None)
         return v.device if isinstance(v, torch.Tensor) else self.x.device
@@ -177,6 +185,33 @@ class Nodes(_lib.TouchingModule, torch.nn.Module):
     def _recordable(self) -> tuple:
         return self._RECORD + (("x",) if self.traces else ())
 
+    # device tensors beyond _STATE, `x` and `s` whose addresses the snn_layer_desc holds: watched by the descriptor cache for a re-homed tensor
+    _WATCHED = ()
+
+    def _watched(self) -> list:
+        return [a for a in self._STATE + ("x",) + self._WATCHED if isinstance(getattr(self, a, None), torch.Tensor)]
+
+    # -- what a layer says about a run before it starts (network/_preflight.py) -------------------
+    _gathers_window = False            # whether its input is a window of currents (Connection.compute_window): CSRMNodes
+
+    def _refusals(self, name: str, req):
+        """Why the run `req` must not start with this layer, filed as `name`, in it: exceptions (None: nothing)."""
+        return ()
+
+    def _multi_device_refusal(self, mode: str, name: str):
+        """The layer's reason against parallel.py's mode `mode`, or None."""
+
+    # State tensors Network.reset_state_variables' one launch fills (`v` with `rest`, the rest with zeros), named in the class's OWN body; None: its own reset.
+    _RESET_FILL = None
+
+    def _reset_fill(self):                                 # [(tensor, 32-bit pattern)] of `_RESET_FILL`, or None
+        names = vars(type(self)).get("_RESET_FILL")
+        if names is None:
+            return None
+        import struct
+        return [(getattr(self, a), struct.unpack("<I", struct.pack("<f", _f(self.rest)))[0] if a == "v" else 0)
+                for a in names if a != "x" or self.traces]
+
     def _node_params(self, pv: Optional[dict] = None, **fields) -> _lib.LifParams:
         """snn_lif_params of a layer that has `thresh`: thresh, dt, lbound and the trace fields, plus the named ones.  Per-neuron
         vectors go into `pv` (their scalar fields are then 0)."""
@@ -219,6 +254,7 @@ class AbstractInput:
 class Input(Nodes, AbstractInput):
     """User-driven spikes (reference: nodes.py:172-228): `s` aliases the input, trace optional."""
     _RECORD = ()
+    _RESET_FILL = ("s", "x")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, **kwargs) -> None:
@@ -246,6 +282,7 @@ class Input(Nodes, AbstractInput):
 class LIFNodes(Nodes):
     """Leaky integrate-and-fire layer (reference: nodes.py:418-559)."""
     _PERVEC = Nodes._PERVEC + ("thresh", "decay")
+    _RESET_FILL = ("s", "x", "refrac_count", "v")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -322,6 +359,7 @@ class _AdaptiveThresholdNodes(Nodes):
     that neither class is an instance of the other, as in the reference."""
     _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
     _RECORD = ("refrac_count", "theta")
+    _WATCHED = ("theta",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -403,6 +441,7 @@ class _AdaptiveThresholdNodes(Nodes):
 
 class DiehlAndCookNodes(_AdaptiveThresholdNodes):
     """LIF with adaptive threshold and one-spike arbitration (reference: nodes.py:981-1144)."""
+    _RESET_FILL = LIFNodes._RESET_FILL
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -52.0, rest: Scalar = -65.0, reset: Scalar = -65.0,
@@ -418,6 +457,7 @@ class AdaptiveLIFNodes(_AdaptiveThresholdNodes):
     """LIF with an adaptive threshold (reference: nodes.py:829-978): DiehlAndCookNodes' step without the one-spike
     arbitration -- every neuron that crosses its threshold spikes.  Same constructor arguments, buffers and decays as the
     reference; runs as an SNN_LAYER_DC layer with one_spike = 0."""
+    _RESET_FILL = LIFNodes._RESET_FILL
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, rest: Scalar = -65.0, reset: Scalar = -65.0, thresh: Scalar = -52.0,
@@ -650,6 +690,7 @@ class IzhikevichNodes(Nodes):
     neurons raise NotImplementedError there: the lateral sum's order is pinned against torch up to that size only."""
     _STATE = ("v", "u")
     _RECORD = ()
+    _WATCHED = ("a", "b", "c", "d")
     _PERVEC = Nodes._PERVEC + ("thresh",)
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
@@ -761,6 +802,11 @@ class SRM0Nodes(Nodes):
     ulp, everything else bit for bit whenever the spikes do."""
     _PERVEC = Nodes._PERVEC + ("thresh", "decay")
     _SCALAR_ONLY = ("eps_0", "rho_0", "d_thresh", "rest", "reset")      # refused as tensors on the device, by name
+    _WATCHED = ("s_prob", "rho")
+
+    def _multi_device_refusal(self, mode, name):
+        return NotImplementedError(f"{mode}: layer '{name}' (SRM0Nodes) draws from the host generator in the global batch's order, which "
+                                   "the multi-device modes do not reproduce; run the network on one device")
 
     def __init__(self, n=None, shape=None, traces=False, traces_additive=False, tc_trace=20.0, trace_scale=1.0,
                  sum_input=False, thresh: Scalar = -50.0, rest: Scalar = -70.0, reset: Scalar = -70.0,
@@ -797,10 +843,7 @@ class SRM0Nodes(Nodes):
         self.refrac_count.zero_()
 
     def _params(self, pv: Optional[dict] = None) -> _lib.LifParams:
-        for name in self._SCALAR_ONLY:
-            t = getattr(self, name)
-            if isinstance(t, torch.Tensor) and t.numel() != 1:
-                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on SRM0Nodes is not supported on the device")
+        self._scalars_only()
         return self._node_params(pv, decay=self.decay, rest=self.rest, reset=self.reset, refrac=self.refrac)
 
     def _prob_buffers(self):
@@ -855,6 +898,8 @@ class CSRMNodes(Nodes):
     bit for bit whenever the spikes do."""
     _STATE = ("v",)
     _RECORD = ("theta",)
+    _WATCHED = ("theta", "last_spikes", "resKernel", "refKernel")
+    _gathers_window = True
     _PERVEC = Nodes._PERVEC + ("thresh", "decay", "theta_decay", "theta_plus")
     # refused as tensors on the device, by name
     _SCALAR_ONLY = ("rest", "tau", "reset_const")
@@ -964,7 +1009,20 @@ class CSRMNodes(Nodes):
                 raise TypeError(f"zeros(): argument 'size' must be tuple of ints, but CSRMNodes.{name} is {t.dtype} with {t.numel()} element(s)")
         return int(self.res_window_size), int(self.ref_window_size)
 
-    def _run_refusal(self, B: int):
+    def _refusals(self, name, req):
+        """The kernels against the windows, and what the device path leaves out: an external current, tensor-valued parameters."""
+        yield self._kernel_refusal()
+        if req.on_device:
+            if name in req.inputs:
+                yield NotImplementedError(f"bindsnet_amd: `inputs['{name}']`, an external current into a CSRMNodes layer, is not "
+                                          "supported on the device")
+            self._csrm_params({})                         # (raises what a tensor-valued parameter cannot run there)
+
+    def _multi_device_refusal(self, mode, name):
+        return NotImplementedError(f"{mode}: layer '{name}' (CSRMNodes) takes a window of currents and shares its threshold adaptation over the "
+                                   "global batch, which the multi-device modes do not reproduce; run the network on one device")
+
+    def _kernel_refusal(self):
         """What the reference's first step raises for this layer, found before a run changes any state: a response kernel that is
         not a vector (RectangularKernel: einsum on a 0-dim operand), kernels whose length is not the window's (dt != 1)."""
         try:
@@ -982,10 +1040,7 @@ class CSRMNodes(Nodes):
         return None
 
     def _csrm_params(self, pv: Optional[dict] = None) -> _lib.DcParams:
-        for name in self._SCALAR_ONLY:
-            t = getattr(self, name)
-            if isinstance(t, torch.Tensor) and t.numel() != 1:
-                raise NotImplementedError(f"bindsnet_amd: a tensor-valued `{name}` on CSRMNodes is not supported on the device")
+        self._scalars_only()
         p = _lib.DcParams()
         pv = {} if pv is None else pv
         p.lif = self._node_params(pv, decay=self.decay)

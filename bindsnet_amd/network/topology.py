@@ -78,7 +78,61 @@ def _fill_norm(d, norm, use_abs: int, ws, n: int, dev) -> None:
         d.norm = norm
 
 
-class AbstractConnection(_lib.TouchingModule, Module):
+class _Asked:
+    """What a run asks of a connection before it starts, for both connection bases; Network.run knows `_refusals` alone."""
+
+    _takes_real = False                # takes a real-valued (float32) source on the device: Connection, Conv2dConnection
+    _has_window = False                # has a compute_window that runs in the reference (topology.py:348): Connection
+
+    def _nothing(self, *args):
+        return None
+
+    # The pieces, each an exception or None.  _run_refusal(mask, monitored): why no run may start on the connection, given its mask and whether
+    # a monitor records it; _learning_refusal(): why no learning run may; _window_refusal(B): why its window cannot take a step at batch size
+    # B; _batch_refusal(B): why no run at batch size B may start.  _rule_refusal(rule), asked by LearningRule.__init__: why not this rule.
+    _run_refusal = _learning_refusal = _window_refusal = _batch_refusal = _rule_refusal = _nothing
+
+    def _refusals(self, key, req):
+        """Why the run `req` must not start with this connection, filed as `key`, in it: exceptions (None: nothing)."""
+        yield self._run_refusal(req.masks.get(key), req.monitored(self, key))
+        if req.learning:
+            yield self._learning_refusal()
+        window = self.target._gathers_window
+        if window:
+            yield self._window_refusal(req.B) if self._has_window else NotImplementedError(
+                f"bindsnet_amd: {type(self).__name__} into a CSRMNodes layer is not supported: only Connection has a compute_window "
+                "(topology.py:348) that runs in the reference")
+        analog = req.analog_source(self) if req.analog else None         # a real-valued input on the device (snnhip.h f17)
+        if analog is not None:
+            name, x = analog
+            if not self._takes_real:
+                yield NotImplementedError(f"bindsnet_amd: {type(self).__name__} out of the Input layer '{name}' takes no real-valued "
+                                          "(analog) values on the device: its input spike trains must be uint8 or bool "
+                                          f"(got {x.dtype}); a float32 input drives Connection and Conv2dConnection only")
+            elif self._rule()._learns:
+                yield NotImplementedError(f"bindsnet_amd: {type(self._rule()).__name__} on a connection out of the Input layer '{name}' "
+                                          "cannot learn from a real-valued (analog) input on the device; use no rule (NoOp)")
+            elif window:
+                yield NotImplementedError(f"bindsnet_amd: a real-valued (analog) input into the CSRMNodes layer '{key[1]}' is not "
+                                          "supported on the device (its window holds spike bytes)")
+        yield self._batch_refusal(req.B)
+
+    def _reduction_refusal(self, mode: str, key):
+        """parallel.py's modes merge per-shard SUMS of updates: a mean, maximum or minimum over a shard's samples is no part of the global batch's."""
+        rule = self._rule()
+        reduction = getattr(rule, "reduction", None) if rule._learns else None
+        if reduction is not None and reduction is not torch.sum and reduction is not torch.squeeze:
+            from ..learning._descriptor import reduction_name
+            return NotImplementedError(f"{mode}: {type(self).__name__} {key} has a rule with reduction={reduction_name(reduction)}; the "
+                                       "multi-device modes reduce with torch.sum (or torch.squeeze) only; run the network on one device")
+
+    def _multi_device_refusal(self, mode: str, key):
+        """The connection's reason against parallel.py's mode `mode`, or None: weights that are no [source.n, target.n] matrices are not routed there."""
+        return self._reduction_refusal(mode, key) or (None if self._multi_device else NotImplementedError(
+            f"{mode}: {type(self).__name__} {key} is not supported by the multi-device modes; run the network on one device"))
+
+
+class AbstractConnection(_Asked, _lib.TouchingModule, Module):
     """Reference: topology.py:17-156 (wmin/wmax/norm/update_rule plumbing).
 
     What a connection family is, is written in its class and asked for by network.py, host_path.py, learning.py and
@@ -209,6 +263,23 @@ class AbstractConnection(_lib.TouchingModule, Module):
         return w
 
 
+class _FixedConnection(AbstractConnection):
+    """The families on which nothing learns and nothing is normalised: NoOp only; a mask, and `norm` where refused, raise `_run_refusal`."""
+
+    _rules = frozenset(("NoOp",))
+    _host_update = host_path._update_nothing
+
+    def update(self, **kwargs) -> None:
+        if kwargs.get("mask", None) is not None:
+            raise self._run_refusal(kwargs["mask"], False)
+
+    def normalize(self) -> None:
+        if self.norm is not None:
+            _lib.raise_if(self._run_refusal(None, False))
+
+    _host_normalize = normalize
+
+
 class _DenseConnection(AbstractConnection):
     """What Connection and LocalConnection share: a [source.n, target.n] matrix, propagated by snn_prop_dense_f32, learned by
     every rule of learning.py, its columns normalised."""
@@ -237,6 +308,8 @@ class _DenseConnection(AbstractConnection):
 
 class Connection(_DenseConnection):
     """Dense all-to-all synapses (reference: topology.py:265-399)."""
+
+    _takes_real = _has_window = True
 
     def __init__(self, source: Nodes, target: Nodes, nu=None, reduction=None, weight_decay: float = 0.0,
                  w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
@@ -315,9 +388,7 @@ class Connection(_DenseConnection):
         if cur is None:
             ring = torch.zeros(B, wres, self.source.n, dtype=torch.uint8, device=dev)
         else:
-            err = self._window_refusal(B)
-            if err is not None:
-                raise err
+            _lib.raise_if(self._window_refusal(B))
             ring = cur.reshape(B, wres, self.source.n).ne(0).to(dev, torch.uint8).contiguous()
         win = self.__dict__["_win"] = {"host": None, "ring": ring, "head": 0}
         return win
@@ -394,7 +465,7 @@ class Connection(_DenseConnection):
         return False
 
 
-class SparseConnection(AbstractConnection):
+class SparseConnection(_FixedConnection):
     """Fixed sparse synapses (reference: topology.py:2009-2017): `Connection`'s constructor, then `w = Parameter(w.to_sparse())`.
     Propagation only.  On the device `compute` is snn_prop_sparse_f32 over a compiled form of `w` (a column-tiled CSR, ops.sparse_compile;
     kept as the non-persistent buffers `sp_ptr` / `sp_col` / `sp_val` and rebuilt when `w` is another tensor, was edited in place or
@@ -407,10 +478,9 @@ class SparseConnection(AbstractConnection):
 
     _kind = _lib.CONN_SPARSE
     _takes_mask = _multi_device = False
-    _rules = frozenset(("NoOp",))
     _rules_only = ("a learning rule adds `update.to_sparse()` to a sparse `w` in the reference, which stores every entry from the "
                    "first step on: that is dense learning, use Connection for it")
-    _host_compute, _host_update = host_path._propagate_sparse, host_path._update_nothing
+    _host_compute = host_path._propagate_sparse
 
     def __init__(self, source: Nodes, target: Nodes, nu=None, reduction=None, weight_decay: float = 0.0,
                  w_dtype: torch.dtype = torch.float32, **kwargs) -> None:
@@ -450,18 +520,10 @@ class SparseConnection(AbstractConnection):
         if kwargs.get("learning", True):
             self.update_rule.update(**kwargs)
 
-    def normalize(self) -> None:
-        if self.norm is not None:
-            raise self._run_refusal(None, False)
-
-    _host_normalize = normalize
-
     def _compiled(self):
         """(sp_ptr, sp_col, sp_val) for `w` as it stands.  The key: which tensor `w` is, its in-place version (shared with its
         values and indices), where its values and indices live, and its device."""
-        err = self._weights_refusal()
-        if err is not None:
-            raise err
+        _lib.raise_if(self._weights_refusal())
         w = self.w
         key = (w._version, w._values().data_ptr(), w._indices().data_ptr(), w._nnz(), str(w.device))
         kept = self.__dict__.get("_sp_key")
@@ -478,9 +540,7 @@ class SparseConnection(AbstractConnection):
         from . import nodes as _nodes
         if self.w.device != dev:
             raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
-        err = self._run_refusal(None, False)
-        if err is not None:
-            raise err
+        _lib.raise_if(self._run_refusal(None, False))
         ptr, col, val = self._compiled()
         d.kind, d.w, d.sparse_nnz = self._kind, None, val.numel()
         d.sparse_ptr, d.sparse_col, d.sparse_val = dptr(ptr), dptr(col), dptr(val)
@@ -495,7 +555,7 @@ class SparseConnection(AbstractConnection):
         return described
 
 
-class _MaxPoolConnection(AbstractConnection):
+class _MaxPoolConnection(_FixedConnection):
     """What MaxPool1dConnection, MaxPool2dConnection and MaxPoo3dConnection (reference: topology.py:1028-1301) share: no weights;
     the state is `firing_rates` [B, *source.shape], an online estimate of every source neuron's rate.  Per `compute(s)` the rates
     decay by `decay` and take the spikes, F.max_poolNd picks every window's highest rate, and the output is the source's spike at
@@ -509,9 +569,7 @@ class _MaxPoolConnection(AbstractConnection):
     one built before its layers joined a network -- `firing_rates` of shape [0], which raises in the reference until
     reset_state_variables() -- gets zero rates of the right shape at first use.  Masks, monitors and Dales_rule raise."""
 
-    _kind, _ndim = _lib.CONN_POOL, 0
-    _rules = frozenset(("NoOp",))
-    _host_compute, _host_update = host_path._propagate_pool, host_path._update_nothing
+    _kind, _ndim, _host_compute = _lib.CONN_POOL, 0, host_path._propagate_pool
 
     def _init_pool(self, source, target, kwargs) -> None:
         AbstractConnection.__init__(self, source, target, None, None, 0.0, **kwargs)
@@ -566,6 +624,10 @@ class _MaxPoolConnection(AbstractConnection):
         if tuple(self.target.shape) != pooled:
             return RuntimeError(f"{type(self).__name__}: the target's shape must be {pooled} (channels, then the pooled sizes), got "
                                 f"{tuple(self.target.shape)}")
+        return None
+
+    def _rates_refusal(self, B: int):
+        """Rates kept from another batch size, as in the reference: RuntimeError until reset_state_variables()."""
         fr = self.firing_rates
         if fr.numel() != 0 and tuple(fr.shape) != (int(B), *self.source.shape):
             return RuntimeError(f"{type(self).__name__}: firing_rates has shape {tuple(fr.shape)}, the run needs "
@@ -581,12 +643,16 @@ class _MaxPoolConnection(AbstractConnection):
                                        "connection.firing_rates after the run")
         return None
 
+    def _refusals(self, key, req):
+        yield from super()._refusals(key, req)
+        # (a run that CHANGES the batch size meets stale rates where the reference does, in `_rates` behind set_batch_size: DESIGN.md section 1)
+        if req.B == self.source.batch_size:
+            yield self._rates_refusal(req.B)
+
     def _rates(self, B: int, dev):
         """`firing_rates` for batch size B on `dev`: zero rates of the right shape where the connection was built before its
         layers joined a network."""
-        err = self._batch_refusal(B)
-        if err is not None:
-            raise err
+        _lib.raise_if(self._batch_refusal(B) or self._rates_refusal(B))
         if self.firing_rates.numel() == 0:
             self.firing_rates = torch.zeros(int(B), *self.source.shape, device=dev)
         if self.firing_rates.device != torch.device(dev) or self.firing_rates.dtype != torch.float32:
@@ -617,16 +683,6 @@ class _MaxPoolConnection(AbstractConnection):
             for a in range(3):
                 getattr(d, name)[a] = arr[a]
         return [(self, "firing_rates")]
-
-    def update(self, **kwargs) -> None:
-        """Nothing learns; a mask has nothing to fill."""
-        if kwargs.get("mask", None) is not None:
-            raise self._run_refusal(kwargs["mask"], False)
-
-    def normalize(self) -> None:
-        """No weights -> no normalization."""
-
-    _host_normalize = normalize
 
     def reset_state_variables(self) -> None:
         """Zero rates for the source's batch size (reference: topology.py:1112-1121)."""
@@ -677,7 +733,7 @@ class MaxPoo3dConnection(_MaxPoolConnection):
 MaxPool3dConnection = MaxPoo3dConnection
 
 
-class MeanFieldConnection(AbstractConnection):
+class MeanFieldConnection(_FixedConnection):
     """Mean-field synapses (reference: topology.py:1920-2006): `compute(s) = s.float().mean() * w`, the mean over the whole
     [B, *source.shape] tensor, the batch included.  `w` is 0-dim (the default: one randn draw) or a tensor that broadcasts onto
     [B, *target.shape]; a recurrent connection with a negative scalar `w` is global inhibition.  On the device the spikes are
@@ -690,9 +746,7 @@ class MeanFieldConnection(AbstractConnection):
     a plain tensor to the Parameter `w`).  Masks, monitors, Dales_rule, a `w` that is not float32 and batch x source.n beyond
     2^24 raise."""
 
-    _kind = _lib.CONN_MEANFIELD
-    _rules = frozenset(("NoOp",))
-    _host_compute, _host_update = host_path._propagate_meanfield, host_path._update_nothing
+    _kind, _host_compute = _lib.CONN_MEANFIELD, host_path._propagate_meanfield
 
     def __init__(self, source: Nodes, target: Nodes, nu=None, weight_decay: float = 0.0, w_dtype: torch.dtype = torch.float32,
                  **kwargs) -> None:
@@ -745,40 +799,23 @@ class MeanFieldConnection(AbstractConnection):
         """A tensor of w's shape, as in the reference (Network.run broadcasts it onto the target)."""
         if not self.w.is_cuda:
             return self._host_compute(s)
-        err = self._batch_refusal(s.size(0))
-        if err is not None:
-            raise err
+        _lib.raise_if(self._batch_refusal(s.size(0)))
         out = torch.empty_like(self.w.data)
         ops.prop_meanfield(self.w.data.contiguous(), s.reshape(1, -1).contiguous(), out.view(1, -1), store=True)
         return out
 
     def _prop_into(self, s, out, accumulate=False) -> None:
-        err = self._batch_refusal(s.size(0))
-        if err is not None:
-            raise err
+        _lib.raise_if(self._batch_refusal(s.size(0)))
         ops.prop_meanfield(self.w.data.contiguous(), s.reshape(s.size(0), -1).contiguous(), out.view(s.size(0), -1), accumulate=accumulate)
 
     def _describe(self, d, B, dev, scratch):
         if self.w.device != dev:
             raise ValueError("connection weights are not on the network's device; call network.to('cuda')")
-        err = self._run_refusal(None, False) or self._batch_refusal(B)
-        if err is not None:
-            raise err
+        _lib.raise_if(self._run_refusal(None, False) or self._batch_refusal(B))
         if not self.w.is_contiguous():
             raise NotImplementedError("bindsnet_amd: connection weights must be contiguous float32")
         d.kind, d.w, d.w_numel = self._kind, dptr(self.w.data), self.w.numel()
         return [(self, "w")]
-
-    def update(self, **kwargs) -> None:
-        """Reference: topology.py:1983-1988 with NoOp, which leaves `w` as it is."""
-        if kwargs.get("mask", None) is not None:
-            raise self._run_refusal(kwargs["mask"], False)
-
-    def normalize(self) -> None:
-        if self.norm is not None:
-            raise self._run_refusal(None, False)
-
-    _host_normalize = normalize
 
 
 class LocalConnection(_DenseConnection):
@@ -857,7 +894,7 @@ class Conv2dConnection(AbstractConnection):
 
     _kind, _ndim = _lib.CONN_CONV2D, 2
     _norm_by = "after"      # every [KH*KW] filter to sum `norm` (topology.py:824-837): not snn_net_run's column step
-    _multi_device = True
+    _multi_device = _takes_real = True
     _rules = frozenset(("NoOp", "PostPre", "Hebbian", "WeightDependentPostPre", "MSTDP"))
     _rules_only = "PostPre, Hebbian, WeightDependentPostPre and MSTDP are"      # (any other rule: named in LearningRule's error)
     _outer_product_rules = (_lib.RULE_POSTPRE, _lib.RULE_HEBBIAN, _lib.RULE_WDPOSTPRE)
@@ -886,10 +923,11 @@ class Conv2dConnection(AbstractConnection):
         """Why `rule` must not be constructed on this connection, or None: asked by LearningRule.__init__ (the connection's own
         constructor has not run yet, so the channel count is the source's)."""
         cin = self.source.shape[0]
-        if cin > 16 and type(rule).__name__ != "NoOp":
-            return (f"bindsnet_amd: {type(rule).__name__} on a Conv2dConnection with {cin} input channels is not supported: the "
-                    f"reference reduces the update with torch.bmm over an operand in_channels * KH * KW wide, whose summation "
-                    f"order has not been characterised beyond 16 input channels (propagation runs at any width; use NoOp or no rule)")
+        if cin > 16 and rule._learns:
+            return NotImplementedError(
+                f"bindsnet_amd: {type(rule).__name__} on a Conv2dConnection with {cin} input channels is not supported: the "
+                f"reference reduces the update with torch.bmm over an operand in_channels * KH * KW wide, whose summation "
+                f"order has not been characterised beyond 16 input channels (propagation runs at any width; use NoOp or no rule)")
         return None
 
     def _prop_into(self, s, out, accumulate=False) -> None:
@@ -971,19 +1009,18 @@ class _ConvNdConnection(AbstractConnection):
         return self.padding if self._ndim == 1 else self.padding[0]
 
     def _postpre_error(self, rule):
-        """Why the reference's PostPre update fails on this connection, or None."""
+        """Why the reference's PostPre update fails on this connection (a RuntimeError), or None."""
         if self._ndim == 3 and bool(rule.nu[0] != 0):
             # learning.py:526-547: source_s is never cast to float, so torch.bmm(target_x, source_s) raises
-            return ("PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference: torch.bmm raises 'expected m1 and m2 "
-                    "to have the same dtype, but got: float != bool' (learning.py:526-551, source_s is never cast to float); "
-                    "use nu[0] == 0 or network.train(False)")
-        return self._pp_error
+            return RuntimeError("PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference: torch.bmm raises 'expected m1 and m2 "
+                                "to have the same dtype, but got: float != bool' (learning.py:526-551, source_s is never cast to float); "
+                                "use nu[0] == 0 or network.train(False)")
+        return None if self._pp_error is None else RuntimeError(self._pp_error)
 
-    def _refusal(self):
-        """Why a learning run must not start on this connection, or None: asked by Network.run, of the families that define it."""
+    def _learning_refusal(self):
         # PostPre on a Conv3dConnection with nu[0] != 0 fails in the reference at its first learning step (a bool bmm
         # operand); here before the run changes any state -- a deliberate deviation in timing (DESIGN.md section 8)
-        return self._postpre_error(self.update_rule) if type(self.update_rule).__name__ == "PostPre" else None
+        return self._postpre_error(self.update_rule) if self.update_rule._rule_code == _lib.RULE_POSTPRE else None
 
     def _prop_into(self, s, out, accumulate=False) -> None:
         ops.prop_convnd(self.w.data, s.reshape(s.size(0), *self.source.shape).contiguous(), out, bias=self.b.data,
@@ -1004,9 +1041,7 @@ class _ConvNdConnection(AbstractConnection):
 
     def _postpre(self, rule, B, lo, hi) -> None:
         """learning.py:422-455 / :499-559."""
-        err = self._postpre_error(rule)
-        if err is not None:
-            raise RuntimeError(err)
+        _lib.raise_if(self._postpre_error(rule))
         src, tgt = self.source, self.target
         ops.convnd_postpre(self.w.data, self.pp_src, src.s.reshape(B, -1).contiguous(), src.x.reshape(B, -1),
                            tgt.s.reshape(B, -1).contiguous(), tgt.x.reshape(B, -1), float(rule.nu[0]), float(rule.nu[1]),
@@ -1201,7 +1236,7 @@ class LocalConnection3D(_LocalConnectionND):
         super().__init__(source, target, self.kernel_size, self.stride, n_filters, nu, reduction, weight_decay, w_dtype, **kwargs)
 
 
-class AbstractMulticompartmentConnection(_lib.TouchingModule, Module):
+class AbstractMulticompartmentConnection(_Asked, _lib.TouchingModule, Module):
     """Reference: topology.py:159-262 (feature pipeline bookkeeping)."""
 
     def __init__(self, source: Nodes, target: Nodes, device, pipeline: list = None, **kwargs) -> None:
@@ -1273,6 +1308,28 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
     @property
     def _multi_device(self) -> bool:
         return self._single()
+
+    def _multi_device_refusal(self, mode, key):
+        half = self._half_dtype()
+        if half is not None:               # the modes merge, slice and gather float32 matrices
+            return NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a {half} Weight; the multi-device modes compute in "
+                                       "float32 only; run the network on one device")
+        if any(getattr(f.learning_rule, "average_update", 0) for f in self.pipeline):
+            # an averaging ring is one history of the GLOBAL batch's updates: a shard's own ring, or a slice of one, is another rule
+            return NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a rule with average_update, whose ring of past updates "
+                                       "the multi-device modes neither merge nor slice; run the network on one device")
+        if any(getattr(f, "norm_frequency", "sample") == "time step" for f in self.pipeline):
+            # every step normalises the GLOBAL matrix's columns before that step's update: a merge of shard deltas after the run cannot
+            return NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a Weight with norm_frequency='time step', which the "
+                                       "multi-device modes do not reproduce; run the network on one device")
+        err = self._reduction_refusal(mode, key)
+        if err is None and self.traces:
+            # `activity` is the step's sum over the GLOBAL source layer and batch: a column or batch shard's own is another tensor
+            return NotImplementedError(f"{mode}: MulticompartmentConnection {key} has traces=True, whose `activity` the multi-device modes "
+                                       "neither merge nor slice; run the network on one device")
+        return err or (None if self._single() else NotImplementedError(
+            f"{mode}: MulticompartmentConnection {key} with the feature pipeline {self._names()} is not supported by the multi-device modes "
+            "(a single Weight is); run the network on one device"))
 
     def _check_pipeline(self) -> None:
         from .topology_features import Bias, Intensity, Mask, Probability, Weight
@@ -1479,9 +1536,7 @@ class MulticompartmentConnection(AbstractMulticompartmentConnection):
             raise NotImplementedError(f"bindsnet_amd: Weight.value must be a contiguous float32, float16 or bfloat16 [{self.source.n}, "
                                       f"{self.target.n}] tensor (got {val.dtype}, shape {tuple(val.shape)}, "
                                       f"contiguous={val.is_contiguous()})")
-        err = self._run_refusal(None, False)
-        if err is not None:
-            raise err
+        _lib.raise_if(self._run_refusal(None, False))
         # (float16 / bfloat16: `w` points at 2-byte elements and the run takes the generic plan's *_h16 kernels, csrc/snn_half.hip)
         d.kind, d.w, d.w_dtype = self._kind, dptr(val.data), ops.HALF.get(val.dtype, _lib.W_F32)
         if feat.norm is not None:

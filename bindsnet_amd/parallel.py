@@ -24,13 +24,15 @@ from typing import Dict
 import torch
 import torch.distributed as dist
 
+from ._lib import raise_if
+
 
 def _learned(network):
     """(tensor, lo, hi, norm_holder) for every connection that learns."""
     out = []
     for conn in network.connections.values():
         rule = conn._rule()
-        if type(rule).__name__ in ("PostPre", "MSTDP", "Hebbian", "WeightDependentPostPre", "MSTDPET"):     # every rule that learns
+        if rule._learns:
             holder, attr = conn._weights()
             out.append((getattr(holder, attr).data, *rule._bounds(), holder))
     return out
@@ -67,65 +69,40 @@ def _shard_buffers(network, tensors):
     return st
 
 
-def _reject_local(network, mode: str) -> None:
-    """None of the multi-device modes handles LocalConnection1D / 2D / 3D or Conv1dConnection / Conv3dConnection (their
-    weights are not [source.n, target.n] matrices): such a graph raises instead of being routed through a mode built for other
-    layouts."""
+def _reject_local(network, mode: str) -> None:          # first part of _refuse: weights that are not [source.n, target.n] float32 matrices merged by sums
     for key, conn in network.connections.items():
-        half = conn._half_dtype() if hasattr(conn, "_half_dtype") else None
-        if half is not None:               # the modes merge, slice and gather float32 matrices
-            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a {half} Weight; the multi-device modes compute in "
-                                      "float32 only; run the network on one device")
-        if hasattr(conn, "pipeline") and any(getattr(f.learning_rule, "average_update", 0) for f in conn.pipeline):
-            # an averaging ring is one history of the GLOBAL batch's updates: a shard's own ring, or a slice of one, is another rule
-            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a rule with average_update, whose ring of past updates "
-                                      "the multi-device modes neither merge nor slice; run the network on one device")
-        if hasattr(conn, "pipeline") and any(getattr(f, "norm_frequency", "sample") == "time step" for f in conn.pipeline):
-            # every step normalises the GLOBAL matrix's columns before that step's update: a merge of shard deltas after the run cannot
-            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has a Weight with norm_frequency='time step', which the "
-                                      "multi-device modes do not reproduce; run the network on one device")
-        rule = conn._rule() if hasattr(conn, "_rule") else None
-        reduction = None if rule is None or type(rule).__name__ == "NoOp" else getattr(rule, "reduction", None)
-        if reduction is not None and reduction is not torch.sum and reduction is not torch.squeeze:
-            # the modes merge per-shard SUMS of updates (or slice the global batch's): a mean, maximum or minimum over a shard's samples
-            # is not a part of the global batch's
-            from .learning._descriptor import reduction_name
-            raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} has a rule with reduction={reduction_name(reduction)}; the "
-                                      "multi-device modes reduce with torch.sum (or torch.squeeze) only; run the network on one device")
-        if getattr(conn, "traces", False):
-            # `activity` is the step's sum over the GLOBAL source layer and batch: a column or batch shard's own is another tensor
-            raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} has traces=True, whose `activity` the multi-device modes "
-                                      "neither merge nor slice; run the network on one device")
-        if not conn._multi_device:
-            if hasattr(conn, "pipeline"):
-                raise NotImplementedError(f"{mode}: MulticompartmentConnection {key} with the feature pipeline {conn._names()} is not supported "
-                                          "by the multi-device modes (a single Weight is); run the network on one device")
-            raise NotImplementedError(f"{mode}: {type(conn).__name__} {key} is not supported by the multi-device modes; "
-                                      "run the network on one device")
+        raise_if(conn._multi_device_refusal(mode, key))
 
 
-def _reject_pervec(network, mode: str, lif_thresh_ok: bool = False) -> None:
-    """None of the multi-device modes reads per-neuron (tensor-valued) node parameters: such a layer raises, naming the layer
-    and the parameter, before any collective.  `lif_thresh_ok`: the mode runs Network.run() itself, which has always taken
-    LIFNodes with a tensor `thresh`."""
-    from .network.nodes import LIFNodes
-    for name, layer in network.layers.items():
+def _refuse(network, mode: str, inputs=None, lif_thresh_ok: bool = False) -> None:
+    """What none of the multi-device modes handles, raised before any collective and before anything changes; every connection, rule and layer
+    gives its own reason (`_multi_device_refusal`).  `lif_thresh_ok`: the mode runs Network.run() itself, which takes LIFNodes with a tensor `thresh`."""
+    from .network.nodes import Input, LIFNodes
+    _reject_local(network, mode)
+    for key, conn in network.connections.items():       # Rmax (the rule before its layer: its target is always an SRM0 layer)
+        raise_if(conn._rule()._multi_device_refusal(mode, key))
+    for name, layer in network.layers.items():          # layers that draw, gather windows or run on the generic plan only
+        raise_if(layer._multi_device_refusal(mode, name))
+    for name, layer in network.layers.items():          # per-neuron (tensor-valued) node parameters: none of the modes reads them
         for param in layer._pervec_names():
-            if lif_thresh_ok and param == "thresh" and type(layer) is LIFNodes:
-                continue
-            raise NotImplementedError(f"{mode}: layer '{name}' ({type(layer).__name__}) has a tensor-valued per-neuron `{param}`, which "
-                                      "the multi-device modes do not support; run the network on one device")
+            if not (lif_thresh_ok and param == "thresh" and type(layer) is LIFNodes):
+                raise NotImplementedError(f"{mode}: layer '{name}' ({type(layer).__name__}) has a tensor-valued per-neuron `{param}`, which "
+                                          "the multi-device modes do not support; run the network on one device")
+    _reject_synparams(network, mode)
+    for name, layer in network.layers.items():          # a real-valued input runs on one device only: the modes exchange and merge spike bytes
+        x = inputs.get(name) if isinstance(inputs, dict) else None
+        if isinstance(layer, Input) and isinstance(x, torch.Tensor) and x.dtype not in (torch.uint8, torch.bool):
+            raise NotImplementedError(f"bindsnet_amd: {mode} takes no real-valued (analog) input for the Input layer '{name}': its input "
+                                      f"spike trains must be uint8 or bool (got {x.dtype}); Network.run on one device takes float32")
 
 
-def _reject_synparams(network, mode: str) -> None:
-    """None of the multi-device modes reads per-synapse (tensor-valued) learning rates, bounds or norms: refused in the words the
-    bounds have always been refused in, before any collective."""
+def _reject_synparams(network, mode: str) -> None:     # part of _refuse: per-synapse learning rates, bounds and norms, in the words they have always been refused in
     for conn in network.connections.values():
-        rule = conn._rule() if hasattr(conn, "_rule") else None
+        rule = conn._rule()
         nu = getattr(rule, "nu", None)
         if isinstance(nu, torch.Tensor) and nu.numel() > 2:
             raise NotImplementedError("bindsnet_amd: per-synapse tensor learning rates are not supported")
-        if hasattr(rule, "_bounds") and getattr(rule, "connection", None) is not None:
+        if getattr(rule, "connection", None) is not None:
             rule._bounds()                   # "per-synapse wmin/wmax tensors are not supported" / "per-synapse clamp ranges are not supported"
         for holder in [conn] + list(getattr(conn, "pipeline", [])):
             norm = getattr(holder, "norm", None)
@@ -133,49 +110,12 @@ def _reject_synparams(network, mode: str) -> None:
                 raise NotImplementedError("bindsnet_amd: tensor norms are not supported")
 
 
-def _reject_stochastic(network, mode: str) -> None:
-    """None of the multi-device modes runs SRM0Nodes or Rmax: the layer draws from the ONE host generator in the global batch's
-    row-major order, which no shard of the batch or of the columns reproduces, and the rule is defined for batch size 1."""
-    from .network.nodes import CSRMNodes, SRM0Nodes
-    for name, layer in network.layers.items():
-        if isinstance(layer, CSRMNodes):
-            raise NotImplementedError(f"{mode}: layer '{name}' (CSRMNodes) takes a window of currents and shares its threshold adaptation over the "
-                                      "global batch, which the multi-device modes do not reproduce; run the network on one device")
-    for name, layer in network.layers.items():          # bindsnet.conversion's layers: generic plan of one device only
-        if type(layer).__name__ in ("SubtractiveResetIFNodes", "PassThroughNodes"):
-            raise NotImplementedError(f"{mode}: layer '{name}' ({type(layer).__name__}) is not supported by the multi-device modes; "
-                                      "run the network on one device")
-    for key, conn in network.connections.items():      # (the rule first: its target is always an SRM0 layer)
-        if type(conn._rule()).__name__ == "Rmax":
-            raise NotImplementedError(f"{mode}: Rmax on connection {key} is not supported by the multi-device modes (the rule is defined for "
-                                      "batch size 1 and reads a layer that draws from the host generator); run the network on one device")
-    for name, layer in network.layers.items():
-        if isinstance(layer, SRM0Nodes):
-            raise NotImplementedError(f"{mode}: layer '{name}' (SRM0Nodes) draws from the host generator in the global batch's order, which "
-                                      "the multi-device modes do not reproduce; run the network on one device")
-
-
-def _reject_analog(network, inputs, mode: str) -> None:
-    """A real-valued (float) input of an Input layer runs on one device only (Network.run, generic plan): the multi-device modes
-    exchange and merge spike bytes."""
-    from .network.nodes import Input
-    for name, layer in network.layers.items():
-        x = inputs.get(name) if isinstance(inputs, dict) else None
-        if isinstance(layer, Input) and isinstance(x, torch.Tensor) and x.dtype not in (torch.uint8, torch.bool):
-            raise NotImplementedError(f"bindsnet_amd: {mode} takes no real-valued (analog) input for the Input layer '{name}': its input "
-                                      f"spike trains must be uint8 or bool (got {x.dtype}); Network.run on one device takes float32")
-
-
 def sharded_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, **kwargs) -> None:
     """network.run on this rank's batch shard, then merge learning across ranks (see module doc): the weights and
     thresholds become  before + sum_over_ranks(after - before), are clamped, and only then normalised.  The post-run
     normalisation inside run() is switched off through the network's `_defer_norm` flag (part of the key of the kept
     descriptor arrays, so consecutive sharded runs re-use them like plain runs do)."""
-    _reject_local(network, "sharded_run")
-    _reject_stochastic(network, "sharded_run")
-    _reject_pervec(network, "sharded_run", lif_thresh_ok=True)
-    _reject_synparams(network, "sharded_run")
-    _reject_analog(network, inputs, "sharded_run")
+    _refuse(network, "sharded_run", inputs, lif_thresh_ok=True)
     learned = _learned(network)
     thetas = [l.theta for l in network.layers.values() if hasattr(l, "theta")] if network.learning else []
     tensors = [t for t, _, _, _ in learned] + thetas
@@ -238,10 +178,7 @@ def column_shard(network, rank: int, world: int):
     full network's numbers for those columns.  Returns (shard_network, lo, hi)."""
     from .network import Network
     from .network.nodes import Input, LIFNodes
-    _reject_local(network, "column_shard")
-    _reject_stochastic(network, "column_shard")
-    _reject_pervec(network, "column_shard")
-    _reject_synparams(network, "column_shard")
+    _refuse(network, "column_shard")
     layers, conns = list(network.layers.items()), list(network.connections.items())
     if len(layers) != 2 or len(conns) != 1 or not isinstance(layers[0][1], Input) or type(layers[1][1]) is not LIFNodes:
         raise NotImplementedError("column sharding applies to Input -> one connection -> LIFNodes graphs (no coupling "
@@ -330,10 +267,7 @@ def gather_columns(local: torch.Tensor, n_columns: int, group=None) -> torch.Ten
 # On the host (CPU tensors, gloo) the same schedule runs on network/host_path.py's operators: tests/test_parallel_gloo.py.
 # =====================================================================================================
 def _exact_check(network):
-    _reject_local(network, "exact_run")
-    _reject_stochastic(network, "exact_run")
-    _reject_pervec(network, "exact_run")
-    _reject_synparams(network, "exact_run")
+    _refuse(network, "exact_run")
     from .network.nodes import DiehlAndCookNodes, Input, LIFNodes
     for name, layer in network.layers.items():
         if type(layer) not in (Input, LIFNodes, DiehlAndCookNodes):
@@ -585,8 +519,7 @@ def exact_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, c
     from .network.monitors import Monitor
     from .network.nodes import DiehlAndCookNodes, Input
     assert type(inputs) == dict, "'inputs' must be a dict of names of layers (str) and relevant input tensors."
-    _reject_local(network, "exact_run")                       # (before the batch size below is taken from the inputs)
-    _reject_analog(network, inputs, "exact_run")
+    _refuse(network, "exact_run", inputs)                     # (before the batch size below is taken from the inputs)
     if comm is not None:
         world, rank = comm.world, comm.rank
     else:
@@ -602,19 +535,8 @@ def exact_run(network, inputs: Dict[str, torch.Tensor], time: int, group=None, c
         else:
             recv[0].copy_(own)
 
-    for key in inputs:                                        # network.py:329-353
-        if inputs[key].dim() == 1:
-            inputs[key] = inputs[key].unsqueeze(0).unsqueeze(0)
-        elif inputs[key].dim() == 2:
-            inputs[key] = inputs[key].unsqueeze(1)
-    for key in inputs:
-        if inputs[key].size(1) != network.batch_size:
-            network.batch_size = inputs[key].size(1)
-            for l in network.layers.values():
-                l.set_batch_size(network.batch_size)
-            for m in network.monitors.values():
-                m.reset_state_variables()
-        break
+    network._normalise(inputs)                                # network.py:329-353
+    network._set_batch_size(next((x.size(1) for x in inputs.values()), network.batch_size))
     learned = _exact_check(network)
     T, Bs = int(time / network.dt), network.batch_size
     B, lo = Bs * world, rank * Bs

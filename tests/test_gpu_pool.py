@@ -194,3 +194,30 @@ def test_refusals_on_the_device_leave_the_state_alone():
         with pytest.raises(exc, match=match):
             net.run(dict(x), time=3, **kwargs)
         assert _same(before, _state(net)), match
+
+
+def test_a_refusal_at_another_batch_size_leaves_the_network_as_it_was_and_the_mended_run_equals_the_host():
+    """Input (2, 4, 4) -> MaxPool2dConnection(2, stride 2) without `decay` -> LIFNodes (2, 2, 2), built at batch size 1 and run at 3:
+    the TypeError comes before the batch size changes.  With decay=1.0 the same call runs, and its spikes are the host path's.
+    (Two channels: with one, [3, 1, 4, 4] is what the reference's squeeze() cannot broadcast, and the run stays refused.  The
+    connection is built before its layers join the network, so its rates take the run's batch size at first use.)"""
+    from bindsnet_amd.network.monitors import Monitor
+    ns = _ns()
+    x = torch.from_numpy((np.random.default_rng(11).random((12, 3, 2, 4, 4)) < 0.5).astype(np.uint8))
+    spikes = {}
+    for dev in (DEV, "cpu"):
+        net = PC._pool_net(ns, (2, 4, 4), 1, decay=None, before=True)
+        net.layers["Y"].thresh.fill_(-64.5)                     # (a pooled spike or two per step must be enough to fire)
+        net.add_monitor(Monitor(net.layers["Y"], ["s"], time=12), "Y")
+        net = net.to(dev)
+        Y = net.layers["Y"]
+        v0 = Y.v.clone()
+        with pytest.raises(TypeError, match="needs `decay=`"):
+            net.run({"X": x.to(dev)}, time=12)
+        assert net.batch_size == 1 and Y.v.shape[0] == 1 and torch.equal(Y.v, v0) and net.monitors["Y"].clean
+        net.connections[("X", "Y")].decay = 1.0
+        net.run({"X": x.to(dev)}, time=12)
+        assert net.batch_size == 3 and Y.v.shape[0] == 3 and net.last_plan == ("generic" if dev == DEV else "host-torch")
+        spikes[dev] = net.monitors["Y"].get("s").cpu()
+    assert spikes[DEV].shape == (12, 3, 2, 2, 2) and int(spikes["cpu"].sum()) > 0
+    assert torch.equal(spikes[DEV].to(torch.uint8), spikes["cpu"].to(torch.uint8))

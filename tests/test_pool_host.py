@@ -217,7 +217,7 @@ def test_refusals_come_before_the_run_changes_any_state():
     from bindsnet_amd import parallel
     for net in (PC._pool_net(ns, (2, 4, 4), 2), PC._mean_net(ns, w=torch.tensor(0.5))):
         with pytest.raises(NotImplementedError, match="MaxPool2dConnection|MeanFieldConnection"):
-            parallel._reject_local(net, "sharded_run")
+            parallel._refuse(net, "sharded_run")
 
 
 def test_meanfield_refuses_more_than_2_24_source_elements():

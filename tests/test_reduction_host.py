@@ -142,4 +142,4 @@ def test_multi_device_modes_raise_before_any_state_changes(kind):
             call()
         assert torch.equal(RC.weights(net), w0) and torch.equal(net.layers["Y"].v, v0)
     ok = _small(NS, kind, torch.sum)               # (the check itself lets sum through)
-    parallel._reject_local(ok, "sharded_run")
+    parallel._refuse(ok, "sharded_run")

@@ -198,7 +198,7 @@ def test_norm_mask_monitor_and_dtype_are_refused_before_the_run_changes_anything
     _pair(w=w).update(learning=True)
     from bindsnet_amd import parallel
     with pytest.raises(NotImplementedError):
-        parallel._reject_local(_net(_pair(w=w)), "sharded_run")
+        parallel._refuse(_net(_pair(w=w)), "sharded_run")
 
 
 def test_changed_weights_are_seen_by_the_next_compute_and_run():

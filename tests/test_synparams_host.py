@@ -216,7 +216,7 @@ def test_multi_device_modes_refuse_tensor_constants():
     rule = net.connections[("X", "Y")].pipeline[0].learning_rule
     rule.min, rule.max = 0.0, 4.0
     with pytest.raises(NotImplementedError, match="tensor norms are not supported"):
-        parallel._reject_synparams(net, "sharded_run")
+        parallel._refuse(net, "sharded_run")
 
 
 def test_drawn_weights_follow_tensor_bounds():
