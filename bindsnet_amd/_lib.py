@@ -146,6 +146,8 @@ class ConnDesc(C.Structure):
                 ("w_dtype", C.c_int), ("syn", SynParams), ("norm_vec", C.c_void_p),
                 ("avg_ring0", C.c_void_p), ("avg_ring1", C.c_void_p), ("avg_k", C.c_int), ("avg_continuous", C.c_int),
                 ("avg_squeeze", C.c_int), ("avg_i0", C.c_int), ("avg_i1", C.c_int), ("reduce", C.c_int),
+                ("avgp_c", C.c_int), ("avgp_in", C.c_int * 2), ("avgp_k", C.c_int * 2), ("avgp_stride", C.c_int * 2),
+                ("avgp_pad", C.c_int * 2), ("avgp_ceil", C.c_int), ("avgp_include_pad", C.c_int), ("avgp_divisor", C.c_int),
                 ("activity", C.c_void_p)]
 
 
@@ -187,7 +189,10 @@ IZH_MAX_N = 1024          # SNN_IZH_MAX_N: the layer size up to which the latera
 CONN_MCC, CONN_DENSE, CONN_CONV2D, CONN_LOCAL, CONN_CONVND, CONN_SPARSE = 0, 1, 2, 3, 4, 5
 CONN_POOL, CONN_MEANFIELD = 6, 7
 CONN_PERMUTE, CONN_PAD = 8, 9      # bindsnet.conversion: PermuteConnection, ConstantPad2dConnection (snn_prop_gather_f32)
-POOL_STAGE = 8192         # SNN_POOL_STAGE: the largest (b, c) plane snn_prop_pool_f32 updates and pools in LDS, in one launch
+CONN_AVGPOOL = 10                  # AvgPool2dConnection (snn_prop_avgpool2d_f32)
+# SNN_AVGPOOL_*: windows of this many taps and more take one wave per output; the workgroup size and the largest grid of either body
+AVGPOOL_COOP_TAPS, AVGPOOL_THREADS, AVGPOOL_MAX_GRID = 64, 256, 1024
+POOL_STAGE = 8192        # SNN_POOL_STAGE: the largest (b, c) plane snn_prop_pool_f32 updates and pools in LDS, in one launch
 MEANFIELD_STORE = 2       # SNN_MEANFIELD_STORE: snn_prop_meanfield_f32 writes mean * w itself
 MEANFIELD_MAX = 1 << 24   # B * source.n up to which f32(count) / f32(numel) is the reference's mean
 SPARSE_TJ = 256           # SNN_SPARSE_TJ: the column-tile width of SparseConnection's compiled form
@@ -243,6 +248,8 @@ _SIGS = {
     "snn_sif_step_pv": ([_vp] * 6 + [_i, _i, C.POINTER(LifParams), C.POINTER(PerVec), _vp, _vp, _vp], _i),
     "snn_pass_step": ([_vp, _vp, _i, _i, _vp, _vp], _i),
     "snn_prop_gather_f32": ([_vp, _vp, _i, _i] + [C.POINTER(_i)] * 4 + [_i, _vp], _i),
+    "snn_prop_avgpool2d_f32": ([_vp, _vp, _i, _i] + [C.POINTER(_i)] * 4 + [_i, _i, _i, _i, _vp], _i),
+    "snn_set_avgpool_body": ([_i], None),
     "snn_rmax_step": ([_vp] * 5 + [_i, _i] + [_f] * 6 + [_i, _f, _i, _f, _vp], _i),
     "snn_mcp_step": ([_vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),
     "snn_if_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(LifParams), _vp, _vp, _vp], _i),

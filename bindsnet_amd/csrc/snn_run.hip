@@ -14,6 +14,7 @@
 #include "snn_synparams.hpp"
 #include "snn_pool.hpp"
 #include "snn_conversion.hpp"
+#include "snn_avgpool.hpp"
 
 static thread_local const char *g_plan = "none";
 static int g_plan_mode = 0;
@@ -212,7 +213,7 @@ static int validate_conn(const snn_layer_desc *L, int nL, const snn_conn_desc &d
             if (d.pipe_kind[k] == SNN_MCC_OP_MUL_DRAW && (!d.pipe_bits[k] || !R->rng)) return SNN_ERR_INVALID;
         }
         if (!d.w && (d.rule != SNN_RULE_NONE || d.has_norm || d.raster_w)) return SNN_ERR_INVALID;
-    } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL && d.kind != SNN_CONN_PERMUTE && d.kind != SNN_CONN_PAD) return SNN_ERR_INVALID;
+    } else if (!d.w && d.kind != SNN_CONN_SPARSE && d.kind != SNN_CONN_POOL && d.kind != SNN_CONN_PERMUTE && d.kind != SNN_CONN_PAD && d.kind != SNN_CONN_AVGPOOL) return SNN_ERR_INVALID;
     if (L[d.dst].kind == SNN_LAYER_INPUT) return SNN_ERR_UNSUPPORTED;
     if (L[d.src].kind == SNN_LAYER_INPUT && L[d.src].ext_real) {      // out of a real-valued Input: the two ordered products, propagation only
         if ((d.kind != SNN_CONN_DENSE && d.kind != SNN_CONN_CONV2D) || d.window || L[d.dst].kind == SNN_LAYER_CSRM || d.rule != SNN_RULE_NONE)
@@ -242,7 +243,7 @@ static int validate_conn(const snn_layer_desc *L, int nL, const snn_conn_desc &d
         if (L[d.dst].kind != SNN_LAYER_SRM0 || !L[d.src].x || !L[d.src].p.lif.traces_additive || !d.e_trace) return SNN_ERR_INVALID;
         if (R->B != 1) return SNN_ERR_UNSUPPORTED;
     }
-    if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_PAD) return SNN_ERR_INVALID;
+    if (d.kind < SNN_CONN_MCC || d.kind > SNN_CONN_AVGPOOL) return SNN_ERR_INVALID;
     if (d.w_dtype != SNN_W_F32) {          // a float16 / bfloat16 Weight: MCC with that one feature, no rule or PostPre, nothing that reads `w` as f32
         if (d.w_dtype != SNN_W_F16 && d.w_dtype != SNN_W_BF16) return SNN_ERR_INVALID;
         if (d.kind != SNN_CONN_MCC || d.pipe_n != 0 || (d.rule != SNN_RULE_NONE && d.rule != SNN_RULE_POSTPRE) || d.raster_w || d.mask)
@@ -273,6 +274,14 @@ static int validate_conn(const snn_layer_desc *L, int nL, const snn_conn_desc &d
         snn::GatherGeom g;
         for (int a = 0; a < 3; ++a) { g.out[a] = d.gat_out[a]; g.src[a] = d.gat_src[a]; g.stride[a] = d.gat_stride[a]; g.off[a] = d.gat_off[a]; }
         if (!snn::gather_valid(g, L[d.src].n, L[d.dst].n)) return SNN_ERR_INVALID;
+        return SNN_OK;
+    }
+    if (d.kind == SNN_CONN_AVGPOOL) {      // AvgPool2dConnection: integer counts over a window, propagation only (NoOp)
+        if (d.rule != SNN_RULE_NONE) return SNN_ERR_UNSUPPORTED;
+        if (d.has_norm || d.mask || d.raster_w || d.bias || d.w || d.avgp_c <= 0) return SNN_ERR_INVALID;
+        snn::AvgGeom g;
+        if (!snn::avg_geometry(g, d.avgp_in, d.avgp_k, d.avgp_stride, d.avgp_pad, d.avgp_ceil, d.avgp_include_pad, d.avgp_divisor)) return SNN_ERR_INVALID;
+        if (d.avgp_c * snn::avg_plane(g) != L[d.src].n || d.avgp_c * snn::avg_out_plane(g) != L[d.dst].n) return SNN_ERR_INVALID;
         return SNN_OK;
     }
     if (d.kind == SNN_CONN_POOL || d.kind == SNN_CONN_MEANFIELD) {     // MaxPoolNdConnection / MeanFieldConnection: propagation only (NoOp)
@@ -413,6 +422,8 @@ static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_
                                                                 D.current, B, S.n, D.n, acc, st));
     else if (d.kind == SNN_CONN_POOL) TRY(snn_prop_pool_f32(d.firing_rates, sp, D.current, B, d.pool_c, d.pool_in, d.pool_k, d.pool_stride,
                                                             d.pool_pad, d.pool_dil, d.pool_decay, acc, st));
+    else if (d.kind == SNN_CONN_AVGPOOL) TRY(snn_prop_avgpool2d_f32(sp, D.current, B, d.avgp_c, d.avgp_in, d.avgp_k, d.avgp_stride, d.avgp_pad,
+                                                                    d.avgp_ceil, d.avgp_include_pad, d.avgp_divisor, acc, st));
     else if (d.kind == SNN_CONN_PERMUTE || d.kind == SNN_CONN_PAD) TRY(snn_prop_gather_f32(sp, D.current, B, S.n, d.gat_out, d.gat_src, d.gat_stride,
                                                                                             d.gat_off, acc, st));
     else if (d.kind == SNN_CONN_MEANFIELD) TRY(snn_prop_meanfield_f32(d.w, d.w_numel, sp, D.current, B, S.n, D.n, acc, st));

@@ -364,6 +364,12 @@ def _propagate_pool(conn, s):
     return s.reshape(B, fr.shape[1], -1).gather(2, idx.flatten(2)).view_as(idx).float()
 
 
+def _propagate_avgpool(conn, s):
+    """AvgPool2dConnection.compute: torch's own avg_pool2d over the spikes as floats (not in the reference; the device's oracle)."""
+    return F.avg_pool2d(s.float().view(s.shape[0], *conn.source.shape), kernel_size=conn.kernel_size, stride=conn.stride, padding=conn.padding,
+                        ceil_mode=conn.ceil_mode, count_include_pad=conn.count_include_pad, divisor_override=conn.divisor_override)
+
+
 def _propagate_permute(conn, s):
     """PermuteConnection.compute (conversion/topology.py:48-56)."""
     return s.permute(conn.dims).float()

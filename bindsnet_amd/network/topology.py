@@ -1,6 +1,6 @@
 """Connections: API mirror of bindsnet/network/topology.py for the connection types on the hot
 path (`Connection`, `SparseConnection`, `MulticompartmentConnection`, `Conv1dConnection`, `Conv2dConnection`, `Conv3dConnection`,
-`LocalConnection`, `LocalConnection1D/2D/3D`, `MaxPool1dConnection`, `MaxPool2dConnection`, `MaxPoo3dConnection`, `MeanFieldConnection`).  `compute()` launches the
+`LocalConnection`, `LocalConnection1D/2D/3D`, `MaxPool1dConnection`, `MaxPool2dConnection`, `MaxPoo3dConnection`, `MeanFieldConnection`), and `AvgPool2dConnection`, which the reference lacks.  `compute()` launches the
 matching propagation kernel of libsnnhip; inside Network.run the same kernels are driven from C++.
 
 `SparseConnection` keeps `w` as a sparse COO Parameter, like the reference, and propagates only: its kernel
@@ -731,6 +731,106 @@ class MaxPoo3dConnection(_MaxPoolConnection):
 
 
 MaxPool3dConnection = MaxPoo3dConnection
+
+
+class AvgPool2dConnection(_FixedConnection):
+    """Average pooling over a (C, H, W) source of 0/1 spikes into a current-driven (C, OH, OW) target: `compute(s)` is
+    `F.avg_pool2d(s.float(), kernel_size, stride, padding, ceil_mode, count_include_pad, divisor_override)`, bit for bit.  Not in
+    the reference: it is the pooling of a converted CNN (`ann_to_snn` builds it for nn.AvgPool2d and nn.AdaptiveAvgPool2d) -- an
+    integrate-and-fire neuron fed count / k^2 fires at the mean rate of its window.  No weights and no state; NoOp only.
+
+    On the device every window is an integer count of spikes, converted to float32 and divided once by the window's divisor
+    (snn_prop_avgpool2d_f32, include/snnhip.h f18), so the summation order cannot show; on the host torch's own call.  Window
+    placement, the output size with `ceil_mode` and the divisor are ATen's.  `stride=None` is the kernel size, as in torch.
+
+    Before a run changes anything (`_refusals`), each naming the class: a target that is not (C, OH, OW); a PassThroughNodes
+    target (its input must be 0 or 1, and an average is a fraction); a real-valued Input source on the device; a mask; a
+    monitor; parallel.py's multi-device modes.  `Dales_rule` and `divisor_override=0` raise in the constructor."""
+
+    _kind, _host_compute = _lib.CONN_AVGPOOL, host_path._propagate_avgpool
+    _rules_only = "it has no weights, so nothing can learn: use no rule (NoOp)"
+
+    def __init__(self, source: Nodes, target: Nodes, kernel_size: Union[int, Tuple[int, int]],
+                 stride: Optional[Union[int, Tuple[int, int]]] = None, padding: Union[int, Tuple[int, int]] = 0, ceil_mode: bool = False,
+                 count_include_pad: bool = True, divisor_override: Optional[int] = None, **kwargs) -> None:
+        if kwargs.get("Dales_rule", None) is not None:
+            raise NotImplementedError("bindsnet_amd: Dales_rule on an AvgPool2dConnection is not supported (it has no weights)")
+        if divisor_override is not None and int(divisor_override) == 0:
+            raise ValueError("AvgPool2dConnection: divisor_override must not be zero (F.avg_pool2d: divisor must be not zero)")
+        AbstractConnection.__init__(self, source, target, kwargs.pop("nu", None), kwargs.pop("reduction", None), kwargs.pop("weight_decay", 0.0),
+                                    **kwargs)
+        self.kernel_size = _pair(kernel_size)
+        self.stride = self.kernel_size if stride is None else _pair(stride)
+        self.padding = _pair(padding)
+        self.ceil_mode, self.count_include_pad = bool(ceil_mode), bool(count_include_pad)
+        self.divisor_override = None if divisor_override is None else int(divisor_override)
+
+    def _pooled(self):
+        """(C, OH, OW) of the source's shape; what F.avg_pool2d itself refuses (a pad beyond half the kernel, an empty output) raises
+        its RuntimeError here."""
+        shape = tuple(self.source.shape)
+        if len(shape) != 3:
+            raise RuntimeError(f"AvgPool2dConnection: the source's shape must be (C, H, W), got {shape}")
+        key = (shape, self.kernel_size, self.stride, self.padding, self.ceil_mode)
+        kept = self.__dict__.get("_pooled_kept")         # (kept beside the attributes, as _MaxPoolConnection keeps its own)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+        probe = torch.nn.functional.avg_pool2d(torch.empty(1, *shape, device="meta"), kernel_size=self.kernel_size, stride=self.stride,
+                                               padding=self.padding, ceil_mode=self.ceil_mode)
+        pooled = tuple(probe.shape[1:])
+        self.__dict__["_pooled_kept"] = (key, pooled)
+        return pooled
+
+    def _batch_refusal(self, B: int):
+        from ..conversion.nodes import PassThroughNodes
+        if isinstance(self.target, PassThroughNodes):
+            return NotImplementedError("bindsnet_amd: AvgPool2dConnection into a PassThroughNodes layer is not supported: that layer's "
+                                       "input must be 0 or 1, and an average over a window is a fraction; use a current-driven layer "
+                                       "(SubtractiveResetIFNodes, IFNodes, ...)")
+        try:
+            pooled = self._pooled()
+        except RuntimeError as e:
+            return RuntimeError(f"AvgPool2dConnection: {e}") if "AvgPool2dConnection" not in str(e) else e
+        if tuple(self.target.shape) != pooled:
+            return RuntimeError(f"AvgPool2dConnection: the target's shape must be {pooled} (channels, then the pooled sizes), got "
+                                f"{tuple(self.target.shape)}")
+        return None
+
+    def _run_refusal(self, mask, monitored: bool):
+        if mask is not None:
+            return NotImplementedError("bindsnet_amd: a mask on an AvgPool2dConnection is not supported (it has no weights)")
+        if monitored:
+            return NotImplementedError("bindsnet_amd: a monitor on an AvgPool2dConnection is not supported (it has no state)")
+        return None
+
+    def _args(self) -> dict:
+        return dict(kernel_size=self.kernel_size, stride=self.stride, padding=self.padding, ceil_mode=self.ceil_mode,
+                    count_include_pad=self.count_include_pad, divisor_override=self.divisor_override)
+
+    def compute(self, s: torch.Tensor) -> torch.Tensor:
+        if not s.is_cuda:
+            return self._host_compute(s)
+        out = torch.empty(s.size(0), *self._pooled(), device=s.device)
+        self._prop_into(s, out)
+        return out
+
+    def _prop_into(self, s, out, accumulate=False) -> None:
+        _lib.raise_if(self._batch_refusal(s.size(0)))
+        if s.dtype not in (torch.bool, torch.uint8):
+            raise NotImplementedError(f"bindsnet_amd: AvgPool2dConnection takes 0/1 spikes (bool or uint8) on the device, got {s.dtype}")
+        B = s.size(0)
+        ops.prop_avgpool(s.reshape(B, *self.source.shape).contiguous(), out.view(B, *self._pooled()), accumulate=accumulate, **self._args())
+
+    def _describe(self, d, B, dev, scratch):
+        _lib.raise_if(self._batch_refusal(B))
+        arrays, _ = ops.avgpool_geometry(self.source.shape[1:], self.kernel_size, self.stride, self.padding, self.ceil_mode)
+        d.kind, d.w, d.avgp_c = self._kind, None, int(self.source.shape[0])
+        for name, arr in zip(("avgp_in", "avgp_k", "avgp_stride", "avgp_pad"), arrays):
+            for a in range(2):
+                getattr(d, name)[a] = arr[a]
+        d.avgp_ceil, d.avgp_include_pad = int(self.ceil_mode), int(self.count_include_pad)
+        d.avgp_divisor = 0 if self.divisor_override is None else self.divisor_override
+        return []
 
 
 class MeanFieldConnection(_FixedConnection):

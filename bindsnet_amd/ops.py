@@ -381,6 +381,40 @@ def prop_pool(fr, s, out, kernel_size, stride=1, padding=0, dilation=1, decay=0.
     return out
 
 
+def avgpool_geometry(plane, kernel_size, stride=None, padding=0, ceil_mode=False):
+    """f18: the four int[2] arrays of snn_prop_avgpool2d_f32 and the pooled sizes as ATen's avg_pool2d computes them (stride None:
+    the kernel's; with ceil_mode a last window that would start in the right padding is dropped)."""
+    pair = lambda v: tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v),) * 2       # noqa: E731
+    k = pair(kernel_size)
+    fields = [tuple(int(x) for x in plane), k, k if stride is None or stride == [] or stride == () else pair(stride), pair(padding)]
+    if any(len(f) != 2 for f in fields):
+        raise ValueError("avgpool_geometry: the plane, kernel_size, stride and padding need two entries (or one int) each")
+    if min(fields[2]) <= 0 or min(k) <= 0:
+        raise ValueError("avgpool_geometry: kernel_size and stride must be positive")
+    out = []
+    for i, kk, s, p in zip(*fields):
+        o = (i + 2 * p - kk + (s - 1 if ceil_mode else 0)) // s + 1
+        out.append(o - 1 if ceil_mode and (o - 1) * s >= i + p else o)
+    return [(C.c_int * 2)(*f) for f in fields], tuple(out)
+
+
+def prop_avgpool(s, out, kernel_size, stride=None, padding=0, ceil_mode=False, count_include_pad=True, divisor_override=None,
+                 accumulate=False):
+    """f18: one AvgPool2dConnection.compute: out [B, C, OH, OW] (+)= F.avg_pool2d(s.float(), ...) for spike bytes s [B, C, H, W], every
+    window an integer count divided once (include/snnhip.h)."""
+    if s.dim() != 4:
+        raise ValueError("prop_avgpool: spikes must be [B, C, H, W]")
+    if divisor_override is not None and int(divisor_override) == 0:
+        raise ValueError("prop_avgpool: divisor_override must not be zero (torch: divisor must be not zero)")
+    arrays, pooled = avgpool_geometry(s.shape[2:], kernel_size, stride, padding, ceil_mode)
+    if min(pooled) <= 0 or tuple(out.shape) != tuple(s.shape[:2]) + pooled:
+        raise ValueError(f"prop_avgpool: out must be {tuple(s.shape[:2]) + pooled}, got {tuple(out.shape)}")
+    check(lib().snn_prop_avgpool2d_f32(_ptr(s, "spike"), _ptr(out, F32), s.shape[0], s.shape[1], *arrays, int(bool(ceil_mode)),
+                                       int(bool(count_include_pad)), 0 if divisor_override is None else int(divisor_override),
+                                       int(accumulate), _stream()), "prop_avgpool")
+    return out
+
+
 def prop_meanfield(w, s, out, accumulate=False, store=False):
     """f11: MeanFieldConnection.compute: out [B, n_tgt] (+)= s.float().mean() * w, the mean over the whole of s [B, n_src]; `w` has
     one element or a shape that is a tail of out's.  store: out = mean * w itself (a zero keeps its sign) instead of 0 + mean * w."""

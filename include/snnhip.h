@@ -464,6 +464,30 @@ int snn_pass_step(uint8_t *s, const float *I, int B, int N, uint8_t *raster_s, s
 int snn_prop_gather_f32(const uint8_t *s, float *out, int B, int n_src, const int *out_ext, const int *src_ext,
                         const int *stride, const int *off, int accumulate, snn_stream_t stream);
 
+/* ---- f18: AvgPool2dConnection.compute ---------------------------------------------------------------
+ * Not in the reference (an extension for converted networks); the oracle is ATen's avg_pool2d on the CPU:
+ *   out (+)= F.avg_pool2d(float(s), k, stride, pad, ceil_mode, count_include_pad, divisor_override)
+ * s spike bytes [B, C, in[0], in[1]] (a non-zero byte counts as one spike), out f32 [B, C, out[0], out[1]] with
+ * out[a] = floor((in[a] + 2 pad[a] - k[a] + (ceil_mode ? stride[a] - 1 : 0)) / stride[a]) + 1, less one with ceil_mode where the
+ * last window would start at or behind in[a] + pad[a].  Per output: the window is clipped to the padded plane (the product of
+ * the two lengths is pool_size), then to the plane; the spikes inside are COUNTED as an integer; the value is
+ * f32(count) / f32(divisor), one correctly rounded division, with divisor = divisor_override where that is non-zero, else
+ * pool_size (count_include_pad) or the number of in-plane taps; a window without an in-plane tap gives 0.  accumulate adds the
+ * value onto out with one rounded add, as snn_prop_local_f32.  Integer counts make every summation order give the same bits:
+ * windows of fewer than SNN_AVGPOOL_COOP_TAPS taps (k[0] * k[1]) take one thread per output, larger ones one wave per output
+ * (csrc/snn_avgpool.hip), on at most SNN_AVGPOOL_MAX_GRID workgroups of SNN_AVGPOOL_THREADS threads striding over the outputs.
+ * in / k / stride / pad are HOST arrays of two ints.  2 * pad[a] > k[a] (torch refuses it), an empty output, k[0] * k[1] beyond
+ * 2^24 or a plane beyond 2^30 elements is SNN_ERR_INVALID; B * C beyond 2^30 or more than 2^40 elements SNN_ERR_UNSUPPORTED.
+ * snn_set_avgpool_body: 0 -- the rule above (the default); 1 / 2 -- the per-thread / the per-wave body for every geometry
+ * (tests and measurements: the crossover, profiles/NOTES_avgpool.md).  (ABI 8, additive)                                  */
+#define SNN_AVGPOOL_COOP_TAPS 64
+#define SNN_AVGPOOL_THREADS 256
+#define SNN_AVGPOOL_MAX_GRID 1024
+int snn_prop_avgpool2d_f32(const uint8_t *s, float *out, int B, int C, const int *in, const int *k, const int *stride,
+                           const int *pad, int ceil_mode, int count_include_pad, int divisor_override, int accumulate,
+                           snn_stream_t stream);
+void snn_set_avgpool_body(int body);
+
 /* ---- device-resident emulation of torch's CPU generator --------------------------------------
  * Replaces the pre-drawn noise_q stream: the library reproduces the draws torch.multinomial
  * (bindsnet/network/nodes.py:1100-1102) would consume -- mt19937 -> random64 -> u in [0,1) ->
@@ -826,8 +850,11 @@ enum { SNN_LAYER_INPUT = 0, SNN_LAYER_LIF = 1, SNN_LAYER_DC = 2, SNN_LAYER_MCP =
 /* SNN_CONN_POOL (MaxPool1d / 2d / 3dConnection: no `w`; firing_rates and the pool_* fields) and SNN_CONN_MEANFIELD
  * (MeanFieldConnection: `w` of w_numel elements) came the same way: propagation only -- a rule is SNN_ERR_UNSUPPORTED, a norm,
  * mask, bias or weight monitor SNN_ERR_INVALID --, generic plan only, SNN_ABI_VERSION unchanged.  */
+/* SNN_CONN_AVGPOOL (AvgPool2dConnection, f18: no `w`, no state; the avgp_* fields in front of snn_conn_desc's last field) came the same way:
+ * propagation only, refused like POOL, generic plan only, SNN_ABI_VERSION unchanged.  Its outputs are fractions, so it may not
+ * feed a PASS layer.  */
 enum { SNN_CONN_MCC = 0, SNN_CONN_DENSE = 1, SNN_CONN_CONV2D = 2, SNN_CONN_LOCAL = 3, SNN_CONN_CONVND = 4, SNN_CONN_SPARSE = 5,
-       SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7, SNN_CONN_PERMUTE = 8, SNN_CONN_PAD = 9 };
+       SNN_CONN_POOL = 6, SNN_CONN_MEANFIELD = 7, SNN_CONN_PERMUTE = 8, SNN_CONN_PAD = 9, SNN_CONN_AVGPOOL = 10 };
 enum { SNN_RULE_NONE = 0, SNN_RULE_POSTPRE = 1, SNN_RULE_MSTDP = 2, SNN_RULE_HEBBIAN = 3, SNN_RULE_WDPOSTPRE = 4,
        SNN_RULE_MSTDPET = 5, SNN_RULE_RMAX = 6 };
 
@@ -994,6 +1021,13 @@ typedef struct {
      * WDPOSTPRE and MSTDP; MSTDPET, RMAX, MSTDP on a CONV2D connection and NONE ignore it).  Outside the enum: SNN_ERR_INVALID.
      * Added like the fields above: SNN_ABI_VERSION stays. */
     int reduce;
+    /* AVGPOOL: the arguments of snn_prop_avgpool2d_f32 -- avgp_c channels, two ints per geometry field, avgp_ceil its ceil_mode,
+     * avgp_include_pad its count_include_pad, avgp_divisor its divisor_override (0: none); `w` is NULL.  avgp_c * the plane must
+     * be the source's n and avgp_c * the pooled plane the target's, else SNN_ERR_INVALID.  Added without changing
+     * SNN_ABI_VERSION, like the fields above; they stand in front of `activity`, which stays the descriptor's last field (the
+     * library and its binding are built from this one header: tests/test_abi.py compares the sizes). */
+    int avgp_c, avgp_in[2], avgp_k[2], avgp_stride[2], avgp_pad[2];
+    int avgp_ceil, avgp_include_pad, avgp_divisor;
     /* MulticompartmentConnection(traces=True) (topology.py:415-435, :473-474): nullable f32 [B, target n], the connection's own
      * summed signal of the step.  With it the connection propagates into `activity` (accumulate = 0) and one elementwise launch
      * feeds the target: current = activity for the target's first connection, current = current + activity behind it -- the
