@@ -765,7 +765,7 @@ int snn_try_fused_convpp(const snn_layer_desc *L, int nL, const snn_conn_desc *C
         if (hipMemsetAsync(a.learning ? (void *)a.gr : (void *)a.fin, 0, (a.learning ? (size_t)4 * c.B * E * sizeof(unsigned long long) : 0) + 16, st) != hipSuccess) return SNN_ERR_LAUNCH;
         void *args[] = {(void *)&a};
         const hipError_t e = hipLaunchCooperativeKernel((const void *)fn, dim3((unsigned)grid), dim3((unsigned)nt), args, (unsigned)lds, st);
-        if (e != hipSuccess) { (void)hipGetLastError(); continue; }          // refused: a coarser chunk, then the generic plan
+        if (e != hipSuccess) { (void)hipGetLastError(); continue; }          // refused (the grid, or cooperative launches to this process: see snn_dc2015_resident_launch): a coarser chunk, then the generic plan
         const int rc = snn_check_launch();
         if (rc) return rc;
         if (a.dbg) {                                       // developer aid: synchronous

@@ -1578,6 +1578,6 @@ int snn_dc2015_async_launch(const DcCtx &c, size_t lds, hipStream_t st, bool ord
                            : (ft ? (const void *)k_dc2015_async<false, true> : (const void *)k_dc2015_async<false, false>);
     if (!coop) return snn_check(hipLaunchKernel(fn, dim3(grid), dim3(ANT), args, lds, st));
     const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(grid), dim3(ANT), args, (unsigned)lds, st);
-    if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return SNN_ERR_UNSUPPORTED; }
+    if (e == hipErrorCooperativeLaunchTooLarge || e == hipErrorIllegalState) { (void)hipGetLastError(); return SNN_ERR_UNSUPPORTED; }   // (see snn_dc2015_resident_launch)
     return snn_check(e);
 }

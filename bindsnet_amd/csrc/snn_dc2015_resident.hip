@@ -1808,7 +1808,9 @@ int snn_dc2015_resident_capacity(int cw, int nt, size_t lds) {
 }
 
 // Cooperative launch: the runtime itself refuses (hipErrorCooperativeLaunchTooLarge) a grid it cannot make co-resident.
-// Returns SNN_ERR_UNSUPPORTED in that case so that the caller takes the one-launch-per-timestep plan instead.
+// Returns SNN_ERR_UNSUPPORTED in that case so that the caller takes the one-launch-per-timestep plan instead.  Likewise where the
+// runtime has no cooperative launch for THIS process (hipErrorIllegalState): a device that several processes share may grant its
+// cooperative queue to one of them only, and the others are refused whatever the grid.
 int snn_dc2015_resident_launch(const DcCtx &c, int cw, int nt, size_t lds, int lean, hipStream_t st, bool ordinary) {
     if (!resident_attr_once()) return SNN_ERR_LAUNCH;
     static const bool coop_env = !(getenv("SNN_DC_COOP") && atoi(getenv("SNN_DC_COOP")) == 0);
@@ -1820,6 +1822,6 @@ int snn_dc2015_resident_launch(const DcCtx &c, int cw, int nt, size_t lds, int l
         return snn_check(hipLaunchKernel(fn, dim3(c.G), dim3(nt), args, lds, st));
     const int gmult = (lean == 2 && (c.spec_flags >> 8) > 1) ? (c.spec_flags >> 8) : 1;
     const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(c.G * gmult), dim3(nt), args, (unsigned)lds, st);
-    if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); return SNN_ERR_UNSUPPORTED; }
+    if (e == hipErrorCooperativeLaunchTooLarge || e == hipErrorIllegalState) { (void)hipGetLastError(); return SNN_ERR_UNSUPPORTED; }
     return snn_check(e);
 }

@@ -858,7 +858,8 @@ __global__ __launch_bounds__(256) void k_conv_pp_apply(float *__restrict__ W, co
 static int conv_pp_partials(const uint8_t *s_src, const float *x_src, const uint8_t *s_tgt, const float *x_tgt, int B, int Cin, int H, int Wd,
                             int Cout, int KH, int KW, int stride, int pad, int OH, int OW, float *ws, hipStream_t stream) {
     const long E = (long)Cout * Cin * KH * KW, n = (long)B * E;
-    static const bool events = [] { const char *v = getenv("SNN_CONV_PP_EVENTS"); return !(v && v[0] == '0'); }();
+    const char *ev_env = getenv("SNN_CONV_PP_EVENTS");          // (test switch, read per call: the tests select the dense body in their own process)
+    const bool events = !(ev_env && ev_env[0] == '0');
     const size_t ev_lds_bytes = ((size_t)H + (size_t)8 * OH + 1) * sizeof(uint32_t) + ((size_t)8 * OH * OW + (size_t)H * Wd) * sizeof(float);
     if (events && Wd <= 32 && OW <= 32 && ev_lds_bytes <= 60 * 1024 && 8 * KH * KW <= 256) {
         const snn::ConvGeom g{Cin, H, Wd, Cout, KH, KW, stride, pad, OH, OW};

@@ -254,7 +254,12 @@ def _check_two_ranks(outs):
 def test_two_ranks_on_one_gpu_gloo(tmp_path):
     """World size 2 on the one GPU of the box (gloo between the processes, the shards and the merged tensors on the
     device): B = 16 + 16 of the cfg2 Poisson fixture, two consecutive inputs.  Every rank's rasters = the oracle on its
-    shard from the merged weights / theta of the previous input, bit for bit; merged W and theta = the numpy merge."""
+    shard from the merged weights / theta of the previous input, bit for bit; merged W and theta = the numpy merge.
+    Both ranks run the resident plan, one cooperative launch per run: skipped where the device grants those to one process at a time."""
+    import coop_probe
+    reason = coop_probe.refusal()
+    if reason:
+        pytest.skip(reason)
     rcs, logs, outs = _two_rank_run("gloo", tmp_path)
     assert rcs == [0, 0], "\n".join(logs)[-3000:]
     _check_two_ranks(outs)
