@@ -222,6 +222,8 @@ _SIGS = {
     "snn_prop_dense_auto_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "snn_set_dense_prop_mode": ([_i], None),
     "snn_prop_conv2d_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
+    "snn_prop_conv2d_mfma_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp, _vp], _i),
+    "snn_conv2d_mfma_takes": ([_i] * 10, _i),
     "snn_prop_dense_real_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "snn_prop_conv2d_real_f32": ([_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp], _i),
     "snn_input_step_real_pv": ([_vp, _vp, _i, _i, _f, _f, _i, C.POINTER(PerVec), _vp, _vp], _i),

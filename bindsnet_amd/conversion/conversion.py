@@ -212,8 +212,9 @@ def _ann_to_snn_helper(prev, current, node_type, last=False, **kwargs):
     if isinstance(current, nn.Conv2d):
         layer = node_type(shape=(current.out_channels, *_conv_output(prev, current)), **spiking)
         bias = current.bias if current.bias is not None else torch.zeros(layer.shape[1])
+        # (prop_auto: a wide convolution between two spiking layers takes the matrix cores; the first one, fed real values, does not)
         return layer, topology.Conv2dConnection(source=prev, target=layer, kernel_size=current.kernel_size, stride=current.stride,
-                                                padding=current.padding, dilation=current.dilation, w=current.weight, b=bias)
+                                                padding=current.padding, dilation=current.dilation, w=current.weight, b=bias, prop_auto=True)
     if isinstance(current, nn.MaxPool2d):
         current.kernel_size, current.padding, current.stride = _pair(current.kernel_size), _pair(current.padding), _pair(current.stride)
         layer = PassThroughNodes(shape=(prev.shape[0], *_conv_output(prev, current)))

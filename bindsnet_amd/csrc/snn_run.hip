@@ -431,6 +431,11 @@ static int feed_conn(const snn_layer_desc *L, const snn_conn_desc &d, const snn_
                                                                  d.conv_kd, d.kh, d.kw, d.stride, d.pad, acc, st));
     else if (d.kind == SNN_CONN_LOCAL) TRY(snn_prop_local_f32(d.w, d.local_src, sp, D.current, B, d.cin, d.local_F,
                                                               d.local_conv_prod, d.local_kernel_prod, d.local_n_src, acc, st));
+    // (a wide convolution whose owner asked: the implicit GEMM on the matrix cores, its 0/1 condition decided inside the launch)
+    else if (d.kind == SNN_CONN_CONV2D && p && d.rule == SNN_RULE_NONE &&
+             snn_conv2d_mfma_takes(B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, p->prop_auto))
+        TRY(snn_prop_conv2d_mfma_f32(d.w, d.bias, sp, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw, d.stride, d.pad, acc,
+                                     p->prop_counters, st));
     else TRY(snn_prop_conv2d_f32(d.w, d.bias, sp, D.current, B, d.cin, d.h, d.wd, d.cout, d.kh, d.kw,
                                  d.stride, d.pad, acc, st));
     if (d.activity)

@@ -306,7 +306,39 @@ class _DenseConnection(AbstractConnection):
                          use_dt=False, decay=float(rule.weight_decay), wmin=lo, wmax=hi, reduce=rule._reduce())
 
 
-class Connection(_DenseConnection):
+class _PropCounted:
+    """What Connection and Conv2dConnection share for `prop_auto`: which body the propagation took, as two int32 words on the device,
+    {matrix, event}, added to by the kernels and read only here.  They live in self.__dict__["_prop_counters"], which .to(), clone()
+    and save() carry along."""
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if self.__dict__.get("_prop_counters") is not None:      # (int32: a cast of the module leaves it, a move takes it along)
+            self.__dict__["_prop_counters"] = fn(self.__dict__["_prop_counters"])
+        return out
+
+    def _prop_counter_words(self, dev):
+        cnt = self.__dict__.get("_prop_counters")
+        if cnt is None:
+            cnt = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.__dict__["_prop_counters"] = cnt = cnt.to(dev)
+        return cnt
+
+    def prop_stats(self) -> dict:
+        """{"matrix_tiles", "event_tiles"}: how often the propagation took the matrix-core body and how often the other one, since
+        construction or the last reset_prop_stats() -- for a Connection in (tile of 16 samples, timestep) pairs of Network.run, for a
+        Conv2dConnection in workgroup-steps (the event count is its scalar body's).  One device read; zeros on the host and for a
+        connection that is not routed.  The two counters are int32 words: they wrap after 2^31 - 1."""
+        cnt = self.__dict__.get("_prop_counters")
+        m, e = (0, 0) if cnt is None else cnt.tolist()
+        return {"matrix_tiles": int(m), "event_tiles": int(e)}
+
+    def reset_prop_stats(self) -> None:
+        if self.__dict__.get("_prop_counters") is not None:
+            self.__dict__["_prop_counters"].zero_()
+
+
+class Connection(_PropCounted, _DenseConnection):
     """Dense all-to-all synapses (reference: topology.py:265-399)."""
 
     _takes_real = _has_window = True
@@ -351,31 +383,7 @@ class Connection(_DenseConnection):
             for key in ("host", "ring"):
                 if win[key] is not None:
                     win[key] = fn(win[key])
-        if self.__dict__.get("_prop_counters") is not None:      # (int32: a cast of the module leaves it, a move takes it along)
-            self.__dict__["_prop_counters"] = fn(self.__dict__["_prop_counters"])
         return out
-
-    # -- which body the generic plan's propagation took (snn_prop_dense_auto_f32): two int32 words on the device, {matrix, event}
-    # tile-steps, added to by the kernels and read only here.  They live in self.__dict__["_prop_counters"], which .to(), clone()
-    # and save() carry along.
-    def _prop_counter_words(self, dev):
-        cnt = self.__dict__.get("_prop_counters")
-        if cnt is None:
-            cnt = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.__dict__["_prop_counters"] = cnt = cnt.to(dev)
-        return cnt
-
-    def prop_stats(self) -> dict:
-        """{"matrix_tiles", "event_tiles"}: how many (tile of 16 samples, timestep) pairs of Network.run took the matrix-core body and
-        how many the event-driven one, since construction or the last reset_prop_stats().  One device read; zeros on the host.  The two
-        counters are int32 words: they wrap after 2^31 - 1 tile-steps."""
-        cnt = self.__dict__.get("_prop_counters")
-        m, e = (0, 0) if cnt is None else cnt.tolist()
-        return {"matrix_tiles": int(m), "event_tiles": int(e)}
-
-    def reset_prop_stats(self) -> None:
-        if self.__dict__.get("_prop_counters") is not None:
-            self.__dict__["_prop_counters"].zero_()
 
     def _window_ring(self, B: int, dev):
         """The window as snn_prop_window_f32 keeps it, made from `s_w` where that was last written on the host: the "_win" entry
@@ -982,7 +990,7 @@ class LocalConnection(_DenseConnection):
         super().update(**kwargs)
 
 
-class Conv2dConnection(AbstractConnection):
+class Conv2dConnection(_PropCounted, AbstractConnection):
     """2-D convolutional synapses (reference: topology.py:686-844): propagation, PostPre, Hebbian, WeightDependentPostPre, and MSTDP
     at batch 1.  MSTDPET is not offered: the reference's conv2d form (learning.py:2654-2745) never adds the point eligibility to its
     eligibility trace, so it leaves the weights as they are at batch 1 and fails at larger batches.
@@ -1018,6 +1026,10 @@ class Conv2dConnection(AbstractConnection):
             "(input_height - filter_height + 2 * padding_height) / stride_height + 1,"
             "(input_width - filter_width + 2 * padding_width) / stride_width + 1")
         _rand_weights(self, (self.out_channels, self.in_channels, *self.kernel_size), self.out_channels, w_dtype, kwargs)
+        # Not in the reference.  True: fed spike bytes and without a learning rule, a wide shape (more than 16 input channels or a bank
+        # beyond 64 KiB) propagates as an implicit GEMM on the matrix cores, bit for bit what it gives otherwise;
+        # False (the default), every other shape and the host path: as ever.
+        self.prop_auto = bool(kwargs.get("prop_auto", False))
 
     def _rule_refusal(self, rule):
         """Why `rule` must not be constructed on this connection, or None: asked by LearningRule.__init__ (the connection's own
@@ -1035,8 +1047,27 @@ class Conv2dConnection(AbstractConnection):
             ops.prop_conv2d_real(self.w.data, s.reshape(s.size(0), *self.source.shape).contiguous(), out, bias=self.b.data,
                                  stride=self.stride[0], pad=self.padding[0], accumulate=accumulate)
             return
+        if self._mfma_route(s.size(0)):
+            ops.prop_conv2d_mfma(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0],
+                                 accumulate=accumulate, counters=self._prop_counter_words(self.w.device))
+            return
         ops.prop_conv2d(self.w.data, s.contiguous(), out, bias=self.b.data, stride=self.stride[0], pad=self.padding[0],
                         accumulate=accumulate)
+
+    def _mfma_route(self, B: int) -> bool:
+        """Whether spike bytes propagate through ops.prop_conv2d_mfma: asked for, no learning rule, and a shape snn_net_run routes too."""
+        if not getattr(self, "prop_auto", False) or getattr(self.update_rule, "_learns", False):
+            return False
+        return ops.conv2d_mfma_takes(B, self.in_channels, self.source.shape[1], self.source.shape[2], self.out_channels,
+                                     *self.kernel_size, self.stride[0], self.padding[0])
+
+    def _describe_prop(self, p, d, B: int, dev, scratch) -> list:
+        """This connection's snn_conn_prop `p`: the request and the two counter words (no flags: the choice is made inside the one
+        launch).  A connection that does not ask keeps an empty entry and no counters."""
+        if not getattr(self, "prop_auto", False):
+            return []
+        p.prop_auto, p.prop_counters = 1, dptr(self._prop_counter_words(dev))
+        return [(self, "_prop_counters")]
 
     def _describe(self, d, B, dev, scratch):
         if self.b.numel() != self.out_channels:       # (F.conv2d's RuntimeError in the first step of the reference; here before the run changes state)

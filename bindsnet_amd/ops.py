@@ -196,6 +196,27 @@ def prop_conv2d(W, s, out, bias=None, stride=1, pad=0, accumulate=False):
     return out
 
 
+def prop_conv2d_mfma(W, s, out, bias=None, stride=1, pad=0, accumulate=False, counters=None):
+    """a7 on the f32 matrix cores, an implicit GEMM with one unsplit chain per 16x16 output tile: bit-identical to prop_conv2d for
+    0/1 spikes; a workgroup that meets another byte computes its outputs in the stated order instead (snn_prop_conv2d_mfma_f32).
+    `counters`: an int32 [2] device tensor that the call adds its {matrix, scalar} workgroup counts to."""
+    B, Cin, H, Wd = s.shape
+    Cout, Cin2, KH, KW = W.shape
+    assert Cin == Cin2
+    if counters is not None and counters.numel() < 2:
+        raise ValueError("prop_conv2d_mfma: counters needs 2 int32 words")
+    check(lib().snn_prop_conv2d_mfma_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(s, "spike"), _ptr(out, F32), B, Cin, H, Wd, Cout, KH,
+                                         KW, stride, pad, int(accumulate), _ptr(counters, torch.int32, True), _stream()),
+          "prop_conv2d_mfma")
+    return out
+
+
+def conv2d_mfma_takes(B, Cin, H, Wd, Cout, KH, KW, stride, pad, asked=True) -> bool:
+    """Whether a Conv2dConnection of this shape that asks (prop_auto) propagates through prop_conv2d_mfma: a wide shape (more than 16
+    input channels or a bank beyond 64 KiB) whose input bands fit the LDS.  Decided on the host."""
+    return bool(lib().snn_conv2d_mfma_takes(B, Cin, H, Wd, Cout, KH, KW, stride, pad, int(bool(asked))))
+
+
 def prop_dense_real(W, x, out, bias=None, accumulate=False):
     """f17: out (+)= x @ W (+ b) over real-valued float32 sources x [B, Nin]: ascending-i sequential f32, one rounded multiply and
     one rounded add per term, bias last (include/snnhip.h)."""

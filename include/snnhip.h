@@ -181,6 +181,25 @@ int snn_prop_conv2d_f32(const float *W, const float *bias, const uint8_t *s, flo
                         int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
                         int stride, int pad, int accumulate, snn_stream_t stream);
 
+/* a7 on the f32 matrix cores: the same arguments, argument checks and stated order, as an implicit GEMM on
+ * v_mfma_f32_16x16x4_f32 (csrc/snn_conv_mfma.hip; M = B*OH*OW output pixels, N = Cout, K = the ordered taps, every tap's channels
+ * padded to a multiple of 16 with zero spikes AND zero weights).  One unsplit accumulator chain per 16x16 output tile walks
+ * (kh,kw,cin): for spike bytes that are all 0 or 1 the result equals snn_prop_conv2d_f32 bit for bit for finite weights (a
+ * non-finite weight under a silent tap gives NaN here, 0 * inf, where the event-driven order skips it).  A workgroup (64 output
+ * pixels x a group of 16 or 32 output channels) that staged a byte above 1 computes its outputs in the stated order thread by
+ * thread instead -- slow, bit-equal for any byte; the choice is made inside the one launch.  counters: nullable device int32 [2],
+ * {workgroups through the matrix body, workgroups through the scalar body} are added.  Any Cin, Cout, KH, KW, stride >= 1,
+ * pad >= 0, B; SNN_ERR_UNSUPPORTED, before any launch, for the int limits of snn_prop_conv2d_f32 (the padded tap count included; a grid below 2^32 threads)
+ * and where two weight slabs and the input bands of one workgroup -- per sample it touches (up to 63 / (OH*OW) + 2), the input rows under
+ * min(OH, (OW + 62) / OW + 1) output rows, Wd pixels each, ceil(Cin / 16) | 1 16-byte units per pixel -- exceed 150 KiB of dynamic LDS (of gfx950's 160).
+ * snn_conv2d_mfma_takes: 1 where snn_net_run sends a CONV2D connection here -- `asked` (snn_conn_prop.prop_auto), a shape
+ * snn_prop_conv2d_f32 gives to its wide kernel (Cin > 16 or a bank beyond 64 KiB) and within the limits above; a fact of shape
+ * and request, never of data, decided on the host.  (ABI 8, additive)                                                        */
+int snn_prop_conv2d_mfma_f32(const float *W, const float *bias, const uint8_t *s, float *out,
+                             int B, int Cin, int H, int Wd, int Cout, int KH, int KW,
+                             int stride, int pad, int accumulate, int *counters, snn_stream_t stream);
+int snn_conv2d_mfma_takes(int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, int asked);
+
 /* ---- f17: a real-valued (analog) Input layer -------------------------------------------------------
  * The reference's Input.forward is `self.s = x` for any dtype (nodes.py:219) and every compute() starts with `s.float()`: a
  * network may be driven by the real-valued sample itself at every step (encoding.repeat), which is how a network made by
@@ -1047,7 +1066,10 @@ typedef struct {
  * every step, 3 to 6 us however sparse the spikes are, so nobody pays it unasked; every other connection keeps the single launch
  * of snn_prop_dense_f32, as without the table.  Modes 1 and 2 (tests, measurements) take every connection that has prop_flags.
  * prop_auto without prop_flags is SNN_ERR_INVALID.  Ignored by every other kind and by the fused plans, which keep the event-driven form; an
- * MCC connection sums in ATen's cascade order, which a single chain cannot reproduce, and stays event-driven too. */
+ * MCC connection sums in ATen's cascade order, which a single chain cannot reproduce, and stays event-driven too.
+ * A CONV2D connection fed by spike bytes, without a learning rule, with prop_auto != 0 and a shape snn_conv2d_mfma_takes accepts
+ * propagates through snn_prop_conv2d_mfma_f32 on the generic plan (prop_counters: {matrix, scalar} workgroup-steps; prop_flags is
+ * not read and may be null); every other CONV2D connection runs snn_prop_conv2d_f32 as without the table. */
 typedef struct {
     int prop_auto;
     int *prop_flags, *prop_counters;

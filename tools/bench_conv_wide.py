@@ -2,9 +2,10 @@
 """Timesteps/s of a converted CNN whose convolutions have 3, 32 and 64 input channels -- ann_to_snn of Conv(3 -> 32, 3, p1) - ReLU -
 MaxPool(2) - Conv(32 -> 64, 3, p1) - ReLU - MaxPool(2) - Conv(64 -> 128, 3, p1) - ReLU - Linear(8192 -> 10) on a (3, 32, 32) input,
 T = 100 -- on the MI355X (generic plan; the second and third convolution run csrc/snn_conv_wide.hip) and on the package's host path,
-same commit, same machine; and the time of one snn_prop_conv2d_f32 call at the three layer shapes.
+same commit, same machine; the time of one snn_prop_conv2d_f32 call at the three layer shapes beside one snn_prop_conv2d_mfma_f32
+call (csrc/snn_conv_mfma.hip); and the device's timesteps/s with and without the converted network's request for the matrix cores.
 
-    python tools/bench_conv_wide.py [--time 100] [--runs 20] [--host-runs 2] [--reps 3] [--batch 1 16] [--calls]
+    python tools/bench_conv_wide.py [--time 100] [--runs 20] [--host-runs 2] [--reps 3] [--batch 1 16] [--calls | --route] [--tree DIR]
 
 End to end, per batch size in {1, 16}: Bernoulli input at 10 %; weights on a 1/64 grid (every sum exact, so the device's rasters must
 equal the host path's: reported).  Per side one untimed run, then `reps` windows of `runs` network.run(time) calls, each followed by
@@ -12,7 +13,13 @@ reset_state_variables(), timed end to end (the device synchronised).  One JSON l
 both sides with the least and the largest, the spikes per neuron-step of every spiking layer, whether the rasters agree.
 
 --calls: per layer shape, batch size in {1, 16} and input density in {1 %, 10 %}: 3 untimed calls, then `reps` windows of 50 calls between
-device events; the median microseconds per call with the least and the largest."""
+device events, the two operators alternating window by window; the median microseconds per call with the least and the largest.  The
+calls go through ctypes: below some 13 to 18 us per call the figure is the host's issue rate, not the kernel.
+
+--route: per batch size, the device's timesteps/s with the convolutions' prop_auto as ann_to_snn sets it and with it cleared, the two
+networks alternating window by window, and how many workgroup-steps took the matrix body.  --tree DIR imports the package from another
+checkout of this project (a parent commit, built there), so that one session can alternate the two commits with one tool; a commit
+without the request reports the plain figure only."""
 import argparse
 import json
 import os
@@ -26,7 +33,7 @@ import torch
 import torch.nn as nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+TREE = "."                                                          # --tree: where the package is imported from (main sets sys.path)
 DEV = "cuda:0"
 SHAPE = (3, 32, 32)
 LAYERS = [(3, 32, 32, 32), (32, 64, 16, 16), (64, 128, 8, 8)]          # Cin, Cout, H, W of the three convolutions (3x3, pad 1)
@@ -108,20 +115,65 @@ def calls(a):
             out = torch.empty(B, cout, h, w, device=DEV)
             for density in (0.01, 0.1):
                 s = (torch.rand(B, cin, h, w, device=DEV) < density).to(torch.uint8)
-                for _ in range(3):
-                    ops.prop_conv2d(W, s, out, bias=bias, stride=1, pad=1)
-                us = []
+                named = {"prop_conv2d": ops.prop_conv2d}
+                if hasattr(ops, "prop_conv2d_mfma"):
+                    named["prop_conv2d_mfma"] = ops.prop_conv2d_mfma
+                us = {name: [] for name in named}
+                for op in named.values():
+                    for _ in range(3):
+                        op(W, s, out, bias=bias, stride=1, pad=1)
                 for _ in range(a.reps):
-                    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    start.record()
-                    for _ in range(50):
-                        ops.prop_conv2d(W, s, out, bias=bias, stride=1, pad=1)
-                    end.record()
-                    torch.cuda.synchronize()
-                    us.append(1000.0 * start.elapsed_time(end) / 50)
-                print(json.dumps({"op": "prop_conv2d", "Cin": cin, "Cout": cout, "image": [h, w], "kernel": [3, 3], "pad": 1, "B": B, "density": density,
-                                  "calls_per_window": 50, "windows": a.reps, "us_per_call": round(statistics.median(us), 2),
-                                  "us_per_call_min_max": [round(min(us), 2), round(max(us), 2)]}), flush=True)
+                    for name, op in named.items():
+                        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        start.record()
+                        for _ in range(50):
+                            op(W, s, out, bias=bias, stride=1, pad=1)
+                        end.record()
+                        torch.cuda.synchronize()
+                        us[name].append(1000.0 * start.elapsed_time(end) / 50)
+                for name in named:
+                    print(json.dumps({"op": name, "Cin": cin, "Cout": cout, "image": [h, w], "kernel": [3, 3], "pad": 1, "B": B, "density": density,
+                                      "calls_per_window": 50, "windows": a.reps, "us_per_call": round(statistics.median(us[name]), 2),
+                                      "us_per_call_min_max": [round(min(us[name]), 2), round(max(us[name]), 2)]}), flush=True)
+
+
+def route(a):
+    from bindsnet_amd.network.topology import Conv2dConnection
+    for B in a.batch:
+        x = (torch.rand(a.time, B, *SHAPE, generator=torch.Generator().manual_seed(B)) < 0.1).to(torch.uint8).to(DEV)
+        nets = {}
+        for name in ("asked", "plain"):
+            net = network(B)
+            convs = [c for c in net.connections.values() if isinstance(c, Conv2dConnection)]
+            if not all(hasattr(c, "prop_auto") for c in convs):
+                if name == "asked":
+                    continue
+            elif name == "plain":
+                for c in convs:
+                    c.prop_auto = False
+            nets[name] = net.to(DEV)
+            nets[name].run({"Input": x.clone()}, time=a.time)                  # untimed
+            nets[name].reset_state_variables()
+        rates = {name: [] for name in nets}
+        for _ in range(a.reps):
+            for name, net in nets.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.runs):
+                    net.run({"Input": x.clone()}, time=a.time)
+                    net.reset_state_variables()
+                torch.cuda.synchronize()
+                rates[name].append(a.runs * a.time / (time.perf_counter() - t0))
+        line = {"graph": "ann_to_snn: Conv 3-32 / pool / Conv 32-64 / pool / Conv 64-128 / Linear 8192-10, input 3x32x32", "B": B, "T": a.time,
+                "runs_per_window": a.runs, "windows": a.reps, "tree": TREE}
+        for name, net in nets.items():
+            line[name + "_timesteps_per_s"] = round(statistics.median(rates[name]), 1)
+            line[name + "_timesteps_per_s_min_max"] = [round(min(rates[name]), 1), round(max(rates[name]), 1)]
+            line[name + "_plan"] = net.last_plan
+            if hasattr(net, "prop_stats"):
+                line[name + "_matrix_workgroup_steps"] = sum(v["matrix_tiles"] for k, v in net.prop_stats().items()
+                                                             if isinstance(net.connections[k], Conv2dConnection))
+        print(json.dumps(line), flush=True)
 
 
 def main():
@@ -131,13 +183,22 @@ def main():
     ap.add_argument("--host-runs", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--calls", action="store_true")
+    ap.add_argument("--route", action="store_true")
+    ap.add_argument("--tree", default=None, help="another checkout of this project, built, to import bindsnet_amd from")
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 16])
     a = ap.parse_args()
     if a.reps < 3:
         raise SystemExit("bench_conv_wide.py reports a spread: at least 3 windows")
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_wide.py measures on the MI355X: no GPU here")
-    return calls(a) if a.calls else end_to_end(a)
+    global TREE
+    root = ROOT
+    if a.tree is not None:                                          # (the package is imported inside the functions below, never before this)
+        root = TREE = os.path.abspath(a.tree)
+        if not os.path.isfile(os.path.join(root, "bindsnet_amd", "__init__.py")):
+            raise SystemExit(f"--tree {a.tree}: no bindsnet_amd package there")
+    sys.path[:0] = [root, os.path.join(root, "tests")]
+    return calls(a) if a.calls else route(a) if a.route else end_to_end(a)
 
 
 if __name__ == "__main__":
