@@ -33,8 +33,10 @@ That analog input -- a float32 [T, B, *shape] entry of `inputs` -- runs on the d
 run as before, and float32 zeros and ones give the bits their bytes give.
 
 On the device the limits of the parts apply: Conv2d with dilation 1, symmetric stride and padding; an analog input into a
-PermuteConnection or ConstantPad2dConnection (a first child Permute / ConstantPad2d) raises; no
-fused plan (`network.last_plan == "generic"`); no monitor on `summed`.  A Conv2d with more than 16 input channels runs in the stated
+PermuteConnection or ConstantPad2dConnection (a first child Permute / ConstantPad2d) raises; no monitor on `summed`.  The run is the
+generic plan, step by step (`network.last_plan == "generic"`), unless `layer_major=True` asks for the layer-major plan
+(`Network.layer_major`, network/layer_major.py): a chain of Linear, Conv2d and AvgPool2d children then runs layer by layer, each
+over all T steps at once, with the same bits (`last_plan == "layer-major"`); a network that does not qualify keeps the generic plan.  A Conv2d with more than 16 input channels runs in the stated
 order of snn_prop_conv2d_f32 (include/snnhip.h): equal to the reference bit for bit where every partial sum is exact, else up to
 summation rounding."""
 import warnings
@@ -252,11 +254,11 @@ def _ann_to_snn_helper(prev, current, node_type, last=False, **kwargs):
 
 
 def ann_to_snn(ann: Union[nn.Module, str], input_shape: Sequence[int], data: Optional[torch.Tensor] = None, percentile: float = 99.9,
-               node_type: Optional[nodes.Nodes] = SubtractiveResetIFNodes, **kwargs) -> Network:
+               node_type: Optional[nodes.Nodes] = SubtractiveResetIFNodes, layer_major: bool = False, **kwargs) -> Network:
     """The spiking Network of the module docstring for `ann` (a deep copy is converted; a path is read with torch.load).  BatchNorm
     children are folded into the copy first (`fold_batchnorm`).  With
     `data` the copy's weights are rescaled by data_based_normalization first; without it a RuntimeWarning says they are not.
-    `kwargs` go to every `node_type` layer."""
+    `kwargs` go to every `node_type` layer; `layer_major` becomes the network's `layer_major` attribute."""
     ann = torch.load(ann) if isinstance(ann, str) else deepcopy(ann)
     assert isinstance(ann, nn.Module)
     ann = fold_batchnorm(ann)                          # (nothing to do, and nothing done, for a model without BatchNorm)
@@ -266,6 +268,7 @@ def ann_to_snn(ann: Union[nn.Module, str], input_shape: Sequence[int], data: Opt
         ann = data_based_normalization(ann=ann, data=data.detach(), percentile=percentile)
 
     snn = Network()
+    snn.layer_major = bool(layer_major)
     prev = nodes.Input(shape=input_shape)
     snn.add_layer(prev, name="Input")
 

@@ -12,6 +12,7 @@
 #include "../../include/snnhip.h"
 #include "snn_common.hpp"
 #include "snn_conversion.hpp"
+#include "snn_run_conv_sif.hpp"
 
 using namespace snn;
 
@@ -41,6 +42,21 @@ __global__ __launch_bounds__(kThreads) void k_sif(float *__restrict__ v, float *
         if (raster_s) raster_s[k] = sp;
         if (raster_v) raster_v[k] = vv;
     }
+}
+
+// The IF scan along time (the layer-major plan of Network.run): thread <-> neuron k of [B, n], its state in registers over the chunk's
+// Tc steps; the currents [Tc, B, n] and the train's bytes are read and written coalesced, step by step.
+template <bool SUM>
+__global__ __launch_bounds__(kThreads) void k_sif_scan(float *__restrict__ v, float *__restrict__ refrac, uint8_t *__restrict__ s,
+                                                       float *__restrict__ x, float *__restrict__ summed, const float *__restrict__ I,
+                                                       uint8_t *__restrict__ train, int Tc, long n, snn_lif_params p) {
+    const long k = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (k >= n) return;
+    float vv = v[k], rc = refrac[k], sm = SUM ? summed[k] : 0.f, xx = p.traces ? x[k] : 0.f;
+    s[k] = run_conv::scan_neuron(vv, rc, SUM, sm, xx, I + k, train + k, Tc, n, p);
+    v[k] = vv; refrac[k] = rc;
+    if (SUM) summed[k] = sm;
+    if (p.traces) x[k] = xx;
 }
 
 __global__ __launch_bounds__(kThreads) void k_pass(uint8_t *__restrict__ s, const float *__restrict__ I, long n,
@@ -89,6 +105,17 @@ extern "C" int snn_sif_step_pv(float *v, float *refrac, uint8_t *s, float *x, fl
 extern "C" int snn_sif_step(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, int B, int N,
                             const snn_lif_params *h_p, uint8_t *raster_s, float *raster_v, snn_stream_t stream) {
     return snn_sif_step_pv(v, refrac, s, x, summed, I, B, N, h_p, nullptr, raster_s, raster_v, stream);
+}
+
+extern "C" int snn_sif_scan(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, uint8_t *train, int Tc, int B, int N,
+                            const snn_lif_params *h_p, snn_stream_t stream) {
+    if (!v || !refrac || !s || !I || !train || !h_p || Tc <= 0 || B <= 0 || N <= 0) return SNN_ERR_INVALID;
+    if (h_p->traces && !x) return SNN_ERR_INVALID;
+    const long n = (long)B * N, blocks = (n + kThreads - 1) / kThreads;
+    if (blocks >= (1L << 31)) return SNN_ERR_UNSUPPORTED;
+    if (summed) hipLaunchKernelGGL(k_sif_scan<true>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, v, refrac, s, x, summed, I, train, Tc, n, *h_p);
+    else hipLaunchKernelGGL(k_sif_scan<false>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, v, refrac, s, x, summed, I, train, Tc, n, *h_p);
+    return snn_check_launch();
 }
 
 extern "C" int snn_pass_step(uint8_t *s, const float *I, int B, int N, uint8_t *raster_s, snn_stream_t stream) {

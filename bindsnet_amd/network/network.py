@@ -16,7 +16,7 @@ import torch
 from .. import _lib
 from .._lib import dptr as _dptr
 from ..rng import DeviceGenerator
-from . import host_path
+from . import host_path, layer_major
 from ._preflight import RunRequest, is_analog
 from .monitors import AbstractMonitor, Monitor, NetworkMonitor
 from .nodes import Input, Nodes
@@ -47,6 +47,12 @@ class _Pipeline:
 
 
 class Network(_lib.TouchingModule, torch.nn.Module):
+    # Not in the reference.  True: a device run of a graph that qualifies -- a converted network: a feed-forward chain of Input and
+    # SubtractiveResetIFNodes layers without learning -- goes layer by layer, each layer over all T steps at once
+    # (network/layer_major.py; `last_plan == "layer-major"`), with the bits of the generic plan.  Any other graph, and every run on the
+    # host, is as ever.  ann_to_snn(..., layer_major=True) sets it.
+    layer_major = False
+
     def __init__(self, dt: float = 1.0, batch_size: int = 1, learning: bool = True,
                  reward_fn: Optional[Type] = None) -> None:
         super().__init__()
@@ -327,6 +333,8 @@ class Network(_lib.TouchingModule, torch.nn.Module):
             return
         if T <= 0:
             self._normalize_all()
+            return
+        if self.layer_major and layer_major.run(self, req, inputs, one_step, kwargs, dev):
             return
         # The descriptor arrays are kept from one call to the next: while nothing has been assigned to any object of the
         # network since they were built (_lib.epoch(), plus the in-place versions of the scalar parameter tensors they

@@ -592,6 +592,38 @@ def sif_step(v, refrac, s, x, I, p: LifParams, summed=None, raster_s=None, raste
                                 B, N, C.byref(p), arg, _ptr(raster_s, "spike", True), _ptr(raster_v, F32, True), _stream()), "sif_step")
 
 
+def run_conv2d_sif_takes(T, B, Cin, H, Wd, Cout, KH, KW, stride, pad) -> int:
+    """f19: whether run_conv2d_sif takes the shape: 0 no, 1 with the filter bank resident in LDS, 2 with the bank streaming."""
+    return int(lib().snn_run_conv2d_sif_takes(T, B, Cin, H, Wd, Cout, KH, KW, stride, pad))
+
+
+def run_conv2d_sif(W, bias, s0, s_train, out_train, v, refrac, s, p: LifParams, x=None, summed=None, stride=1, pad=0):
+    """f19: a Conv2dConnection over spike bytes and its SubtractiveResetIFNodes over all T steps in one launch.  s0 [B,Cin,H,W] the
+    source's spikes at entry, s_train [T,B,Cin,H,W] its train (frames 0 .. T-2 are read; None at T == 1), out_train [T,B,Cout,OH,OW]
+    the target's train; v, refrac, summed, x, s the target's state, left as T generic steps leave it."""
+    T, B = out_train.shape[0], s0.shape[0]
+    Cout, Cin, KH, KW = W.shape
+    H, Wd = s0.shape[2], s0.shape[3]
+    n = v.numel()
+    if s0.numel() != B * Cin * H * Wd or (s_train is not None and s_train.numel() < (T - 1) * s0.numel()) or out_train.numel() != T * n \
+            or any(t is not None and t.numel() != n for t in (refrac, s, x, summed)):
+        raise ValueError("run_conv2d_sif: operand sizes do not match")
+    check(lib().snn_run_conv2d_sif_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(s0, "spike"), _ptr(s_train, "spike", True),
+                                       _ptr(out_train, "spike"), _ptr(v, F32), _ptr(refrac, F32), _ptr(summed, F32, True), _ptr(x, F32, True),
+                                       _ptr(s, "spike"), C.byref(p), T, B, Cin, H, Wd, Cout, KH, KW, stride, pad, _stream()), "run_conv2d_sif")
+
+
+def sif_scan(v, refrac, s, x, I, train, p: LifParams, summed=None):
+    """f19: the IF step over a time chunk: I f32 [Tc, B, N] currents, train [Tc, B, N] spike bytes out; v, refrac, summed, x updated in
+    place, s the last step's spikes."""
+    B, N = _node_args(v)
+    Tc = I.shape[0]
+    if I.numel() != Tc * B * N or train.numel() != Tc * B * N or s.numel() != B * N or (summed is not None and summed.numel() != B * N):
+        raise ValueError("sif_scan: the currents and the train must be [Tc, B, N], the state [B, N]")
+    check(lib().snn_sif_scan(_ptr(v, F32), _ptr(refrac, F32), _ptr(s, "spike"), _ptr(x, F32, True), _ptr(summed, F32, True), _ptr(I, F32),
+                             _ptr(train, "spike"), Tc, B, N, C.byref(p), _stream()), "sif_scan")
+
+
 def pass_step(s, I, raster_s=None):
     """f14: PassThroughNodes.forward (conversion/nodes.py:161-169) with the spikes kept as bytes: s [B, N] = (I != 0)."""
     B = s.shape[0]

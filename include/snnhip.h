@@ -483,6 +483,28 @@ int snn_pass_step(uint8_t *s, const float *I, int B, int N, uint8_t *raster_s, s
 int snn_prop_gather_f32(const uint8_t *s, float *out, int B, int n_src, const int *out_ext, const int *src_ext,
                         const int *stride, const int *off, int accumulate, snn_stream_t stream);
 
+/* ---- f19: a layer of a converted network over ALL steps of a run (the layer-major plan of Network.run) ----------------
+ * Layer k of a feed-forward chain reads, at step t, layer k-1's spikes of step t-1 and nothing else: its whole train follows
+ * from its source's.  Both entry points leave, bit for bit, what T generic steps leave (snn_prop_* with accumulate 0, then
+ * snn_sif_step); scalar layer parameters only.
+ *   snn_run_conv2d_sif_f32  a Conv2dConnection over spike bytes and its SubtractiveResetIFNodes in ONE launch
+ *       (csrc/snn_run_conv_sif.hip).  s0 [B,Cin,H,Wd]: the source's frame at entry; s_train [T,B,Cin,H,Wd]: its train, of which
+ *       frames 0 .. T-2 are read (nullable at T == 1).  Step t: the current is snn_prop_conv2d_f32 of frame t-1 (s0 for t = 0), then
+ *       the step of snn_sif_step.  out_train [T,B,Cout,OH,OW] takes every step's spike bytes; v, refrac, summed (nullable), x
+ *       (needed where h_p->traces) and s [B,Cout,OH,OW] hold the state behind step T-1.  Frames of 0/1 bytes run on the matrix
+ *       cores; a workgroup that meets another byte computes that step in the stated order (as snn_prop_conv2d_mfma_f32).
+ *       SNN_ERR_UNSUPPORTED before any launch: the int limits of snn_prop_conv2d_mfma_f32, or two weight slabs and two input bands
+ *       of one sample (the rows under 64 consecutive output pixels) beyond 150 KiB of LDS.
+ *   snn_run_conv2d_sif_takes  0: refused; 1: taken, the channel group's filter bank stays in LDS for all T; 2: taken, it streams.
+ *   snn_sif_scan  the IF step over a chunk: I [Tc,B,N] currents, train [Tc,B,N] spike bytes out, v / refrac / summed (nullable) /
+ *       x (where traces) updated in place, s [B,N] the last step's spikes.  One thread per neuron.  (ABI 8, additive)          */
+int snn_run_conv2d_sif_f32(const float *W, const float *bias, const uint8_t *s0, const uint8_t *s_train, uint8_t *out_train,
+                           float *v, float *refrac, float *summed, float *x, uint8_t *s, const snn_lif_params *h_p, int T, int B,
+                           int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, snn_stream_t stream);
+int snn_run_conv2d_sif_takes(int T, int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad);
+int snn_sif_scan(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, uint8_t *train, int Tc, int B, int N,
+                 const snn_lif_params *h_p, snn_stream_t stream);
+
 /* ---- f18: AvgPool2dConnection.compute ---------------------------------------------------------------
  * Not in the reference (an extension for converted networks); the oracle is ATen's avg_pool2d on the CPU:
  *   out (+)= F.avg_pool2d(float(s), k, stride, pad, ceil_mode, count_include_pad, divisor_override)
