@@ -18,12 +18,12 @@ static snn_lif_params params(float thresh, float refrac, float dt, int has_lboun
 
 // 0, or -3 for a band word or a tap outside its slot
 extern "C" int hostcheck_run_conv_sif(const float *W, const float *bias, const uint8_t *s0, const uint8_t *s_train, uint8_t *out_train, float *v,
-                                      float *refrac, float *summed, float *x, uint8_t *s, int T, int B, int Cin, int H, int Wd, int Cout, int K,
-                                      int stride, int pad, float thresh, float refrac_p, float dt, int has_lbound, float lbound, int traces,
+                                      float *refrac, float *summed, float *x, uint8_t *s, int T, int B, int Cin, int H, int Wd, int Cout, int KH,
+                                      int KW, int stride, int pad, float thresh, float refrac_p, float dt, int has_lbound, float lbound, int traces,
                                       float trace_decay, float trace_scale) {
     const snn_lif_params p = params(thresh, refrac_p, dt, has_lbound, lbound, traces, trace_decay, trace_scale);
-    const int OH = (H + 2 * pad - K) / stride + 1, OW = (Wd + 2 * pad - K) / stride + 1, nps = OH * OW;
-    const WideGeom g = {Cin, H, Wd, K, K, stride, pad, OH, OW, Cout};
+    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (Wd + 2 * pad - KW) / stride + 1, nps = OH * OW;
+    const WideGeom g = {Cin, H, Wd, KH, KW, stride, pad, OH, OW, Cout};
     const size_t img = (size_t)Cin * H * Wd, slot_bytes = (size_t)(rcs::bands_bytes(g) / 2);
     std::vector<uint32_t> slot(slot_bytes / 4 + 4);
     for (int b = 0; b < B; ++b)

@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conv_mfma_cases import SHAPES, case, stated_order
+from conv_mfma_cases import SHAPES, case, khw, stated_order
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -27,13 +27,13 @@ def host(tmp_path_factory):
     return lib
 
 
-@pytest.mark.parametrize("shape,NT", [(SHAPES[0], 1), (SHAPES[1], 2)])
+@pytest.mark.parametrize("shape,NT", [(SHAPES[0], 1), (SHAPES[1], 2), (SHAPES[8], 1), (SHAPES[9], 2), (SHAPES[10], 1), (SHAPES[11], 1)])
 @pytest.mark.parametrize("levels", (2, 4), ids=("chain", "scalar"))
 def test_bodies_equal_the_stated_order(host, shape, NT, levels):
     Cin, Cout, K, stride, pad, H, Wd, B = shape
     W, bias, s, oshape = case(shape, seed=levels, levels=levels, density=0.4)
     out, cnt = np.full(oshape, 7.5, np.float32), np.zeros(2, np.int32)
-    assert host.hostcheck_conv_mfma(W.ctypes.data, bias.ctypes.data, s.ctypes.data, out.ctypes.data, B, Cin, H, Wd, Cout, K, K, stride, pad,
+    assert host.hostcheck_conv_mfma(W.ctypes.data, bias.ctypes.data, s.ctypes.data, out.ctypes.data, B, Cin, H, Wd, Cout, *khw(K), stride, pad,
                                     0, NT, cnt.ctypes.data) == 0
     assert np.array_equal(out.view(np.uint32), stated_order(W, s, bias, stride, pad).view(np.uint32))
     assert (cnt[0] > 0 and cnt[1] == 0) if levels == 2 else (cnt[0] == 0 and cnt[1] > 0)
