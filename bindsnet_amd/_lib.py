@@ -252,6 +252,8 @@ _SIGS = {
     "snn_run_conv2d_sif_f32": ([_vp] * 10 + [C.POINTER(LifParams)] + [_i] * 10 + [_vp], _i),
     "snn_run_conv2d_sif_takes": ([_i] * 10, _i),
     "snn_sif_scan": ([_vp] * 7 + [_i, _i, _i, C.POINTER(LifParams), _vp], _i),
+    "snn_run_dense_sif_f32": ([_vp] * 10 + [C.POINTER(LifParams)] + [_i] * 4 + [_vp], _i),
+    "snn_run_dense_sif_takes": ([_i] * 4, _i),
     "snn_prop_gather_f32": ([_vp, _vp, _i, _i] + [C.POINTER(_i)] * 4 + [_i, _vp], _i),
     "snn_prop_avgpool2d_f32": ([_vp, _vp, _i, _i] + [C.POINTER(_i)] * 4 + [_i, _i, _i, _i, _vp], _i),
     "snn_set_avgpool_body": ([_i], None),

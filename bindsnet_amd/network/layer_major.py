@@ -6,7 +6,10 @@ Why it is the same run: on the generic plan layer k at step t reads layer k-1's 
 nothing else, so layer k's whole spike train [T, B, n] follows from layer k-1's whole train.  Per layer, in insertion order:
   * route 1 -- a Conv2dConnection fed spike bytes whose shape `ops.run_conv2d_sif_takes`: ONE launch of snn_run_conv2d_sif_f32, the
     convolution and the IF neurons of all T steps with the neurons' state in registers (csrc/snn_run_conv_sif.hip);
-  * route 2 -- every other connection (Connection, AvgPool2dConnection, a Conv2dConnection the kernel refuses, and a Connection or
+  * route 3 -- a Connection fed spike bytes whose shape passes `_fuse_dense` (what `ops.run_dense_sif_takes`, with or without
+    `prop_auto`): ONE launch of snn_run_dense_sif_f32, 16 steps of a sample on the rows of a matrix-core tile and the IF neurons'
+    scan along time as the tile's epilogue (csrc/snn_run_dense_sif.hip); no currents scratch;
+  * route 2 -- every other connection (AvgPool2dConnection, a Conv2dConnection or Connection its kernel refuses, and a Connection or
     Conv2dConnection fed a real-valued Input): the operator the generic plan calls, called once per time chunk with the chunk's
     frames as Tc x B samples (the frames of a train are contiguous samples; the start frame is a call of its own), into a currents
     scratch, then `ops.sif_scan`, the IF step along time with one thread per neuron.
@@ -93,9 +96,19 @@ def _operator(conn, analog: bool, net, dev):
     return conn._prop_into                                  # AvgPool2dConnection
 
 
+# Route 3 walks ceil(Nin / 64) slabs per 64 steps whatever N is, about 2.8 us each (profiles/NOTES_layer_major_dense.md): 13 slabs
+# (784 sources) is the widest layer measured to win end to end, 128 slabs (8192 -> 10) loses to route 2's one GEMM over T x B samples.
+FUSED_DENSE_MAX_SOURCES = 13 * 64
+
+
+def _fuse_dense(T, B, Nin, N) -> bool:
+    """Route 3's gate: whether a Connection fed spike bytes runs as one snn_run_dense_sif_f32 launch."""
+    return Nin <= FUSED_DENSE_MAX_SOURCES and ops.run_dense_sif_takes(T, B, Nin, N) != 0
+
+
 def run(net, req, inputs, one_step, kwargs, dev) -> bool:
     """Run `req` layer-major if the network qualifies (True), else touch nothing (False)."""
-    from .topology import Conv2dConnection
+    from .topology import Connection, Conv2dConnection
     chain = _chain(net, req, one_step, kwargs)
     if chain is None:
         return False
@@ -152,6 +165,9 @@ def run(net, req, inputs, one_step, kwargs, dev) -> bool:
         if geom is not None and ops.run_conv2d_sif_takes(T, B, *geom):
             ops.run_conv2d_sif(conn.w.data, conn.b.data, s0.view(B, *src.shape), s_train if T > 1 else None, train, layer.v,
                                layer.refrac_count, layer.s, p, x=x, summed=summed, stride=conn.stride[0], pad=conn.padding[0])
+        elif type(conn) is Connection and not real and _fuse_dense(T, B, src.n, n):
+            ops.run_dense_sif(conn.w.data.view(src.n, n), None if conn.b is None else conn.b.data, s0.view(B, src.n),
+                              s_train if T > 1 else None, train, layer.v, layer.refrac_count, layer.s, p, x=x, summed=summed)
         else:
             op = _operator(conn, real, net, dev)
             Tc = max(1, min(T, CURRENTS_BUDGET_BYTES // (4 * B * n), MAX_OPERATOR_BATCH // B))

@@ -613,6 +613,26 @@ def run_conv2d_sif(W, bias, s0, s_train, out_train, v, refrac, s, p: LifParams, 
                                        _ptr(s, "spike"), C.byref(p), T, B, Cin, H, Wd, Cout, KH, KW, stride, pad, _stream()), "run_conv2d_sif")
 
 
+def run_dense_sif_takes(T, B, Nin, N) -> int:
+    """f19: whether run_dense_sif takes the shape: 0 no, 1 with the weight panel resident in LDS, 2 with the panel streaming."""
+    return int(lib().snn_run_dense_sif_takes(T, B, Nin, N))
+
+
+def run_dense_sif(W, bias, s0, s_train, out_train, v, refrac, s, p: LifParams, x=None, summed=None):
+    """f19: a Connection over spike bytes and its SubtractiveResetIFNodes over all T steps in one launch.  W f32 [Nin,N], s0 [B,Nin] the
+    source's spikes at entry, s_train [T,B,Nin] its train (frames 0 .. T-2 are read; None at T == 1), out_train [T,B,N] the target's
+    train; v, refrac, summed, x, s the target's state, left as T generic steps leave it."""
+    T, B = out_train.shape[0], s0.shape[0]
+    Nin, N = W.shape
+    n = B * N
+    if s0.numel() != B * Nin or (s_train is not None and s_train.numel() < (T - 1) * s0.numel()) or out_train.numel() != T * n \
+            or any(t is not None and t.numel() != n for t in (v, refrac, s, x, summed)):
+        raise ValueError("run_dense_sif: operand sizes do not match")
+    check(lib().snn_run_dense_sif_f32(_ptr(W, F32), _ptr(bias, F32, True), _ptr(s0, "spike"), _ptr(s_train, "spike", True),
+                                      _ptr(out_train, "spike"), _ptr(v, F32), _ptr(refrac, F32), _ptr(summed, F32, True), _ptr(x, F32, True),
+                                      _ptr(s, "spike"), C.byref(p), T, B, Nin, N, _stream()), "run_dense_sif")
+
+
 def sif_scan(v, refrac, s, x, I, train, p: LifParams, summed=None):
     """f19: the IF step over a time chunk: I f32 [Tc, B, N] currents, train [Tc, B, N] spike bytes out; v, refrac, summed, x updated in
     place, s the last step's spikes."""

@@ -497,13 +497,27 @@ int snn_prop_gather_f32(const uint8_t *s, float *out, int B, int n_src, const in
  *       of one sample (the rows under 64 consecutive output pixels) beyond 150 KiB of LDS.
  *   snn_run_conv2d_sif_takes  0: refused; 1: taken, the channel group's filter bank stays in LDS for all T; 2: taken, it streams.
  *   snn_sif_scan  the IF step over a chunk: I [Tc,B,N] currents, train [Tc,B,N] spike bytes out, v / refrac / summed (nullable) /
- *       x (where traces) updated in place, s [B,N] the last step's spikes.  One thread per neuron.  (ABI 8, additive)          */
+ *       x (where traces) updated in place, s [B,N] the last step's spikes.  One thread per neuron.  (ABI 8, additive)
+ *   snn_run_dense_sif_f32  a Connection over spike bytes (W [Nin,N] row-major, bias nullable) and its SubtractiveResetIFNodes in
+ *       ONE launch (csrc/snn_run_dense_sif.hip).  s0 [B,Nin], s_train [T,B,Nin] (frames 0 .. T-2 are read; nullable at T == 1),
+ *       out_train [T,B,N] and the state as for snn_run_conv2d_sif_f32.  Step t: the current is snn_prop_dense_auto_f32 of frame t-1
+ *       (s0 for t = 0) -- one unsplit f32 chain per (sample, target), sources ascending, the bias last --, then the step of
+ *       snn_sif_step.  16 consecutive steps of a sample are the rows of a matrix-core tile, the IF step along time is the tile's
+ *       epilogue; 64 steps whose frames hold a byte other than 0/1 are summed in the stated order instead.
+ *       SNN_ERR_UNSUPPORTED before any launch: Nin >= 2^24 or B > 65535 (the limits of snn_prop_dense_auto_f32), or T * B * N or
+ *       T * B * Nin beyond 2^31 - 1.
+ *   snn_run_dense_sif_takes  0: refused; 1: taken, the 64-target weight panel stays in LDS for all T; 2: taken, it streams.
+ *       (ABI 8, additive)                                                                                                       */
 int snn_run_conv2d_sif_f32(const float *W, const float *bias, const uint8_t *s0, const uint8_t *s_train, uint8_t *out_train,
                            float *v, float *refrac, float *summed, float *x, uint8_t *s, const snn_lif_params *h_p, int T, int B,
                            int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad, snn_stream_t stream);
 int snn_run_conv2d_sif_takes(int T, int B, int Cin, int H, int Wd, int Cout, int KH, int KW, int stride, int pad);
 int snn_sif_scan(float *v, float *refrac, uint8_t *s, float *x, float *summed, const float *I, uint8_t *train, int Tc, int B, int N,
                  const snn_lif_params *h_p, snn_stream_t stream);
+int snn_run_dense_sif_f32(const float *W, const float *bias, const uint8_t *s0, const uint8_t *s_train, uint8_t *out_train,
+                          float *v, float *refrac, float *summed, float *x, uint8_t *s, const snn_lif_params *h_p, int T, int B,
+                          int Nin, int N, snn_stream_t stream);
+int snn_run_dense_sif_takes(int T, int B, int Nin, int N);
 
 /* ---- f18: AvgPool2dConnection.compute ---------------------------------------------------------------
  * Not in the reference (an extension for converted networks); the oracle is ATen's avg_pool2d on the CPU:
